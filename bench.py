@@ -20,7 +20,11 @@ contracts, combines and decomposes ONLY the theta blocks of its own sectors (the
 all_gather makes every singular value known everywhere (the truncation is a global selection), and one all_gather of the
 KEPT U / S / Vh columns completes the truncated factors on every rank (cyten_amd.sharding).
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the --steps steps and prints that line (`value`,
+`ms_per_step`, and the GEMM / SVD phase times of the timed steps as `roofline` / `roofline_svd`).  Everything measured in runs
+of its own -- the CPU baseline (oracle thread sweep), the U(1)xU(1), dominant-block and full-rank-SVD rooflines, the measured
+MFMA ceiling, the truncating caller's step and torch.linalg.svd on the same device -- runs only with --full.
+--dump-outputs DIR writes what the last timed step computed (see dump_outputs) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -48,13 +52,20 @@ def parse(argv=None):
     ap.add_argument('--chi', type=int, default=4096)
     ap.add_argument('--symmetry', choices=['u1', 'u1u1'], default='u1')
     ap.add_argument('--chi-max', type=int, default=None, help='truncation target (default: chi)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline line\'s steps also run the CPU baseline and the untimed extras (single GPU)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--cpu-budget', type=float, default=100.0, help='seconds of host time the CPU baseline may use')
     ap.add_argument('--no-extras', action='store_true',
-                    help='skip the untimed extras after the timed loop (U(1)xU(1) GEMM roofline, torch.linalg.svd on the device)')
+                    help='with --full: skip the untimed extras after the timed loop (U(1)xU(1) GEMM roofline, torch.linalg.svd on the device)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the truncated U / S / Vh of the last timed step as DIR/<name>.npy (float64, at most 64 MB)')
     ap.add_argument('--master-port', type=int, default=29533)
     ap.add_argument('--dry-run', action='store_true', help='print the launch decision as JSON and exit (no GPU)')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 # --------------------------------------------------------------------------------------- launcher (no GPU calls here)
@@ -232,6 +243,48 @@ class ThetaStep:
                          shapes=shapes_all, local_sectors=mine_sec, plan=plan, kept_n=kept_n,
                          imbalance_svd=sp.layout.imbalance(svd_cost))
         return self.last
+
+
+# ------------------------------------------------------------------------------------------------------ outputs
+
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(bb, res, out_dir, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Write what a caller of the timed path receives from the step `res`: the truncated factors of every coupled-charge
+    sector, float64, sector by sector in block-table order.
+
+      S.npy               every kept singular value, (K,)
+      kept_per_sector.npy the number of kept values of each sector
+      sector_shapes.npy   (m, n) of each sector's matrix: U of a sector is m x kept, Vh is kept x n
+      truncation.npy      [err, new_norm] of the truncation
+      triplets.npy        indices into S of the singular triplets whose vectors follow (ascending)
+      U.npy, Vh.npy       the kept columns of U / rows of Vh of those triplets, one after the other, flattened
+
+    All triplets are written when they fit the byte budget; otherwise a fixed sample of them drawn with `seed` (whole
+    columns / rows, so that every vector can be compared up to its sign), the same for the same arguments."""
+    os.makedirs(out_dir, exist_ok=True)
+    kept_n = np.asarray(res['kept_n'], dtype=np.int64)
+    sec = [u for u in range(len(kept_n)) if kept_n[u] > 0]
+    host = {u: tuple(bb.to_numpy(x) for x in res['kept'][u]) for u in sec}
+    S = np.concatenate([host[u][1] for u in sec]) if sec else np.zeros(0)
+    sector_of = np.repeat(np.arange(len(kept_n)), kept_n)
+    col_in_sector = np.concatenate([np.arange(c) for c in kept_n]) if len(kept_n) else np.zeros(0, dtype=np.int64)
+    m = np.array([res['shapes'][u][0] for u in range(len(kept_n))], dtype=np.int64)
+    n = np.array([res['shapes'][u][1] for u in range(len(kept_n))], dtype=np.int64)
+    cost = 8 * (m[sector_of] + n[sector_of])                    # bytes of one triplet's U column + Vh row
+    room = budget - 8 * (2 * len(S) + 3 * len(kept_n) + 2) - 7 * 128    # S, triplets (at most len(S)), small files, .npy headers
+    if cost.sum() <= room:
+        sel = np.arange(len(S))
+    else:
+        order = np.random.default_rng(seed).permutation(len(S))
+        sel = np.sort(order[:int(np.searchsorted(np.cumsum(cost[order]), room, side='right'))])
+    U = [host[sector_of[j]][0][:, col_in_sector[j]] for j in sel]
+    Vh = [host[sector_of[j]][2][col_in_sector[j], :] for j in sel]
+    arrays = {'S': S, 'kept_per_sector': kept_n, 'sector_shapes': np.stack([m, n], axis=1), 'truncation': [res['err'], res['new_norm']], 'triplets': sel,
+              'U': np.concatenate(U) if U else np.zeros(0), 'Vh': np.concatenate(Vh) if Vh else np.zeros(0)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), np.asarray(a, dtype=np.float64))
 
 
 # ------------------------------------------------------------------------------------------------------ CPU baseline
@@ -585,6 +638,9 @@ def main(argv=None):
     total_flops = gemm_flops + svd_flops
     ms_per_step = 1e3 * dt / args.steps
     value = total_flops / (dt / args.steps) / 1e9
+    if args.dump_outputs and rank == 0:     # the kept factors of every sector are on every rank after the last all_gather
+        dump_outputs(bb, res, args.dump_outputs)
+    extras = rank == 0 and world == 1 and args.full and not args.no_extras
 
     # roofline of the dominant north-star kernel: the grouped fp64 MFMA GEMM, HIP events on the launch stream
     gms = runner.t_gemm.ms()
@@ -603,7 +659,7 @@ def main(argv=None):
         'note': 'the kernel north_star names (dominant-block GEMM of the tdot); it is about one per cent of the step -- the step IS the '
                 'batched SVD (roofline_svd), whose nominal-flop rate is a latency chain, not a throughput kernel',
     }
-    if rank == 0 and world == 1 and not args.no_extras:
+    if extras:
         try:    # the measured ceiling beside the spec one: back-to-back v_mfma_f64_16x16x4_f64 on every SIMD, outside the timed region
             tf, _ = bb.ctx.mfma_f64_peak(200000, 4, 4)
             roofline['peak_measured'] = {'value': round(tf, 2), 'unit': 'TFLOP/s', 'frac_of_measured': round(achieved / tf, 4),
@@ -658,7 +714,7 @@ def main(argv=None):
         'truncation': {'err': res['err'], 'new_norm': res['new_norm'], 'kept': int(res['kept_n'].sum())},
         'ranks': ranks_report,
     }
-    if rank == 0 and world == 1 and not args.no_extras:
+    if extras:
         try:    # the same step as a truncating caller runs it (not the metric: the null vectors of the rank-deficient
             # sectors are never formed, see cyb_svd_batched_ex_f64); same truncation result is asserted
             for _ in range(2):
@@ -690,7 +746,7 @@ def main(argv=None):
             out['roofline_svd']['reference_same_hw'] = ref_hw
         except Exception as e:
             out['roofline_svd']['reference_same_hw'] = {'error': repr(e)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cb = cpu_baseline(A, B, chi_max, args.cpu_budget)
         best_s = cb['seconds_best']
         out['cpu_baseline'] = {'value': round(total_flops / best_s / 1e9, 2), 'unit': 'GFLOP/s', 'cores': cb['best_threads'],
@@ -701,7 +757,7 @@ def main(argv=None):
                                **{k: cb[k] for k in ('sweep_seconds_per_step', 'best_threads', 'all_threads', 'seconds_all',
                                                      'split_best', 'single_thread', 'blas', 'host_seconds_used')}}
         out['speedup_vs_cpu'] = round(value / out['cpu_baseline']['value'], 2)
-    if rank == 0 and world == 1 and not args.no_extras:
+    if extras:
         try:
             threads = out.get('cpu_baseline', {}).get('cores', 16)
             out['roofline_svd_fullrank'] = fullrank_svd_roofline(bb, res['shapes'], threads)

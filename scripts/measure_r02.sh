@@ -5,7 +5,7 @@ set -e
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
 O=gpurun_out/r02
 mkdir -p $O
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 echo "bench done"
 python bench.py --symmetry u1u1 --no-cpu-baseline --no-extras > $O/bench_u1u1.json 2> $O/bench_u1u1.err
 python bench.py --chi 1024 --no-cpu-baseline --no-extras > $O/bench_chi1024.json 2> $O/bench_chi1024.err

@@ -1,26 +1,25 @@
 """Mechanical checks of the cyten integration surface that need neither cyten nor a GPU:
 
-* every pure virtual (`= 0`) of the reference's ``BlockBackend`` / ``BlockBackend::Block`` (parsed from the TEXT of
-  include/cyten/block_backend/block_backend.h when /root/reference exists) has a same-named counterpart with a compatible
-  number of parameters on ``HipBlockBackend`` / ``HipBlock`` -- the mirror a C++ subclass forwards to;
+* every pure virtual (`= 0`) of the reference's ``BlockBackend`` / ``BlockBackend::Block`` (include/cyten/block_backend/
+  block_backend.h) has a same-named counterpart with a compatible number of parameters on ``HipBlockBackend`` / ``HipBlock``
+  -- the mirror a C++ subclass forwards to;
 * every attribute of the Array-API namespace and of its array objects that the reference's ``ArrayApiBlockBackend`` uses
-  (parsed from src/block_backend/array_api.cpp) exists on ``HipArrayNamespace`` / ``HipArray`` -- the route by which an
+  (src/block_backend/array_api.cpp) exists on ``HipArrayNamespace`` / ``HipArray`` -- the route by which an
   UNMODIFIED cyten runs on the device (integration/cyten_hip.py);
 * the operations the reference base leaves NotImplemented are exactly the ones the registration subclass overrides.
 
-Skipped where the reference tree is absent (the GPU box)."""
+What the reference declares is read from tests/golden/ref_integration_surface.json (names and parameter counts, extracted
+from the reference's text by scripts/make_integration_surface_golden.py)."""
 import inspect
+import json
 import os
 import re
-
-import pytest
 
 from cyten_amd.block_backend import HipBlock, HipBlockBackend, Scalar
 from integration import cyten_hip
 from integration.hip_array_api import HipArray, HipArrayNamespace
 
-REF = '/root/reference'
-need_ref = pytest.mark.skipif(not os.path.isdir(REF), reason='reference sources not present')
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'ref_integration_surface.json')
 
 # C++ operator -> the Python special method that carries it on the mirror
 OPERATORS = {'operator+': '__add__', 'operator-': '__sub__', 'operator*': '__mul__', 'operator/': '__truediv__',
@@ -30,19 +29,9 @@ OPERATORS = {'operator+': '__add__', 'operator-': '__sub__', 'operator*': '__mul
 RENAMED = {'get_backend': 'get_backend', '_item_as_complex128': None, '_item_as_int64': None}   # host accessors live on Scalar
 
 
-def _pure_virtuals(text):
-    """[(name, n_params)] of the `virtual ... name(args) ... = 0;` declarations in a class body"""
-    out = []
-    for m in re.finditer(r'virtual\s+[^;{}]*?\b(operator\s*[^\s(]+|[A-Za-z_]\w*)\s*\(([^;{}]*?)\)\s*(?:const\s*)?=\s*0\s*;', text, re.S):
-        name = re.sub(r'\s+', '', m.group(1))
-        args = m.group(2).strip()
-        depth, n = 0, (1 if args else 0)
-        for ch in args:
-            depth += ch in '<(' 
-            depth -= ch in '>)'
-            n += (ch == ',' and depth == 0)
-        out.append((name, n))
-    return out
+def _surface():
+    with open(GOLDEN) as f:
+        return json.load(f)
 
 
 def _accepts(fn, n):
@@ -56,14 +45,10 @@ def _accepts(fn, n):
     return len(required) <= n <= len(pos)
 
 
-@need_ref
 def test_every_pure_virtual_of_the_reference_header_has_a_counterpart():
-    text = open(os.path.join(REF, 'include/cyten/block_backend/block_backend.h')).read()
-    i_block = text.index('class Block : public std::enable_shared_from_this<Block>')
-    i_scalar = text.index('/// Holds a single scalar value', i_block)
-    block_virtuals = _pure_virtuals(text[i_block:i_scalar])
-    backend_virtuals = _pure_virtuals(text[i_scalar:])
-    assert len(block_virtuals) >= 20 and len(backend_virtuals) >= 70          # the parser found the interface
+    ref = _surface()
+    block_virtuals, backend_virtuals = ref['block_virtuals'], ref['backend_virtuals']
+    assert len(block_virtuals) >= 20 and len(backend_virtuals) >= 70          # the fixture holds the whole interface
     missing = []
     for name, n in block_virtuals:
         if name in OPERATORS:
@@ -89,12 +74,10 @@ def test_every_pure_virtual_of_the_reference_header_has_a_counterpart():
     assert not missing, missing
 
 
-@need_ref
 def test_array_api_namespace_provides_what_the_reference_backend_calls():
-    src = open(os.path.join(REF, 'src/block_backend/array_api.cpp')).read()
-    api_names = set(re.findall(r'api_\.attr\("(\w+)"\)(?!\.attr)', src)) | set(re.findall(r'api\(\)\.attr\("(\w+)"\)', src))
-    linalg_names = set(re.findall(r'api_\.attr\("linalg"\)\.attr\("(\w+)"\)', src))
-    array_names = set(re.findall(r'(?:arr_|obj\([a-z_]*\)|\ba|\bb)\.attr\("(\w+)"\)', src))
+    ref = _surface()
+    api_names, linalg_names = set(ref['array_api_namespace']), set(ref['array_api_linalg'])
+    array_names = set(ref['array_api_array'])
     assert {'matmul', 'tensordot', 'asarray', 'zeros', 'permute_dims', 'reshape'} <= api_names and {'svd', 'qr', 'eigh'} <= linalg_names
     lacking = sorted(n for n in api_names - {'linalg'} if not hasattr(HipArrayNamespace, n))
     lacking += sorted('linalg.' + n for n in linalg_names if not hasattr(__import__('integration.hip_array_api', fromlist=['_Linalg'])._Linalg, n))
@@ -102,10 +85,8 @@ def test_array_api_namespace_provides_what_the_reference_backend_calls():
     assert not lacking, lacking
 
 
-@need_ref
 def test_cold_overrides_are_exactly_what_the_reference_base_leaves_open():
-    src = open(os.path.join(REF, 'src/block_backend/array_api.cpp')).read()
-    left_open = set(re.findall(r'NotImplemented\("ArrayApiBlockBackend does not support (\w+)\.', src)) | {'tile'}
+    left_open = set(_surface()['array_api_not_implemented']) | {'tile'}
     assert left_open == set(cyten_hip.COLD_OVERRIDES)
     code = inspect.getsource(cyten_hip._make_backend_class)
     for name in cyten_hip.COLD_OVERRIDES:       # override name == method name (the trampoline looks it up by the C++ name)
