@@ -1187,8 +1187,8 @@ class HipBlockBackend:
 
     def inner_many(self, a_blocks, b_blocks):
         """sum_i <a_i, b_i> = sum conj(a) b over a block list: one launch + one 8-byte D2H
-        (abelian.cpp:2159-2211).  Complex lists: the real part is the same reduction over the interleaved
-        storage, the imaginary part sum(ar bi - ai br) is two more reductions over the real / imaginary planes."""
+        (abelian.cpp:2159-2211).  Complex lists: one pass of the complex reduction (cyb_dot_batched_c128) over the
+        interleaved storage, a real block of a mixed pair promoted first."""
         for x, y in zip(a_blocks, b_blocks):
             if x.shape != y.shape:
                 raise ValueError('inner: shape mismatch')
@@ -1199,15 +1199,10 @@ class HipBlockBackend:
             a = self.contiguous_many(a_blocks)
             b = self.contiguous_many(b_blocks)
             return float(self._reduce(self.lib.cyb_dot_batched_f64, a, b)[0])
-        a_blocks = [self.as_complex(x) for x in a_blocks]
-        b_blocks = [self.as_complex(y) for y in b_blocks]
-        re = float(self._reduce(self.lib.cyb_dot_batched_f64, self._as_float_lists(a_blocks), self._as_float_lists(b_blocks))[0])
-        ar = self.contiguous_many([self._plane(x, 0) for x in a_blocks])
-        ai = self.contiguous_many([self._plane(x, 1) for x in a_blocks])
-        br = self.contiguous_many([self._plane(y, 0) for y in b_blocks])
-        bi = self.contiguous_many([self._plane(y, 1) for y in b_blocks])
-        im = float(self._reduce(self.lib.cyb_dot_batched_f64, ar, bi)[0]) - float(self._reduce(self.lib.cyb_dot_batched_f64, ai, br)[0])
-        return complex(re, im)
+        a = self.contiguous_many([self.as_complex(x) for x in a_blocks])
+        b = self.contiguous_many([self.as_complex(y) for y in b_blocks])
+        re, im = self._reduce(self.lib.cyb_dot_batched_c128, a, b, 2)
+        return complex(float(re), float(im))
 
     def norm_many(self, blocks) -> float:
         """2-norm of a whole block list (abelian.cpp:2781-2792)."""
@@ -1522,7 +1517,10 @@ class HipBlockBackend:
         """complex128 groups through the real grouped GEMM (include/cyten_amd.h, complex section): A is read in
         place as a real M x 2K matrix, B is expanded once into the real 2K x 2N matrix [[br, bi], [-bi, br]],
         C is written in place as a real M x 2N matrix -- 8 M N K real flops, no waste.  Real operands of a mixed
-        product are promoted first."""
+        product are promoted first -- except a real A with complex B (a real operator on a complex vector), which
+        runs as a real product on the interleaved storage (`_real_complex_gemm`)."""
+        if not any(a.is_complex for g in groups for a, _ in g) and all(b.is_complex for g in groups for _, b in g):
+            return self._real_complex_gemm(groups, outs, enqueue)
         n_b = sum(len(g) for g in groups)
         a_list = self.contiguous_many([self.as_complex(a) for g in groups for a, _ in g])
         b_list = [self.as_complex(b) for g in groups for _, b in g]
@@ -1562,6 +1560,50 @@ class HipBlockBackend:
             return list(c_outs)
         res.outs = list(c_outs)
         res._keepalive = (res._keepalive, a_list, b_exp)
+        return res
+
+    def _real_complex_gemm(self, groups, outs, enqueue):
+        """Real A (M x K) times complex B (K x N): the interleaved storage of B read in place as the real K x 2N matrix
+        [br0, bi0, br1, bi1, ...] and C written in place as the real M x 2N matrix -- ONE real grouped GEMM of 4 M N K
+        flops, no promotion of A, no expansion of B.  A B operand without unit column stride is made contiguous."""
+        fbufs = {}
+
+        def fview(x, shape, strides):
+            fb = fbufs.get(id(x.buf))
+            if fb is None:
+                fb = fbufs[id(x.buf)] = (self.ctx.torch.view_as_real(x.buf).reshape(-1), x.buf)
+            return HipBlock._trusted(self, fb[0], 2 * x.offset, shape, strides)
+
+        b_list = [b for g in groups for _, b in g]
+        for b in b_list:
+            if b.ndim != 2:
+                raise ValueError('matrix operand must be 2-D')
+        fix = [i for i, b in enumerate(b_list) if b.shape[1] > 1 and b.strides[1] != 1]
+        if fix:
+            for i, c in zip(fix, self.contiguous_many([b_list[i] for i in fix])):
+                b_list[i] = c
+        c_outs = outs
+        if c_outs is None:
+            c_outs = self._new_many([(g[0][0].shape[0], g[0][1].shape[1]) for g in groups], True)
+        rgroups, k = [], 0
+        for g in groups:
+            rg = []
+            for a, _ in g:
+                b = b_list[k]
+                K, N = b.shape
+                rg.append((a, fview(b, (K, 2 * N), (2 * b.strides[0] if K > 1 else 2 * N, 1))))
+                k += 1
+            rgroups.append(rg)
+        f_outs = []
+        for c in c_outs:
+            if not (c.is_complex and c.is_contiguous()):
+                raise ValueError('complex GEMM output must be a contiguous complex block')
+            f_outs.append(fview(c, (c.shape[0], 2 * c.shape[1]), (2 * c.shape[1], 1)))
+        res = self.make_gemm_plan(rgroups, f_outs, enqueue)
+        if enqueue:
+            return list(c_outs)
+        res.outs = list(c_outs)
+        res._keepalive = (res._keepalive, b_list)
         return res
 
     def matrix_dot_grouped(self, groups, outs=None):

@@ -11,6 +11,9 @@
   same convergence test, same result assembly; ``inner`` / ``norm`` / ``axpy`` run as one launch
   each over the whole block list, the (k+1) x (k+1) tridiagonal problem stays on the host as in the
   reference (numpy.linalg.eigh, :922-946).
+* :class:`LanczosEvolution`, :class:`Arnoldi`, :class:`ArnoldiEvolution` -- exp(delta H) psi (the TDVP step) and the
+  non-Hermitian eigensolver of the reference (krylov_based.cpp:532-800, 948-1019), on the same flat pools: float64 while the
+  operator and the start vector are real, complex128 otherwise.
 
 Leg orders used here (signs: + ket-like, - dual):
     theta [vL, p0, p1, vR]
@@ -23,6 +26,10 @@ from __future__ import annotations
 import numpy as np
 
 from . import abelian as ab
+
+
+def _is_complex_block(b) -> bool:
+    return np.iscomplexobj(b) if isinstance(b, np.ndarray) else bool(b.is_complex)
 
 
 class HEffective:
@@ -40,8 +47,24 @@ class HEffective:
         # issues C-ABI launches can be recorded
         self._recordings = (cache if cache is not None else {}) if (replay and hasattr(bb, 'ctx')) else None
         self._op_layout = None
+        self._op_layout_rc = None
+        self._RP_t = None
+        self.is_complex = any(_is_complex_block(b) for t in (LP, W1, W2, RP) for b in t.blocks)
         self.n_replayed = 0
         self.n_recorded = 0
+
+    def _real_on_complex(self, theta) -> bool:
+        """A complex vector under a real operator: every compose runs as real A x complex B (`_real_complex_gemm`)."""
+        return not self.is_complex and any(_is_complex_block(b) for b in theta.blocks)
+
+    def _rp_t(self):
+        """RP with its legs in the order [vR', vR*, wR*], contiguous: the last compose of a complex vector takes RP as
+        its (real) A operand.  Made ONCE; it is part of the fixed operator layout of the recordings, so a shared cache
+        relocates it like the other operands."""
+        if self._RP_t is None:
+            t = ab.permute_legs(self.bb, self.RP, [2, 1, 0])
+            self._RP_t = ab.AbelianTensor(t.symmetry, t.legs, self.bb.contiguous_many(t.blocks), t.block_inds, t.num_codomain)
+        return self._RP_t
 
     def _compose(self, tag, a, b, k):
         key = (tag, a.block_inds.tobytes(), b.block_inds.tobytes())
@@ -63,12 +86,19 @@ class HEffective:
         if self._recordings is None:
             return self._matvec(theta)
         from .replay import apply_recorded, tensor_layout
-        if self._op_layout is None:
-            bufs, sizes = [], {}
-            sig = tensor_layout([self.LP, self.W1, self.W2, self.RP], bufs, sizes)
-            self._op_layout = (sig, bufs, sizes)
-        out, how, rec = apply_recorded(self.bb, self._recordings, 'heff', lambda: self._matvec(theta), [theta],
-                                       fixed=self._op_layout)
+        if self._real_on_complex(theta):
+            if self._op_layout_rc is None:
+                bufs, sizes = [], {}
+                sig = tensor_layout([self.LP, self.W1, self.W2, self._rp_t()], bufs, sizes)
+                self._op_layout_rc = (sig, bufs, sizes)
+            tag, fixed = 'heff_rc', self._op_layout_rc
+        else:
+            if self._op_layout is None:
+                bufs, sizes = [], {}
+                sig = tensor_layout([self.LP, self.W1, self.W2, self.RP], bufs, sizes)
+                self._op_layout = (sig, bufs, sizes)
+            tag, fixed = 'heff', self._op_layout
+        out, how, rec = apply_recorded(self.bb, self._recordings, tag, lambda: self._matvec(theta), [theta], fixed=fixed)
         if how == 'recorded':
             self.n_recorded += 1
             rec.flops = self.flops_per_matvec
@@ -88,16 +118,31 @@ class HEffective:
         x = ab.permute_legs(bb, x, [1, 2, 3, 4, 0])                   # [wC, p1, vR, vL', p0']
         x, f = self._compose('W2', self.W2, x, 2)                     # [p1', wR, vR, vL', p0']
         flops += f
-        x = ab.permute_legs(bb, x, [3, 4, 0, 2, 1])                   # [vL', p0', p1', vR, wR]
-        x, f = self._compose('RP', x, self.RP, 2)                     # [vL', p0', p1', vR']
-        flops += f
+        if self._real_on_complex(theta):
+            # the vector stays the B operand: RP^T x instead of x RP, the result legs rotated back as views
+            x = ab.permute_legs(bb, x, [1, 2, 3, 4, 0])               # [wR, vR, vL', p0', p1']
+            x, f = self._compose('RPt', self._rp_t(), x, 2)           # [vR', vL', p0', p1']
+            flops += f
+            x = ab.permute_legs(bb, x, [1, 2, 3, 0])                  # [vL', p0', p1', vR']
+        else:
+            x = ab.permute_legs(bb, x, [3, 4, 0, 2, 1])               # [vL', p0', p1', vR, wR]
+            x, f = self._compose('RP', x, self.RP, 2)                 # [vL', p0', p1', vR']
+            flops += f
         self.flops_per_matvec = flops
         x.num_codomain = theta.num_codomain
         return x
 
 
 class _NotFlat(Exception):
-    """The vector left the block structure the flat representation was built for (caught by LanczosGroundState.run)."""
+    """The vector left the block structure the flat representation was built for (caught by the solvers' run)."""
+
+
+class _NeedComplex(_NotFlat):
+    """A complex vector met a float64 pool (the operator is complex): the run restarts on complex128 pools."""
+
+
+def _is_real_scalar(c) -> bool:
+    return not isinstance(c, (complex, np.complexfloating)) or complex(c).imag == 0.0
 
 
 class _TensorOps:
@@ -127,22 +172,35 @@ class _TensorOps:
     def lincomb(self, a, w, b, v):
         return ab.linear_combination(self.bb, a, w, b, v)
 
+    def combine(self, coeffs, vecs, acc=None):
+        """acc + sum_k coeffs[k] vecs[k] (acc None: 0)."""
+        out = acc
+        for c, v in zip(coeffs, vecs):
+            out = self.scale(c, v) if out is None else self.lincomb(1.0, out, c, v)
+        return out
+
 
 class _FlatOps:
-    """The same operations on Krylov vectors kept as ONE contiguous float64 pool each: the block
-    offsets of the structure are computed once, every ``scale / axpy / inner / norm`` of the recurrences is a
-    single-descriptor launch over the whole pool -- no per-block host work, one descriptor copy.  The pools are zero
-    between blocks (32-element alignment gaps), so reductions over the flat range are exact.  Only the operator
-    application sees tensors: its input is a list of views into the pool, its output is copied back in one batched
-    launch.  Real float64 tensors on the HIP backend only; anything else uses :class:`_TensorOps`."""
+    """The same operations on Krylov vectors kept as ONE contiguous pool each: the block offsets of
+    the structure are computed once, every ``scale / axpy / inner / norm`` of the recurrences is a single-descriptor
+    launch over the whole pool -- no per-block host work, one descriptor copy.  The pools are zero between blocks
+    (32-element alignment gaps), so reductions over the flat range are exact.  Only the operator application sees
+    tensors: its input is a list of views into the pool, its output is copied back in one batched launch.
 
-    def __init__(self, bb, H, template, block_inds=None):
+    Pools are float64 while the start vector and the operator are real -- the Lanczos / Arnoldi bases of a real operator
+    are real whatever the evolution step delta; only the result assembly ``sum_k c_k v_k`` then has complex coefficients,
+    ONE launch of the complex linear combination with real sources.  A complex start vector or operator uses complex128
+    pools (interleaved, the same offsets).  Every operation dispatches on the dtype of its pools.  HIP backend only;
+    anything else uses :class:`_TensorOps`."""
+
+    def __init__(self, bb, H, template, block_inds=None, cplx=False):
         """`template`: a tensor on the legs of the vectors; `block_inds` (default: the template's): the block table of the
-        pool -- a superset of the template's when the operator creates blocks the start vector does not have."""
+        pool -- a superset of the template's when the operator creates blocks the start vector does not have.
+        `cplx`: the Krylov vectors are complex128 pools."""
         from .block_backend import HipBlock, _c_strides
         from . import _lib
         import ctypes
-        self.bb, self.H, self.t = bb, H, template
+        self.bb, self.H, self.t, self.cplx = bb, H, template, bool(cplx)
         self._HipBlock, self._lib, self._C = HipBlock, _lib, ctypes
         self.block_inds = template.block_inds if block_inds is None else block_inds
         self.shapes = [template.block_shape(r) for r in self.block_inds]
@@ -164,16 +222,17 @@ class _FlatOps:
 
     @staticmethod
     def usable(bb, t) -> bool:
-        return (hasattr(bb, 'ctx') and len(t.blocks) > 0 and not any(b.is_complex or b.is_bool for b in t.blocks)
+        return (hasattr(bb, 'ctx') and len(t.blocks) > 0 and not any(b.is_bool for b in t.blocks)
                 and type(bb).__name__ != 'DeferredBlockBackend')
 
     # -- pools
-    def _alloc(self, zero):
+    def _alloc(self, zero, cplx=None):
         bb = self.bb
-        buf = bb.ctx.empty(self.total)
+        cplx = self.cplx if cplx is None else cplx
+        buf = bb.ctx.empty(self.total, 'complex128' if cplx else 'float64')
         if zero:
             bb.ctx.sync_stream()
-            self._lib.check(bb.lib.cyb_memset(bb.ctx.handle, self._C.c_void_p(buf.data_ptr()), 0, 8 * self.total))
+            self._lib.check(bb.lib.cyb_memset(bb.ctx.handle, self._C.c_void_p(buf.data_ptr()), 0, buf.element_size() * self.total))
         return buf
 
     def _views(self, buf, which=None):
@@ -182,7 +241,9 @@ class _FlatOps:
         return [mk(bb, buf, self.offs[i], self.shapes[i], self.strides[i], True) for i in idx]
 
     def enter(self, t):
-        """tensor -> pool (one memset + one batched copy)."""
+        """tensor -> pool (one memset + one batched copy); a real tensor enters a complex pool as its real plane."""
+        if not self.cplx and any(b.is_complex for b in t.blocks):
+            raise _NeedComplex()
         buf = self._alloc(True)
         if t.block_inds.tobytes() == self.key:
             which = None
@@ -194,10 +255,10 @@ class _FlatOps:
             except KeyError:
                 raise _NotFlat()
         views = self._views(buf, which)
-        if any(v.shape != tuple(b.shape) or b.is_complex for v, b in zip(views, t.blocks)):
+        if any(v.shape != tuple(b.shape) for v, b in zip(views, t.blocks)):
             raise _NotFlat()
         self.support.update(range(len(self.offs)) if which is None else which)
-        self.bb.copy_many(list(zip(views, t.blocks)))
+        self.bb.copy_many([(v if b.is_complex or not self.cplx else self.bb._plane(v, 0), b) for v, b in zip(views, t.blocks)])
         return buf
 
     def leave(self, buf):
@@ -211,43 +272,101 @@ class _FlatOps:
         return self.enter(self.H.matvec(self.leave(buf)))
 
     # -- BLAS-1 over the flat range
-    def _desc(self, x, y, out):
+    def _desc(self, x, y, out, n=None):
         arr = np.zeros(1, dtype=self._lib.VEC_DTYPE)
         arr['x'][0] = x.data_ptr()
         arr['y'][0] = y.data_ptr() if y is not None else 0
         arr['out'][0] = out.data_ptr() if out is not None else 0
-        arr['n'][0] = self.total
+        arr['n'][0] = self.total if n is None else n
         return arr
 
-    def lincomb(self, a, w, b, v):
+    def _call(self, name, arr, *args):
         bb = self.bb
-        out = self._alloc(False)
-        arr = self._desc(w, v, out)
         bb.ctx.sync_stream()
-        self._lib.check(bb.lib.cyb_axpby_batched_f64(bb.ctx.handle, arr.ctypes.data_as(self._C.POINTER(self._lib.VecDesc)), 1,
-                                                     float(a), float(b)))
+        self._lib.check(getattr(bb.lib, name)(bb.ctx.handle, arr.ctypes.data_as(self._C.POINTER(self._lib.VecDesc)), 1, *args))
+
+    def combine(self, coeffs, vecs, acc=None):
+        """acc + sum_k coeffs[k] vecs[k] in ONE launch over the flat range (the result assembly of the solvers).  Complex
+        coefficients or pools: the complex linear combination, float64 pools read as real sources (`src_real`), the
+        result a complex pool; `acc` (a complex pool) is updated in place.  Real throughout: the float64 form."""
+        bb, L = self.bb, self._lib
+        cplx = (any(v.is_complex() for v in vecs) or not all(_is_real_scalar(c) for c in coeffs)
+                or (acc is not None and acc.is_complex()))
+        if acc is not None and acc.is_complex() != cplx:
+            acc = self._promote(acc)
+        out = acc if acc is not None else self._alloc(False, cplx)
+        desc = np.zeros(1, dtype=L.LINCOMB_DTYPE)
+        desc['dst'][0] = out.data_ptr()
+        desc['ndim'][0] = 1
+        desc['accumulate'][0] = 1 if acc is not None else 0
+        desc['term_begin'][0], desc['term_end'][0] = 0, len(vecs)
+        desc['shape'][0, 0] = self.total
+        desc['dst_strides'][0, 0] = 1
+        terms = np.zeros(len(vecs), dtype=L.LINTERM_C128_DTYPE if cplx else L.LINTERM_DTYPE)
+        terms['src'] = [v.data_ptr() for v in vecs]
+        terms['src_strides'][:, 0] = 1
+        if cplx:
+            cs = [complex(c) for c in coeffs]
+            terms['coeff_re'] = [c.real for c in cs]
+            terms['coeff_im'] = [c.imag for c in cs]
+            terms['src_real'] = [0 if v.is_complex() else 1 for v in vecs]
+        else:
+            terms['coeff'] = [float(np.real(c)) for c in coeffs]
+        bb.ctx.sync_stream()
+        fn = bb.lib.cyb_lincomb_strided_batched_c128 if cplx else bb.lib.cyb_lincomb_strided_batched_f64
+        T = L.LincombTermC128 if cplx else L.LincombTerm
+        self._lib.check(fn(bb.ctx.handle, desc.ctypes.data_as(self._C.POINTER(L.LincombDesc)), 1,
+                           terms.ctypes.data_as(self._C.POINTER(T)), len(vecs)))
+        return out
+
+    def _promote(self, w):
+        """complex128 copy of a float64 pool."""
+        return self.combine([1.0 + 0.0j], [w])
+
+    def lincomb(self, a, w, b, v):
+        if w.is_complex() != v.is_complex() or (not w.is_complex() and not (_is_real_scalar(a) and _is_real_scalar(b))):
+            return self.combine([a, b], [w, v])
+        out = self._alloc(False, w.is_complex())
+        if w.is_complex():
+            a, b = complex(a), complex(b)
+            self._call('cyb_axpby_batched_c128', self._desc(w, v, out), a.real, a.imag, b.real, b.imag)
+        else:
+            self._call('cyb_axpby_batched_f64', self._desc(w, v, out), float(np.real(a)), float(np.real(b)))
         return out
 
     def scale(self, a, w):
-        bb = self.bb
-        out = self._alloc(False)
-        arr = self._desc(w, None, out)
-        bb.ctx.sync_stream()
-        self._lib.check(bb.lib.cyb_axpby_batched_f64(bb.ctx.handle, arr.ctypes.data_as(self._C.POINTER(self._lib.VecDesc)), 1,
-                                                     float(a), 0.0))
+        if not w.is_complex() and not _is_real_scalar(a):
+            return self.combine([a], [w])
+        out = self._alloc(False, w.is_complex())
+        if w.is_complex():
+            a = complex(a)
+            self._call('cyb_axpby_batched_c128', self._desc(w, None, out), a.real, a.imag, 0.0, 0.0)
+        else:
+            self._call('cyb_axpby_batched_f64', self._desc(w, None, out), float(np.real(a)), 0.0)
         return out
 
     def inner(self, v, w):
+        """<v, w> = sum conj(v) w: a float on float64 pools, a complex number otherwise (cyb_dot_batched_c128)."""
         bb = self.bb
-        res = bb.ctx.empty(1)
-        arr = self._desc(v, w, None)
-        bb.ctx.sync_stream()
-        self._lib.check(bb.lib.cyb_dot_batched_f64(bb.ctx.handle, arr.ctypes.data_as(self._C.POINTER(self._lib.VecDesc)), 1,
-                                                   self._C.c_void_p(res.data_ptr())))
-        return float(bb.ctx.d2h(res, 1, np.float64)[0])
+        if not v.is_complex() and not w.is_complex():
+            res = bb.ctx.empty(1)
+            self._call('cyb_dot_batched_f64', self._desc(v, w, None), self._C.c_void_p(res.data_ptr()))
+            return float(bb.ctx.d2h(res, 1, np.float64)[0])
+        v = v if v.is_complex() else self._promote(v)
+        w = w if w.is_complex() else self._promote(w)
+        res = bb.ctx.empty(2)
+        self._call('cyb_dot_batched_c128', self._desc(v, w, None), self._C.c_void_p(res.data_ptr()))
+        re, im = bb.ctx.d2h(res, 2, np.float64)
+        return complex(float(re), float(im))
 
     def norm(self, w):
-        return float(np.sqrt(self.inner(w, w)))
+        if not w.is_complex():
+            return float(np.sqrt(self.inner(w, w)))
+        # the float64 reduction over the interleaved storage: sum re^2 + im^2
+        bb = self.bb
+        res = bb.ctx.empty(1)
+        self._call('cyb_dot_batched_f64', self._desc(w, w, None, 2 * self.total), self._C.c_void_p(res.data_ptr()))
+        return float(np.sqrt(bb.ctx.d2h(res, 1, np.float64)[0]))
 
 
 class LanczosGroundState:
@@ -274,6 +393,10 @@ class LanczosGroundState:
             raise ValueError('Should perform at least 2 steps.')
         if self.N_cache < 2:
             raise ValueError('Need to cache at least two vectors.')
+        self._psi0_norm = None
+        self._reset_krylov_state()
+
+    def _reset_krylov_state(self):
         self._h = np.zeros((self.N_max + 1, self.N_max + 1))
         self.Es = np.zeros((self.N_max, self.N_max))
         self._cache = []
@@ -292,33 +415,43 @@ class LanczosGroundState:
             out = V.lincomb(1.0, out, float(self.E_shift), self._cache[-1])
         return out
 
-    def run(self):
-        """The recurrences run on flat pools where the backend allows it (:class:`_FlatOps`); a vector that leaves the
-        block structure of psi0 (an operator that creates blocks psi0 does not have) restarts them on tensors."""
+    def _solve(self, body):
+        """``body()`` with the recurrences on flat pools where the backend allows it (:class:`_FlatOps`): float64 pools
+        while the start vector and the operator are real, complex128 pools otherwise (a complex vector out of the operator
+        restarts the run on them); a vector that leaves the block structure of psi0 (an operator that creates blocks psi0
+        does not have) restarts it on tensors."""
         psi_in = self.psi0
         flat = bool(self.flat) and _FlatOps.usable(self.bb, psi_in)
         # pool structure: every block the charge rule allows on these legs (what an operator can create at most)
         allowed = ab.AbelianTensor.allowed_block_inds(psi_in.symmetry, psi_in.legs) if flat else None
-        for use_flat in ([True, False] if flat else [False]):
-            self.V = _FlatOps(self.bb, self.H, psi_in, allowed) if use_flat else _TensorOps(self.bb, self.H)
-            self._h[:] = 0.0
-            self.Es[:] = 0.0
-            self._cache = []
-            self._result_krylov = np.ones(1)
+        cplx = any(_is_complex_block(b) for b in psi_in.blocks) or bool(getattr(self.H, 'is_complex', False))
+        modes = ([cplx] if cplx else [False, True]) if flat else []
+        modes.append(None)   # tensors
+        i = 0
+        while True:
+            mode = modes[i]
+            self.V = _FlatOps(self.bb, self.H, psi_in, allowed, mode) if mode is not None else _TensorOps(self.bb, self.H)
+            self._reset_krylov_state()
             try:
                 self.psi0 = self.V.enter(psi_in)
-                N = self._build_krylov()
-                E0 = float(self.Es[N - 1, 0])
-                if self.E_shift is not None:
-                    E0 -= float(self.E_shift)
-                if N == 1:
-                    return E0, self.V.leave(self.psi0), N
-                return E0, self.V.leave(self._calc_result_full(N)), N
+                return body()
+            except _NeedComplex:
+                i += 1
             except _NotFlat:
-                continue
+                i = len(modes) - 1
             finally:
                 self.psi0 = psi_in     # (the working copy is a pool buffer: a second run() starts from the caller's tensor again)
-        raise RuntimeError('unreachable')
+
+    def run(self):
+        def body():
+            N = self._build_krylov()
+            E0 = float(self.Es[N - 1, 0])
+            if self.E_shift is not None:
+                E0 -= float(self.E_shift)
+            if N == 1:
+                return E0, self.V.leave(self.psi0), N
+            return E0, self.V.leave(self._calc_result_full(N)), N
+        return self._solve(body)
 
     def _build_krylov(self):
         V = self.V
@@ -327,6 +460,8 @@ class LanczosGroundState:
         if beta < self.cutoff:
             raise ValueError(f'Norm of self.psi0 too small: {beta}')
         self.psi0 = V.scale(1.0 / beta, w)
+        if self._psi0_norm is None:     # (only LanczosEvolution uses it, krylov_based.cpp:851-854)
+            self._psi0_norm = beta
         performed = 0
         for k in range(self.N_max):
             w = V.scale(1.0 / beta, w)
@@ -400,10 +535,246 @@ class LanczosGroundState:
                 w = V.lincomb(1.0, w, -beta, self._cache[-2])
             beta = self._h[k, k + 1]
             w = V.scale(1.0 / beta, w)
-            psif = V.lincomb(1.0, psif, float(vf[k + 1]), w)
+            psif = self._add_to_result(psif, vf[k + 1], w)
         return psif
+
+    def _add_to_result(self, psif, c, w):
+        return self.V.lincomb(1.0, psif, float(c), w)
 
 
 def lanczos(bb, H, psi, options=None):
     """(E0, psi0, N) -- krylov_based.cpp:1022-1025."""
     return LanczosGroundState(bb, H, psi, options).run()
+
+
+class LanczosEvolution(LanczosGroundState):
+    """exp(delta H) psi0 for a Hermitian ``H`` by Lanczos (krylov_based.cpp:948-1019): the Krylov recurrences of
+    :class:`LanczosGroundState` (real tridiagonal matrix), the small problem solved as exp(delta E) in the eigenbasis of
+    that matrix, converged when the last Krylov coefficient is below P_tol.  With a real ``H`` and a real psi0 the Krylov
+    vectors stay float64 whatever delta; the complex coefficients only enter the result assembly."""
+
+    def __init__(self, bb, H, psi0, options=None):
+        super().__init__(bb, H, psi0, options)
+        self._result_norm = 1.0
+        self.delta = None
+
+    def run(self, delta, normalize=None):
+        """(psi, N).  `normalize` (default: delta.real == 0): return the normalised state, else the state scaled by
+        |psi0| times the norm of the Krylov result, i.e. exp(delta H) psi0 itself."""
+        self.delta = delta
+        do_normalize = (complex(delta).real == 0.0) if normalize is None else bool(normalize)
+
+        def body():
+            V = self.V
+            N = self._build_krylov()
+            if N == 1:
+                res = V.scale(self._result_krylov[0], self.psi0)    # (a phase)
+            else:
+                res = self._calc_result_full(N)
+            if not do_normalize:
+                res = V.scale((1.0 if self._psi0_norm is None else self._psi0_norm) * self._result_norm, res)
+            return V.leave(res), N
+        return self._solve(body)
+
+    def _calc_result_krylov(self, k):
+        d = self.delta
+        if k == 0:
+            e = np.exp(d * self._h[0, 0])
+            self._result_norm = float(abs(e))
+            self._result_krylov = np.array([e / self._result_norm])
+            return
+        n = k + 1
+        E_kr, v_kr = np.linalg.eigh(self._h[:n, :n])
+        r = v_kr @ (np.exp(E_kr * d) * np.conj(v_kr[0]))
+        self._result_norm = float(np.linalg.norm(r))
+        self._result_krylov = r / self._result_norm
+
+    def _converged(self, k):
+        return abs(self._result_krylov[k]) < self.P_tol
+
+    def _calc_result_full(self, N):
+        """sum_k c_k v_k as ONE combination of psi0 and the cached vectors (krylov_based.cpp:310-341), the vectors that
+        fell out of the cache regenerated and added one at a time."""
+        V = self.V
+        vf = self._result_krylov
+        if not (N == len(vf) and len(vf) > 1):
+            raise RuntimeError('KrylovBased._calc_result_full: expected N == len(vf) > 1')
+        len_cache = len(self._cache)
+        n_loop = min(len_cache + 1, N)
+        psif = V.combine([vf[0]] + [vf[N - k] for k in range(1, n_loop)],
+                         [self.psi0] + [self._cache[len_cache - k] for k in range(1, n_loop)])
+        self._cache = []
+        psif = self._rebuild_krylov_for_result_full(psif, N - len_cache - 1)
+        nrm = V.norm(psif)
+        return V.scale(1.0 / nrm, psif)
+
+    def _add_to_result(self, psif, c, w):
+        return self.V.combine([c], [w], acc=psif)
+
+
+def argsort_which(values, which):
+    """Order of Ritz values by the reference's `which` names and aliases (krylov_based.cpp:166-195)."""
+    v = np.asarray(values, dtype=np.complex128)
+    if which in ('LM', 'm>'):
+        key = -np.abs(v)
+    elif which in ('SM', 'm<'):
+        key = np.abs(v)
+    elif which in ('LR', '>', 'LA'):
+        key = -v.real
+    elif which in ('SR', '<', 'SA'):
+        key = v.real
+    elif which == 'LI':
+        key = -v.imag
+    elif which == 'SI':
+        key = v.imag
+    else:
+        key = v.real
+    return np.argsort(key, kind='stable')
+
+
+class Arnoldi(LanczosGroundState):
+    """Arnoldi for eigenvalues of a general (non-Hermitian) ``H`` (krylov_based.cpp:532-695): complex Hessenberg matrix,
+    modified Gram-Schmidt against every cached vector in the reference's order, Ritz pairs from numpy.linalg.eig sorted
+    by `which`.  Options beyond LanczosGroundState's: which='LM', num_ev=1, E_tol=inf; requires N_cache >= N_max."""
+
+    def __init__(self, bb, H, psi0, options=None):
+        o = dict(options or {})
+        super().__init__(bb, H, psi0, o)
+        self.which = str(o.get('which', 'LM'))
+        self.num_ev = int(o.get('num_ev', 1))
+
+    def _reset_krylov_state(self):
+        self._h = np.zeros((self.N_max + 1, self.N_max + 1), dtype=np.complex128)
+        self.Es = np.zeros((self.N_max, self.N_max), dtype=np.complex128)
+        self._cache = []
+        self._result_krylov = np.ones((1, 1), dtype=np.complex128)
+
+    def _to_cache(self, w):
+        self._cache.append(w)
+        if len(self._cache) > self.N_cache:
+            raise RuntimeError('Arnoldi cache exceeded N_cache')
+
+    def run(self):
+        """(Es, psis, N): the first num_ev Ritz values in `which` order and their normalised Ritz vectors."""
+        if self.N_cache < self.N_max:
+            raise ValueError('Arnoldi requires N_cache >= N_max')
+
+        def body():
+            N = self._build_krylov()
+            E0 = [complex(self.Es[N - 1, i]) for i in range(self.num_ev)]
+            if self.E_shift is not None:
+                E0 = [e - self.E_shift for e in E0]
+            if N == 1:
+                return E0, [self.V.leave(self.psi0)], N
+            return E0, [self.V.leave(p) for p in self._calc_result_full_multi(N)], N
+        return self._solve(body)
+
+    def _build_krylov(self):
+        V = self.V
+        w = self.psi0
+        w_norm = V.norm(w)
+        self.psi0 = V.scale(1.0 / w_norm, w)
+        performed = 0
+        for k in range(self.N_max):
+            w = V.scale(1.0 / w_norm, w)
+            self._to_cache(w)
+            w = self._matvec(w)
+            for i, v in enumerate(self._cache):
+                ov = V.inner(v, w)
+                self._h[i, k] = ov
+                w = V.lincomb(1.0, w, -ov, v)
+            w_norm = V.norm(w)
+            self._h[k + 1, k] = w_norm
+            self._calc_result_krylov(k)
+            performed = k + 1
+            if w_norm < self.cutoff or (k + 1 >= self.N_min and self._converged(k)):
+                break
+        return performed
+
+    def _calc_result_krylov(self, k):
+        if k == 0:
+            self.Es[0, 0] = self._h[0, 0]
+            self._result_krylov = np.ones((1, 1), dtype=np.complex128)
+            return
+        n = k + 1
+        E_kr, v_kr = np.linalg.eig(self._h[:n, :n])
+        order = argsort_which(E_kr, self.which)
+        self.Es[k, :n] = E_kr[order]
+        self._result_krylov = v_kr[:, order]
+
+    def _converged(self, k):
+        v0k = self._result_krylov[k, 0]
+        ritz_res = abs(v0k) * abs(self._h[k + 1, k])
+        min_diff = np.inf
+        for i in range(self.num_ev):
+            d = np.abs(self.Es[k, i + 1:self.N_max] - self.Es[k, i])
+            min_diff = min(min_diff, float(d.min()) if len(d) else np.inf)
+        gap = max(min_diff, self.min_gap)
+        P_err = (ritz_res / gap) ** 2
+        Delta_E0 = self.Es[k - 1, 0] - self.Es[k, 0]
+        return P_err < self.P_tol and Delta_E0.real < self.E_tol
+
+    def _calc_result_full_multi(self, N):
+        V = self.V
+        if len(self._cache) < N:
+            raise RuntimeError('Arnoldi._calc_result_full: Krylov basis shorter than N')
+        psis = []
+        for i in range(min(N, self.num_ev)):
+            # real_if_close: the dominant eigenvector of a real operator stays real (the power-method answer)
+            vf = np.real_if_close(self._result_krylov[:N, i])
+            psi = V.combine(list(vf), self._cache[:N])
+            psis.append(V.scale(1.0 / V.norm(psi), psi))
+        return psis
+
+
+class ArnoldiEvolution(Arnoldi):
+    """exp(delta H) psi0 for a general ``H`` by Arnoldi (krylov_based.cpp:697-800): the small problem solved through
+    numpy.linalg.eig and a linear solve for the start vector's coefficients; converged when the last Krylov coefficient is
+    below P_tol.  `normalize` defaults to False."""
+
+    def __init__(self, bb, H, psi0, options=None):
+        super().__init__(bb, H, psi0, options)
+        self._result_norm = 1.0
+        self.delta = None
+        self._psi0_norm = ab.norm(bb, psi0)     # (Arnoldi._build_krylov does not record it)
+
+    def run(self, delta, normalize=None):
+        if self.N_cache < self.N_max:
+            raise ValueError('ArnoldiEvolution requires N_cache >= N_max')
+        self.delta = delta
+        do_normalize = False if normalize is None else bool(normalize)
+
+        def body():
+            V = self.V
+            N = self._build_krylov()
+            res = V.scale(self._result_krylov[0], self.psi0) if N == 1 else self._calc_result_full_evolution(N)
+            if not do_normalize:
+                res = V.scale(self._psi0_norm * self._result_norm, res)
+            return V.leave(res), N
+        return self._solve(body)
+
+    def _calc_result_krylov(self, k):
+        d = self.delta
+        if k == 0:
+            e = np.exp(d * self._h[0, 0])
+            self._result_norm = float(abs(e))
+            self._result_krylov = np.array([e / self._result_norm])
+            return
+        n = k + 1
+        E_kr, v_kr = np.linalg.eig(self._h[:n, :n])
+        e0 = np.zeros(n, dtype=np.complex128)
+        e0[0] = 1.0
+        coeff = np.linalg.solve(v_kr, e0)
+        r = v_kr @ (np.exp(E_kr * d) * coeff)
+        self._result_norm = float(np.linalg.norm(r))
+        self._result_krylov = r / self._result_norm
+
+    def _converged(self, k):
+        return abs(self._result_krylov[k]) < self.P_tol
+
+    def _calc_result_full_evolution(self, N):
+        V = self.V
+        if len(self._cache) < N:
+            raise RuntimeError('ArnoldiEvolution: Krylov basis shorter than N')
+        psif = V.combine(list(self._result_krylov[:N]), self._cache[:N])
+        return V.scale(1.0 / V.norm(psif), psif)

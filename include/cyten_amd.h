@@ -333,6 +333,10 @@ int cyb_complex_expand_batched_f64(cyb_ctx_t ctx, const cyb_cexpand_desc* descs,
 int cyb_elementwise_batched_c128(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t n, int32_t op);
 int cyb_axpby_batched_c128(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t n,
                            double a_re, double a_im, double b_re, double b_im);
+/* result_dev[0] = re, result_dev[1] = im of sum over all list entries of sum_i conj(x_i) * y_i; x, y interleaved
+ * complex, desc.n counts complex elements (`out` unused).  Deterministic two-stage reduction: bit-identical from run to
+ * run.  The inner product of complex Krylov vectors and of complex block lists (abelian.cpp:2159-2211). */
+int cyb_dot_batched_c128(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t n, double* result_dev);
 
 /* ---- host-side sector matching of a contraction (no device work) ------------------------------------------------
  * The int64 bookkeeping of abelian_compose_worker (src/backends/abelian.cpp:1239-1469) in C++, as in the reference:
