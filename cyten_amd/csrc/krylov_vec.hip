@@ -169,3 +169,374 @@ int cyb_dot_batched_c128(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t n, do
 }
 
 } // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Projections against a list of basis vectors: multi-dot, multi-axpy and the fused classical Gram-Schmidt step of GMRES
+// (krylov_based.cpp:453-469) and of the projected operator (sparse.cpp:294-327).
+//
+// One kernel template serves all three.  The grid and the row range of every workgroup depend on (n, m) only: workgroup g
+// owns the tiles [g * tpg, (g + 1) * tpg) of TS = 64 * EL elements.  Inside a tile the four waves split the basis (wave q
+// takes j = q, q + 4, ...) and hold their V rows in registers, so the update w + alpha sum_j h_j V_j (summed per wave, then
+// over the waves in a fixed order through LDS) and the partial dots of the updated w read V from HBM once.  Partials go to
+// a (workgroup, j) table that a second kernel sums in a fixed order: no float atomics, bit-identical from run to run.
+// CGS with passes = 2 is three such sweeps, dot / update+dot / update+norm: (3m + 5) n words.
+namespace {
+
+constexpr int GS_MAX_M = 64;
+constexpr int GS_WAVES = 4;
+constexpr int GS_MAX_GRID = 2048;
+
+struct BasisPtrs {
+    const double* v[GS_MAX_M];
+};
+
+enum GsMode : int { GS_DOT = 0, GS_UPD_DOT = 1, GS_UPD_NORM = 2, GS_UPD = 3 };
+
+template <bool CPLX> struct GsT;
+template <> struct GsT<false> {
+    typedef double T;
+    static constexpr int EL = 4;
+    static __device__ __forceinline__ T zero() { return 0.0; }
+    static __device__ __forceinline__ void cdot(T v, T w, double& re, double&) { re += v * w; }
+    static __device__ __forceinline__ T madd(T acc, double hre, double, T v) { return acc + hre * v; }
+    static __device__ __forceinline__ T scale(double are, double, T u) { return are * u; }
+    static __device__ __forceinline__ double sq(T w) { return w * w; }
+    static __device__ __forceinline__ T add(T a, T b) { return a + b; }
+};
+template <> struct GsT<true> {
+    typedef d2v T;
+    static constexpr int EL = 2;
+    static __device__ __forceinline__ T zero() { return T{0.0, 0.0}; }
+    static __device__ __forceinline__ void cdot(T v, T w, double& re, double& im)
+    {
+        re += v.x * w.x + v.y * w.y;
+        im += v.x * w.y - v.y * w.x;
+    }
+    static __device__ __forceinline__ T madd(T acc, double hre, double him, T v)
+    {
+        return T{acc.x + (hre * v.x - him * v.y), acc.y + (hre * v.y + him * v.x)};
+    }
+    static __device__ __forceinline__ T scale(double are, double aim, T u) { return T{are * u.x - aim * u.y, are * u.y + aim * u.x}; }
+    static __device__ __forceinline__ double sq(T w) { return w.x * w.x + w.y * w.y; }
+    static __device__ __forceinline__ T add(T a, T b) { return T{a.x + b.x, a.y + b.y}; }
+};
+
+// partial[(g * (m + 1) + j) * 2 + {0, 1}]: (re, im) of the workgroup's partial dot with V_j (j < m) or its partial |w|^2
+// (j == m).  coef: m (real) or 2m (interleaved complex) device doubles, scaled by alpha in the update.
+template <bool CPLX, int J, int MODE>
+__global__ void __launch_bounds__(64 * GS_WAVES) gs_sweep_kernel(BasisPtrs P, int m, double* __restrict__ w_, int64_t n, int64_t tpg,
+                                                                const double* __restrict__ coef, double are, double aim,
+                                                                double* __restrict__ partial)
+{
+    typedef GsT<CPLX> O;
+    typedef typename O::T T;
+    constexpr int EL = O::EL;
+    constexpr int TS = 64 * EL;
+    constexpr bool UPD = MODE != GS_DOT;
+    constexpr bool DOT = MODE == GS_DOT || MODE == GS_UPD_DOT;
+    __shared__ T red[GS_WAVES][EL][64];
+    T* __restrict__ w = reinterpret_cast<T*>(w_);
+    const int lane = threadIdx.x & 63;
+    const int q = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    double hre[J], him[J], dre[J], dim[J];
+#pragma unroll
+    for (int jj = 0; jj < J; ++jj) {
+        const int j = q + GS_WAVES * jj;
+        hre[jj] = him[jj] = dre[jj] = dim[jj] = 0.0;
+        if (UPD && j < m) {
+            hre[jj] = CPLX ? coef[2 * j] : coef[j];
+            him[jj] = CPLX ? coef[2 * j + 1] : 0.0;
+        }
+    }
+    double nrm = 0.0;
+    const int64_t t_end = min(((int64_t)blockIdx.x + 1) * tpg, (n + TS - 1) / TS);
+    for (int64_t t = (int64_t)blockIdx.x * tpg; t < t_end; ++t) {
+        const int64_t base = t * TS + lane;
+        T vr[J][EL];
+#pragma unroll
+        for (int jj = 0; jj < J; ++jj) {
+            const int j = q + GS_WAVES * jj;
+            const T* __restrict__ v = reinterpret_cast<const T*>(j < m ? P.v[j] : nullptr);
+#pragma unroll
+            for (int e = 0; e < EL; ++e) {
+                const int64_t i = base + 64 * e;
+                vr[jj][e] = (j < m && i < n) ? v[i] : O::zero();
+            }
+        }
+        T wr[EL];
+#pragma unroll
+        for (int e = 0; e < EL; ++e) {
+            const int64_t i = base + 64 * e;
+            wr[e] = i < n ? w[i] : O::zero();
+        }
+        if (UPD) {
+#pragma unroll
+            for (int e = 0; e < EL; ++e) {
+                T u = O::zero();
+#pragma unroll
+                for (int jj = 0; jj < J; ++jj) u = O::madd(u, hre[jj], him[jj], vr[jj][e]);
+                red[q][e][lane] = u;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int e = 0; e < EL; ++e) {
+                const T u = O::add(O::add(red[0][e][lane], red[1][e][lane]), O::add(red[2][e][lane], red[3][e][lane]));
+                wr[e] = O::add(wr[e], O::scale(are, aim, u));
+                const int64_t i = base + 64 * e;
+                if (q == 0 && i < n) w[i] = wr[e];
+            }
+            __syncthreads(); // (red is refilled by the next tile)
+        }
+        if (DOT) {
+#pragma unroll
+            for (int jj = 0; jj < J; ++jj)
+#pragma unroll
+                for (int e = 0; e < EL; ++e) O::cdot(vr[jj][e], wr[e], dre[jj], dim[jj]);
+        }
+        if (MODE == GS_UPD_NORM && q == 0) {
+#pragma unroll
+            for (int e = 0; e < EL; ++e) nrm += O::sq(wr[e]);
+        }
+    }
+    double* out = partial + (int64_t)blockIdx.x * (m + 1) * 2;
+    if (DOT) {
+#pragma unroll
+        for (int jj = 0; jj < J; ++jj) {
+            const int j = q + GS_WAVES * jj;
+            const double r = wave_sum(dre[jj]);
+            const double s = CPLX ? wave_sum(dim[jj]) : 0.0;
+            if (lane == 0 && j < m) {
+                out[2 * j] = r;
+                out[2 * j + 1] = s;
+            }
+        }
+    }
+    if (MODE == GS_UPD_NORM && q == 0) {
+        const double r = wave_sum(nrm);
+        if (lane == 0) {
+            out[2 * m] = r;
+            out[2 * m + 1] = 0.0;
+        }
+    }
+}
+
+// Sums the partial table over the n_groups workgroups in a fixed order, one workgroup per column c in [c0, c0 + gridDim.x).
+// Columns j < m: coef_out[j] = the sum (the coefficients of the next sweep) and, with `add`, sum_out[j] = add[j] + sum (the
+// CGS2 coefficients of both passes); real results take one double each, complex two.  Column m: norm_out = sqrt(sum).
+__global__ void __launch_bounds__(NT) gs_reduce_kernel(const double* __restrict__ partial, int64_t n_groups, int m, int cplx, int c0,
+                                                       double* __restrict__ coef_out, const double* __restrict__ add,
+                                                       double* __restrict__ sum_out, double* __restrict__ norm_out)
+{
+    __shared__ double red[2][NT / 64];
+    const int c = c0 + blockIdx.x;
+    double re = 0.0, im = 0.0;
+    for (int64_t g = threadIdx.x; g < n_groups; g += NT) {
+        re += partial[(g * (m + 1) + c) * 2];
+        im += partial[(g * (m + 1) + c) * 2 + 1];
+    }
+    re = wave_sum(re);
+    im = wave_sum(im);
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = re;
+        red[1][threadIdx.x >> 6] = im;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double r = red[0][0], s = red[1][0];
+    for (int k = 1; k < NT / 64; ++k) {
+        r += red[0][k];
+        s += red[1][k];
+    }
+    if (c == m) {
+        norm_out[0] = sqrt(r);
+        return;
+    }
+    if (cplx) {
+        if (coef_out) {
+            coef_out[2 * c] = r;
+            coef_out[2 * c + 1] = s;
+        }
+        if (add) {
+            sum_out[2 * c] = add[2 * c] + r;
+            sum_out[2 * c + 1] = add[2 * c + 1] + s;
+        }
+    } else {
+        if (coef_out) coef_out[c] = r;
+        if (add) sum_out[c] = add[c] + r;
+    }
+}
+
+struct GsGrid {
+    int64_t groups, tpg;
+};
+
+static GsGrid gs_grid(int64_t n, bool cplx)
+{
+    const int64_t ts = 64 * (cplx ? GsT<true>::EL : GsT<false>::EL);
+    const int64_t tiles = cdiv64(n, ts);
+    const int64_t tpg = std::max<int64_t>(1, cdiv64(tiles, GS_MAX_GRID));
+    return GsGrid{cdiv64(tiles, tpg), tpg};
+}
+
+template <bool CPLX, int MODE>
+static void gs_launch_j(int J, const GsGrid& g, hipStream_t s, const BasisPtrs& P, int m, double* w, int64_t n, const double* coef,
+                        double are, double aim, double* partial)
+{
+    const dim3 grid((unsigned)g.groups), block(64 * GS_WAVES);
+#define GS_CASE(JJ)                                                                                                    \
+    case JJ: hipLaunchKernelGGL((gs_sweep_kernel<CPLX, JJ, MODE>), grid, block, 0, s, P, m, w, n, g.tpg, coef, are, aim, partial); break;
+    switch (J) {
+        GS_CASE(1)
+        GS_CASE(2)
+        GS_CASE(4)
+        GS_CASE(8)
+        default: GS_CASE(16)
+    }
+#undef GS_CASE
+}
+
+template <bool CPLX>
+static void gs_sweep(int mode, const GsGrid& g, hipStream_t s, const BasisPtrs& P, int m, double* w, int64_t n, const double* coef,
+                     double are, double aim, double* partial)
+{
+    if (g.groups == 0) return;
+    int J = 1;
+    while (J * GS_WAVES < m) J *= 2;
+    switch (mode) {
+    case GS_DOT: gs_launch_j<CPLX, GS_DOT>(J, g, s, P, m, w, n, coef, are, aim, partial); break;
+    case GS_UPD_DOT: gs_launch_j<CPLX, GS_UPD_DOT>(J, g, s, P, m, w, n, coef, are, aim, partial); break;
+    case GS_UPD_NORM: gs_launch_j<CPLX, GS_UPD_NORM>(J, g, s, P, m, w, n, coef, are, aim, partial); break;
+    default: gs_launch_j<CPLX, GS_UPD>(J, g, s, P, m, w, n, coef, are, aim, partial); break;
+    }
+}
+
+static int gs_args(const char* fn, const double* const* basis, int64_t m, const void* w, int64_t n, bool cplx, BasisPtrs* P)
+{
+    if (m > GS_MAX_M) {
+        cyb::set_error("%s: %lld basis vectors, at most %d are supported", fn, (long long)m, GS_MAX_M);
+        return CYB_ERR_UNSUPPORTED;
+    }
+    CYB_REQUIRE(m >= 0 && n >= 0, "%s: negative size", fn);
+    CYB_REQUIRE(m == 0 || basis, "%s: NULL basis list", fn);
+    const uintptr_t align = cplx ? 16 : 8;
+    CYB_REQUIRE(n == 0 || (w && (uintptr_t)w % align == 0), "%s: NULL or misaligned vector", fn);
+    for (int64_t j = 0; j < m; ++j) {
+        CYB_REQUIRE(n == 0 || (basis[j] && (uintptr_t)basis[j] % align == 0), "%s: basis vector %lld NULL or misaligned", fn, (long long)j);
+        P->v[j] = basis[j];
+    }
+    for (int64_t j = m; j < GS_MAX_M; ++j) P->v[j] = nullptr;
+    return CYB_OK;
+}
+
+// partial table of one sweep + (for CGS2) the pass-1 and pass-2 coefficients, in workspace slot 0
+static int gs_workspace(cyb_ctx_t ctx, const GsGrid& g, int64_t m, double** partial, double** h1, double** h2)
+{
+    const size_t np = (size_t)std::max<int64_t>(g.groups, 1) * (size_t)(m + 1) * 2;
+    void* ws = nullptr;
+    CYB_TRY(ctx->workspace(sizeof(double) * (np + 4 * GS_MAX_M), &ws));
+    *partial = static_cast<double*>(ws);
+    *h1 = *partial + np;
+    *h2 = *h1 + 2 * GS_MAX_M;
+    return CYB_OK;
+}
+
+template <bool CPLX>
+static int gram_schmidt(const char* fn, cyb_ctx_t ctx, const double* const* basis, int64_t m, double* w, int64_t n, int32_t passes,
+                        double* out_dev)
+{
+    CYB_REQUIRE(ctx && out_dev, "%s: NULL argument", fn);
+    BasisPtrs P;
+    CYB_TRY(gs_args(fn, basis, m, w, n, CPLX, &P));
+    CYB_REQUIRE(passes == 1 || passes == 2, "%s: passes must be 1 or 2, got %d", fn, (int)passes);
+    const GsGrid g = gs_grid(n, CPLX);
+    double *partial, *h1, *h2;
+    CYB_TRY(gs_workspace(ctx, g, m, &partial, &h1, &h2));
+    const int mi = (int)m, c = CPLX ? 1 : 0;
+    const hipStream_t s = ctx->stream;
+    double* norm_out = out_dev + (CPLX ? 2 : 1) * m;
+    // pass 1: h1 = V^H w (straight into out_dev for one pass)
+    double* hp1 = passes == 1 ? out_dev : h1;
+    if (m > 0) {
+        gs_sweep<CPLX>(GS_DOT, g, s, P, mi, w, n, nullptr, 0.0, 0.0, partial);
+        hipLaunchKernelGGL(gs_reduce_kernel, dim3((unsigned)m), dim3(NT), 0, s, partial, g.groups, mi, c, 0, hp1, nullptr, nullptr, nullptr);
+    }
+    const double* last = hp1;
+    if (passes == 2 && m > 0) { // w -= V h1, h2 = V^H w; out = h1 + h2
+        gs_sweep<CPLX>(GS_UPD_DOT, g, s, P, mi, w, n, hp1, -1.0, 0.0, partial);
+        hipLaunchKernelGGL(gs_reduce_kernel, dim3((unsigned)m), dim3(NT), 0, s, partial, g.groups, mi, c, 0, h2, hp1, out_dev, nullptr);
+        last = h2;
+    }
+    // w -= V h_last, |w|
+    gs_sweep<CPLX>(GS_UPD_NORM, g, s, P, mi, w, n, m > 0 ? last : nullptr, -1.0, 0.0, partial);
+    hipLaunchKernelGGL(gs_reduce_kernel, dim3(1), dim3(NT), 0, s, partial, g.groups, mi, c, mi, nullptr, nullptr, nullptr, norm_out);
+    CYB_HIP(hipGetLastError());
+    return CYB_OK;
+}
+
+template <bool CPLX>
+static int multi_dot(const char* fn, cyb_ctx_t ctx, const double* const* basis, int64_t m, const double* w, int64_t n, double* h_dev)
+{
+    CYB_REQUIRE(ctx && (m == 0 || h_dev), "%s: NULL argument", fn);
+    BasisPtrs P;
+    CYB_TRY(gs_args(fn, basis, m, w, n, CPLX, &P));
+    if (m == 0) return CYB_OK;
+    const GsGrid g = gs_grid(n, CPLX);
+    double *partial, *h1, *h2;
+    CYB_TRY(gs_workspace(ctx, g, m, &partial, &h1, &h2));
+    gs_sweep<CPLX>(GS_DOT, g, ctx->stream, P, (int)m, const_cast<double*>(w), n, nullptr, 0.0, 0.0, partial);
+    hipLaunchKernelGGL(gs_reduce_kernel, dim3((unsigned)m), dim3(NT), 0, ctx->stream, partial, g.groups, (int)m, CPLX ? 1 : 0, 0, h_dev,
+                       nullptr, nullptr, nullptr);
+    CYB_HIP(hipGetLastError());
+    return CYB_OK;
+}
+
+template <bool CPLX>
+static int multi_axpy(const char* fn, cyb_ctx_t ctx, const double* const* basis, int64_t m, const double* h_dev, double are, double aim,
+                      double* w, int64_t n)
+{
+    CYB_REQUIRE(ctx && (m == 0 || n == 0 || h_dev), "%s: NULL argument", fn);
+    BasisPtrs P;
+    CYB_TRY(gs_args(fn, basis, m, w, n, CPLX, &P));
+    if (m == 0 || n == 0) return CYB_OK;
+    const GsGrid g = gs_grid(n, CPLX);
+    gs_sweep<CPLX>(GS_UPD, g, ctx->stream, P, (int)m, w, n, h_dev, are, aim, nullptr);
+    CYB_HIP(hipGetLastError());
+    return CYB_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int cyb_gram_schmidt_f64(cyb_ctx_t ctx, const double* const* basis, int64_t m, double* w, int64_t n, int32_t passes, double* out_dev)
+{
+    return gram_schmidt<false>("cyb_gram_schmidt_f64", ctx, basis, m, w, n, passes, out_dev);
+}
+
+int cyb_gram_schmidt_c128(cyb_ctx_t ctx, const double* const* basis, int64_t m, double* w, int64_t n, int32_t passes, double* out_dev)
+{
+    return gram_schmidt<true>("cyb_gram_schmidt_c128", ctx, basis, m, w, n, passes, out_dev);
+}
+
+int cyb_multi_dot_f64(cyb_ctx_t ctx, const double* const* basis, int64_t m, const double* w, int64_t n, double* h_dev)
+{
+    return multi_dot<false>("cyb_multi_dot_f64", ctx, basis, m, w, n, h_dev);
+}
+
+int cyb_multi_dot_c128(cyb_ctx_t ctx, const double* const* basis, int64_t m, const double* w, int64_t n, double* h_dev)
+{
+    return multi_dot<true>("cyb_multi_dot_c128", ctx, basis, m, w, n, h_dev);
+}
+
+int cyb_multi_axpy_f64(cyb_ctx_t ctx, const double* const* basis, int64_t m, const double* h_dev, double alpha, double* w, int64_t n)
+{
+    return multi_axpy<false>("cyb_multi_axpy_f64", ctx, basis, m, h_dev, alpha, 0.0, w, n);
+}
+
+int cyb_multi_axpy_c128(cyb_ctx_t ctx, const double* const* basis, int64_t m, const double* h_dev, double alpha_re, double alpha_im,
+                        double* w, int64_t n)
+{
+    return multi_axpy<true>("cyb_multi_axpy_c128", ctx, basis, m, h_dev, alpha_re, alpha_im, w, n);
+}
+
+} // extern "C"

@@ -179,6 +179,11 @@ class _TensorOps:
             out = self.scale(c, v) if out is None else self.lincomb(1.0, out, c, v)
         return out
 
+    def project_out(self, basis, w, passes=2):
+        """(w - sum_j h_j basis_j, h, |w|) by the reference's modified Gram-Schmidt loop (krylov_based.cpp:458-465): one pass,
+        each coefficient taken against the vector the earlier ones left (`passes` concerns the fused step of the pools)."""
+        return _mgs(self, basis, w)
+
 
 class _FlatOps:
     """The same operations on Krylov vectors kept as ONE contiguous pool each: the block offsets of
@@ -269,7 +274,109 @@ class _FlatOps:
         return ab.AbelianTensor(t.symmetry, t.legs, self._views(buf, idx), self.block_inds[idx], t.num_codomain, t.labels)
 
     def matvec(self, buf):
-        return self.enter(self.H.matvec(self.leave(buf)))
+        return self._apply(self.H, buf)
+
+    def _apply(self, op, buf):
+        """op(buf) on the pools.  The wrappers of cyten_amd.sparse do their vector work here: a shift is one axpby, a sum
+        one combine, a projection runs on the device with its coefficients kept there (no host synchronisation); anything
+        else sees tensors."""
+        from . import sparse
+        if isinstance(op, sparse.ShiftedLinearOperator):
+            return self.lincomb(1.0, self._apply(op.original_operator, buf), sparse._plain(op.shift), buf)
+        if isinstance(op, sparse.SumLinearOperator):
+            terms = [self._apply(o, buf) for o in [op.original_operator] + op.more_operators]
+            return self.combine([1.0] * len(terms), terms)
+        if isinstance(op, sparse.ProjectedLinearOperator):
+            return self._projected(op, buf)
+        if type(op) is sparse.LinearOperatorWrapper:
+            return self._apply(op.original_operator, buf)
+        return self.enter(op.matvec(self.leave(buf)))
+
+    def _ortho_pools(self, op):
+        """The ortho vectors of a projected operator as pools of this run (entered once)."""
+        if not hasattr(self, '_ortho'):
+            self._ortho = {}
+        got = self._ortho.get(id(op))
+        if got is None or got[0] is not op:
+            got = (op, [self.enter(o) for o in op.ortho_vecs])
+            self._ortho[id(op)] = got
+        return got[1]
+
+    def _projected(self, op, buf):
+        """The sequential projection of sparse.cpp:294-327 on the pools: every coefficient stays in device memory, each
+        projection is one m = 1 Gram-Schmidt launch sequence in the reference's order, the penalty one multi-axpy per vector
+        (m = 1: the reference's order) or, for project_operator=False, one multi-dot and one multi-axpy over all of them."""
+        O = self._ortho_pools(op)
+        cplx = self.cplx
+        if any(o.is_complex() != cplx for o in O) or buf.is_complex() != cplx:
+            raise _NeedComplex()
+        m, stride = len(O), (3 if cplx else 2)
+        coef = self.bb.ctx.empty(max(m, 1) * stride)
+        res = self.scale(1.0, buf)
+        if op.project_operator:
+            for j, o in enumerate(O):
+                self._gs([o], res, 1, coef, j * stride)
+        elif op.penalty is not None and m:
+            self._multi('dot', O, res, coef)
+        res = self._apply(op.original_operator, res)
+        if res.is_complex() != cplx:
+            raise _NeedComplex()
+        if op.project_operator:
+            scratch = self.bb.ctx.empty(stride)
+            for o in O:
+                self._gs([o], res, 1, scratch, 0)
+        if op.penalty is not None and m:
+            p = op.penalty if cplx else op.penalty.real
+            if op.project_operator:
+                for j, o in enumerate(O):
+                    self._multi('axpy', [o], res, coef, j * stride, p)
+            else:
+                self._multi('axpy', O, res, coef, 0, p)
+        return res
+
+    # -- projections against a basis (krylov_vec.hip: cyb_gram_schmidt / cyb_multi_dot / cyb_multi_axpy)
+    MAX_BASIS = 64
+
+    def _ptrs(self, basis):
+        return (self._C.c_void_p * max(len(basis), 1))(*[v.data_ptr() for v in basis])
+
+    def _gs(self, basis, w, passes, out, off=0):
+        bb = self.bb
+        fn = bb.lib.cyb_gram_schmidt_c128 if w.is_complex() else bb.lib.cyb_gram_schmidt_f64
+        bb.ctx.sync_stream()
+        self._lib.check(fn(bb.ctx.handle, self._ptrs(basis), len(basis), self._C.c_void_p(w.data_ptr()), self.total, int(passes),
+                           self._C.c_void_p(out.data_ptr() + 8 * off)))
+
+    def _multi(self, kind, basis, w, h, off=0, alpha=1.0):
+        bb, C = self.bb, self._C
+        cp = w.is_complex()
+        bb.ctx.sync_stream()
+        hp = C.c_void_p(h.data_ptr() + 8 * off)
+        if kind == 'dot':
+            fn = bb.lib.cyb_multi_dot_c128 if cp else bb.lib.cyb_multi_dot_f64
+            self._lib.check(fn(bb.ctx.handle, self._ptrs(basis), len(basis), C.c_void_p(w.data_ptr()), self.total, hp))
+        elif cp:
+            a = complex(alpha)
+            self._lib.check(bb.lib.cyb_multi_axpy_c128(bb.ctx.handle, self._ptrs(basis), len(basis), hp, a.real, a.imag,
+                                                       C.c_void_p(w.data_ptr()), self.total))
+        else:
+            self._lib.check(bb.lib.cyb_multi_axpy_f64(bb.ctx.handle, self._ptrs(basis), len(basis), hp, float(np.real(alpha)),
+                                                      C.c_void_p(w.data_ptr()), self.total))
+
+    def project_out(self, basis, w, passes=2):
+        """(w - V h, h, |w - V h|) with h = V^H w: ONE fused classical Gram-Schmidt call (passes=2: CGS2, h summed over the
+        passes) that updates w in place, and ONE device-to-host copy of the m coefficients and the norm.  A basis of mixed
+        dtypes or longer than the kernel takes runs the modified Gram-Schmidt loop of _TensorOps."""
+        m = len(basis)
+        cplx = w.is_complex()
+        if m > self.MAX_BASIS or any(v.is_complex() != cplx for v in basis):
+            return _mgs(self, basis, w)
+        k = 2 if cplx else 1
+        out = self.bb.ctx.empty(k * m + 1)
+        self._gs(basis, w, passes, out)
+        r = self.bb.ctx.d2h(out, k * m + 1, np.float64)
+        h = (r[0:2 * m:2] + 1j * r[1:2 * m:2]) if cplx else r[:m].copy()
+        return w, h, float(r[k * m])
 
     # -- BLAS-1 over the flat range
     def _desc(self, x, y, out, n=None):
@@ -369,6 +476,15 @@ class _FlatOps:
         return float(np.sqrt(bb.ctx.d2h(res, 1, np.float64)[0]))
 
 
+def _mgs(V, basis, w):
+    h = []
+    for v in basis:
+        c = V.inner(v, w)
+        h.append(c)
+        w = V.lincomb(1.0, w, -c, v)
+    return w, np.array(h), V.norm(w)
+
+
 class LanczosGroundState:
     """Lanczos for the lowest eigenvector of a Hermitian ``H`` (krylov_based.cpp:803-946).
 
@@ -394,6 +510,13 @@ class LanczosGroundState:
         if self.N_cache < 2:
             raise ValueError('Need to cache at least two vectors.')
         self._psi0_norm = None
+        # E_shift shifts the operator INSIDE a projected operator (krylov_based.cpp:289-296): the projection then keeps the
+        # ortho vectors at eigenvalue `penalty`, not penalty + E_shift.  (A copy: the caller's operator is not changed.)
+        self._shift_outside = self.E_shift is not None
+        from .sparse import ProjectedLinearOperator, ShiftedLinearOperator
+        if self.E_shift is not None and isinstance(H, ProjectedLinearOperator):
+            self.H = H.with_original(ShiftedLinearOperator(H.original_operator, float(self.E_shift), H.bb))
+            self._shift_outside = False
         self._reset_krylov_state()
 
     def _reset_krylov_state(self):
@@ -411,7 +534,7 @@ class LanczosGroundState:
     def _matvec(self, w):
         V = self.V
         out = V.matvec(w)
-        if self.E_shift is not None:
+        if self._shift_outside:
             out = V.lincomb(1.0, out, float(self.E_shift), self._cache[-1])
         return out
 
@@ -778,3 +901,199 @@ class ArnoldiEvolution(Arnoldi):
             raise RuntimeError('ArnoldiEvolution: Krylov basis shorter than N')
         psif = V.combine(list(self._result_krylov[:N]), self._cache[:N])
         return V.scale(1.0 / V.norm(psif), psif)
+
+
+def _same_legs(a, b) -> bool:
+    return len(a.legs) == len(b.legs) and all(
+        x.sign == y.sign and np.array_equal(x.sectors, y.sectors) and np.array_equal(x.mults, y.mults)
+        for x, y in zip(a.legs, b.legs))
+
+
+class GMRES:
+    """Restarted GMRES for ``A x = b`` (krylov_based.cpp:358-530): Arnoldi with Givens rotations, a back-substitution per
+    cycle and a restart from the current x.  Options and defaults of :369-373: N_min=5, N_max=20, restart=10, res=1e-8 (no
+    N_min >= 2 check); ``flat`` (not a reference option) as in the other solvers.
+
+    Vectors are flat pools where the backend allows it: float64 while A, x and b are real, complex128 otherwise (a complex
+    shift or a complex b); the Arnoldi step orthogonalises by ONE fused CGS2 call (_FlatOps.project_out), the reference's
+    modified Gram-Schmidt on tensors.  x += sum_i y_i q_i is one combine.
+
+    Two deliberate deviations from the reference:
+
+    1. Unitary Givens rotations.  The reference takes t = sqrt(v1^2 + v2^2), c = v1 / t, s = v2 / t and rotates with
+       [[c, s], [-s, c]] (:471-498), which is not unitary for complex entries: |e1[k+1]| is then not the residual, y does
+       not minimise it, and v1^2 + v2^2 = 0 divides by zero.  Here t = sqrt(|v1|^2 + |v2|^2) and H and e1 are rotated
+       with [[conj(c), conj(s)], [-s, c]]: the reference's formula for real data, unitary for complex data, so |e1[k+1]| /
+       |b| is the true relative residual of the cycle.
+    2. Exact breakdown.  A new Krylov vector of norm 0 ends the cycle as converged (the reference would go on and divide by
+       zero before N_min)."""
+
+    def __init__(self, bb, A, x, b, options=None):
+        o = dict(options or {})
+        if A is None:
+            raise ValueError('A must not be null')
+        if x is None or b is None:
+            raise ValueError('x and b must not be null')
+        if not _same_legs(x, b):
+            raise ValueError('x and b must have the same legs')
+        self.bb, self.A, self.x_in, self.b_in = bb, A, x, b
+        self.options = o
+        self.N_min = int(o.get('N_min', 5))
+        self.N_max = int(o.get('N_max', 20))
+        self.restart = int(o.get('restart', 10))
+        self.res = float(o.get('res', 1e-8))
+        self.flat = o.get('flat', True)
+        flat = bool(self.flat) and _FlatOps.usable(bb, b)
+        cplx = (any(_is_complex_block(t) for v in (x, b) for t in v.blocks) or bool(getattr(A, 'is_complex', False)))
+        self._modes = ([cplx] if cplx else [False, True]) if flat else []
+        self._modes.append(None)   # tensors
+        self._mode_i = 0
+        self._start_any()
+
+    # -- state -------------------------------------------------------------------------------------
+    def _start_any(self):
+        """The constructor's work (:375-386) in the first vector representation that holds: pools, else tensors."""
+        while True:
+            try:
+                self._start(self._modes[self._mode_i])
+                return
+            except _NeedComplex:
+                self._mode_i += 1
+            except _NotFlat:
+                self._mode_i = len(self._modes) - 1
+
+    def _start(self, mode):
+        bb = self.bb
+        self.V = (_FlatOps(bb, self.A, self.b_in, ab.AbelianTensor.allowed_block_inds(self.b_in.symmetry, self.b_in.legs), mode)
+                  if mode is not None else _TensorOps(bb, self.A))
+        V = self.V
+        self.x = V.enter(self.x_in)
+        self.b = V.enter(self.b_in)
+        r0 = V.lincomb(1.0, self.b, -1.0, V.matvec(self.x))
+        self.rs = [r0]
+        self.b_norm = V.norm(self.b)
+        self.r_norm = V.norm(r0)
+        self.total_error = [[self.r_norm / self._denom()]]
+        self.total_iters = []
+        self.qs = [V.scale(1.0 / self.r_norm, r0) if self.r_norm > 0 else r0]
+        self._init_hessenberg()
+
+    def _denom(self):
+        return self.b_norm if self.b_norm != 0.0 else 1.0
+
+    def _init_hessenberg(self):
+        self.sine = np.zeros(self.N_max, dtype=np.complex128)
+        self.cosine = np.zeros(self.N_max, dtype=np.complex128)
+        self.e1 = np.zeros(self.N_max + 1, dtype=np.complex128)
+        self.e1[0] = self.r_norm
+        self.H = np.zeros((self.N_max + 1, self.N_max), dtype=np.complex128)
+        self.y = np.zeros(0, dtype=np.complex128)
+        self._h_next = None
+
+    def H_numpy(self):
+        """The (N_max + 1) x N_max Hessenberg matrix (complex128), rotated to upper triangular as far as the cycle got."""
+        return self.H.copy()
+
+    # -- the iteration -----------------------------------------------------------------------------
+    def run(self):
+        """(x, rel_residual, total_error, total_iters): total_error holds one list per cycle (the residual after the restart,
+        then one entry per step), total_iters the steps of each cycle, rel_residual = |A x - b| / |b| recomputed at the end."""
+        while True:
+            try:
+                return self._run()
+            except _NeedComplex:
+                self._mode_i += 1
+            except _NotFlat:
+                self._mode_i = len(self._modes) - 1
+            self._start_any()
+
+    def _run(self):
+        V = self.V
+        if self.total_error[0][0] < self.res:
+            return V.leave(self.x), self.total_error[0][0], self.total_error, self.total_iters
+        for _ in range(self.restart):
+            converged = False
+            performed = 0
+            for k in range(self.N_max):
+                self.arnoldi(k)
+                self.apply_givens_rotation(k)
+                self.e1[k + 1] = -self.sine[k] * self.e1[k]
+                self.e1[k] = np.conj(self.cosine[k]) * self.e1[k]
+                # the residual is the last element of the rotated right-hand side
+                error = float(abs(self.e1[k + 1])) / self._denom()
+                self.total_error[-1].append(error)
+                performed = k + 1
+                if (error < self.res and k >= self.N_min) or self._h_next == 0.0:
+                    converged = True
+                    break
+            self.total_iters.append(performed)
+            self.backsolve(performed)
+            y = [_plain_scalar(c) for c in self.y[:performed]]
+            self.x = V.combine(y, self.qs[:performed], acc=self.x)
+            if not converged:
+                self.reset()
+            else:
+                break
+        rel = V.norm(V.lincomb(1.0, V.matvec(self.x), -1.0, self.b))
+        if self.b_norm != 0.0:
+            rel /= self.b_norm
+        return V.leave(self.x), rel, self.total_error, self.total_iters
+
+    def arnoldi(self, k):
+        """q = A q_k, orthogonalised against q_0..q_k (:453-469): column k of H and |q| (fused CGS2 on pools)."""
+        V = self.V
+        q = V.matvec(self.qs[-1])
+        q, h, h_next = V.project_out(self.qs[:k + 1], q, 2)
+        self.H[:k + 1, k] = h
+        self.H[k + 1, k] = h_next
+        if h_next > 0:
+            q = V.scale(1.0 / h_next, q)
+        self.qs.append(q)
+        self._h_next = h_next
+
+    def apply_givens_rotation(self, k):
+        """Rotate column k by the earlier rotations, then eliminate H[k+1, k] (:471-487; unitary form, see the class)."""
+        H, c, s = self.H, self.cosine, self.sine
+        for i in range(k):
+            temp = np.conj(c[i]) * H[i, k] + np.conj(s[i]) * H[i + 1, k]
+            H[i + 1, k] = -s[i] * H[i, k] + c[i] * H[i + 1, k]
+            H[i, k] = temp
+        self.givens_rotation(k)
+        H[k, k] = np.conj(c[k]) * H[k, k] + np.conj(s[k]) * H[k + 1, k]
+        H[k + 1, k] = 0
+
+    def givens_rotation(self, k):
+        """c, s with [[conj(c), conj(s)], [-s, c]] (v1, v2) = (t, 0) (:489-498 with |v|^2 in place of v^2)."""
+        v1, v2 = self.H[k, k], self.H[k + 1, k]
+        t = np.sqrt(v1.real * v1.real + v1.imag * v1.imag + v2.real * v2.real + v2.imag * v2.imag)
+        if t == 0.0:   # (a zero column: nothing to eliminate)
+            self.cosine[k], self.sine[k] = 1.0, 0.0
+            return
+        self.cosine[k] = v1 / t
+        self.sine[k] = v2 / t
+
+    def backsolve(self, k):
+        """y = R^-1 e1 over the first k rows (:500-513)."""
+        y = np.zeros(k, dtype=np.complex128)
+        for i in range(k - 1, -1, -1):
+            y[i] = self.e1[i]
+            for j in range(i + 1, k):
+                y[i] -= self.H[i, j] * y[j]
+            y[i] /= self.H[i, i]
+        self.y = y
+
+    def reset(self):
+        """Restart from the current x (:515-530)."""
+        V = self.V
+        r = V.lincomb(1.0, self.b, -1.0, V.matvec(self.x))
+        self.rs.append(r)
+        self.r_norm = V.norm(r)
+        self.total_error.append([self.r_norm / self._denom()])
+        self.qs = [V.scale(1.0 / self.r_norm, r) if self.r_norm > 0 else r]
+        self._init_hessenberg()
+
+
+def _plain_scalar(c):
+    """A complex coefficient with a zero imaginary part as a float: float64 pools stay real."""
+    c = complex(c)
+    return c.real if c.imag == 0.0 else c

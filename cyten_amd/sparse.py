@@ -1,0 +1,149 @@
+"""Linear-operator wrappers of the Krylov solvers (include/cyten/tensors/sparse.h:66-128, src/tensors/sparse.cpp:188-344).
+
+* :class:`LinearOperatorWrapper` -- forwards to ``original_operator``; ``unwrapped()`` peels wrappers off.
+* :class:`SumLinearOperator` -- ``op + sum(more_operators)`` (sparse.cpp:196-241).
+* :class:`ShiftedLinearOperator` -- ``op + shift`` (sparse.cpp:243-275); complex when the shift is.
+* :class:`ProjectedLinearOperator` -- ``P op P + penalty (1 - P)`` with ``P = 1 - sum_o |o><o|``, or ``op + penalty (1 - P)``
+  with ``project_operator=False`` (sparse.cpp:277-344).  The projection is the reference's SEQUENTIAL one: each ortho vector
+  is removed from the current vector in turn.  For orthonormal ortho vectors that is the projector above; for others it is
+  what the reference computes (its docstring, py_sparse.cpp:322-324, promises a Gram-Schmidt the code does not do).
+
+Every wrapper acts on block-sparse tensors through ``.matvec(tensor)`` with the block backend of the wrapped operator (or the
+``bb`` given), exposes ``is_complex`` as the solvers expect and has ``adjoint()`` where the wrapped operators have one.  On
+flat Krylov pools the solvers do not call these ``matvec``s: ``krylov._FlatOps`` recognises the wrappers and does their
+vector work on the pools.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import abelian as ab
+
+
+def _is_complex_op(op) -> bool:
+    return bool(getattr(op, 'is_complex', False))
+
+
+def _is_complex_tensor(t) -> bool:
+    return any(np.iscomplexobj(b) if isinstance(b, np.ndarray) else bool(b.is_complex) for b in t.blocks)
+
+
+def _plain(c):
+    """A complex number with a zero imaginary part as a float (keeps float64 vectors real)."""
+    c = complex(c)
+    return c.real if c.imag == 0.0 else c
+
+
+class LinearOperatorWrapper:
+    """Base class of the wrappers: forwards to ``original_operator`` (sparse.cpp:160-186)."""
+
+    def __init__(self, original_operator, bb=None):
+        self.original_operator = original_operator
+        self.bb = bb if bb is not None else getattr(original_operator, 'bb', None)
+
+    @property
+    def is_complex(self) -> bool:
+        return _is_complex_op(self.original_operator)
+
+    def unwrapped(self, recursive: bool = True):
+        op = self.original_operator
+        while recursive and isinstance(op, LinearOperatorWrapper):
+            op = op.original_operator
+        return op
+
+    def matvec(self, vec):
+        return self.original_operator.matvec(vec)
+
+    def adjoint(self):
+        return LinearOperatorWrapper(self.original_operator.adjoint(), self.bb)
+
+
+class SumLinearOperator(LinearOperatorWrapper):
+    """``original_operator + sum(more_operators)``."""
+
+    def __init__(self, original_operator, more_operators=(), bb=None):
+        super().__init__(original_operator, bb)
+        self.more_operators = list(more_operators)
+
+    @property
+    def is_complex(self) -> bool:
+        return _is_complex_op(self.original_operator) or any(_is_complex_op(op) for op in self.more_operators)
+
+    def matvec(self, vec):
+        res = self.original_operator.matvec(vec)
+        for op in self.more_operators:
+            res = ab.linear_combination(self.bb, 1.0, op.matvec(vec), 1.0, res)
+        return res
+
+    def adjoint(self):
+        return SumLinearOperator(self.original_operator.adjoint(), [op.adjoint() for op in self.more_operators], self.bb)
+
+
+class ShiftedLinearOperator(LinearOperatorWrapper):
+    """``original_operator + shift * 1``; complex if ``shift.imag != 0``."""
+
+    def __init__(self, original_operator, shift, bb=None):
+        super().__init__(original_operator, bb)
+        self.shift = complex(shift)
+
+    @property
+    def is_complex(self) -> bool:
+        return _is_complex_op(self.original_operator) or self.shift.imag != 0.0
+
+    def matvec(self, vec):
+        res = self.original_operator.matvec(vec)
+        return ab.linear_combination(self.bb, _plain(self.shift), vec, 1.0, res)
+
+    def adjoint(self):
+        return ShiftedLinearOperator(self.original_operator.adjoint(), self.shift.conjugate(), self.bb)
+
+
+class ProjectedLinearOperator(LinearOperatorWrapper):
+    """``P H P + penalty (1 - P)`` (``project_operator=True``) or ``H + penalty (1 - P)``, ``P = 1 - sum_o |o><o|``;
+    ``penalty=None`` means 0.  The coefficients of the penalty term are those the sequential projection of the input
+    produced (sparse.cpp:294-327)."""
+
+    def __init__(self, original_operator, ortho_vecs, project_operator: bool = True, penalty=None, bb=None):
+        super().__init__(original_operator, bb)
+        self.ortho_vecs = list(ortho_vecs)
+        self.project_operator = bool(project_operator)
+        self.penalty = None if penalty is None else complex(penalty)
+        for v in self.ortho_vecs[1:]:
+            if len(v.legs) != len(self.ortho_vecs[0].legs) or not all(
+                    a.sign == b.sign and np.array_equal(a.sectors, b.sectors) and np.array_equal(a.mults, b.mults)
+                    for a, b in zip(v.legs, self.ortho_vecs[0].legs)):
+                raise ValueError('All ortho_vecs must be mutually compatible')
+
+    @property
+    def is_complex(self) -> bool:
+        return (_is_complex_op(self.original_operator) or any(_is_complex_tensor(v) for v in self.ortho_vecs)
+                or (self.penalty is not None and self.penalty.imag != 0.0))
+
+    def with_original(self, op) -> 'ProjectedLinearOperator':
+        """The same projection around another operator."""
+        return ProjectedLinearOperator(op, self.ortho_vecs, self.project_operator, self.penalty, self.bb)
+
+    def matvec(self, vec):
+        bb = self.bb
+        res = vec
+        coeffs = []
+        if self.project_operator:
+            for o in self.ortho_vecs:
+                c = ab.inner(bb, o, res)
+                coeffs.append(c)
+                res = ab.linear_combination(bb, 1.0, res, _plain(-c), o)
+        else:
+            coeffs = [ab.inner(bb, o, res) for o in self.ortho_vecs]
+        res = self.original_operator.matvec(res)
+        if self.project_operator:
+            for o in self.ortho_vecs:
+                c = ab.inner(bb, o, res)
+                res = ab.linear_combination(bb, 1.0, res, _plain(-c), o)
+        if self.penalty is not None:
+            for o, c in zip(self.ortho_vecs, coeffs):
+                res = ab.linear_combination(bb, 1.0, res, _plain(self.penalty * c), o)
+        return res
+
+    def adjoint(self):
+        p = None if self.penalty is None else self.penalty.conjugate()
+        return ProjectedLinearOperator(self.original_operator.adjoint(), self.ortho_vecs, self.project_operator, p, self.bb)

@@ -338,6 +338,27 @@ int cyb_axpby_batched_c128(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t n,
  * run.  The inner product of complex Krylov vectors and of complex block lists (abelian.cpp:2159-2211). */
 int cyb_dot_batched_c128(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t n, double* result_dev);
 
+/* ---- projections against a list of m <= 64 basis vectors (GMRES and the projected operator) ----------------------------
+ * basis: a HOST array of m device pointers, each a contiguous vector of n elements (f64: doubles; c128: interleaved complex,
+ * n counts complex elements, 16-byte aligned); w: a contiguous vector of the same kind.  Coefficients are device arrays of m
+ * doubles (f64) or m interleaved complex numbers (c128).  Enqueued on the context stream with no host synchronisation;
+ * fixed work split for a given (n, m), fixed summation order: bit-identical from run to run.  m > 64: CYB_ERR_UNSUPPORTED.
+ *
+ * multi-dot: h_dev[j] = sum_i conj(V_j[i]) w[i], w read once -- the coefficients of ProjectedLinearOperator with
+ * project_operator=False (sparse.cpp:302-306). */
+int cyb_multi_dot_f64(cyb_ctx_t ctx, const double* const* basis, int64_t m, const double* w, int64_t n, double* h_dev);
+int cyb_multi_dot_c128(cyb_ctx_t ctx, const double* const* basis, int64_t m, const double* w, int64_t n, double* h_dev);
+/* multi-axpy: w += alpha * sum_j h_dev[j] V_j, h read from device memory -- the penalty term of ProjectedLinearOperator
+ * (sparse.cpp:316-321). */
+int cyb_multi_axpy_f64(cyb_ctx_t ctx, const double* const* basis, int64_t m, const double* h_dev, double alpha, double* w, int64_t n);
+int cyb_multi_axpy_c128(cyb_ctx_t ctx, const double* const* basis, int64_t m, const double* h_dev, double alpha_re, double alpha_im,
+                        double* w, int64_t n);
+/* classical Gram-Schmidt step, passes 1 or 2 (CGS2): w <- (1 - V V^H)^passes w in place.  out_dev receives the coefficients
+ * summed over the passes (m doubles, or 2m for c128: the Hessenberg column of GMRES::arnoldi, krylov_based.cpp:453-469)
+ * followed by |w| after the last update (one double). */
+int cyb_gram_schmidt_f64(cyb_ctx_t ctx, const double* const* basis, int64_t m, double* w, int64_t n, int32_t passes, double* out_dev);
+int cyb_gram_schmidt_c128(cyb_ctx_t ctx, const double* const* basis, int64_t m, double* w, int64_t n, int32_t passes, double* out_dev);
+
 /* ---- host-side sector matching of a contraction (no device work) ------------------------------------------------
  * The int64 bookkeeping of abelian_compose_worker (src/backends/abelian.cpp:1239-1469) in C++, as in the reference:
  * contracts the last `num_contr` legs of a with the first `num_contr` legs of b (a.legs[na_legs - 1 - i] pairs with
