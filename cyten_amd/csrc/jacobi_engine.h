@@ -21,7 +21,8 @@ struct JMat {
     int32_t nb;     // nvp / JB (even)
     int32_t nv;     // true vector count
     int32_t len;    // true vector length
-    int32_t pad;
+    int32_t rec_j;  // J == nullptr because the caller rebuilds the rotations afterwards (svd_jacobi.hip, rotation recovery): the
+                    // matrix keeps the parts per pair it would have with J (see the chain estimate of jacobi_orthogonalise)
     double tol;     // convergence threshold on |g_ij| / sqrt(g_ii g_jj)
     double thr2;    // rows with 0 < |w|^2 <= thr2 are numerically null and get zeroed (deflation); 0: off
 };

@@ -1863,7 +1863,11 @@ int jacobi_orthogonalise(cyb_ctx_t ctx, const std::vector<JMat>& h_mats, int max
             std::vector<int> Gm((size_t)n, 1);
             auto chain = [&](int m) {
                 const JMat& jm = h_mats[(size_t)m];
-                const double per_round = 8.0 + 22.0 * (double)(jm.lenp + (jm.J ? jm.nvp : 0)) / 2240.0 / (double)Gm[(size_t)m]
+                // (rec_j: a matrix whose rotations are rebuilt afterwards streams half the columns, but the estimate keeps counting
+                //  J for it.  Its fixed part is too small -- a round of the largest chi=4096 block is 12 us of wait + pivot solve +
+                //  sort and 6-11 us of exchange whatever G is -- so with the halved width the greedy loop gave that block five parts
+                //  and every other block one: list 26.5 ms against 24.3 ms with the parts of the accumulating run, 3 / 2 / 1)
+                const double per_round = 8.0 + 22.0 * (double)(jm.lenp + ((jm.J || jm.rec_j) ? jm.nvp : 0)) / 2240.0 / (double)Gm[(size_t)m]
                                          + (Gm[(size_t)m] > 1 ? 4.0 : 0.0); // us: fixed part + MFMA share (+ exchange)
                 return per_round * (double)(jm.nb - 1);
             };
