@@ -12,6 +12,7 @@ PKG_DIR = Path(__file__).resolve().parent
 LIB_PATH = PKG_DIR / 'lib' / 'libcyten_amd.so'
 
 CYB_MAX_NDIM = 8
+CYB_TRACE_MAX_PAIRS = 4
 CYB_SVD_SKIP_NULL_VECTORS = 1
 CYB_SVD_EMBEDDED_COMPLEX = 2
 CYB_EIGH_EMBEDDED_COMPLEX = 2
@@ -106,6 +107,16 @@ class MaskDesc(C.Structure):
                 ('outer', C.c_int64), ('axis', C.c_int64), ('inner', C.c_int64), ('n_keep', C.c_int64)]
 
 
+class TraceOut(C.Structure):
+    _fields_ = [('dst', C.c_void_p), ('ndim', C.c_int32), ('reserved', C.c_int32), ('first_term', C.c_int64), ('n_terms', C.c_int64),
+                ('shape', C.c_int64 * CYB_MAX_NDIM)]
+
+
+class TraceTerm(C.Structure):
+    _fields_ = [('src', C.c_void_p), ('n_pairs', C.c_int32), ('reserved', C.c_int32), ('rem_strides', C.c_int64 * CYB_MAX_NDIM),
+                ('pair_extent', C.c_int64 * CYB_TRACE_MAX_PAIRS), ('pair_stride', C.c_int64 * CYB_TRACE_MAX_PAIRS)]
+
+
 # numpy views of the descriptor structs (same layout: numpy derives the dtype from the ctypes Structure), for the
 # vectorised marshalling of long block lists
 import numpy as _np  # noqa: E402
@@ -121,6 +132,8 @@ LINCOMB_DTYPE = _np.dtype(LincombDesc)
 LINTERM_DTYPE = _np.dtype(LincombTerm)
 LINTERM_C128_DTYPE = _np.dtype(LincombTermC128)
 CEXPAND_DTYPE = _np.dtype(CExpandDesc)
+TRACE_OUT_DTYPE = _np.dtype(TraceOut)
+TRACE_TERM_DTYPE = _np.dtype(TraceTerm)
 
 _P = C.POINTER
 _ctx = C.c_void_p
@@ -192,6 +205,8 @@ PROTOTYPES = {
     'cyb_random_normal_f64': [_ctx, _vp, C.c_int64, C.c_uint64, C.c_double],
     'cyb_lincomb_strided_batched_f64': [_ctx, _P(LincombDesc), C.c_int64, _P(LincombTerm), C.c_int64],
     'cyb_lincomb_strided_batched_c128': [_ctx, _P(LincombDesc), C.c_int64, _P(LincombTermC128), C.c_int64],
+    'cyb_trace_grouped_f64': [_ctx, _P(TraceOut), C.c_int64, _P(TraceTerm), C.c_int64],
+    'cyb_trace_grouped_c128': [_ctx, _P(TraceOut), C.c_int64, _P(TraceTerm), C.c_int64],
     'cyb_truncate_select_f64': [_ctx, _P(VecDesc), C.c_int64, _P(TruncOpts), _vp, _vp, _vp],
     'cyb_truncate_select_weighted_f64': [_ctx, _P(VecDesc), C.c_int64, _vp, _P(TruncOpts), _vp, _vp, _vp],
     'cyb_random_uniform_f64': [_ctx, _vp, C.c_int64, C.c_uint64, C.c_double, C.c_double],

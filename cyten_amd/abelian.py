@@ -16,6 +16,12 @@ reference's ``AbelianBackend`` callers of the block backend (SURVEY.md section 8
   + ``abelian.cpp:3623-3638``; the S blocks live in one device pool so the forced device->host
   transfer is a single copy.
 * :func:`qr`, :func:`eigh` <- ``AbelianBackend::qr`` (:3084-3151), ``::eigh`` (:1759-1788).
+* :func:`partial_trace`, :func:`trace_full` <- ``AbelianBackend::partial_trace`` (:2954-3081), ``::trace_full`` (:3595-3620):
+  ONE grouped trace launch for all result blocks instead of ``trace_partial`` + ``operator+`` per block.
+* :func:`conj`, :func:`dagger`, :class:`DiagonalTensor`, :func:`diagonal_unary`, :func:`scale_axis`, :func:`to_dense_block`,
+  :func:`from_dense_block` <- ``::dagger`` (:694-703), ``::diagonal_from_block`` (:1636-1652), ``::diagonal_elementwise_unary``
+  (:743-782), ``::scale_axis`` (:3178-3232), ``::to_dense_block`` (:3571-3592), ``::from_dense_block`` (:1829-1858): one batched
+  launch per block list each.
 
 The functions only need the block-backend *interface* (`matrix_dot_grouped`, `matrix_svd_batched`,
 ...), not a particular implementation.
@@ -30,7 +36,9 @@ import numpy as np
 
 __all__ = ['Symmetry', 'Leg', 'AbelianTensor', 'compose', 'compose_plan', 'compose_plan_py', 'combine_legs_to_matrix', 'svd',
            'truncate_singular_values', 'truncated_svd', 'qr', 'lq', 'eigh', 'norm', 'inner', 'split_matrix_legs', 'partial_compose',
-           'Mask', 'mask_contract', 'qr_tensor', 'lq_tensor', 'to_block_backend', 'move_to_device']
+           'Mask', 'mask_contract', 'qr_tensor', 'lq_tensor', 'to_block_backend', 'move_to_device',
+           'conj', 'dagger', 'DiagonalTensor', 'diagonal_unary', 'scale_axis', 'partial_trace', 'trace_full', 'to_dense_block',
+           'from_dense_block', 'dual_sector_map']
 
 
 class Symmetry:
@@ -1021,3 +1029,222 @@ def move_to_device(bb, t: AbelianTensor, device) -> AbelianTensor:
     dev = bb.as_device(device)
     return AbelianTensor(t.symmetry, list(t.legs), [bb.as_block(b, device=dev) for b in t.blocks], t.block_inds.copy(),
                          t.num_codomain, list(t.labels))
+
+
+# ---------------------------------------------------------------------------------------------
+# adjoint, diagonal tensors, traces, dense conversion
+# ---------------------------------------------------------------------------------------------
+
+def _is_complex_block(b) -> bool:
+    return np.dtype(getattr(b, 'dtype', np.float64)).kind == 'c'
+
+
+def conj(bb, t: AbelianTensor) -> AbelianTensor:
+    """Complex conjugate in the same leg order: every leg becomes its dual (same sectors, opposite sign), so the charge
+    rule holds for the same block table.  Real blocks are their own conjugate (no launch); the complex blocks of the tensor
+    go through ONE conjugating batched copy."""
+    blocks = list(t.blocks)
+    todo = [i for i, b in enumerate(blocks) if _is_complex_block(b)]
+    if todo:
+        new = bb.empty_many([t.blocks[i].shape for i in todo], dtype='complex128')
+        bb.copy_many([(d, t.blocks[i]) for d, i in zip(new, todo)], conj=True)
+        for d, i in zip(new, todo):
+            blocks[i] = d
+    return AbelianTensor(t.symmetry, [l.dual() for l in t.legs], blocks, t.block_inds.copy(), t.num_codomain, list(t.labels))
+
+
+def dagger(bb, t: AbelianTensor) -> AbelianTensor:
+    """``AbelianBackend::dagger`` (abelian.cpp:694-703): conjugate, reverse the flat legs (codomain and domain change
+    places) and the columns of the block table, re-sort.  The axis reversal of the blocks is a view."""
+    c = conj(bb, t)
+    n = t.nlegs
+    rev = list(range(n - 1, -1, -1))
+    blocks = [bb.permute_axes(b, rev) for b in c.blocks]
+    bi = c.block_inds[:, ::-1] if len(blocks) else c.block_inds.reshape(0, n)
+    return AbelianTensor(t.symmetry, c.legs[::-1], blocks, bi, n - t.num_codomain, list(t.labels)[::-1]).sorted()
+
+
+@dataclass
+class DiagonalTensor:
+    """cyten ``DiagonalTensor`` data: the diagonal of an operator from `leg` to itself, one 1-D block per sector that has
+    one.  ``block_inds``: the sorted sector indices of the blocks (the reference stores the two equal columns
+    ``[i, i]``, abelian.cpp:1643-1644)."""
+    symmetry: Symmetry
+    leg: Leg
+    blocks: list
+    block_inds: np.ndarray
+
+    def __post_init__(self):
+        self.block_inds = np.asarray(self.block_inds, dtype=np.int64).reshape(len(self.blocks))
+
+    @classmethod
+    def from_numpy(cls, bb, leg: Leg, values) -> 'DiagonalTensor':
+        """``diagonal_from_block`` (abelian.cpp:1636-1652): the full diagonal cut into one block per sector of `leg`"""
+        values = np.asarray(values)
+        if values.shape != (leg.dim,):
+            raise ValueError('diagonal length does not match the leg')
+        blocks = [bb.as_block(values[int(leg.slices[i]):int(leg.slices[i + 1])]) for i in range(leg.nsec)]
+        return cls(leg.symmetry, leg, blocks, np.arange(leg.nsec))
+
+    def to_numpy(self, bb) -> np.ndarray:
+        """the full diagonal, zeros in the sectors without a block"""
+        cplx = any(_is_complex_block(b) for b in self.blocks)
+        out = np.zeros(self.leg.dim, dtype=np.complex128 if cplx else np.float64)
+        for blk, i in zip(self.blocks, self.block_inds):
+            out[int(self.leg.slices[i]):int(self.leg.slices[i + 1])] = bb.to_numpy(blk)
+        return out
+
+
+_UNARY_NAMES = ('abs', 'sqrt', 'exp', 'log', 'neg', 'square', 'reciprocal')
+_UNARY_PARAM_NAMES = ('cutoff_inverse', 'stable_log', 'pow')
+
+
+def diagonal_unary(bb, d: DiagonalTensor, func: str, param=None, maps_zero_to_zero: bool = True) -> DiagonalTensor:
+    """``AbelianBackend::diagonal_elementwise_unary`` (abelian.cpp:743-782) for the elementwise functions the device
+    serves by name: abs, sqrt, exp, log, neg, square, reciprocal, and -- with `param` -- cutoff_inverse (the pseudo-inverse of
+    singular values), stable_log, pow.  The whole diagonal is ONE launch (``bb.unary_many``).  With
+    ``maps_zero_to_zero=False`` the sectors without a block first get a zero block, as in the reference (:759-773)."""
+    if func not in _UNARY_NAMES + _UNARY_PARAM_NAMES:
+        raise ValueError(f'diagonal_unary: unknown function {func!r}')
+    blocks, inds = list(d.blocks), d.block_inds
+    if not maps_zero_to_zero:
+        have = {int(i): b for i, b in zip(d.block_inds, d.blocks)}
+        missing = [i for i in range(d.leg.nsec) if i not in have]
+        for i, z in zip(missing, bb.zeros_many([(int(d.leg.mults[i]),) for i in missing]) if missing else []):
+            have[i] = z
+        inds = np.arange(d.leg.nsec)
+        blocks = [have[i] for i in range(d.leg.nsec)]
+    outs = bb.unary_many(blocks, func, param) if blocks else []
+    return DiagonalTensor(d.symmetry, d.leg, list(outs), np.array(inds, dtype=np.int64))
+
+
+def _same_space(a: Leg, b: Leg) -> bool:
+    return a.nsec == b.nsec and np.array_equal(a.sectors, b.sectors) and np.array_equal(a.mults, b.mults)
+
+
+def scale_axis(bb, t: AbelianTensor, d: DiagonalTensor, leg: int) -> AbelianTensor:
+    """``AbelianBackend::scale_axis`` (abelian.cpp:3178-3232): multiply leg `leg` of `t` by the diagonal `d`.  Blocks of
+    `t` whose sector on that leg has no block in `d` multiply to zero and are dropped (:3181-3182); the others go through
+    ONE ``scale_axis_many`` launch instead of one ``scale_axis`` per block (:3223).  `d` is real."""
+    leg = int(leg) % t.nlegs
+    if t.symmetry != d.symmetry or not _same_space(t.legs[leg], d.leg):
+        raise ValueError('scale_axis: the leg of the diagonal does not have the sectors and multiplicities of the leg of the tensor')
+    if any(_is_complex_block(b) for b in d.blocks):
+        raise NotImplementedError('scale_axis with a complex diagonal is not on the device path yet')
+    by_sector = {int(i): b for i, b in zip(d.block_inds, d.blocks)}
+    keep = [r for r, row in enumerate(t.block_inds) if int(row[leg]) in by_sector]
+    blocks = bb.scale_axis_many([(t.blocks[r], by_sector[int(t.block_inds[r, leg])], leg) for r in keep]) if keep else []
+    return AbelianTensor(t.symmetry, list(t.legs), list(blocks), t.block_inds[keep].reshape(len(keep), t.nlegs), t.num_codomain,
+                         list(t.labels))
+
+
+def dual_sector_map(symmetry: Symmetry, a: Leg, b: Leg):
+    """For every sector index of `a` the index of the sector of `b` whose charge cancels it (``sign_a q_a + sign_b q_b = 0``
+    under the moduli); None unless this is a bijection between the two sector lists that keeps the multiplicities -- i.e.
+    unless the legs are dual to each other and can be traced."""
+    if a.nsec != b.nsec:
+        return None
+    where = {tuple(q): k for k, q in enumerate(b.sectors.tolist())}
+    want = symmetry.reduce(-a.sign * b.sign * a.sectors).reshape(a.nsec, symmetry.n)
+    out = np.zeros(a.nsec, dtype=np.int64)
+    for i, q in enumerate(want.tolist()):
+        k = where.get(tuple(q))
+        if k is None or int(a.mults[i]) != int(b.mults[k]):
+            return None
+        out[i] = k
+    return out if len(set(out.tolist())) == a.nsec else None
+
+
+def partial_trace(bb, t: AbelianTensor, pairs):
+    """``AbelianBackend::partial_trace`` (abelian.cpp:2954-3081): trace leg ``i`` against leg ``j`` for every ``(i, j)`` of
+    `pairs`.  A pair is traceable if the legs are dual to each other (:func:`dual_sector_map`); a block contributes if its
+    charges cancel on every pair -- one rule for legs on opposite sides and on the same side (:2996-3014).  The remaining legs
+    keep their order, ``num_codomain`` counts those that were in the codomain, and blocks with the same remaining sector
+    indices are summed.  ALL result blocks are computed by ONE ``trace_partial_grouped`` launch; the reference calls
+    ``trace_partial`` per block and adds with ``operator+`` (:3016-3029).  With no remaining leg the result is a Python
+    float / complex (the ``Scalar`` case, :3042-3055; 0 if no block is on the diagonal)."""
+    n = t.nlegs
+    pairs = [(int(i) % n, int(j) % n) for i, j in pairs]
+    traced = [k for p in pairs for k in p]
+    if len(set(traced)) != len(traced):
+        raise ValueError('partial_trace: a leg is listed twice')
+    maps = []
+    for i, j in pairs:
+        m = dual_sector_map(t.symmetry, t.legs[i], t.legs[j])
+        if m is None:
+            raise ValueError(f'partial_trace: legs {i} and {j} are not dual to each other')
+        maps.append(m)
+    idcs1, idcs2 = [i for i, _ in pairs], [j for _, j in pairs]
+    remaining = [k for k in range(n) if k not in traced]
+    bi = t.block_inds
+    on_diag = np.ones(len(t.blocks), dtype=bool)
+    for (i, j), m in zip(pairs, maps):
+        on_diag &= m[bi[:, i]] == bi[:, j]
+    groups: dict = {}
+    for r in np.flatnonzero(on_diag).tolist():    # ascending block index: the summation order of every result block
+        groups.setdefault(tuple(bi[r, remaining].tolist()), []).append(r)
+    legs = [t.legs[k] for k in remaining]
+    if not remaining:
+        if not groups:
+            return 0.0
+        blk = bb.trace_partial_grouped([((), [(t.blocks[r], idcs1, idcs2, []) for r in groups[()]])])[0]
+        return np.asarray(bb.to_numpy(blk)).reshape(()).item()
+    rows = np.array(list(groups.keys()), dtype=np.int64).reshape(len(groups), len(remaining))
+    order = _lexsort_rows(rows)
+    rows = rows[order]
+    members = [groups[tuple(r)] for r in rows.tolist()]
+    outputs = [(tuple(int(l.mults[s]) for l, s in zip(legs, row)), [(t.blocks[r], idcs1, idcs2, remaining) for r in mem])
+               for row, mem in zip(rows.tolist(), members)]
+    blocks = bb.trace_partial_grouped(outputs) if outputs else []
+    labels = [t.labels[k] for k in remaining] if len(t.labels) == n else []
+    return AbelianTensor(t.symmetry, legs, list(blocks), rows, sum(1 for k in remaining if k < t.num_codomain), labels)
+
+
+def trace_full(bb, t: AbelianTensor):
+    """``AbelianBackend::trace_full`` (abelian.cpp:3595-3620): leg ``c`` against leg ``nlegs - 1 - c`` (codomain against
+    domain), through :func:`partial_trace` -- one launch, one number back."""
+    if t.nlegs % 2:
+        raise ValueError('trace_full: the tensor needs as many domain as codomain legs')
+    return partial_trace(bb, t, [(c, t.nlegs - 1 - c) for c in range(t.nlegs // 2)])
+
+
+def _block_slices(legs, row):
+    return tuple(slice(int(l.slices[i]), int(l.slices[i + 1])) for l, i in zip(legs, row))
+
+
+def to_dense_block(bb, t: AbelianTensor):
+    """``AbelianBackend::to_dense_block`` (abelian.cpp:3571-3592): ONE zero-filled block of the full shape, all blocks
+    placed by ONE batched copy (the reference assigns ``res[slices] = block`` per block)."""
+    cplx = any(_is_complex_block(b) for b in t.blocks)
+    dense = bb.zeros_many([tuple(l.dim for l in t.legs)], dtype='complex128' if cplx else None)[0]
+    pairs = []
+    for blk, row in zip(t.blocks, t.block_inds):
+        if cplx and not _is_complex_block(blk):
+            blk = bb.as_complex(blk)
+        pairs.append((bb.get_item(dense, _block_slices(t.legs, row)), blk))
+    if pairs:
+        bb.copy_many(pairs)
+    return dense
+
+
+def from_dense_block(bb, symmetry: Symmetry, legs, block, num_codomain: int = 0, tol=1e-6) -> AbelianTensor:
+    """``AbelianBackend::from_dense_block`` (abelian.cpp:1829-1858): every charge-allowed block (zero ones included) is cut
+    out of the dense `block` by ONE batched copy.  With a `tol` (default: that of symmetric_tensor.h:76) the part of
+    `block` outside the allowed blocks must be small, ``norm(block - projected) <= tol * norm(block)`` -- both norms are
+    reductions on the device -- else ``ValueError('Block is not symmetric up to tolerance.')``."""
+    legs = list(legs)
+    if tuple(block.shape) != tuple(l.dim for l in legs):
+        raise ValueError('from_dense_block: the block does not have the shape of the legs')
+    inds = AbelianTensor.allowed_block_inds(symmetry, legs)
+    cplx = _is_complex_block(block)
+    views = [bb.get_item(block, _block_slices(legs, row)) for row in inds]
+    blocks = bb.empty_many([v.shape for v in views], dtype='complex128' if cplx else None) if views else []
+    if views:
+        bb.copy_many(list(zip(blocks, views)))
+    res = AbelianTensor(symmetry, legs, list(blocks), inds, num_codomain)
+    if tol is not None:
+        projected = to_dense_block(bb, res)
+        diff = bb.linear_combination_many(1.0, [block], -1.0, [projected])
+        if bb.norm_many(diff) > tol * bb.norm_many([block]):
+            raise ValueError('Block is not symmetric up to tolerance.')
+    return res

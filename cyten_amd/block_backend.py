@@ -2651,6 +2651,115 @@ class HipBlockBackend:
         diag = HipBlock(self, t.buf, t.offset, (R, T), (T * T, T + 1))
         return self.reshape(self.sum(diag, 1), rshape)
 
+    def trace_partial_grouped(self, outputs):
+        """``trace_partial`` for a whole tensor, ONE launch.  `outputs`: one ``(remaining_shape, terms)`` per result block,
+        ``terms`` a list of ``(block, idcs1, idcs2, remaining_idcs)`` as `trace_partial` takes them (axis ``idcs1[k]`` is traced
+        against ``idcs2[k]``); a result block is the SUM of the partial traces of its terms (none: zeros).  Sources are read
+        in place through their strides -- no contiguous copy -- and the result blocks live in one pooled allocation.  float64 and
+        complex128 sources; in a list that mixes both, the float64 sources are first promoted to complex128 into one pooled
+        allocation (one memset and one batched copy more, as `mul_many` promotes).  More than ``CYB_MAX_NDIM`` source axes
+        (hence more than 4 pairs): ValueError.  Fixed summation order, bit-identical from run to run (csrc/trace_grouped.hip)."""
+        outputs = [(tuple(int(x) for x in shape), list(terms)) for shape, terms in outputs]
+        srcs = [tm[0] for _, terms in outputs for tm in terms]
+        self._numeric_only(srcs, 'trace_partial_grouped')
+        cplx = any(b.is_complex for b in srcs)
+        nd_max, np_max = _lib.CYB_MAX_NDIM, _lib.CYB_TRACE_MAX_PAIRS
+        # one row per term / per output, written into the descriptor arrays column by column
+        t_pairs, t_rem, t_ext, t_str, t_axes, o_first, o_n, o_shape = [], [], [], [], [], [], [], []
+        zeros_nd, zeros_np = (0,) * nd_max, (0,) * np_max
+
+        def strides_of(st, idcs1, idcs2, remaining):
+            """(strides of the remaining axes, per pair the sum of its two strides), zero-padded"""
+            return ((tuple(st[k] for k in remaining) + zeros_nd)[:nd_max],
+                    (tuple(st[p] + st[q] for p, q in zip(idcs1, idcs2)) + zeros_np)[:np_max])
+
+        for shape, terms in outputs:
+            if len(shape) > nd_max:
+                raise ValueError(f'trace_partial_grouped: more than {nd_max} axes')
+            o_first.append(len(t_pairs))
+            o_n.append(len(terms))
+            o_shape.append((shape + zeros_nd)[:nd_max])
+            for a, idcs1, idcs2, remaining in terms:
+                nd = a.ndim
+                if nd > nd_max:
+                    raise ValueError(f'trace_partial_grouped: a block with more than {nd_max} axes')
+                idcs1, idcs2, remaining = [i % nd for i in idcs1], [i % nd for i in idcs2], [i % nd for i in remaining]
+                if len(idcs1) != len(idcs2) or sorted(idcs1 + idcs2 + remaining) != list(range(nd)):
+                    raise ValueError('trace_partial_grouped: idcs1, idcs2 and remaining_idcs must list every axis once, in pairs')
+                sh, st = a.shape, a.strides
+                if any(sh[p] != sh[q] for p, q in zip(idcs1, idcs2)):
+                    raise ValueError('trace_partial: traced legs do not match')
+                if tuple(sh[k] for k in remaining) != shape:
+                    raise ValueError(f'trace_partial_grouped: remaining axes {tuple(sh[k] for k in remaining)} of a term do not '
+                                     f'have the shape {shape} of its result block')
+                rem_st, pair_st = strides_of(st, idcs1, idcs2, remaining)
+                t_pairs.append(len(idcs1))
+                t_axes.append((idcs1, idcs2, remaining))
+                t_rem.append(rem_st)
+                t_ext.append((tuple(sh[p] for p in idcs1) + zeros_np)[:np_max])
+                t_str.append(pair_st)
+        outs = self._new_many([shape for shape, _ in outputs], cplx)
+        if not outputs:
+            return outs
+        promoted = []      # (kept alive until the launch is enqueued: the term records hold raw addresses)
+        if cplx:
+            real = [i for i, a in enumerate(srcs) if not a.is_complex]
+            if real:
+                promoted = self._new_many([srcs[i].shape for i in real], True, zero=True)
+                self.copy_many([(self._plane(d, 0), srcs[i]) for d, i in zip(promoted, real)])
+                for d, i in zip(promoted, real):    # a C-contiguous copy: its strides replace the source's
+                    idcs1, idcs2, remaining = t_axes[i]
+                    t_rem[i], t_str[i] = strides_of(d.strides, idcs1, idcs2, remaining)
+                    srcs[i] = d
+        oarr = np.zeros(len(outputs), dtype=_lib.TRACE_OUT_DTYPE)
+        oarr['dst'], oarr['ndim'] = [o.ptr for o in outs], [len(shape) for shape, _ in outputs]
+        oarr['first_term'], oarr['n_terms'], oarr['shape'] = o_first, o_n, o_shape
+        n_t = len(srcs)
+        tarr = np.zeros(max(n_t, 1), dtype=_lib.TRACE_TERM_DTYPE)
+        if n_t:
+            tarr['src'], tarr['n_pairs'] = [a.ptr for a in srcs], t_pairs
+            tarr['rem_strides'], tarr['pair_extent'], tarr['pair_stride'] = t_rem, t_ext, t_str
+        fn = self.lib.cyb_trace_grouped_c128 if cplx else self.lib.cyb_trace_grouped_f64
+        self.ctx.sync_stream()
+        _lib.check(fn(self.ctx.handle, oarr.ctypes.data_as(C.POINTER(_lib.TraceOut)), len(outputs),
+                      tarr.ctypes.data_as(C.POINTER(_lib.TraceTerm)), n_t))
+        del promoted
+        return outs
+
+    _UNARY_OPS = {'abs': 0, 'sqrt': 1, 'exp': 2, 'log': 3, 'neg': 4, 'square': 5, 'reciprocal': 6}
+    _UNARY_PARAM_OPS = {'cutoff_inverse': 0, 'stable_log': 1, 'pow': 2}
+
+    def unary_many(self, blocks, op: str, param=None):
+        """An elementwise function of every float64 block of a list, ONE launch: `op` names a function of
+        ``cyb_unary_batched_f64`` (abs, sqrt, exp, log, neg, square, reciprocal) or, with its parameter `param`, of
+        ``cyb_unary_param_batched_f64`` (cutoff_inverse, stable_log, pow) -- the per-block `sqrt` / `cutoff_inverse` / ... are
+        its n = 1 case.  The results live in one pooled allocation."""
+        blocks = list(blocks)
+        if op in self._UNARY_PARAM_OPS:
+            if param is None:
+                raise ValueError(f'unary_many: {op} takes a parameter')
+        elif op not in self._UNARY_OPS:
+            raise ValueError(f'unary_many: unknown function {op!r}')
+        elif param is not None:
+            raise ValueError(f'unary_many: {op} takes no parameter')
+        if any(b.is_complex or b.is_bool for b in blocks):
+            raise NotImplementedError('unary_many is on the device path for float64 blocks')
+        src = self.contiguous_many(blocks)
+        outs = self._new_many([b.shape for b in src])
+        sel = [(a, o) for a, o in zip(src, outs) if a.size]
+        if sel:
+            descs = self._vec_descs([a for a, _ in sel], None, [o for _, o in sel])
+            self.ctx.sync_stream()
+            if op in self._UNARY_PARAM_OPS:
+                _lib.check(self.lib.cyb_unary_param_batched_f64(self.ctx.handle, descs, len(sel), self._UNARY_PARAM_OPS[op], float(param)))
+            else:
+                _lib.check(self.lib.cyb_unary_batched_f64(self.ctx.handle, descs, len(sel), self._UNARY_OPS[op]))
+        return outs
+
+    def empty_many(self, shapes, dtype=None, device=None):
+        """uninitialised blocks of the given shapes in one pooled allocation (destinations of a batched copy)"""
+        return self._new_many(shapes, dtype is not None and np.dtype(dtype).kind == 'c')
+
     def apply_leg_permutations(self, block: HipBlock, perms) -> HipBlock:
         """``block[np.ix_(*perms)]`` (numpy.cpp:1345-1356): one index gather per axis."""
         if len(perms) != block.ndim:

@@ -448,6 +448,40 @@ typedef struct {
 int cyb_lincomb_strided_batched_c128(cyb_ctx_t ctx, const cyb_lincomb_desc* descs, int64_t n, const cyb_lincomb_term_c128* terms,
                                      int64_t n_terms);
 
+/* ---- grouped partial trace ------------------------------------------------------------------------------------
+ * Every result block of AbelianBackend::partial_trace (src/backends/abelian.cpp:2954-3081) in ONE launch: replaces the
+ * per-block block_backend->trace_partial (numpy.cpp:1166-1195: transpose + reshape + trace, a copy of the whole block) and
+ * the Block::operator+ per further contribution to the same result block (abelian.cpp:3026-3029); also the Scalar case
+ * (:3042-3055) and trace_full (:3595-3620).
+ *   out[r] = sum_{t in [first_term, first_term + n_terms)} sum_tau src_t[r . rem_strides_t + tau . pair_stride_t]
+ * for r over `shape` (C order; dst is C-contiguous over these remaining axes) and tau over the pair extents of term t.
+ * pair_stride[p] is the SUM of the source strides of the two traced axes of pair p, so that walking it walks the diagonal
+ * of the pair.  All strides count elements; sources are read in place as strided views.  ndim + 2 * n_pairs <=
+ * CYB_MAX_NDIM.  Entries of pair_extent / pair_stride beyond n_pairs and of shape / rem_strides beyond ndim are ignored.
+ * An output with no terms is written as zero; zero extents and empty lists are valid.  Every output element is summed by
+ * one owner in a fixed order (terms ascending, tau with pair 0 fastest; tree shapes fixed): no atomics, no zero fill,
+ * bit-identical from run to run.  The owner -- one lane, one wave or one workgroup -- is chosen per output record from
+ * its element count and its number of addends (csrc/trace_grouped.hip).  The c128 entry reads and writes interleaved
+ * (re, im) storage, strides counted in complex elements. */
+#define CYB_TRACE_MAX_PAIRS 4
+typedef struct {
+    double* dst;
+    int32_t ndim;     /* number of remaining axes */
+    int32_t reserved;
+    int64_t first_term, n_terms;
+    int64_t shape[CYB_MAX_NDIM];
+} cyb_trace_out;
+typedef struct {
+    const double* src;
+    int32_t n_pairs;
+    int32_t reserved;
+    int64_t rem_strides[CYB_MAX_NDIM];
+    int64_t pair_extent[CYB_TRACE_MAX_PAIRS];
+    int64_t pair_stride[CYB_TRACE_MAX_PAIRS];
+} cyb_trace_term;
+int cyb_trace_grouped_f64(cyb_ctx_t ctx, const cyb_trace_out* outs, int64_t n_outs, const cyb_trace_term* terms, int64_t n_terms);
+int cyb_trace_grouped_c128(cyb_ctx_t ctx, const cyb_trace_out* outs, int64_t n_outs, const cyb_trace_term* terms, int64_t n_terms);
+
 /* ---- truncation of singular values on the device -----------------------------------------
  * TensorBackend::_truncate_singular_values_selection (src/backends/tensor_backend.cpp:139-242) applied to the
  * concatenation of the per-sector singular values WITHOUT the host round trip of
