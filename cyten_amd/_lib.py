@@ -65,6 +65,12 @@ class CopyDesc(C.Structure):
                 ('src_strides', C.c_int64 * CYB_MAX_NDIM)]
 
 
+class PlaceRec(C.Structure):
+    _fields_ = [('src_block', C.c_int32), ('dst_block', C.c_int32), ('ndim', C.c_int32), ('pad', C.c_int32),
+                ('src_offset', C.c_int64), ('dst_offset', C.c_int64), ('shape', C.c_int64 * CYB_MAX_NDIM),
+                ('src_strides', C.c_int64 * CYB_MAX_NDIM), ('dst_strides', C.c_int64 * CYB_MAX_NDIM)]
+
+
 class VecDesc(C.Structure):
     _fields_ = [('x', C.c_void_p), ('y', C.c_void_p), ('out', C.c_void_p), ('n', C.c_int64)]
 
@@ -125,6 +131,7 @@ GEMM_SEG_DTYPE = _np.dtype(GemmSeg)
 GEMM_PROB_DTYPE = _np.dtype(GemmProb)
 VEC_DTYPE = _np.dtype(VecDesc)
 COPY_DTYPE = _np.dtype(CopyDesc)
+PLACE_DTYPE = _np.dtype(PlaceRec)
 SVD_DTYPE = _np.dtype(SvdDesc)
 QR_DTYPE = _np.dtype(QrDesc)
 EIGH_DTYPE = _np.dtype(EighDesc)
@@ -181,6 +188,9 @@ PROTOTYPES = {
     'cyb_eigh_batched_f64': [_ctx, _P(EighDesc), C.c_int64, _P(C.c_int32)],
     'cyb_eigh_batched_ex_f64': [_ctx, _P(EighDesc), C.c_int64, _P(C.c_int32), C.c_int32],
     'cyb_copy_strided_batched': [_ctx, _P(CopyDesc), C.c_int64, C.c_int32],
+    'cyb_place_plan_create': [_ctx, _P(PlaceRec), C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P(_vp)],
+    'cyb_place_plan_enqueue': [_ctx, _vp, _vp, _vp, C.c_int32],
+    'cyb_place_plan_destroy': [_vp],
     'cyb_dot_batched_f64': [_ctx, _P(VecDesc), C.c_int64, _vp],
     'cyb_dot_each_f64': [_ctx, _P(VecDesc), C.c_int64, _vp],
     'cyb_axpby_batched_f64': [_ctx, _P(VecDesc), C.c_int64, C.c_double, C.c_double],

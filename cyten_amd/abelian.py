@@ -23,11 +23,18 @@ reference's ``AbelianBackend`` callers of the block backend (SURVEY.md section 8
   (:743-782), ``::scale_axis`` (:3178-3232), ``::to_dense_block`` (:3571-3592), ``::from_dense_block`` (:1829-1858): one batched
   launch per block list each.
 
+* :class:`LegPipe`, :func:`combine_legs`, :func:`split_legs` <- ``AbelianLegPipe``, ``AbelianBackend::combine_legs`` (:1022-1219) behind
+  the tensor level's permutation, ``::split_legs`` (:3235-3437): any number of leg groups anywhere in the tensor become pipes that
+  can be contracted, decomposed and split again.  ONE launch per kernel class places all old blocks, read through their
+  (permuted) strides, from a device-resident placement plan built once per block structure (``csrc/place_plan.hip``); the split
+  is views, or one plan launch in reverse.
+
 The functions only need the block-backend *interface* (`matrix_dot_grouped`, `matrix_svd_batched`,
 ...), not a particular implementation.
 """
 from __future__ import annotations
 
+import itertools
 import math
 from dataclasses import dataclass, field
 from typing import Sequence
@@ -38,7 +45,7 @@ __all__ = ['Symmetry', 'Leg', 'AbelianTensor', 'compose', 'compose_plan', 'compo
            'truncate_singular_values', 'truncated_svd', 'qr', 'lq', 'eigh', 'norm', 'inner', 'split_matrix_legs', 'partial_compose',
            'Mask', 'mask_contract', 'qr_tensor', 'lq_tensor', 'to_block_backend', 'move_to_device',
            'conj', 'dagger', 'DiagonalTensor', 'diagonal_unary', 'scale_axis', 'partial_trace', 'trace_full', 'to_dense_block',
-           'from_dense_block', 'dual_sector_map']
+           'from_dense_block', 'dual_sector_map', 'LegPipe', 'combine_legs', 'split_legs']
 
 
 class Symmetry:
@@ -261,6 +268,9 @@ def compose_plan(a: AbelianTensor, b: AbelianTensor, num_contr: int) -> ComposeP
     nat = _native_planner()
     if not nat or a.symmetry != b.symmetry:
         return compose_plan_py(a, b, num_contr)
+    for i in range(min(num_contr, a.nlegs, b.nlegs)):   # (the C++ planner compares sectors; pipes also need the same internal order)
+        if isinstance(a.legs[a.nlegs - 1 - i], LegPipe) and not a.legs[a.nlegs - 1 - i].can_contract_with(b.legs[i]):
+            raise ValueError(f'legs a[{a.nlegs - 1 - i}] and b[{i}] are not contractible')
     # the matching depends on the legs and the two block tables only: cached by content like the placement tables of
     # combine_legs (the same structures come back bond after bond, sweep after sweep)
     key = (_legs_key(a.symmetry, a.legs, [l.sign for l in a.legs]), _legs_key(b.symmetry, b.legs, [l.sign for l in b.legs]), num_contr,
@@ -1248,3 +1258,426 @@ def from_dense_block(bb, symmetry: Symmetry, legs, block, num_codomain: int = 0,
         if bb.norm_many(diff) > tol * bb.norm_many([block]):
             raise ValueError('Block is not symmetric up to tolerance.')
     return res
+
+
+# ---------------------------------------------------------------------------------------------
+# leg pipes: combine_legs / split_legs
+# ---------------------------------------------------------------------------------------------
+
+CYB_MAX_NDIM = 8    # most axes a strided copy of the library takes (include/cyten_amd.h)
+
+
+_PIPE_CACHE: dict = {}
+
+
+class LegPipe(Leg):
+    """``AbelianLegPipe`` mirror: the product of k >= 1 legs seen as ONE leg (build it with :meth:`from_legs`).
+
+    Sector ``Q`` of the pipe satisfies ``sign * Q = sum_k sign_k * q_k`` under the moduli; sectors are sorted as `Leg` sorts
+    them and the multiplicity of ``Q`` is the sum of ``prod_k mult`` over the sector combinations that fuse to it.
+
+    * ``block_ind_map``: int64, one row ``[start, stop, i_1 .. i_k, J]`` per sector combination, sorted by ``J``; within a ``J``
+      in C order of ``(i_1 .. i_k)`` (last leg fastest) for ``cstyle=True``, in F order (first leg fastest) otherwise.
+      ``start:stop`` is the slice of sector ``J`` the combination occupies; inside it the basis states run in the same style
+      over the constituents' multiplicities.  ``block_ind_map_slices[J]:block_ind_map_slices[J + 1]`` are the rows of ``J``.
+    * ``basis_perm``: int64 of length ``dim``; entry ``j`` is the flat C index, in the dense product of the constituent legs,
+      of basis state ``j`` of the pipe -- the dense statement of what the pipe is.
+
+    The reference decides the internal order of a pipe by ``combine_cstyle != in_domain`` because its flat leg list reverses
+    the domain; this mirror does not reverse domain legs, so the style of a pipe is its ``cstyle`` wherever it stands, and
+    :meth:`dual` keeps it (no style flip)."""
+
+    def __init__(self, symmetry, sectors, mults, sign, legs, cstyle, block_ind_map, block_ind_map_slices):
+        super().__init__(symmetry, sectors, mults, sign)     # (sectors arrive sorted: the order is kept)
+        self.legs = list(legs)
+        self.cstyle = bool(cstyle)
+        self.block_ind_map = block_ind_map
+        self.block_ind_map_slices = block_ind_map_slices
+        self._shared = {}
+
+    @classmethod
+    def from_legs(cls, symmetry: Symmetry, legs, sign: int = +1, cstyle: bool = True) -> 'LegPipe':
+        legs = list(legs)
+        if not legs:
+            raise ValueError('LegPipe: at least one leg')
+        sign = int(sign)
+        if sign not in (+1, -1):
+            raise ValueError('LegPipe: sign must be +1 or -1')
+        k = len(legs)
+        # the tables depend on the content of the constituents only: built once, shared by every pipe of that content
+        # (callers must not modify them); the pipe object itself is new, so that it holds the legs it was given
+        key = (_legs_key(symmetry, legs, [l.sign for l in legs]), sign, bool(cstyle))
+        hit = _PIPE_CACHE.get(key)
+        if hit is None:
+            # C order of the reversed legs is F order of the legs: fuse the reversed list and turn the index tuples back
+            walk = legs if cstyle else legs[::-1]
+            fmap = _fused_sector_maps(symmetry, walk, [sign * l.sign for l in walk])
+            charges = sorted(fmap.keys(), key=lambda c: tuple(reversed(c)))
+            rows, slices, mults = [], [0], []
+            for J, ch in enumerate(charges):
+                for idx, off, sz in fmap[ch]:
+                    rows.append((off, off + sz) + (idx if cstyle else idx[::-1]) + (J,))
+                slices.append(len(rows))
+                mults.append(fmap[ch][-1][1] + fmap[ch][-1][2])
+            bim = np.array(rows, dtype=np.int64).reshape(len(rows), k + 3)
+            sectors = np.array(charges, dtype=np.int64).reshape(len(charges), symmetry.n)
+            hit = _cache_put(_PIPE_CACHE, key, (sectors, np.array(mults, dtype=np.int64), bim, np.array(slices, dtype=np.int64), {}))
+        sectors, mults, bim, slices, shared = hit
+        pipe = cls(symmetry, sectors, mults, sign, legs, cstyle, bim, slices)
+        pipe._shared = shared        # (lazily built `where` / `basis_perm` of this content)
+        return pipe
+
+    @property
+    def num_legs(self):
+        return len(self.legs)
+
+    def where(self) -> dict:
+        """{(i_1 .. i_k): (J, start, stop)}"""
+        out = self._shared.get('where')
+        if out is None:
+            out = self._shared['where'] = {tuple(r[2:-1]): (r[-1], r[0], r[1]) for r in self.block_ind_map.tolist()}
+        return out
+
+    @property
+    def basis_perm(self) -> np.ndarray:
+        if self._shared.get('basis_perm') is None:
+            dims = [l.dim for l in self.legs]
+            dense_strides = [int(np.prod(dims[i + 1:], dtype=np.int64)) for i in range(len(dims))]
+            out = np.zeros(self.dim, dtype=np.int64)
+            for r in self.block_ind_map.tolist():
+                start, stop, idx, J = r[0], r[1], r[2:-1], r[-1]
+                flat = np.zeros((), dtype=np.int64)
+                for l, i, ds in zip(self.legs, idx, dense_strides):
+                    flat = flat[..., None] + ds * np.arange(int(l.slices[i]), int(l.slices[i + 1]), dtype=np.int64)
+                base = int(self.slices[J])
+                out[base + start:base + stop] = flat.reshape(-1) if self.cstyle else flat.T.reshape(-1)
+            self._shared['basis_perm'] = out
+        return self._shared['basis_perm']
+
+    def dual(self) -> 'LegPipe':
+        """The pipe of the dual legs with the opposite sign: the same sectors, multiplicities, internal order and style."""
+        return LegPipe.from_legs(self.symmetry, [l.dual() for l in self.legs], -self.sign, self.cstyle)
+
+    def can_contract_with(self, other: 'Leg') -> bool:
+        """The base rule; against another pipe also pairwise contractible constituents and the same style (two pipes with
+        equal sectors but another internal order would otherwise contract silently wrong)."""
+        if not Leg.can_contract_with(self, other):
+            return False
+        if isinstance(other, LegPipe):
+            return (self.cstyle == other.cstyle and len(self.legs) == len(other.legs)
+                    and all(a.can_contract_with(b) for a, b in zip(self.legs, other.legs)))
+        return True
+
+    def __repr__(self):
+        return f'LegPipe({len(self.legs)} legs, nsec={self.nsec}, dim={self.dim}, sign={self.sign:+d}, {"C" if self.cstyle else "F"})'
+
+
+def _same_leg(a: Leg, b: Leg) -> bool:
+    return a.sign == b.sign and _same_space(a, b)
+
+
+def _sub_strides(stride: int, mults, cstyle: bool):
+    """strides of the constituent axes a slice of a pipe axis (element stride `stride`) splits into"""
+    out, acc = [0] * len(mults), int(stride)
+    for k in (range(len(mults) - 1, -1, -1) if cstyle else range(len(mults))):
+        out[k] = acc
+        acc *= int(mults[k])
+    return out
+
+
+def _c_strides_of(shape):
+    out, acc = [0] * len(shape), 1
+    for k in range(len(shape) - 1, -1, -1):
+        out[k] = acc
+        acc *= int(shape[k])
+    return out
+
+
+def _place_records(n):
+    from . import _lib
+    return np.zeros(n, dtype=_lib.PLACE_DTYPE)
+
+
+def _block_strides(bb, blocks):
+    """element strides of device blocks (None for the blocks of a backend without placement plans)"""
+    return tuple(tuple(b.strides) for b in blocks) if _has_plans(bb) else None
+
+
+def _has_plans(bb) -> bool:
+    return getattr(bb, 'place_plan', None) is not None
+
+
+_COMBINE_CACHE: dict = {}
+_SPLIT_CACHE: dict = {}
+
+
+def _promote_mixed(bb, blocks):
+    """(blocks, is complex): a list mixing float64 and complex128 blocks is promoted to complex128 first"""
+    # (device blocks answer `is_complex` from their buffer; the dtype property behind _is_complex_block costs more per block)
+    kinds = [b.is_complex for b in blocks] if blocks and hasattr(blocks[0], 'is_complex') else [_is_complex_block(b) for b in blocks]
+    if any(kinds) and not all(kinds):
+        if hasattr(bb, 'as_complex_many'):
+            blocks = bb.as_complex_many(blocks)
+        else:
+            blocks = [b if c else bb.as_complex(b) for b, c in zip(blocks, kinds)]
+    return list(blocks), any(kinds)
+
+
+def combine_legs(bb, t: AbelianTensor, groups, pipes=None, signs=None, cstyle=True, num_codomain=None) -> AbelianTensor:
+    """``AbelianBackend::combine_legs`` (abelian.cpp:1022-1219) behind the tensor level's leg permutation: every group of
+    `groups` (disjoint lists of leg indices, in any order, not necessarily adjacent) becomes ONE :class:`LegPipe`, standing
+    where the first-listed leg of the group stood among the legs that remain; the other legs keep their relative order.
+
+    `pipes`: ready-made pipes (checked against the legs), else they are built with `signs` (default +1 each) and `cstyle`
+    (one flag, or one per group).  Labels become ``'(a.b)'``; ``num_codomain`` defaults to the number of result legs whose
+    first constituent lay in the codomain.  All old blocks that land in one new block are embedded in it, zeros elsewhere;
+    the result is lexsorted.
+
+    The permutation is no separate pass: each old block is read through its (possibly permuted) strides by the SAME launch
+    that writes it to its place.  With a backend that offers ``place_plan`` the records of the structure -- legs, groups,
+    block table, element size, source strides -- become a device-resident plan once (cached by content) and a call uploads
+    the two address tables only; the zero fill is skipped when the old blocks cover the result.  Other backends take
+    ``zeros_many`` + one ``copy_many``."""
+    n = t.nlegs
+    if n > CYB_MAX_NDIM:
+        raise ValueError(f'combine_legs: tensors of more than {CYB_MAX_NDIM} legs are not supported')
+    groups = [[int(i) % n for i in g] for g in groups]
+    flat = [i for g in groups for i in g]
+    if any(len(g) == 0 for g in groups):
+        raise ValueError('combine_legs: empty group')
+    if len(set(flat)) != len(flat):
+        raise ValueError('combine_legs: the groups overlap')
+    ng = len(groups)
+    styles = [bool(cstyle)] * ng if isinstance(cstyle, (bool, int)) else [bool(c) for c in cstyle]
+    signs = [+1] * ng if signs is None else [int(s) for s in signs]
+    if len(styles) != ng or len(signs) != ng or (pipes is not None and len(pipes) != ng):
+        raise ValueError('combine_legs: one pipe / sign / style per group')
+    sym = t.symmetry
+    if pipes is None:
+        pipes = [LegPipe.from_legs(sym, [t.legs[i] for i in g], sg, cs) for g, sg, cs in zip(groups, signs, styles)]
+    else:
+        pipes = list(pipes)
+        for g, p in zip(groups, pipes):
+            if not isinstance(p, LegPipe) or len(p.legs) != len(g) or not all(_same_leg(a, t.legs[i]) for a, i in zip(p.legs, g)):
+                raise ValueError('combine_legs: a pipe does not consist of the legs of its group')
+    # ---- result legs: (group number | None, source legs) in result order
+    first = {g[0]: k for k, g in enumerate(groups)}
+    grouped = set(flat)
+    res = []
+    for i in range(n):
+        if i in first:
+            res.append((first[i], groups[first[i]]))
+        elif i not in grouped:
+            res.append((None, [i]))
+    legs = [t.legs[src[0]] if g is None else pipes[g] for g, src in res]
+    labels = []
+    if len(t.labels) == n:
+        labels = [t.labels[src[0]] if g is None else '(' + '.'.join(str(t.labels[i]) for i in src) + ')' for g, src in res]
+    if num_codomain is None:
+        num_codomain = sum(1 for _, src in res if src[0] < t.num_codomain)
+    if len(t.blocks) == 0:
+        return AbelianTensor(sym, legs, [], np.zeros((0, len(res)), np.int64), num_codomain, labels)
+    blocks, cplx = _promote_mixed(bb, t.blocks)
+    esz = 16 if cplx else 8
+    native = _has_plans(bb)
+    binds = np.ascontiguousarray(t.block_inds, dtype=np.int64)
+    key = (_legs_key(sym, t.legs, [l.sign for l in t.legs]), tuple(map(tuple, groups)), tuple((p.sign, p.cstyle) for p in pipes),
+           binds.shape, binds.tobytes(), esz, _block_strides(bb, blocks))
+    plan = _COMBINE_CACHE.get(key)
+    if plan is None:
+        plan = _cache_put(_COMBINE_CACHE, key, _combine_plan(t.legs, binds, res, pipes, legs,
+                                                             [tuple(b.strides) for b in blocks] if native else None))
+    new_rows, new_shapes = plan['rows'], plan['shapes']
+    if native:
+        if plan.get('native') is None:
+            plan['native'] = bb.place_plan(plan['records'], len(blocks), len(new_shapes), esz)
+        dt = 'complex128' if cplx else None
+        new_blocks = bb.empty_many(new_shapes, dtype=dt) if plan['covers'] else bb.zeros_many(new_shapes, dtype=dt)
+        # address tables from the blocks at hand (never from a cached table: block lists are mutable)
+        bb.place_enqueue(plan['native'], [b.ptr for b in blocks], [b.ptr for b in new_blocks])
+    else:
+        new_blocks = bb.zeros_many(new_shapes, dtype='complex128' if cplx else None)
+        pairs = []
+        for blk, (dst, key_sl, perm, merged) in zip(blocks, plan['generic']):
+            pairs.append((bb.get_item(new_blocks[dst], key_sl), bb.reshape(bb.permute_axes(blk, perm), merged)))
+        bb.copy_many(pairs)
+    return AbelianTensor(sym, legs, list(new_blocks), new_rows.copy(), num_codomain, labels)
+
+
+def _combine_plan(old_legs, binds, res, pipes, legs, src_strides):
+    """The placement of one combine_legs structure: result block table (lexsorted, no duplicates), result shapes, and per
+    old block where it goes -- as placement records (`src_strides` given) and as (slices, axis order, merged shape) for
+    the generic route."""
+    nres = len(res)
+    rows = np.zeros((len(binds), nres), dtype=np.int64)
+    starts = np.zeros((len(binds), nres), dtype=np.int64)
+    stops = np.zeros((len(binds), nres), dtype=np.int64)
+    bl = binds.tolist()
+    for r, (g, src) in enumerate(res):
+        if g is None:
+            rows[:, r] = binds[:, src[0]]
+            stops[:, r] = old_legs[src[0]].mults[binds[:, src[0]]]
+        else:
+            where = pipes[g].where()
+            for b, row in enumerate(bl):
+                rows[b, r], starts[b, r], stops[b, r] = where[tuple(row[i] for i in src)]
+    order = _lexsort_rows(rows)
+    srt = rows[order]
+    new_of = np.zeros(len(binds), dtype=np.int64)
+    if len(srt):
+        is_new = np.concatenate([[True], np.any(srt[1:] != srt[:-1], axis=1)])
+        new_of[order] = np.cumsum(is_new) - 1
+        new_rows = srt[is_new]
+    else:
+        new_rows = srt
+    shapes = [tuple(int(l.mults[i]) for l, i in zip(legs, row)) for row in new_rows.tolist()]
+    # axis order of the source: result order, the constituents of a pipe in the order the pipe lists them
+    perm_c = [i for _, src in res for i in src]
+    out = dict(rows=new_rows, shapes=shapes, generic=[], records=None, native=None)
+    placed = 0
+    recs = _place_records(len(binds)) if src_strides is not None else None
+    for b, row in enumerate(bl):
+        dst = int(new_of[b])
+        dstr = _c_strides_of(shapes[dst])
+        ext = [int(old_legs[i].mults[row[i]]) for i in range(len(row))]
+        placed += math.prod(ext)
+        # generic route: an F-style pipe reads its constituents in reversed axis order, so that a C-order reshape merges them
+        perm_g, merged = [], []
+        for r, (g, src) in enumerate(res):
+            perm_g += src if (g is None or pipes[g].cstyle) else src[::-1]
+            merged.append(int(stops[b, r] - starts[b, r]))
+        key_sl = tuple(slice(int(starts[b, r]), int(stops[b, r])) for r in range(nres))
+        out['generic'].append((dst, key_sl, perm_g, merged))
+        if recs is not None:
+            ds, off = [], 0
+            for r, (g, src) in enumerate(res):
+                off += int(starts[b, r]) * dstr[r]
+                ds += [dstr[r]] if g is None else _sub_strides(dstr[r], [ext[i] for i in src], pipes[g].cstyle)
+            nd = len(perm_c)
+            rec = recs[b]
+            rec['src_block'], rec['dst_block'], rec['ndim'], rec['dst_offset'] = b, dst, nd, off
+            rec['shape'][:nd] = [ext[i] for i in perm_c]
+            rec['src_strides'][:nd] = [src_strides[b][i] for i in perm_c]
+            rec['dst_strides'][:nd] = ds
+    out['records'] = recs
+    out['covers'] = placed == sum(math.prod(sh) for sh in shapes)    # (distinct old blocks never overlap: equal sizes = all covered)
+    return out
+
+
+def _split_label(label, k):
+    """the k labels inside ``'(a.b)'`` (dots inside nested brackets do not split), else ``label.0 .. label.k-1``"""
+    s = str(label)
+    if s.startswith('(') and s.endswith(')'):
+        parts, depth, cur = [], 0, ''
+        for ch in s[1:-1]:
+            depth += ch == '('
+            depth -= ch == ')'
+            if ch == '.' and depth == 0:
+                parts.append(cur)
+                cur = ''
+            else:
+                cur += ch
+        parts.append(cur)
+        if len(parts) == k:
+            return parts
+    return [f'{s}.{j}' for j in range(k)]
+
+
+def split_legs(bb, t: AbelianTensor, leg_idcs=None, contiguous: bool = False) -> AbelianTensor:
+    """``AbelianBackend::split_legs`` (abelian.cpp:3235-3437), the inverse of :func:`combine_legs`: every leg of `leg_idcs`
+    (default: all legs that are pipes; one level of nesting per call) is replaced by its constituents.  Every old block
+    yields one new block per row of the pipe's ``block_ind_map`` inside its sector (for several split legs: per element of
+    the product of the rows): the slice ``start:stop`` of that axis, reshaped into the constituent extents (reversed
+    sub-axes for an F-style pipe).  Slicing and splitting an axis is always expressible in strides, so the new blocks are
+    VIEWS of the old ones (no launch; the next ``compose`` makes contiguous what it needs).  ``contiguous=True`` gathers all
+    new blocks into one pooled allocation with one placement-plan launch (``reverse``: the plan's records are those of the
+    combination that would undo the split)."""
+    n = t.nlegs
+    if leg_idcs is None:
+        leg_idcs = [i for i, l in enumerate(t.legs) if isinstance(l, LegPipe)]
+    leg_idcs = sorted({int(i) % n for i in leg_idcs})
+    for i in leg_idcs:
+        if not isinstance(t.legs[i], LegPipe):
+            raise ValueError('Not a LegPipe.')
+    split = set(leg_idcs)
+    legs, labels = [], []
+    have_labels = len(t.labels) == n
+    for i, l in enumerate(t.legs):
+        legs += l.legs if i in split else [l]
+        if have_labels:
+            labels += _split_label(t.labels[i], len(l.legs)) if i in split else [t.labels[i]]
+    if len(legs) > CYB_MAX_NDIM:
+        raise ValueError(f'split_legs: tensors of more than {CYB_MAX_NDIM} legs are not supported')
+    num_codomain = sum(len(t.legs[i].legs) if i in split else 1 for i in range(min(t.num_codomain, n)))
+    sym = t.symmetry
+    if len(t.blocks) == 0:
+        return AbelianTensor(sym, legs, [], np.zeros((0, len(legs)), np.int64), num_codomain, labels)
+    new_rows, views, origin = [], [], []     # origin: (old block, [(old axis, start, constituent extents, cstyle) ...])
+    for b, (blk, row) in enumerate(zip(t.blocks, t.block_inds.tolist())):
+        choices = []
+        for i in leg_idcs:
+            p = t.legs[i]
+            lo, hi = int(p.block_ind_map_slices[row[i]]), int(p.block_ind_map_slices[row[i] + 1])
+            choices.append(p.block_ind_map[lo:hi].tolist())
+        for combo in itertools.product(*choices):
+            key_sl, shape, perm, new_row, parts = [slice(None)] * n, [], [], [], []
+            it = iter(combo)
+            for i, l in enumerate(t.legs):
+                if i not in split:
+                    shape.append(int(l.mults[row[i]]))
+                    perm.append(len(perm))
+                    new_row.append(row[i])
+                    continue
+                m = next(it)
+                idx = m[2:-1]
+                ext = [int(c.mults[j]) for c, j in zip(l.legs, idx)]
+                key_sl[i] = slice(m[0], m[1])
+                k0 = len(perm)
+                shape += ext if l.cstyle else ext[::-1]
+                perm += list(range(k0, k0 + len(ext))) if l.cstyle else list(range(k0 + len(ext) - 1, k0 - 1, -1))
+                new_row += idx
+                parts.append((i, m[0], ext, l.cstyle))
+            v = bb.reshape(bb.get_item(blk, tuple(key_sl)), shape)
+            views.append(v if perm == sorted(perm) else bb.permute_axes(v, perm))
+            new_rows.append(new_row)
+            origin.append((b, parts))
+    new_rows = np.array(new_rows, dtype=np.int64).reshape(len(views), len(legs))
+    if contiguous and _has_plans(bb):
+        views = _split_gather(bb, t, leg_idcs, [v.shape for v in views], origin)
+    elif contiguous:
+        views = bb.contiguous_many(views)
+    return AbelianTensor(sym, legs, list(views), new_rows, num_codomain, labels).sorted()
+
+
+def _split_gather(bb, t, leg_idcs, shapes, origin):
+    """the new blocks of a split as C-contiguous blocks of ONE pool, gathered by one placement-plan launch in reverse"""
+    blocks, cplx = _promote_mixed(bb, t.blocks)
+    esz = 16 if cplx else 8
+    binds = np.ascontiguousarray(t.block_inds, dtype=np.int64)
+    key = (_legs_key(t.symmetry, t.legs, [l.sign for l in t.legs]),
+           tuple((i, t.legs[i].cstyle, _legs_key(t.symmetry, t.legs[i].legs, [l.sign for l in t.legs[i].legs])) for i in leg_idcs),
+           binds.shape, binds.tobytes(), esz, _block_strides(bb, blocks))
+    plan = _SPLIT_CACHE.get(key)
+    if plan is None:
+        recs = _place_records(len(shapes))
+        for j, (shape, (b, parts)) in enumerate(zip(shapes, origin)):
+            old = blocks[b].strides
+            by_axis = {i: (start, ext, cs) for i, start, ext, cs in parts}
+            ds, off = [], 0
+            for i in range(t.nlegs):
+                if i in by_axis:
+                    start, ext, cs = by_axis[i]
+                    off += start * old[i]
+                    ds += _sub_strides(old[i], ext, cs)
+                else:
+                    ds.append(old[i])
+            nd = len(shape)
+            rec = recs[j]
+            rec['src_block'], rec['dst_block'], rec['ndim'], rec['dst_offset'] = j, b, nd, off
+            rec['shape'][:nd] = shape
+            rec['src_strides'][:nd] = _c_strides_of(shape)
+            rec['dst_strides'][:nd] = ds
+        plan = _cache_put(_SPLIT_CACHE, key, dict(native=bb.place_plan(recs, len(shapes), len(blocks), esz)))
+    new_blocks = bb.empty_many(shapes, dtype='complex128' if cplx else None)
+    bb.place_enqueue(plan['native'], [b.ptr for b in new_blocks], [b.ptr for b in blocks], reverse=True)
+    return new_blocks

@@ -467,6 +467,19 @@ class GemmPlan:
             pass
 
 
+class PlacePlan:
+    """owner of a `cyb_place_plan_t` (``HipBlockBackend.place_plan``)"""
+
+    def __init__(self, lib, handle, n_src, n_dst):
+        self.lib, self.handle, self.n_src, self.n_dst = lib, handle, n_src, n_dst
+
+    def __del__(self):
+        try:
+            self.lib.cyb_place_plan_destroy(self.handle)
+        except Exception:
+            pass
+
+
 class HipBlockBackend:
     """MI355X block backend (see module docstring)."""
 
@@ -944,6 +957,40 @@ class HipBlockBackend:
                 return
         self.ctx.sync_stream()
         _lib.check(self.lib.cyb_copy_strided_batched(self.ctx.handle, arr.ctypes.data_as(C.POINTER(_lib.CopyDesc)), len(arr), elem_size))
+
+    def as_complex_many(self, blocks):
+        """``as_complex`` of a block list: the float64 blocks among them become complex128 copies in ONE pooled allocation
+        (one memset, one batched copy); complex blocks are returned as they are."""
+        outs = list(blocks)
+        real = [i for i, b in enumerate(outs) if not b.is_complex]
+        if real:
+            new = self._new_many([outs[i].shape for i in real], True, zero=True)
+            self.copy_many([(self._plane(d, 0), outs[i]) for d, i in zip(new, real)])
+            for d, i in zip(new, real):
+                outs[i] = d
+        return outs
+
+    def place_plan(self, records, n_src: int, n_dst: int, elem_size: int) -> 'PlacePlan':
+        """``cyb_place_plan_create``: the strided copies `records` (numpy array of ``_lib.PLACE_DTYPE``: block numbers into
+        two address tables, offsets, shape, strides) normalised, classified, cut into work items and stored on the device
+        ONCE.  The returned object owns the handle."""
+        records = np.ascontiguousarray(records, dtype=_lib.PLACE_DTYPE)
+        handle = C.c_void_p()
+        _lib.check(self.lib.cyb_place_plan_create(self.ctx.handle, records.ctypes.data_as(C.POINTER(_lib.PlaceRec)), len(records),
+                                                  int(n_src), int(n_dst), int(elem_size), C.byref(handle)))
+        return PlacePlan(self.lib, handle, int(n_src), int(n_dst))
+
+    def place_enqueue(self, plan: 'PlacePlan', src_ptrs, dst_ptrs, reverse: bool = False):
+        """``cyb_place_plan_enqueue``: run `plan` on the blocks whose device addresses are `src_ptrs` / `dst_ptrs` (one per
+        row of the tables the records index); ``reverse``: copy from the dst side to the src side.  One upload of the two
+        tables, at most one launch per kernel class.  The caller keeps the blocks alive until the stream has run."""
+        src_ptrs = np.ascontiguousarray(src_ptrs, dtype=np.int64)
+        dst_ptrs = np.ascontiguousarray(dst_ptrs, dtype=np.int64)
+        if len(src_ptrs) != plan.n_src or len(dst_ptrs) != plan.n_dst:
+            raise ValueError(f'place_enqueue: the plan expects tables of {plan.n_src} and {plan.n_dst} addresses')
+        self.ctx.sync_stream()
+        _lib.check(self.lib.cyb_place_plan_enqueue(self.ctx.handle, plan.handle, src_ptrs.ctypes.data, dst_ptrs.ctypes.data,
+                                                   1 if reverse else 0))
 
     def contiguous(self, a: HipBlock) -> HipBlock:
         if a.is_contiguous():
@@ -2933,7 +2980,8 @@ _INT_BINARY_OPS = (0, 1, 2)     # `_binary` op codes add / sub / mul
 _POLICY_SKIP = frozenset({'to_dtype', 'to_numpy', 'as_scalar', 'block_from_numpy', 'as_block', 'get_dtype', 'get_shape', 'get_device', 'is_real',
                           'synchronize', 'test_block_sanity', 'is_correct_block_type', 'as_device', 'possible_svd_algorithms',
                           'get_backend_name', 'concatenate_to_numpy', 'item', 'get_block_element', 'block_from_hdf5', 'make_gemm_plan',
-                          'truncate_select', 'argsort', 'abs_argmax', 'argmin', 'any', 'all', 'allclose', 'get_block_mask_element'})
+                          'truncate_select', 'argsort', 'abs_argmax', 'argmin', 'any', 'all', 'allclose', 'get_block_mask_element',
+                          'place_plan', 'place_enqueue'})
 _CREATE_WITH_DTYPE = frozenset({'zeros', 'zeros_many', 'ones_block', 'eye_matrix', 'eye_block', 'random_normal', 'random_uniform',
                                 'block_from_mask'})
 

@@ -8,31 +8,13 @@
 // LIST instead of one numpy call per block.  All are bandwidth-class work: 16-B accesses where
 // the layout allows, grid-stride loops, deterministic two-stage reductions (no float atomics).
 #include "common.h"
+#include "copy_kernels.h"
 
 #include <algorithm>
 
 namespace {
 
-#define GLOBAL_AS __attribute__((address_space(1)))
-typedef GLOBAL_AS double* gp;
-typedef const GLOBAL_AS double* gcp;
-
-constexpr int NT = 256;
-constexpr int64_t CHUNK = 1 << 16; // largest number of elements per workgroup work item
-// Work-item size for a list of `total` elements: 64 K elements once the list fills the chip eight workgroups per CU
-// deep, smaller (down to 8 K, always a multiple of 1024) for the 10-100 MB lists of one tensor operation, which
-// would otherwise run as a few hundred workgroups on 256 CUs.
-static int64_t chunk_for(int64_t total)
-{
-    int64_t c = ((total / 2048) + 1023) & ~(int64_t)1023;
-    return std::min(CHUNK, std::max<int64_t>(8192, c));
-}
-
-struct Item {
-    int32_t desc;
-    int32_t pad;
-    int64_t start, count;
-};
+using namespace cyb_copy; // GLOBAL_AS, NT, chunk_for, Item, the copy descriptors and device bodies
 
 template <typename D>
 static int make_items(const D* descs, int64_t n, std::vector<Item>& items, int64_t (*count_of)(const D&))
@@ -61,127 +43,14 @@ __device__ __forceinline__ double wave_max(double v)
 }
 
 // ---------------------------------------------------------------------------------------------
-// strided copy
-struct CopyDev {
-    void* dst;
-    const void* src;
-    int32_t ndim, conj;
-    int64_t total;
-    int64_t shape[CYB_MAX_NDIM];
-    int64_t ds[CYB_MAX_NDIM];
-    int64_t ss[CYB_MAX_NDIM];
-};
-
-typedef unsigned long long u128 __attribute__((ext_vector_type(2)));
-
-// One wave copies one contiguous run of n elements: 16-byte accesses when source and destination are misaligned the
-// same way (one element peeled), four independent accesses in flight per lane.
-template <typename V>
-__device__ __forceinline__ void wave_copy_run(const GLOBAL_AS V* sp, GLOBAL_AS V* dp, int64_t n, int lane, int W = 64)
-{
-    int64_t i = lane;
-    for (; i + 3 * W < n; i += 4 * W) {
-        const V a = sp[i], b = sp[i + W], c = sp[i + 2 * W], e = sp[i + 3 * W];
-        dp[i] = a;
-        dp[i + W] = b;
-        dp[i + 2 * W] = c;
-        dp[i + 3 * W] = e;
-    }
-    for (; i < n; i += W) dp[i] = sp[i];
-}
-// W = 64: the calling wave owns the run; W = NT: the whole workgroup shares it (lane = threadIdx.x)
-__device__ __forceinline__ void wave_copy_row8(const GLOBAL_AS uint64_t* sp, GLOBAL_AS uint64_t* dp, int64_t n, int lane, int W = 64)
-{
-    if (n <= 0) return;
-    const unsigned ms = (unsigned)((uintptr_t)sp & 15), md = (unsigned)((uintptr_t)dp & 15);
-    if (ms != md) {
-        wave_copy_run<uint64_t>(sp, dp, n, lane, W);
-        return;
-    }
-    if (ms) {
-        if (lane == 0) dp[0] = sp[0];
-        ++sp, ++dp, --n;
-    }
-    wave_copy_run<u128>((const GLOBAL_AS u128*)sp, (GLOBAL_AS u128*)dp, n >> 1, lane, W);
-    if ((n & 1) && lane == 0) dp[n - 1] = sp[n - 1];
-}
-
+// strided copy (device bodies: copy_kernels.h)
 template <typename T>
 __global__ void __launch_bounds__(NT) copy_strided_kernel(const CopyDev* __restrict__ descs, const Item* __restrict__ items)
 {
     const Item it = items[blockIdx.x];
     const CopyDev d = descs[it.desc];
-    const GLOBAL_AS T* src = (const GLOBAL_AS T*)d.src;
-    GLOBAL_AS T* dst = (GLOBAL_AS T*)d.dst;
-    // The innermost (merged) axis is contiguous on both sides in most copies (plain copies, the sub-block scatter of
-    // combine_legs, the gather of split_legs, permutations that keep the last axis): every wave walks whole rows of it
-    // -- no division per element, the outer index is decoded once per row, 16-byte accesses where the alignment allows.
-    const int last = d.ndim - 1;
-    if (d.ndim >= 1 && d.ss[last] == 1 && d.ds[last] == 1 && d.shape[last] >= 16 && !(sizeof(T) == 16 && d.conj)) {
-        const int64_t inner = d.shape[last];
-        const int64_t e0 = it.start, e1 = it.start + it.count;
-        const int64_t r0 = e0 / inner, r1 = (e1 - 1) / inner;
-        // short rows: one wave per row (four rows in flight per workgroup); long rows: the waves share a row
-        const bool shared_row = inner >= 2048;
-        const int wave = shared_row ? 0 : (int)(threadIdx.x >> 6), lane = shared_row ? (int)threadIdx.x : (int)(threadIdx.x & 63);
-        for (int64_t row = r0 + wave; row <= r1; row += shared_row ? 1 : NT / 64) {
-            const int64_t c0 = (row == r0) ? e0 - r0 * inner : 0;
-            const int64_t c1 = (row == r1) ? e1 - r1 * inner : inner;
-            int64_t rem = row, so = 0, dof = 0;
-            for (int k = last - 1; k >= 0; --k) {
-                const int64_t sh = d.shape[k];
-                const int64_t q = rem / sh, i = rem - q * sh;
-                rem = q;
-                so += i * d.ss[k];
-                dof += i * d.ds[k];
-            }
-            const GLOBAL_AS T* sp = src + so + c0;
-            GLOBAL_AS T* dp = dst + dof + c0;
-            const int W = shared_row ? NT : 64;
-            if constexpr (sizeof(T) == 8) wave_copy_row8((const GLOBAL_AS uint64_t*)sp, (GLOBAL_AS uint64_t*)dp, c1 - c0, lane, W);
-            else wave_copy_run<T>(sp, dp, c1 - c0, lane, W);
-        }
-        return;
-    }
-    for (int64_t e = it.start + threadIdx.x; e < it.start + it.count; e += NT) {
-        int64_t rem = e, so = 0, dof = 0;
-#pragma unroll
-        for (int k = CYB_MAX_NDIM - 1; k >= 0; --k) {
-            if (k < d.ndim) {
-                const int64_t sh = d.shape[k];
-                const int64_t q = rem / sh, i = rem - q * sh;
-                rem = q;
-                so += i * d.ss[k];
-                dof += i * d.ds[k];
-            }
-        }
-        T v = src[so];
-        if constexpr (sizeof(T) == 16) {
-            if (d.conj) v.y ^= 0x8000000000000000ull; // flip the sign of the imaginary part
-        }
-        dst[dof] = v;
-    }
+    copy_strided_body<T>(d, (const GLOBAL_AS T*)d.src, (GLOBAL_AS T*)d.dst, it);
 }
-
-
-// Transposing copies (the fastest axis of the destination is not the fastest axis of the source: permute_axes
-// of a compose operand, the leg rotations of a Krylov matvec): 32 x 32 tiles through LDS so that BOTH the reads
-// (along the source's unit-stride axis S) and the writes (along the destination's unit-stride axis D) are
-// coalesced, and the index arithmetic (64-bit div/mod over up to 8 axes) runs once per tile, not per element.
-struct CopyT {
-    void* dst;
-    const void* src;
-    int32_t n_outer, conj;
-    int64_t nS, nD;       // extents of the two tiled axes
-    int64_t ssD, dsS;     // source stride of D, destination stride of S (ss of S and ds of D are 1)
-    // A tiled axis may be the flattening of TWO axes that are contiguous on its own side (a short innermost axis
-    // such as the MPO bond of [.., vR, wR] and its neighbour): index i of D then sits at source offset
-    // (i / nD2) * ssD + (i % nD2) * ssD2, index i of S at destination offset (i / nS2) * dsS + (i % nS2) * dsS2.
-    // nD2 = nS2 = 1 for a plain axis.
-    int64_t nD2, ssD2, nS2, dsS2;
-    int64_t tilesS, tilesD;
-    int64_t oshape[CYB_MAX_NDIM], ods[CYB_MAX_NDIM], oss[CYB_MAX_NDIM]; // the remaining (outer) axes
-};
 
 template <typename T>
 __global__ void __launch_bounds__(NT) copy_transpose_kernel(const CopyT* __restrict__ descs, const Item* __restrict__ items)
@@ -189,106 +58,17 @@ __global__ void __launch_bounds__(NT) copy_transpose_kernel(const CopyT* __restr
     __shared__ T tile[32][33];
     const Item it = items[blockIdx.x];
     const CopyT d = descs[it.desc];
-    const GLOBAL_AS T* src = (const GLOBAL_AS T*)d.src;
-    GLOBAL_AS T* dst = (GLOBAL_AS T*)d.dst;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    for (int64_t t = it.start; t < it.start + it.count; ++t) {
-        int64_t rem = t;
-        const int64_t td = rem % d.tilesD;
-        rem /= d.tilesD;
-        const int64_t ts = rem % d.tilesS;
-        rem /= d.tilesS;
-        int64_t so = 0, dof = 0;
-        for (int k = d.n_outer - 1; k >= 0; --k) {
-            const int64_t q = rem / d.oshape[k], i = rem - q * d.oshape[k];
-            rem = q;
-            so += i * d.oss[k];
-            dof += i * d.ods[k];
-        }
-        const int64_t s0 = ts * 32, d0 = td * 32;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int64_t sI = s0 + tx, dI = d0 + ty + 8 * q;
-            if (sI < d.nS && dI < d.nD) {
-                T v = src[so + sI + (dI / d.nD2) * d.ssD + (dI % d.nD2) * d.ssD2];
-                if constexpr (sizeof(T) == 16) {
-                    if (d.conj) v.y ^= 0x8000000000000000ull;
-                }
-                tile[ty + 8 * q][tx] = v;
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int64_t dI = d0 + tx, sI = s0 + ty + 8 * q;
-            if (sI < d.nS && dI < d.nD) dst[dof + dI + (sI / d.nS2) * d.dsS + (sI % d.nS2) * d.dsS2] = tile[tx][ty + 8 * q];
-        }
-        __syncthreads();
-    }
+    copy_transpose_body<T>(d, (const GLOBAL_AS T*)d.src, (GLOBAL_AS T*)d.dst, it, tile);
 }
 
-// 8-byte elements: 64 x 64 tiles, two elements per 16-byte access on both sides (falls back to 8-byte accesses
-// row by row when a row start is not 16-byte aligned).  LDS image is [s][d] so that the write phase reads pairs.
 __global__ void __launch_bounds__(NT) copy_transpose64_kernel(const CopyT* __restrict__ descs, const Item* __restrict__ items)
 {
-    typedef double d2v __attribute__((ext_vector_type(2)));
-    constexpr int TS = 64, LS = TS + 2;
-    __shared__ __attribute__((aligned(16))) double tile[TS * LS]; // tile[s * LS + d]
+    __shared__ __attribute__((aligned(16))) double tile[T64_TS * T64_LS];
     const Item it = items[blockIdx.x];
     const CopyT d = descs[it.desc];
-    gcp src = (gcp)d.src;
-    gp dst = (gp)d.dst;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    for (int64_t t = it.start; t < it.start + it.count; ++t) {
-        int64_t rem = t;
-        const int64_t td = rem % d.tilesD;
-        rem /= d.tilesD;
-        const int64_t ts = rem % d.tilesS;
-        rem /= d.tilesS;
-        int64_t so = 0, dof = 0;
-        for (int k = d.n_outer - 1; k >= 0; --k) {
-            const int64_t q = rem / d.oshape[k], i = rem - q * d.oshape[k];
-            rem = q;
-            so += i * d.oss[k];
-            dof += i * d.ods[k];
-        }
-        const int64_t s0 = ts * TS, d0 = td * TS;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) { // read: rows along D, pairs along S
-            const int64_t dI = d0 + ty + 8 * q, sI = s0 + 2 * tx;
-            if (dI < d.nD && sI < d.nS) {
-                gcp p = src + so + (dI / d.nD2) * d.ssD + (dI % d.nD2) * d.ssD2 + sI;
-                double v0, v1 = 0.0;
-                if (sI + 1 < d.nS && (((uintptr_t)p) & 15) == 0) {
-                    const d2v v = *(const GLOBAL_AS d2v*)p;
-                    v0 = v.x;
-                    v1 = v.y;
-                } else {
-                    v0 = p[0];
-                    if (sI + 1 < d.nS) v1 = p[1];
-                }
-                tile[(2 * tx) * LS + ty + 8 * q] = v0;
-                tile[(2 * tx + 1) * LS + ty + 8 * q] = v1;
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 8; ++q) { // write: rows along S, pairs along D
-            const int64_t sI = s0 + ty + 8 * q, dI = d0 + 2 * tx;
-            if (sI < d.nS && dI < d.nD) {
-                gp p = dst + dof + (sI / d.nS2) * d.dsS + (sI % d.nS2) * d.dsS2 + dI;
-                const d2v v = *reinterpret_cast<const d2v*>(&tile[(ty + 8 * q) * LS + 2 * tx]);
-                if (dI + 1 < d.nD && (((uintptr_t)p) & 15) == 0) {
-                    *(GLOBAL_AS d2v*)p = v;
-                } else {
-                    p[0] = v.x;
-                    if (dI + 1 < d.nD) p[1] = v.y;
-                }
-            }
-        }
-        __syncthreads();
-    }
+    copy_transpose64_body(d, (gcp)d.src, (gp)d.dst, it, tile);
 }
+
 
 // ---------------------------------------------------------------------------------------------
 // complex128 support of the tdot path.  A complex block is stored interleaved (re, im) like numpy's
@@ -1065,90 +845,19 @@ int cyb_copy_strided_batched(cyb_ctx_t ctx, const cyb_copy_desc* descs, int64_t 
         c.dst = d.dst;
         c.src = d.src;
         c.conj = d.conj;
-        int64_t tot = 1;
         // drop singleton axes and merge axes that are contiguous in BOTH operands
-        int nd = 0;
-        for (int k = 0; k < d.ndim; ++k) {
-            CYB_REQUIRE(d.shape[k] >= 0, "copy desc %lld: negative extent", (long long)i);
-            tot *= d.shape[k];
-            if (d.shape[k] == 1) continue;
-            if (nd > 0 && c.ds[nd - 1] == d.dst_strides[k] * d.shape[k] && c.ss[nd - 1] == d.src_strides[k] * d.shape[k]) {
-                c.shape[nd - 1] *= d.shape[k];
-                c.ds[nd - 1] = d.dst_strides[k];
-                c.ss[nd - 1] = d.src_strides[k];
-            } else {
-                c.shape[nd] = d.shape[k];
-                c.ds[nd] = d.dst_strides[k];
-                c.ss[nd] = d.src_strides[k];
-                ++nd;
-            }
-        }
-        for (int k = nd; k < CYB_MAX_NDIM; ++k) {
-            c.shape[k] = 1;
-            c.ds[k] = c.ss[k] = 0;
-        }
-        c.ndim = nd;
-        c.total = tot;
+        CYB_REQUIRE(normalize_copy(d.shape, d.dst_strides, d.src_strides, d.ndim, c), "copy desc %lld: negative extent", (long long)i);
+        const int64_t tot = c.total;
         CYB_REQUIRE(tot == 0 || (d.dst && d.src), "copy desc %lld: NULL pointer", (long long)i);
-        // transposing copy?  (unit-stride axes of source and destination differ and are both long enough)
-        int aS = -1, aD = -1;
-        for (int k = 0; k < nd; ++k) {
-            if (c.ss[k] == 1 && aS < 0) aS = k;
-            if (c.ds[k] == 1 && aD < 0) aD = k;
-        }
         static const bool no_tiled = getenv("CYB_COPY_NOTILED") != nullptr;
-        // a short unit-stride axis may be flattened with the axis that is next-contiguous on the same side
-        int pD = -1, pS = -1; // partner axes (outer halves of the composites)
-        if (aS >= 0 && aD >= 0 && aS != aD) {
-            if (c.shape[aD] < 16)
-                for (int k = 0; k < nd; ++k)
-                    if (k != aD && k != aS && c.ds[k] == c.shape[aD]) pD = k;
-            if (c.shape[aS] < 16)
-                for (int k = 0; k < nd; ++k)
-                    if (k != aS && k != aD && k != pD && c.ss[k] == c.shape[aS]) pS = k;
-        }
-        const int64_t extS = aS >= 0 ? c.shape[aS] * (pS >= 0 ? c.shape[pS] : 1) : 0;
-        const int64_t extD = aD >= 0 ? c.shape[aD] * (pD >= 0 ? c.shape[pD] : 1) : 0;
-        if (!no_tiled && tot > 0 && aS >= 0 && aD >= 0 && aS != aD && extS >= 16 && extD >= 16) {
-            CopyT t;
-            memset(&t, 0, sizeof(t));
+        const int64_t tsz = (elem_size == 8 && !d.conj) ? 64 : 32;
+        CopyT t;
+        int64_t ntile = 0;
+        if (!no_tiled && classify_transpose(c, tsz, t, ntile)) {
             t.dst = d.dst;
             t.src = d.src;
             t.conj = d.conj;
-            t.nS = extS;
-            t.nD = extD;
-            if (pD >= 0) {
-                t.nD2 = c.shape[aD];
-                t.ssD = c.ss[pD];
-                t.ssD2 = c.ss[aD];
-            } else {
-                t.nD2 = 1;
-                t.ssD = c.ss[aD];
-                t.ssD2 = 0;
-            }
-            if (pS >= 0) {
-                t.nS2 = c.shape[aS];
-                t.dsS = c.ds[pS];
-                t.dsS2 = c.ds[aS];
-            } else {
-                t.nS2 = 1;
-                t.dsS = c.ds[aS];
-                t.dsS2 = 0;
-            }
-            const int64_t tsz = (elem_size == 8 && !d.conj) ? 64 : 32;
-            t.tilesS = (t.nS + tsz - 1) / tsz;
-            t.tilesD = (t.nD + tsz - 1) / tsz;
-            int64_t outer = 1;
-            for (int k = 0; k < nd; ++k) {
-                if (k == aS || k == aD || k == pS || k == pD) continue;
-                t.oshape[t.n_outer] = c.shape[k];
-                t.ods[t.n_outer] = c.ds[k];
-                t.oss[t.n_outer] = c.ss[k];
-                ++t.n_outer;
-                outer *= c.shape[k];
-            }
-            const int64_t ntile = outer * t.tilesS * t.tilesD;
-            const int64_t kTilesPerItem = tsz == 64 ? 4 : 16;
+            const int64_t kTilesPerItem = tiles_per_item(tsz);
             for (int64_t s0 = 0; s0 < ntile; s0 += kTilesPerItem)
                 titems.push_back(Item{(int32_t)ht.size(), 0, s0, std::min(kTilesPerItem, ntile - s0)});
             ht.push_back(t);

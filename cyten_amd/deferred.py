@@ -144,6 +144,10 @@ class DeferredBlockBackend(HipBlockBackend):
         self.n_deferred = 0         # matrix_dot calls served lazily
         self.n_decomp_batches = 0   # batched decomposition calls issued by flush()
 
+    # a lazy block has no address and no strides until it is flushed: combine_legs / split_legs take the generic
+    # zeros_many + copy_many route with this backend instead of a placement plan
+    place_plan = None
+
     # ---- the lazy producer
     def matrix_dot(self, a: HipBlock, b: HipBlock) -> HipBlock:
         if a.ndim != 2 or b.ndim != 2:

@@ -250,6 +250,33 @@ typedef struct {
 } cyb_copy_desc;
 int cyb_copy_strided_batched(cyb_ctx_t ctx, const cyb_copy_desc* descs, int64_t n, int32_t elem_size);
 
+/* ---- placement plans: the same strided copies for a block STRUCTURE that comes back (combine_legs / split_legs of the same
+ *      legs and block table, bond after bond).  A record names its two blocks by their row in two address tables instead of
+ *      by address:  dst_ptrs[dst_block][dst_offset + sum_d i_d*dst_strides[d]] = src_ptrs[src_block][src_offset + sum_d
+ *      i_d*src_strides[d]], offsets and strides in elements of elem_size bytes (8 or 16).
+ * create (synchronous, once per structure): validates (ndim <= CYB_MAX_NDIM, block numbers inside the tables, extents and
+ *      offsets >= 0), merges axes, decides per record between the row-run and the LDS-tiled transposing kernel, cuts the
+ *      work items and stores records and items in device memory the plan owns -- what cyb_copy_strided_batched does per call.
+ * enqueue (asynchronous): src_ptrs[n_src], dst_ptrs[n_dst] = device addresses of the blocks at hand (host arrays, copied
+ *      by ONE upload; an address may be 0 only for a block no non-empty record names); at most one launch per kernel class.
+ *      reverse = 1 copies the other way, dst side -> src side (the gather of split_legs); the records of that direction
+ *      are classified on its first use.  Nothing is checked per element: the caller vouches that every block holds what
+ *      the records address.  Records may not overlap on the side that is written.
+ * destroy: waits for the device, then frees the plan's memory. */
+typedef struct {
+    int32_t src_block, dst_block; /* rows of the two address tables given at enqueue */
+    int32_t ndim, pad;
+    int64_t src_offset, dst_offset;
+    int64_t shape[CYB_MAX_NDIM];
+    int64_t src_strides[CYB_MAX_NDIM];
+    int64_t dst_strides[CYB_MAX_NDIM];
+} cyb_place_rec;
+typedef struct cyb_place_plan_s* cyb_place_plan_t;
+int cyb_place_plan_create(cyb_ctx_t ctx, const cyb_place_rec* recs, int64_t n, int64_t n_src, int64_t n_dst, int32_t elem_size,
+                          cyb_place_plan_t* out);
+int cyb_place_plan_enqueue(cyb_ctx_t ctx, cyb_place_plan_t plan, const int64_t* src_ptrs, const int64_t* dst_ptrs, int32_t reverse);
+int cyb_place_plan_destroy(cyb_place_plan_t plan);
+
 /* ---- BLAS-1 class block-list ops (Lanczos / truncation callers: norm, inner,
  *      linear_combination, mul, scale_axis; numpy.cpp:898-913, :815-842, :1358-1385) ----------- */
 typedef struct {
