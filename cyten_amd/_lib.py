@@ -16,6 +16,8 @@ CYB_TRACE_MAX_PAIRS = 4
 CYB_SVD_SKIP_NULL_VECTORS = 1
 CYB_SVD_EMBEDDED_COMPLEX = 2
 CYB_EIGH_EMBEDDED_COMPLEX = 2
+CYB_EXPM_SMALL_MAX_N_F64 = 96
+CYB_EXPM_SMALL_MAX_N_C128 = 64
 
 CYB_OK, CYB_ERR_INVALID, CYB_ERR_HIP, CYB_ERR_NOCONV, CYB_ERR_NOMEM, CYB_ERR_UNSUPPORTED = range(6)
 
@@ -123,6 +125,11 @@ class TraceTerm(C.Structure):
                 ('pair_extent', C.c_int64 * CYB_TRACE_MAX_PAIRS), ('pair_stride', C.c_int64 * CYB_TRACE_MAX_PAIRS)]
 
 
+class ExpmDesc(C.Structure):
+    _fields_ = [('A', C.c_void_p), ('lda', C.c_int64), ('n', C.c_int64), ('a_is_real', C.c_int32), ('reserved', C.c_int32),
+                ('E', C.c_void_p), ('lde', C.c_int64)]
+
+
 # numpy views of the descriptor structs (same layout: numpy derives the dtype from the ctypes Structure), for the
 # vectorised marshalling of long block lists
 import numpy as _np  # noqa: E402
@@ -141,6 +148,7 @@ LINTERM_C128_DTYPE = _np.dtype(LincombTermC128)
 CEXPAND_DTYPE = _np.dtype(CExpandDesc)
 TRACE_OUT_DTYPE = _np.dtype(TraceOut)
 TRACE_TERM_DTYPE = _np.dtype(TraceTerm)
+EXPM_DTYPE = _np.dtype(ExpmDesc)
 
 _P = C.POINTER
 _ctx = C.c_void_p
@@ -217,6 +225,10 @@ PROTOTYPES = {
     'cyb_lincomb_strided_batched_c128': [_ctx, _P(LincombDesc), C.c_int64, _P(LincombTermC128), C.c_int64],
     'cyb_trace_grouped_f64': [_ctx, _P(TraceOut), C.c_int64, _P(TraceTerm), C.c_int64],
     'cyb_trace_grouped_c128': [_ctx, _P(TraceOut), C.c_int64, _P(TraceTerm), C.c_int64],
+    'cyb_expm_small_batched_f64': [_ctx, _P(ExpmDesc), C.c_int64, C.c_double],
+    'cyb_expm_small_batched_c128': [_ctx, _P(ExpmDesc), C.c_int64, C.c_double, C.c_double],
+    'cyb_norm1_batched_f64': [_ctx, _P(ExpmDesc), C.c_int64, _vp],
+    'cyb_norm1_batched_c128': [_ctx, _P(ExpmDesc), C.c_int64, _vp],
     'cyb_truncate_select_f64': [_ctx, _P(VecDesc), C.c_int64, _P(TruncOpts), _vp, _vp, _vp],
     'cyb_truncate_select_weighted_f64': [_ctx, _P(VecDesc), C.c_int64, _vp, _P(TruncOpts), _vp, _vp, _vp],
     'cyb_random_uniform_f64': [_ctx, _vp, C.c_int64, C.c_uint64, C.c_double, C.c_double],

@@ -28,6 +28,10 @@ reference's ``AbelianBackend`` callers of the block backend (SURVEY.md section 8
   can be contracted, decomposed and split again.  ONE launch per kernel class places all old blocks, read through their
   (permuted) strides, from a device-resident placement plan built once per block structure (``csrc/place_plan.hip``); the split
   is views, or one plan launch in reverse.
+* :func:`exp`, :func:`act_block_diagonal_square_matrix`, :func:`eye`, :func:`hermitian_function` <- ``exp`` of
+  ``src/tensors/ops_elementwise.cpp:174-223`` on ``AbelianBackend::act_block_diagonal_square_matrix`` (:562-593): all diagonal
+  blocks of the tensor seen as a matrix of pipes go through ONE block-list call (``matrix_exp_many``: one launch of the in-LDS
+  kernel ``csrc/expm_small.hip`` for the blocks that fit), instead of one block method per sector.
 
 The functions only need the block-backend *interface* (`matrix_dot_grouped`, `matrix_svd_batched`,
 ...), not a particular implementation.
@@ -45,7 +49,8 @@ __all__ = ['Symmetry', 'Leg', 'AbelianTensor', 'compose', 'compose_plan', 'compo
            'truncate_singular_values', 'truncated_svd', 'qr', 'lq', 'eigh', 'norm', 'inner', 'split_matrix_legs', 'partial_compose',
            'Mask', 'mask_contract', 'qr_tensor', 'lq_tensor', 'to_block_backend', 'move_to_device',
            'conj', 'dagger', 'DiagonalTensor', 'diagonal_unary', 'scale_axis', 'partial_trace', 'trace_full', 'to_dense_block',
-           'from_dense_block', 'dual_sector_map', 'LegPipe', 'combine_legs', 'split_legs']
+           'from_dense_block', 'dual_sector_map', 'LegPipe', 'combine_legs', 'split_legs',
+           'act_block_diagonal_square_matrix', 'exp', 'eye', 'hermitian_function']
 
 
 class Symmetry:
@@ -1681,3 +1686,134 @@ def _split_gather(bb, t, leg_idcs, shapes, origin):
     new_blocks = bb.empty_many(shapes, dtype='complex128' if cplx else None)
     bb.place_enqueue(plan['native'], [b.ptr for b in new_blocks], [b.ptr for b in blocks], reverse=True)
     return new_blocks
+
+
+# ---------------------------------------------------------------------------------------------
+# functions of a square tensor
+# ---------------------------------------------------------------------------------------------
+
+def _square_half(t: AbelianTensor, what: str) -> int:
+    """k of a tensor of 2k legs that maps its first k legs to themselves: ``legs[n - 1 - i]`` contracts with ``legs[i]``,
+    the pairing ``compose(t, t, k)`` uses"""
+    n = t.nlegs
+    if n == 0 or n % 2:
+        raise ValueError(f'{what}: a tensor of {n} legs is not square (an even number of legs is required)')
+    for i in range(n // 2):
+        if not t.legs[n - 1 - i].can_contract_with(t.legs[i]):
+            raise ValueError(f'{what}: leg {n - 1 - i} cannot be contracted with leg {i}')
+    return n // 2
+
+
+def _act_diagonal(bb, t: AbelianTensor, block_method_many, all_sectors: bool) -> AbelianTensor:
+    if t.nlegs != 2 or not t.legs[1].can_contract_with(t.legs[0]):
+        raise ValueError('act_block_diagonal_square_matrix: a two-leg tensor [leg, leg.dual()] is required')
+    leg = t.legs[0]
+    have = {}
+    for (i, j), b in zip(t.block_inds.tolist(), t.blocks):
+        if i != j:
+            raise ValueError(f'act_block_diagonal_square_matrix: block ({i}, {j}) is not on the diagonal')
+        have[i] = b
+    sectors = list(range(leg.nsec)) if all_sectors else sorted(have)
+    entries = [have[j] if j in have else (int(leg.mults[j]), None) for j in sectors]
+    blocks = list(block_method_many(entries)) if entries else []
+    if len(blocks) != len(entries):
+        raise ValueError('act_block_diagonal_square_matrix: the block method must return one block per entry')
+    return AbelianTensor(t.symmetry, list(t.legs), blocks, np.array([[j, j] for j in sectors], dtype=np.int64).reshape(len(sectors), 2),
+                         t.num_codomain, list(t.labels))
+
+
+def act_block_diagonal_square_matrix(bb, t: AbelianTensor, block_method_many, dtype_map=None) -> AbelianTensor:
+    """``AbelianBackend::act_block_diagonal_square_matrix`` (abelian.cpp:562-593) for a two-leg tensor ``[leg, leg.dual()]``:
+    a function of a block-diagonal matrix is that function of every diagonal block.  The result holds ALL ``leg.nsec``
+    diagonal blocks -- a sector without a block is a zero block and f(0) need not vanish (:574-584) --, so
+    ``block_inds == [[j, j] for j in range(nsec)]``.  Where the reference calls a block method once per sector,
+    `block_method_many` receives the whole list once: the present blocks and ``(n, None)`` for the zero blocks, in sector
+    order; it returns one block per entry.  `dtype_map` (the reference's map from the dtype of the tensor to that of the
+    result, :566-569) is accepted for the same call shape; a tensor here has no dtype of its own: it is that of the blocks the
+    method returns."""
+    return _act_diagonal(bb, t, block_method_many, True)
+
+
+def _on_square_matrix(bb, t: AbelianTensor, k: int, block_method_many, all_sectors: bool = True) -> AbelianTensor:
+    """`t` as a two-leg tensor of pipes -> `_act_diagonal` -> split and permuted back.  The codomain ``0 .. k-1`` becomes a
+    pipe and the REVERSED domain ``n-1 .. k`` its dual: the same sectors in the same internal order, so that every block is
+    square with the same basis on its rows and columns."""
+    n = t.nlegs
+    if n == 2:
+        return _act_diagonal(bb, t, block_method_many, all_sectors)
+    pipe = LegPipe.from_legs(t.symmetry, t.legs[:k], +1)
+    m = combine_legs(bb, t, [list(range(k)), list(range(n - 1, k - 1, -1))], pipes=[pipe, pipe.dual()], num_codomain=1)
+    r = split_legs(bb, _act_diagonal(bb, m, block_method_many, all_sectors))
+    r = permute_legs(bb, r, list(range(k)) + list(range(n - 1, k - 1, -1)))
+    return AbelianTensor(t.symmetry, list(t.legs), r.blocks, r.block_inds, t.num_codomain, list(t.labels))
+
+
+def exp(bb, t: AbelianTensor, factor=1.0) -> AbelianTensor:
+    """``exp(factor * t)`` of a tensor of 2k legs that maps its first k legs to themselves (``legs[n-1-i]`` contracts with
+    ``legs[i]``, as in ``compose(t, t, k)``): the reference's ``exp`` (src/tensors/ops_elementwise.cpp:174-223) -- combine
+    codomain and domain into one pipe each, exponentiate every diagonal block, split again.  ALL blocks go through ONE
+    ``bb.matrix_exp_many`` call (one launch if every block fits the in-LDS kernel); sectors without a block become
+    identities.  A ``complex`` factor on a real tensor gives a complex result without a promotion pass.  Labels and
+    ``num_codomain`` are kept.  A backend without ``matrix_exp_many`` runs ``bb.matrix_exp`` per block."""
+    k = _square_half(t, 'exp')
+    many = getattr(bb, 'matrix_exp_many', None)
+    if many is not None:
+        def method(entries):
+            return many(entries, factor)
+    else:
+        def method(entries):
+            blocks = [bb.zeros((e[0], e[0])) if isinstance(e, tuple) else e for e in entries]
+            return [bb.matrix_exp(b) for b in bb.mul_many(factor, blocks)]
+    return _on_square_matrix(bb, t, k, method)
+
+
+def eye(bb, symmetry: Symmetry, legs, dtype=None) -> AbelianTensor:
+    """The identity from `legs` to themselves (``eye_data``, include/cyten/backends/abelian.h:200): legs
+    ``legs + [l.dual() for l in reversed(legs)]``, ``num_codomain = len(legs)``.  One ``eye_matrix`` block per sector of the
+    pipe of `legs`, split into views."""
+    legs = list(legs)
+    if not legs:
+        raise ValueError('eye: at least one leg')
+    k = len(legs)
+    lead = legs[0] if k == 1 else LegPipe.from_legs(symmetry, legs, +1)
+    blocks = [bb.eye_matrix(int(m), dtype) for m in lead.mults]
+    t = AbelianTensor(symmetry, [lead, lead.dual()], blocks, np.array([[j, j] for j in range(lead.nsec)], dtype=np.int64).reshape(lead.nsec, 2), 1)
+    if k > 1:
+        t = permute_legs(bb, split_legs(bb, t), list(range(k)) + list(range(2 * k - 1, k - 1, -1)), num_codomain=k)
+    return t
+
+
+_F0_NONZERO = ('exp', 'log', 'reciprocal')
+
+
+def hermitian_function(bb, t: AbelianTensor, func: str, param=None) -> AbelianTensor:
+    """``f(t)`` for a Hermitian tensor (leg requirements of :func:`exp`) through the eigendecomposition of its diagonal blocks,
+    ``V f(w) V^dagger``: `func` is a name :func:`diagonal_unary` knows (exp, sqrt, log, stable_log, cutoff_inverse, pow, ...),
+    applied to the real eigenvalues.  A fixed number of launches per tensor: ``eigh_batched``, ``unary_many`` on the list of
+    eigenvalue vectors, ``scale_axis_many`` on the eigenvector columns, (complex blocks: one conjugating ``copy_many``) and ONE
+    grouped GEMM with the adjoint views.  Functions with f(0) != 0 (exp, log, reciprocal, pow with an exponent <= 0) treat
+    the sectors without a block as zero blocks, like :func:`act_block_diagonal_square_matrix`; the others leave them out.
+    Hermiticity is the caller's promise: only what ``eigh`` reads of a block enters."""
+    if func not in _UNARY_NAMES + _UNARY_PARAM_NAMES:
+        raise ValueError(f'hermitian_function: unknown function {func!r}')
+    k = _square_half(t, 'hermitian_function')
+    all_sectors = func in _F0_NONZERO or (func == 'pow' and param is not None and param <= 0)
+
+    def method(entries):
+        missing = [i for i, e in enumerate(entries) if isinstance(e, tuple)]
+        if missing:
+            entries = list(entries)
+            for i, z in zip(missing, bb.zeros_many([(entries[i][0],) * 2 for i in missing])):
+                entries[i] = z
+        wv = bb.eigh_batched(entries)
+        fw = bb.unary_many([w for w, _ in wv], func, param)
+        scaled = bb.scale_axis_many([(v, f, 1) for (_, v), f in zip(wv, fw)])
+        adj = [bb.permute_axes(v, [1, 0]) for _, v in wv]
+        todo = [i for i, a in enumerate(adj) if _is_complex_block(a)]
+        if todo:
+            new = bb.empty_many([adj[i].shape for i in todo], dtype='complex128')
+            bb.copy_many([(d, adj[i]) for d, i in zip(new, todo)], conj=True)
+            for d, i in zip(new, todo):
+                adj[i] = d
+        return bb.matrix_dot_grouped([[(x, a)] for x, a in zip(scaled, adj)])
+    return _on_square_matrix(bb, t, k, method, all_sectors)

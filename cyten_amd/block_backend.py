@@ -2899,6 +2899,102 @@ class HipBlockBackend:
             P = self.matrix_dot(P, P)
         return P
 
+    @staticmethod
+    def _expm_squarings(norm1: float) -> int:
+        """s of `matrix_exp`: ||A / 2^s||_1 <= 1/2"""
+        if not math.isfinite(norm1):
+            raise ValueError('matrix_exp_many: a block has a 1-norm that is not finite')
+        return 0 if norm1 <= 0.5 else int(math.ceil(math.log2(norm1 / 0.5)))
+
+    def matrix_exp_many(self, blocks, alpha=1.0):
+        """``[exp(alpha * b) for b in blocks]``, the algorithm of `matrix_exp` for a whole list
+        (act_block_diagonal_square_matrix with matrix_exp, abelian.cpp:562-593; numpy.cpp:1227-1234).
+
+        An entry is a square 2-D float64 / complex128 block (any strided view) or ``(n, None)``: the n x n zero block, whose
+        result is the identity.  The results are complex128 if a block is or if `alpha` is a ``complex``, else float64.
+
+        * blocks of at most ``CYB_EXPM_SMALL_MAX_N_*`` rows: ONE ``cyb_expm_small_batched_*`` launch, one workgroup per block,
+          everything in LDS (csrc/expm_small.hip); float64 sources of a complex result are read in place; no host
+          synchronisation.
+        * larger blocks together: one ``cyb_norm1_batched_*`` launch and ONE download of the norm table (the only host
+          synchronisation), one launch for all scaled copies ``alpha A / 2^s``, per Horner step one grouped GEMM and one
+          ``lincomb_many`` (``I + T / k``) over all of them -- a complex list adds the expansion of the right operand --,
+          per squaring level one grouped GEMM over the blocks whose s exceeds that level.  The number of launches does not
+          depend on the number of blocks."""
+        entries = []
+        for b in blocks:
+            if isinstance(b, tuple):
+                n, none = b
+                if none is not None or int(n) < 0:
+                    raise ValueError('matrix_exp_many: a zero block is given as (n, None)')
+                entries.append((int(n), None))
+            else:
+                if not isinstance(b, HipBlock) or b.is_bool or b.ndim != 2 or b.shape[0] != b.shape[1]:
+                    raise ValueError('matrix_exp_many: square 2-D float64 / complex128 blocks required')
+                entries.append((b.shape[0], b))
+        cplx = isinstance(alpha, (complex, np.complexfloating)) or any(b is not None and b.is_complex for _, b in entries)
+        a_c = complex(alpha)
+        have = [i for i, (_, b) in enumerate(entries) if b is not None]
+        for i, c in zip(have, self.contiguous_many([entries[i][1] for i in have])):
+            entries[i] = (entries[i][0], c)
+        limit = _lib.CYB_EXPM_SMALL_MAX_N_C128 if cplx else _lib.CYB_EXPM_SMALL_MAX_N_F64
+        small = [i for i, (n, _) in enumerate(entries) if n <= limit]
+        large = [i for i, (n, b) in enumerate(entries) if n > limit and b is not None]
+        outs = [None] * len(entries)
+        for i, o in zip(small, self._new_many([(entries[i][0],) * 2 for i in small], cplx)):
+            outs[i] = o
+        live = [i for i in small if entries[i][0] > 0]
+        if live:
+            arr = np.zeros(len(live), dtype=_lib.EXPM_DTYPE)
+            arr['A'] = [0 if entries[i][1] is None else entries[i][1].ptr for i in live]
+            arr['n'] = arr['lda'] = arr['lde'] = [entries[i][0] for i in live]
+            arr['a_is_real'] = [0 if (entries[i][1] is not None and entries[i][1].is_complex) else 1 for i in live]
+            arr['E'] = [outs[i].ptr for i in live]
+            descs = arr.ctypes.data_as(C.POINTER(_lib.ExpmDesc))
+            self.ctx.sync_stream()
+            if cplx:
+                _lib.check(self.lib.cyb_expm_small_batched_c128(self.ctx.handle, descs, len(live), a_c.real, a_c.imag))
+            else:
+                _lib.check(self.lib.cyb_expm_small_batched_f64(self.ctx.handle, descs, len(live), a_c.real))
+        for i, (n, b) in enumerate(entries):   # (a zero block beyond the limit: no arithmetic)
+            if outs[i] is None and b is None:
+                outs[i] = self.eye_matrix(n, 'complex128' if cplx else None)
+        if large:
+            for i, o in zip(large, self._expm_large([entries[i][1] for i in large], a_c, cplx)):
+                outs[i] = o
+        return outs
+
+    def _expm_large(self, srcs, alpha: complex, cplx: bool):
+        """`matrix_exp_many` for contiguous blocks beyond the limit of the in-LDS kernel: every step is one launch for all"""
+        m = len(srcs)
+        arr = np.zeros(m, dtype=_lib.EXPM_DTYPE)
+        arr['A'] = [a.ptr for a in srcs]
+        arr['n'] = arr['lda'] = [a.shape[0] for a in srcs]
+        arr['a_is_real'] = [0 if a.is_complex else 1 for a in srcs]
+        table = self.ctx.empty(m)
+        self.ctx.sync_stream()
+        fn = self.lib.cyb_norm1_batched_c128 if any(a.is_complex for a in srcs) else self.lib.cyb_norm1_batched_f64
+        _lib.check(fn(self.ctx.handle, arr.ctypes.data_as(C.POINTER(_lib.ExpmDesc)), m, C.c_void_p(table.data_ptr())))
+        norms = abs(alpha) * self.ctx.d2h(table, m, np.float64)
+        s = [self._expm_squarings(float(x)) for x in norms]
+        coef = alpha if cplx else alpha.real
+        shapes = [a.shape for a in srcs]
+        A = self._new_many(shapes, cplx)
+        self.lincomb_many([(d, [(coef * 0.5 ** si, a)], False) for d, a, si in zip(A, srcs, s)])
+        eye = self.eye_matrix(max(sh[0] for sh in shapes))
+        eyes = [self.subblock(eye, 0, sh[0], 0, sh[0]) for sh in shapes]
+        P = self._new_many(shapes, cplx)
+        self.lincomb_many([(d, [(1.0, e), (1.0 / 18, a)], False) for d, e, a in zip(P, eyes, A)])   # k = 18: A times the identity
+        for k in range(17, 0, -1):  # P = I + (A / k) P
+            T = self.matrix_dot_grouped([[(a, p)] for a, p in zip(A, P)])
+            P = self._new_many(shapes, cplx)
+            self.lincomb_many([(d, [(1.0, e), (1.0 / k, t)], False) for d, e, t in zip(P, eyes, T)])
+        for level in range(max(s)):
+            sel = [i for i in range(m) if s[i] > level]
+            for i, o in zip(sel, self.matrix_dot_grouped([[(P[i], P[i])] for i in sel])):
+                P[i] = o
+        return P
+
     def permute_combined_matrix(self, block: HipBlock, dims1, idcs1, dims2, idcs2) -> HipBlock:
         """block_backend.cpp:857-884."""
         b = self.reshape(block, list(dims1) + list(dims2))

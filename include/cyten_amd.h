@@ -509,6 +509,37 @@ typedef struct {
 int cyb_trace_grouped_f64(cyb_ctx_t ctx, const cyb_trace_out* outs, int64_t n_outs, const cyb_trace_term* terms, int64_t n_terms);
 int cyb_trace_grouped_c128(cyb_ctx_t ctx, const cyb_trace_out* outs, int64_t n_outs, const cyb_trace_term* terms, int64_t n_terms);
 
+/* ---- grouped matrix exponential of small blocks ---------------------------------------------------------------------
+ * E = exp(alpha * A) for every listed square matrix in ONE launch, one workgroup per matrix, the whole computation in LDS
+ * (csrc/expm_small.hip).  Replaces NumpyBlockBackend::matrix_exp = scipy.linalg.expm (src/block_backend/numpy.cpp:1227-1234),
+ * called once per diagonal block by AbelianBackend::act_block_diagonal_square_matrix (src/backends/abelian.cpp:562-593).
+ * Algorithm: 1-norm of alpha * A; s = 0 if it is <= 1/2, else ceil(log2(norm / (1/2))); degree-18 Taylor polynomial of
+ * alpha * A / 2^s in Horner form; s squarings -- the steps of HipBlockBackend.matrix_exp, with the same truncation bound
+ * (< 2e-23).  Matrices are row-major; lda counts elements of the SOURCE type, lde elements of the result type.
+ *   A == NULL: the zero matrix, E becomes the identity (a sector of a tensor that holds no block).
+ *   a_is_real (c128 entry only): A addresses float64 data although E is complex -- a real Hamiltonian under
+ *       alpha = -i dt needs no promotion pass.  The f64 entry reads and writes float64 and takes a real alpha.
+ *   n == 0: the entry is skipped.  n above CYB_EXPM_SMALL_MAX_N_*: CYB_ERR_INVALID, nothing is launched (the caller runs such
+ *       blocks on the grouped GEMM, see HipBlockBackend.matrix_exp_many).
+ * The limits are what two n x n matrices (row length n | 1) take of one workgroup's LDS next to a 16 x 16 thread grid with
+ * at most 6 x 6 (f64) / 4 x 4 (c128) result elements in the registers of a thread.  E may be A. */
+#define CYB_EXPM_SMALL_MAX_N_F64 96
+#define CYB_EXPM_SMALL_MAX_N_C128 64
+typedef struct {
+    const double* A; int64_t lda;
+    int64_t n;
+    int32_t a_is_real;
+    int32_t reserved;
+    double* E; int64_t lde;
+} cyb_expm_desc;
+int cyb_expm_small_batched_f64(cyb_ctx_t ctx, const cyb_expm_desc* descs, int64_t n, double alpha);
+int cyb_expm_small_batched_c128(cyb_ctx_t ctx, const cyb_expm_desc* descs, int64_t n, double alpha_re, double alpha_im);
+/* result_dev[i] = max_j sum_i |a_ij| of matrix i (A, lda, n, a_is_real of the descriptor; E is ignored; 0 for A == NULL or
+ * n == 0): ONE launch for the list, no host synchronisation -- the norm table from which the host chooses the scaling of the
+ * blocks beyond the limits above.  Column sums are added in a fixed order; the maximum is order independent. */
+int cyb_norm1_batched_f64(cyb_ctx_t ctx, const cyb_expm_desc* descs, int64_t n, double* result_dev);
+int cyb_norm1_batched_c128(cyb_ctx_t ctx, const cyb_expm_desc* descs, int64_t n, double* result_dev);
+
 /* ---- truncation of singular values on the device -----------------------------------------
  * TensorBackend::_truncate_singular_values_selection (src/backends/tensor_backend.cpp:139-242) applied to the
  * concatenation of the per-sector singular values WITHOUT the host round trip of
