@@ -130,6 +130,13 @@ class ExpmDesc(C.Structure):
                 ('E', C.c_void_p), ('lde', C.c_int64)]
 
 
+class OuterRec(C.Structure):
+    _fields_ = [('dst', C.c_void_p), ('a', C.c_void_p), ('b', C.c_void_p), ('n_a', C.c_int32), ('n_b', C.c_int32), ('k', C.c_int32),
+                ('a_is_real', C.c_int32), ('b_is_real', C.c_int32), ('reserved', C.c_int32),
+                ('a_shape', C.c_int64 * CYB_MAX_NDIM), ('a_strides', C.c_int64 * CYB_MAX_NDIM),
+                ('b_shape', C.c_int64 * CYB_MAX_NDIM), ('b_strides', C.c_int64 * CYB_MAX_NDIM)]
+
+
 # numpy views of the descriptor structs (same layout: numpy derives the dtype from the ctypes Structure), for the
 # vectorised marshalling of long block lists
 import numpy as _np  # noqa: E402
@@ -149,6 +156,7 @@ CEXPAND_DTYPE = _np.dtype(CExpandDesc)
 TRACE_OUT_DTYPE = _np.dtype(TraceOut)
 TRACE_TERM_DTYPE = _np.dtype(TraceTerm)
 EXPM_DTYPE = _np.dtype(ExpmDesc)
+OUTER_DTYPE = _np.dtype(OuterRec)
 
 _P = C.POINTER
 _ctx = C.c_void_p
@@ -229,6 +237,8 @@ PROTOTYPES = {
     'cyb_expm_small_batched_c128': [_ctx, _P(ExpmDesc), C.c_int64, C.c_double, C.c_double],
     'cyb_norm1_batched_f64': [_ctx, _P(ExpmDesc), C.c_int64, _vp],
     'cyb_norm1_batched_c128': [_ctx, _P(ExpmDesc), C.c_int64, _vp],
+    'cyb_outer_grouped_f64': [_ctx, _P(OuterRec), C.c_int64],
+    'cyb_outer_grouped_c128': [_ctx, _P(OuterRec), C.c_int64],
     'cyb_truncate_select_f64': [_ctx, _P(VecDesc), C.c_int64, _P(TruncOpts), _vp, _vp, _vp],
     'cyb_truncate_select_weighted_f64': [_ctx, _P(VecDesc), C.c_int64, _vp, _P(TruncOpts), _vp, _vp, _vp],
     'cyb_random_uniform_f64': [_ctx, _vp, C.c_int64, C.c_uint64, C.c_double, C.c_double],

@@ -33,6 +33,13 @@ reference's ``AbelianBackend`` callers of the block backend (SURVEY.md section 8
   blocks of the tensor seen as a matrix of pipes go through ONE block-list call (``matrix_exp_many``: one launch of the in-LDS
   kernel ``csrc/expm_small.hip`` for the blocks that fit), instead of one block method per sector.
 
+* :func:`outer`, :func:`tensor_from_grid`, :func:`direct_sum`, :func:`add_trivial_leg`, :func:`squeeze_legs` <-
+  ``AbelianBackend::outer`` (:2794-2850), ``tensor_from_grid`` (src/tensors/constructors.cpp:304-499) on ``::from_grid`` (:1875-1978),
+  ``ElementarySpace.direct_sum``, ``::add_trivial_leg`` (:596-613), ``::squeeze_legs`` (:3439-3458): what the model layer builds bond
+  terms and MPO tensors from.  ALL block pairs of a tensor product go through ONE ``tensor_outer_many`` call (one launch of
+  ``csrc/outer_grouped.hip``, results contiguous in their final axis order) instead of one ``tensor_outer`` per pair; a grid is one
+  placement-plan launch; trivial legs are metadata.
+
 The functions only need the block-backend *interface* (`matrix_dot_grouped`, `matrix_svd_batched`,
 ...), not a particular implementation.
 """
@@ -50,7 +57,8 @@ __all__ = ['Symmetry', 'Leg', 'AbelianTensor', 'compose', 'compose_plan', 'compo
            'Mask', 'mask_contract', 'qr_tensor', 'lq_tensor', 'to_block_backend', 'move_to_device',
            'conj', 'dagger', 'DiagonalTensor', 'diagonal_unary', 'scale_axis', 'partial_trace', 'trace_full', 'to_dense_block',
            'from_dense_block', 'dual_sector_map', 'LegPipe', 'combine_legs', 'split_legs',
-           'act_block_diagonal_square_matrix', 'exp', 'eye', 'hermitian_function']
+           'act_block_diagonal_square_matrix', 'exp', 'eye', 'hermitian_function',
+           'outer', 'direct_sum', 'tensor_from_grid', 'add_trivial_leg', 'squeeze_legs']
 
 
 class Symmetry:
@@ -1817,3 +1825,243 @@ def hermitian_function(bb, t: AbelianTensor, func: str, param=None) -> AbelianTe
                 adj[i] = d
         return bb.matrix_dot_grouped([[(x, a)] for x, a in zip(scaled, adj)])
     return _on_square_matrix(bb, t, k, method, all_sectors)
+
+
+# ---------------------------------------------------------------------------------------------
+# building operators: outer, direct_sum, tensor_from_grid, trivial legs
+# ---------------------------------------------------------------------------------------------
+
+def _relabelled(labels, mapping, n):
+    labels = list(labels) if len(labels) == n else [None] * n
+    return [mapping.get(l, l) for l in labels] if mapping else labels
+
+
+def outer(bb, a: AbelianTensor, b: AbelianTensor, relabel_a=None, relabel_b=None) -> AbelianTensor:
+    """The tensor product ``a (x) b`` (``AbelianBackend::outer``, abelian.cpp:2794-2850): legs ``a.legs[:K] + b.legs +
+    a.legs[K:]`` with ``K = a.num_codomain``, ``num_codomain = K + b.num_codomain``; the block table is the F-style grid of
+    all (a-block, b-block) pairs, lexsorted (the reference leaves it unsorted).  ALL blocks come from ONE
+    ``bb.tensor_outer_many`` call, C-contiguous in their final axis order; a backend without that method runs
+    ``tensor_outer`` + ``contiguous`` per pair.  `relabel_a` / `relabel_b` map old to new labels; a label that then occurs
+    twice is a ``ValueError``.  Real next to complex gives a complex result."""
+    if a.symmetry != b.symmetry:
+        raise ValueError('outer: the tensors have different symmetries')
+    na, nb, K = a.nlegs, b.nlegs, a.num_codomain
+    if na + nb > CYB_MAX_NDIM:
+        raise ValueError(f'outer: tensors of more than {CYB_MAX_NDIM} legs are not supported')
+    labels = []
+    if len(a.labels) == na or len(b.labels) == nb:
+        la, lb = _relabelled(a.labels, relabel_a, na), _relabelled(b.labels, relabel_b, nb)
+        labels = la[:K] + lb + la[K:]
+        named = [l for l in labels if l is not None]
+        if len(set(named)) != len(named):
+            raise ValueError(f'outer: duplicate labels in {labels}')
+    legs = list(a.legs[:K]) + list(b.legs) + list(a.legs[K:])
+    l_a, l_b = len(a.blocks), len(b.blocks)
+    ia, ib = np.tile(np.arange(l_a), l_b), np.repeat(np.arange(l_b), l_a)      # (first index fastest: make_grid(cstyle=False))
+    rows = np.concatenate([a.block_inds[ia, :K], b.block_inds[ib], a.block_inds[ia, K:]], axis=1).reshape(l_a * l_b, na + nb)
+    order = _lexsort_rows(rows)
+    ia, ib, rows = ia[order], ib[order], rows[order]
+    pairs = [(a.blocks[i], b.blocks[j]) for i, j in zip(ia.tolist(), ib.tolist())]
+    many = getattr(bb, 'tensor_outer_many', None)
+    if many is not None:
+        blocks = many(pairs, K)
+    else:
+        cplx = any(_is_complex_block(x) for x in list(a.blocks) + list(b.blocks))
+        blocks = [bb.contiguous(bb.tensor_outer(bb.as_complex(x) if cplx else x, bb.as_complex(y) if cplx else y, K)) for x, y in pairs]
+    return AbelianTensor(a.symmetry, legs, list(blocks), rows, K + b.num_codomain, labels)
+
+
+def direct_sum(legs) -> Leg:
+    """``ElementarySpace.direct_sum``: the leg whose sectors are the union of the sectors of `legs` (same symmetry and sign),
+    multiplicities added.  Pipes are refused: a sum of products is no product (constructors.cpp:364-367)."""
+    legs = list(legs)
+    if not legs:
+        raise ValueError('direct_sum: at least one leg')
+    first = legs[0]
+    mults: dict = {}
+    for l in legs:
+        if isinstance(l, LegPipe):
+            raise RuntimeError('stacking legs must be ElementarySpace')
+        if l.symmetry != first.symmetry or l.sign != first.sign:
+            raise ValueError('direct_sum: the legs must have the same symmetry and sign')
+        for s, m in zip(l.sectors.tolist(), l.mults.tolist()):
+            mults[tuple(s)] = mults.get(tuple(s), 0) + int(m)
+    keys = list(mults)
+    return Leg(first.symmetry, np.array(keys, dtype=np.int64).reshape(len(keys), first.symmetry.n), [mults[k] for k in keys], first.sign)
+
+
+_GRID_CACHE: dict = {}
+
+
+def _sector_where(leg: Leg) -> dict:
+    return {tuple(s): i for i, s in enumerate(leg.sectors.tolist())}
+
+
+def _mult_slices(total: Leg, spaces):
+    """per sector of `total` the cumulative sums (leading zero) of its multiplicity in each of `spaces` (constructors.cpp:439-460)"""
+    wheres = [_sector_where(s) for s in spaces]
+    out = []
+    for sec in total.sectors.tolist():
+        m = [int(sp.mults[w[tuple(sec)]]) if tuple(sec) in w else 0 for sp, w in zip(spaces, wheres)]
+        out.append([0] + np.cumsum(m).tolist())
+    return out
+
+
+def tensor_from_grid(bb, grid, labels=None, dtype=None) -> AbelianTensor:
+    """Stack a grid of tensors into one (``tensor_from_grid``, src/tensors/constructors.cpp:304-499, on
+    ``AbelianBackend::from_grid``, abelian.cpp:1875-1978): `grid` is a list of rows of ``AbelianTensor | None``; the rows stack
+    on leg 0, the columns on leg ``num_codomain``, every other leg is equal across the entries.  The stacked legs are the
+    :func:`direct_sum` of one representative per row / column (the entry of the first column / row, else the first entry
+    found), and an entry occupies, in every sector, the slice its row / column has in the cumulative multiplicities.
+
+    Cells never overlap, so every block is *copied* to its place (the reference adds into zeros): one ``zeros_many``
+    (``empty_many`` if the cells cover the result) and ONE placement launch for the whole grid from a device-resident
+    plan cached by structure, as :func:`combine_legs` does; views are read through their strides.  A backend without plans
+    takes ``zeros_many`` + one ``copy_many``.  Real next to complex entries (or ``dtype='complex128'``) give complex128."""
+    grid = [list(row) for row in grid]
+    ops = [op for row in grid for op in row if op is not None]
+    if not ops:
+        raise ValueError('grid must contain at least one tensor')
+    ref = ops[0]
+    sym, n, n_cod = ref.symmetry, ref.nlegs, ref.num_codomain
+    if n_cod < 1 or n - n_cod < 1:
+        raise ValueError('tensor_from_grid: the entries need at least one codomain and one domain leg')
+    if n > CYB_MAX_NDIM:
+        raise ValueError(f'tensor_from_grid: tensors of more than {CYB_MAX_NDIM} legs are not supported')
+    others = [k for k in range(n) if k not in (0, n_cod)]
+    for op in ops:
+        if op.symmetry != sym:
+            raise ValueError('tensor_from_grid: the entries have different symmetries')
+        if op.nlegs != n or op.num_codomain != n_cod:
+            raise RuntimeError('inconsistent number of legs in grid')
+        if not all(_same_leg(op.legs[k], ref.legs[k]) for k in others):
+            raise RuntimeError('inconsistent legs in grid')
+        if isinstance(op.legs[0], LegPipe) or isinstance(op.legs[n_cod], LegPipe):
+            raise RuntimeError('stacking legs must be ElementarySpace')
+    n_rows, n_cols = len(grid), len(grid[0])
+    if any(len(row) != n_cols for row in grid):
+        raise ValueError('grid rows must have equal length')
+    right_ops = [next((grid[r][j] for r in range(n_rows) if grid[r][j] is not None), None) for j in range(n_cols)]
+    if any(op is None for op in right_ops):
+        raise ValueError('Must have at least one nonzero entry in each column.')
+    left_ops = [next((op for op in row if op is not None), None) for row in grid]
+    if any(op is None for op in left_ops):
+        raise ValueError('Must have at least one nonzero entry in each row.')
+    left_spaces, right_spaces = [op.legs[0] for op in left_ops], [op.legs[n_cod] for op in right_ops]
+    cells = [(i, j, op) for i, row in enumerate(grid) for j, op in enumerate(row) if op is not None]
+    for i, j, op in cells:        # (the reference trusts this; a cell of another size would be placed outside its slice)
+        if not _same_leg(op.legs[0], left_spaces[i]) or not _same_leg(op.legs[n_cod], right_spaces[j]):
+            raise RuntimeError('inconsistent legs in grid')
+    left, right = direct_sum(left_spaces), direct_sum(right_spaces)
+    legs = [left] + list(ref.legs[1:n_cod]) + [right] + list(ref.legs[n_cod + 1:])
+    if labels is None:
+        labels = list(ref.labels) if len(ref.labels) == n else []
+    elif len(labels) != n:
+        raise ValueError(f'tensor_from_grid: {n} labels expected')
+    blocks = [b for _, _, op in cells for b in op.blocks]
+    want_cplx = dtype is not None and np.dtype(dtype).kind == 'c'
+    if dtype is not None and not want_cplx and any(_is_complex_block(b) for b in blocks):
+        raise ValueError('tensor_from_grid: complex entries cannot be stored in a real dtype')
+    if not blocks:
+        return AbelianTensor(sym, legs, [], np.zeros((0, n), np.int64), n_cod, list(labels))
+    blocks, cplx = _promote_mixed(bb, blocks)
+    if want_cplx and not cplx:
+        blocks, cplx = [bb.as_complex(b) for b in blocks] if not hasattr(bb, 'as_complex_many') else bb.as_complex_many(blocks), True
+    esz = 16 if cplx else 8
+    native = _has_plans(bb)
+    key = (n_cod, n_rows, n_cols, esz, _block_strides(bb, blocks),
+           tuple((i, j, _legs_key(sym, op.legs, [l.sign for l in op.legs]), np.ascontiguousarray(op.block_inds).tobytes()) for i, j, op in cells))
+    plan = _GRID_CACHE.get(key)
+    if plan is None:
+        plan = _cache_put(_GRID_CACHE, key, _grid_plan(cells, legs, n_cod, _mult_slices(left, left_spaces), _mult_slices(right, right_spaces),
+                                                       [tuple(b.strides) for b in blocks] if native else None))
+    new_rows, new_shapes = plan['rows'], plan['shapes']
+    dt = 'complex128' if cplx else None
+    if native:
+        if plan.get('native') is None:
+            plan['native'] = bb.place_plan(plan['records'], len(blocks), len(new_shapes), esz)
+        new_blocks = bb.empty_many(new_shapes, dtype=dt) if plan['covers'] else bb.zeros_many(new_shapes, dtype=dt)
+        bb.place_enqueue(plan['native'], [b.ptr for b in blocks], [b.ptr for b in new_blocks])
+    else:
+        new_blocks = bb.zeros_many(new_shapes, dtype=dt)
+        bb.copy_many([(bb.get_item(new_blocks[dst], key_sl), blk) for blk, (dst, key_sl) in zip(blocks, plan['generic'])])
+    return AbelianTensor(sym, legs, list(new_blocks), new_rows.copy(), n_cod, list(labels))
+
+
+def _grid_plan(cells, legs, n_cod, left_slices, right_slices, src_strides):
+    """The placement of one grid structure: result block table (lexsorted, no duplicates), result shapes and per entry block
+    its result block and slice -- as placement records (`src_strides` given) and as slices for the generic route."""
+    n = len(legs)
+    left_where, right_where = _sector_where(legs[0]), _sector_where(legs[n_cod])
+    rows, spans, ext = [], [], []
+    for i, j, op in cells:
+        l0, lc = op.legs[0], op.legs[n_cod]
+        for row in op.block_inds.tolist():
+            li, ri = left_where[tuple(l0.sectors[row[0]].tolist())], right_where[tuple(lc.sectors[row[n_cod]].tolist())]
+            rows.append([li] + row[1:n_cod] + [ri] + row[n_cod + 1:])
+            spans.append((left_slices[li][i], left_slices[li][i + 1], right_slices[ri][j], right_slices[ri][j + 1]))
+            ext.append([int(l.mults[k]) for l, k in zip(op.legs, row)])
+    rows = np.array(rows, dtype=np.int64).reshape(len(rows), n)
+    order = _lexsort_rows(rows)
+    srt = rows[order]
+    is_new = np.concatenate([[True], np.any(srt[1:] != srt[:-1], axis=1)])
+    new_of = np.zeros(len(rows), dtype=np.int64)
+    new_of[order] = np.cumsum(is_new) - 1
+    new_rows = srt[is_new]
+    shapes = [tuple(int(l.mults[k]) for l, k in zip(legs, row)) for row in new_rows.tolist()]
+    out = dict(rows=new_rows, shapes=shapes, generic=[], records=None, native=None)
+    recs = _place_records(len(rows)) if src_strides is not None else None
+    placed = 0
+    for b in range(len(rows)):
+        dst = int(new_of[b])
+        r0, r1, c0, c1 = spans[b]
+        placed += math.prod(ext[b])
+        out['generic'].append((dst, tuple(slice(r0, r1) if k == 0 else (slice(c0, c1) if k == n_cod else slice(None)) for k in range(n))))
+        if recs is not None:
+            dstr = _c_strides_of(shapes[dst])
+            rec = recs[b]
+            rec['src_block'], rec['dst_block'], rec['ndim'], rec['dst_offset'] = b, dst, n, r0 * dstr[0] + c0 * dstr[n_cod]
+            rec['shape'][:n], rec['src_strides'][:n], rec['dst_strides'][:n] = ext[b], src_strides[b], dstr
+    out['records'] = recs
+    out['covers'] = placed == sum(math.prod(sh) for sh in shapes)    # (cells never overlap: equal sizes = all covered)
+    return out
+
+
+def add_trivial_leg(bb, t: AbelianTensor, pos: int, to_domain: bool = False, label=None) -> AbelianTensor:
+    """A leg with the one sector of charge 0, multiplicity 1, inserted at position `pos` of the flat leg list
+    (``AbelianBackend::add_trivial_leg``, abelian.cpp:596-613): metadata only -- ``bb.add_axis`` per block and a constant column
+    in the block table, which stays sorted.  In the codomain (``pos <= num_codomain``, not `to_domain`) the leg has sign +1
+    and ``num_codomain`` grows; in the domain (``pos >= num_codomain``) it has sign -1."""
+    n, K = t.nlegs, t.num_codomain
+    pos = int(pos)
+    if not 0 <= pos <= n:
+        raise ValueError(f'add_trivial_leg: position {pos} outside [0, {n}]')
+    if (to_domain and pos < K) or (not to_domain and pos > K):
+        raise ValueError(f'add_trivial_leg: position {pos} does not lie in the {"domain" if to_domain else "codomain"}')
+    leg = Leg(t.symmetry, np.zeros((1, t.symmetry.n), dtype=np.int64), [1], -1 if to_domain else +1)
+    labels = list(t.labels[:pos]) + [label] + list(t.labels[pos:]) if len(t.labels) == n else ([] if label is None else [None] * pos + [label] + [None] * (n - pos))
+    return AbelianTensor(t.symmetry, list(t.legs[:pos]) + [leg] + list(t.legs[pos:]), [bb.add_axis(b, pos) for b in t.blocks],
+                         np.insert(t.block_inds, pos, 0, axis=1), K + (0 if to_domain else 1), labels)
+
+
+def _is_trivial_leg(symmetry: Symmetry, leg: Leg) -> bool:
+    return leg.nsec == 1 and int(leg.mults[0]) == 1 and not np.any(leg.sectors)
+
+
+def squeeze_legs(bb, t: AbelianTensor, idcs=None) -> AbelianTensor:
+    """Remove trivial legs (one sector of charge 0, multiplicity 1), by default all of them (``AbelianBackend::squeeze_legs``,
+    abelian.cpp:3439-3458): metadata only -- ``bb.squeeze_axes`` per block, the columns deleted from the block table.  A listed
+    leg that is not trivial is a ``ValueError``."""
+    n = t.nlegs
+    if idcs is None:
+        idcs = [k for k in range(n) if _is_trivial_leg(t.symmetry, t.legs[k])]
+    elif isinstance(idcs, (int, np.integer)):
+        idcs = [int(idcs)]
+    idcs = sorted({int(i) % n for i in idcs})
+    for k in idcs:
+        if not _is_trivial_leg(t.symmetry, t.legs[k]):
+            raise ValueError(f'squeeze_legs: leg {k} is not trivial')
+    keep = [k for k in range(n) if k not in idcs]
+    blocks = [bb.squeeze_axes(b, idcs) for b in t.blocks] if idcs else list(t.blocks)
+    return AbelianTensor(t.symmetry, [t.legs[k] for k in keep], blocks, t.block_inds[:, keep].reshape(len(blocks), len(keep)),
+                         t.num_codomain - sum(1 for k in idcs if k < t.num_codomain), [t.labels[k] for k in keep] if len(t.labels) == n else [])

@@ -3023,6 +3023,37 @@ class HipBlockBackend:
         N, M = a.ndim, b.ndim
         return self.permute_axes(res, list(range(K)) + [N + i for i in range(M)] + list(range(K, N)))
 
+    def tensor_outer_many(self, pairs, K: int):
+        """``tensor_outer(a, b, K)`` for a list of ``(a, b)`` pairs, ONE launch (csrc/outer_grouped.hip): the block loop of
+        ``AbelianBackend::outer`` (abelian.cpp:2843-2848).  Unlike `tensor_outer` the results are C-contiguous in their final
+        axis order ``a.shape[:K] + b.shape + a.shape[K:]`` and live in one pooled allocation.  Operands are float64 or
+        complex128, contiguous blocks or views (read in place through their strides); if any operand of the list is complex
+        every result is complex128, and the real operands are read as they stand.  ``a.ndim + b.ndim <= CYB_MAX_NDIM``."""
+        pairs = [(a, b) for a, b in pairs]
+        K = int(K)
+        self._numeric_only([x for p in pairs for x in p], 'tensor_outer_many')
+        nd_max = _lib.CYB_MAX_NDIM
+        for a, b in pairs:
+            if a.ndim + b.ndim > nd_max:
+                raise ValueError(f'tensor_outer_many: a pair with more than {nd_max} axes')
+            if not 0 <= K <= a.ndim:
+                raise ValueError(f'tensor_outer_many: K = {K} outside [0, {a.ndim}]')
+        cplx = any(a.is_complex or b.is_complex for a, b in pairs)
+        outs = self._new_many([a.shape[:K] + b.shape + a.shape[K:] for a, b in pairs], cplx)
+        if not pairs:
+            return outs
+        n = len(pairs)
+        recs = np.zeros(n, dtype=_lib.OUTER_DTYPE)
+        recs['dst'], recs['a'], recs['b'] = [o.ptr for o in outs], [a.ptr for a, _ in pairs], [b.ptr for _, b in pairs]
+        recs['n_a'], recs['n_b'], recs['k'] = [a.ndim for a, _ in pairs], [b.ndim for _, b in pairs], K
+        recs['a_is_real'], recs['b_is_real'] = [0 if a.is_complex else 1 for a, _ in pairs], [0 if b.is_complex else 1 for _, b in pairs]
+        recs['a_shape'], recs['a_strides'] = [a.shape + _ZERO_PAD[a.ndim] for a, _ in pairs], [a.strides + _ZERO_PAD[a.ndim] for a, _ in pairs]
+        recs['b_shape'], recs['b_strides'] = [b.shape + _ZERO_PAD[b.ndim] for _, b in pairs], [b.strides + _ZERO_PAD[b.ndim] for _, b in pairs]
+        fn = self.lib.cyb_outer_grouped_c128 if cplx else self.lib.cyb_outer_grouped_f64
+        self.ctx.sync_stream()
+        _lib.check(fn(self.ctx.handle, recs.ctypes.data_as(C.POINTER(_lib.OuterRec)), n))
+        return outs
+
     def random_uniform(self, dims, dtype=None, device=None, seed=None) -> HipBlock:
         """Uniform on [-1, 1) (numpy.cpp:965-988), real and imaginary part independently for complex dtypes."""
         if seed is None:
@@ -3070,7 +3101,7 @@ _INT_KEEPS = frozenset({'permute_axes', 'reshape', 'add_axis', 'squeeze_axes', '
                         'combine_legs', 'split_legs', 'apply_mask', 'enlarge_leg', 'enlarge_leg_many', 'mask_gather_many', 'tile',
                         'get_diagonal', 'block_from_diagonal', 'abs', 'sum', 'multiply_blocks', 'apply_leg_permutations',
                         'apply_basis_perm', 'permute_combined_matrix', 'permute_combined_idx', 'subblock', 'dagger', 'conj', 'real',
-                        'outer', 'kron', 'tensor_outer'})
+                        'outer', 'kron', 'tensor_outer', 'tensor_outer_many'})
 _INT_BINARY_OPS = (0, 1, 2)     # `_binary` op codes add / sub / mul
 # methods the policy does not touch: they take no blocks, return no blocks, or set the dtype themselves
 _POLICY_SKIP = frozenset({'to_dtype', 'to_numpy', 'as_scalar', 'block_from_numpy', 'as_block', 'get_dtype', 'get_shape', 'get_device', 'is_real',

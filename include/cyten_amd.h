@@ -540,6 +540,36 @@ int cyb_expm_small_batched_c128(cyb_ctx_t ctx, const cyb_expm_desc* descs, int64
 int cyb_norm1_batched_f64(cyb_ctx_t ctx, const cyb_expm_desc* descs, int64_t n, double* result_dev);
 int cyb_norm1_batched_c128(cyb_ctx_t ctx, const cyb_expm_desc* descs, int64_t n, double* result_dev);
 
+/* ---- grouped tensor product of blocks --------------------------------------------------------------------------------
+ * Every result block of AbelianBackend::outer (src/backends/abelian.cpp:2794-2850) in ONE launch: replaces the call of
+ * BlockBackend::tensor_outer (src/block_backend/block_backend.cpp:994-1010: outer + permute_axes, the result a
+ * non-contiguous view) per pair of blocks (abelian.cpp:2843-2848); with k = n_a it is the plain outer of
+ * _compose_no_contraction (abelian.cpp:1518-1565).
+ *   dst[i_0 .. i_{k-1}, j_0 .. j_{n_b-1}, i_k .. i_{n_a-1}] = a[i_0 .. i_{n_a-1}] * b[j_0 .. j_{n_b-1}]
+ * dst is C-contiguous in this axis order; a and b are read in place as strided views (strides in elements of their own
+ * type).  n_a + n_b <= CYB_MAX_NDIM, 0 <= k <= n_a; entries of the shape / stride arrays beyond n_a / n_b are ignored.
+ * A record with a zero extent is skipped; an empty list is valid.  Every element is one product written by one plain
+ * vector store: no atomics, no zero fill, no second pass, bit-identical from run to run.  The host merges adjacent
+ * axes, cuts the records into work items of bounded size and hands the kernel precomputed index increments
+ * (csrc/outer_grouped.hip).  f64 entry: dst, a, b are float64 (8-byte aligned).  c128 entry: dst is interleaved
+ * (re, im), 16-byte aligned; a_is_real / b_is_real != 0 say that the operand addresses float64 data (strides in doubles),
+ * so that a real operand next to a complex one needs no promotion pass; a complex operand is 16-byte aligned.  The f64
+ * entry ignores the two flags. */
+typedef struct {
+    void* dst;
+    const void* a;
+    const void* b;
+    int32_t n_a, n_b, k;
+    int32_t a_is_real, b_is_real;
+    int32_t reserved;
+    int64_t a_shape[CYB_MAX_NDIM];
+    int64_t a_strides[CYB_MAX_NDIM];
+    int64_t b_shape[CYB_MAX_NDIM];
+    int64_t b_strides[CYB_MAX_NDIM];
+} cyb_outer_rec;
+int cyb_outer_grouped_f64(cyb_ctx_t ctx, const cyb_outer_rec* recs, int64_t n);
+int cyb_outer_grouped_c128(cyb_ctx_t ctx, const cyb_outer_rec* recs, int64_t n);
+
 /* ---- truncation of singular values on the device -----------------------------------------
  * TensorBackend::_truncate_singular_values_selection (src/backends/tensor_backend.cpp:139-242) applied to the
  * concatenation of the per-sector singular values WITHOUT the host round trip of
