@@ -18,8 +18,10 @@ struct BqrMat {
     double* V;       // col-major m x k (same ld): explicit unit-lower-trapezoidal reflectors
     double* T;       // ceil(k/NBK) blocks of NBK x NBK (row-major, upper triangular)
     double* tau;     // k
-    double* scratch; // (1 + kWSplit) * scr_half doubles: W2, then the row-chunk partials of W1
+    double* scratch; // (1 + kWSplit) * scr_half doubles: W2, then the row-chunk partials of W1; the wide application of Q
+                     // (bqr_apply_q) keeps the row-chunk partials of a whole group's W1 here instead: scr_total doubles
     int64_t scr_half; // NBK * max(n, kc_max)
+    int64_t scr_total = 0; // doubles behind `scratch` (set by bqr_carve)
     int32_t v_zeroed = 0; // the caller has zero-filled V (a memset of its workspace): the panel kernels skip the rows above a panel
     // Early stop (SVD preconditioner only): ctl -> 2 zeroed doubles, parts -> ceil(n / NBK) * bqr_strip_slots(m) doubles, stop_rel2 > 0: the
     // factorisation stops once ||A[j:, j:]||_F^2 <= stop_rel2 x (largest trailing norm seen); the remaining reflectors are the
@@ -51,9 +53,13 @@ struct BqrTarget {
     double* C;    // col-major m x kc, ld = ldc
     int64_t ldc;
     int32_t kc;
+    int32_t n_pan = -1; // panels the factorisation did not skip (a matrix with early stop: ctl[0] - 1 once ctl[0] != 0, read by
+                        // the caller); -1: all.  The wide route stages no group behind it and needs it for a matrix with ctl.
 };
 // C <- Q C for every target (asynchronous). At most one target per matrix per call (the targets
 // share the matrix' scratch), kc <= the kc the matrix was carved for.
+// Two routes, chosen per target from its shape alone (bqr_apply_wide): 32-column strips, panel by panel, or groups of
+// CYB_QR_APPLY_WIDTH reflector columns through the grouped GEMM (merged T factors, two GEMM launches per group).
 int bqr_apply_q(cyb_ctx_t ctx, const std::vector<BqrMat>& mats, const std::vector<BqrTarget>& targets);
 
 // Batched tile transpose  out[r*ldo + c] = in[c*ldi + r]  for r < R, c < C  (row-major <-> col-major).

@@ -1261,6 +1261,102 @@ __global__ void __launch_bounds__(ST_NT) strip_apply_kernel(const ChunkDesc* __r
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Merged T factor of a GROUP of consecutive panels (the wide application of Q, see bqr_apply_q): the w <= W reflector
+// columns of the group act as ONE block reflector I - V_S T_S V_S^T with T_S (w x w, upper triangular) built from the
+// stored 32 x 32 factors T_b on its diagonal and, for the block column b at offset a,
+//     T_S[0:a, a:a+w_b] = -T_S[0:a, 0:a] (V_S[:, 0:a]^T V_S[:, a:a+w_b]) T_b .
+// The Gram blocks come from a grouped-GEMM launch (n_gp row-chunk partials, summed here in a fixed order); one workgroup
+// per group runs the dependent block columns.  Every entry of the W x W image is written (the workspace is not zeroed).
+struct MergeDesc {
+    const double* G;  // n_gp partial Gram images, W x W row-major each (only the blocks above the block diagonal are set)
+    const double* T;  // the group's first stored panel factor; panel b at T + b * NBK * NBK
+    double* TS;       // W x W row-major
+    int64_t g_stride; // doubles between two partials
+    int32_t w, W, n_gp, pad;
+};
+constexpr int MG_NT = 256;
+// AMAX: rows of the largest left factor T_S[0:a, 0:a], W - 32.  Up to 96 (W <= 128) the finished part of T_S stays in LDS; a
+// 256-wide group reads it back from its global image (its workgroup wrote it: same CU, write-through L1).
+template <int AMAX>
+__global__ void __launch_bounds__(MG_NT) merge_t_kernel(const MergeDesc* __restrict__ descs)
+{
+    constexpr bool TS_LDS = AMAX <= 96;
+    __shared__ double Gs[AMAX][NBK + 1], X[AMAX][NBK + 1];
+    __shared__ double Tb[NBK][NBK + 1];
+    __shared__ double TSs[TS_LDS ? AMAX : 1][TS_LDS ? AMAX + 1 : 1];
+    const MergeDesc d = descs[blockIdx.x];
+    const int tid = threadIdx.x;
+    const int W = d.W, w = d.w;
+    gcp G = (gcp)d.G;
+    gcp T = (gcp)d.T;
+    gp TS = (gp)d.TS;
+    for (int e = tid; e < W * W; e += MG_NT) {
+        const int r = e / W, c = e % W;
+        double v = 0.0;
+        if (r / NBK == c / NBK && r < w && c < w) v = T[(size_t)(r / NBK) * (NBK * NBK) + (r % NBK) * NBK + (c % NBK)];
+        TS[e] = v;
+        if constexpr (TS_LDS)
+            if (r < AMAX && c < AMAX) TSs[r][c] = v;
+    }
+    const int nb = (w + NBK - 1) / NBK;
+    for (int b = 1; b < nb; ++b) {
+        const int a = b * NBK, wb = min(NBK, w - a);
+        __syncthreads(); // (the part of T_S written so far is visible to the whole workgroup; Gs, X and Tb are free)
+        for (int e = tid; e < NBK * NBK; e += MG_NT) Tb[e / NBK][e % NBK] = T[(size_t)b * (NBK * NBK) + e];
+        for (int e = tid; e < a * NBK; e += MG_NT) { // the Gram block, partials summed in a fixed order
+            const int i = e / NBK, l = e % NBK;
+            double g = 0.0;
+            if (l < wb)
+                for (int p = 0; p < d.n_gp; ++p) g += G[(size_t)p * d.g_stride + (size_t)i * W + a + l];
+            Gs[i][l] = g;
+        }
+        __syncthreads();
+        // X = G[0:a, a:a+wb] T_b
+        for (int e = tid; e < a * NBK; e += MG_NT) {
+            const int i = e / NBK, c = e % NBK;
+            double acc = 0.0;
+#pragma unroll
+            for (int l = 0; l < NBK; ++l) acc += Gs[i][l] * Tb[l][c];
+            X[i][c] = acc;
+        }
+        __syncthreads();
+        // T_S[0:a, a:a+wb] = -T_S[0:a, 0:a] X   (T_S[0:a, 0:a] is upper triangular)
+        for (int e = tid; e < a * NBK; e += MG_NT) {
+            const int i = e / NBK, c = e % NBK;
+            double acc = 0.0;
+            if constexpr (TS_LDS) {
+                for (int l = i; l < a; ++l) acc += TSs[i][l] * X[l][c];
+            } else {
+                for (int l = i; l < a; ++l) acc += TS[(size_t)i * W + l] * X[l][c];
+            }
+            if (c < wb) {
+                TS[(size_t)i * W + a + c] = -acc;
+                if constexpr (TS_LDS)
+                    if (a + c < AMAX) TSs[i][a + c] = -acc;
+            }
+        }
+    }
+}
+
+// W1 = sum of its row-chunk partials, in place of the first (the wide application sums them once here instead of carrying
+// every partial as a K-segment of the update: the update is the larger of the two products)
+struct SumDesc {
+    double* W1;     // partial s at W1 + s * stride
+    int64_t n, stride;
+    int32_t ns, pad;
+};
+__global__ void __launch_bounds__(256) sum_partials_kernel(const SumDesc* __restrict__ descs)
+{
+    const SumDesc d = descs[blockIdx.y];
+    gp W1 = (gp)d.W1;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < d.n; e += (int64_t)gridDim.x * 256) {
+        double t = W1[e];
+        for (int sidx = 1; sidx < d.ns; ++sidx) t += W1[e + (int64_t)sidx * d.stride];
+        W1[e] = t;
+    }
+}
+
 inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
 
 __global__ void __launch_bounds__(256) xpose_kernel(const XposeDesc* __restrict__ descs)
@@ -1439,12 +1535,51 @@ static void make_chunks(const std::vector<StripDesc>& sd, double* wbase, int ch,
     }
 }
 
+// ---- wide application of Q (bqr_apply_q): switches, read once per process
+//   CYB_QR_APPLY_WIDE   unset: the shape rule below; 0: strips for every target; 1: wide for every target with more than one panel
+//   CYB_QR_APPLY_WIDTH  reflector columns per group: 64, 128 (default) or 256
+static int wide_mode()
+{
+    static const int v = getenv("CYB_QR_APPLY_WIDE") ? (atoi(getenv("CYB_QR_APPLY_WIDE")) != 0 ? 1 : 0) : -1;
+    return v;
+}
+static int wide_width()
+{
+    static const int v = [] {
+        const int e = getenv("CYB_QR_APPLY_WIDTH") ? atoi(getenv("CYB_QR_APPLY_WIDTH")) : 128;
+        return (e == 64 || e == 256) ? e : 128;
+    }();
+    return v;
+}
+constexpr int64_t kWideMinK = 256, kWideMinKc = 256, kWideMinCols = 4096;
+// The shape rule: reflector columns of the matrix, columns of the target -- never data.  A target with fewer than kWideMinK
+// reflector columns has at most one full group: the three launches that build the merged factors cost more than the panel
+// steps they replace.  And the W1 product of a group has only W x (columns of all wide targets of the call) outputs: below
+// kWideMinCols columns (bqr_apply_q) it cannot fill the chip and the row-split strips win -- measured: one 1442^2 theta block
+// 18.2 ms on strips, 19.0 wide; the chi = 1024 list (three targets, 1030 columns) 4.75 ms against 5.2; the 15-block chi = 4096
+// list (8462 columns) 25.1 against 24.3 ms per step.
+static bool wide_target(const BqrMat& q, const BqrTarget& t)
+{
+    const int mode = wide_mode();
+    if (mode == 0 || q.k <= NBK || t.kc <= 0) return false;
+    if (q.ctl && q.stop_rel2 > 0.0 && t.n_pan < 0) return false; // (skipped panels must be known: their V is never read)
+    if (mode == 1) return true;
+    return q.k >= kWideMinK && t.kc >= kWideMinKc;
+}
+// doubles of scratch: the strips' W2 + partials, or the row-chunk partials of one group's W1 (W x kc each)
+static size_t scratch_doubles(int64_t m, int64_t n, int64_t kc)
+{
+    const size_t strips = (size_t)(1 + kWSplit) * NBK * (size_t)std::max<int64_t>(std::max(n, kc), 1);
+    const size_t wide = (size_t)w_split(m) * (size_t)wide_width() * (size_t)std::max<int64_t>(kc, 1);
+    return std::max(strips, wide);
+}
+
 size_t bqr_aux_bytes(int64_t m, int64_t n, int64_t ld, int64_t kc)
 {
     const int64_t k = std::min(m, n);
     const int64_t npan = (k + NBK - 1) / NBK;
     return al256(sizeof(double) * (size_t)ld * (size_t)std::max<int64_t>(k, 1)) + al256(sizeof(double) * (size_t)npan * NBK * NBK) +
-           al256(sizeof(double) * (size_t)std::max<int64_t>(k, 1)) + al256(sizeof(double) * (1 + kWSplit) * NBK * (size_t)std::max<int64_t>(std::max(n, kc), 1));
+           al256(sizeof(double) * (size_t)std::max<int64_t>(k, 1)) + al256(sizeof(double) * scratch_doubles(m, n, kc));
 }
 
 size_t bqr_carve(BqrMat& q, char* base, int64_t kc)
@@ -1460,7 +1595,8 @@ size_t bqr_carve(BqrMat& q, char* base, int64_t kc)
     off += al256(sizeof(double) * (size_t)std::max<int64_t>(k, 1));
     q.scratch = reinterpret_cast<double*>(base + off);
     q.scr_half = (int64_t)NBK * std::max<int64_t>(std::max<int64_t>(q.n, kc), 1);
-    off += al256(sizeof(double) * (1 + kWSplit) * NBK * (size_t)std::max<int64_t>(std::max<int64_t>(q.n, kc), 1));
+    q.scr_total = (int64_t)scratch_doubles(q.m, q.n, kc);
+    off += al256(sizeof(double) * (size_t)q.scr_total);
     return off;
 }
 
@@ -1870,7 +2006,8 @@ int bqr_factor(cyb_ctx_t ctx, const std::vector<BqrMat>& mats)
     return CYB_OK;
 }
 
-int bqr_apply_q(cyb_ctx_t ctx, const std::vector<BqrMat>& mats, const std::vector<BqrTarget>& targets)
+// the strip route of bqr_apply_q: one panel step (32 reflector columns) at a time, last panel first
+static int apply_q_strips(cyb_ctx_t ctx, const std::vector<BqrMat>& mats, const std::vector<BqrTarget>& targets)
 {
     int max_pan = 0;
     for (const auto& t : targets) max_pan = std::max(max_pan, (mats[(size_t)t.mat].k + NBK - 1) / NBK);
@@ -1982,6 +2119,191 @@ int bqr_apply_q(cyb_ctx_t ctx, const std::vector<BqrMat>& mats, const std::vecto
         CYB_TRY(gemm_launch_staged(ctx, st.s3, d_image));
     }
     } // chunks of panel steps
+    return CYB_OK;
+}
+
+// The wide route of bqr_apply_q.  Nothing between two panel steps of an application depends on a factorisation, so the
+// reflectors are applied in groups of W = CYB_QR_APPLY_WIDTH columns, last group first:
+//   once per call, off the chain of C:  Gram blocks of every group (one grouped-GEMM launch) -> merged factors T_S
+//   (merge_t_kernel) -> VT_S = V_S T_S (one grouped-GEMM launch);
+//   per group, for the whole batch:     W1 = V_S^T C[j0_S:, :] in row chunks (w_split: the narrow output fills the chip), the
+//   partials summed in a fixed order (sum_partials_kernel), then C[j0_S:, :] -= VT_S W1.
+// C is streamed once per W reflector columns instead of once per 32, and both products have the shape of an ordinary GEMM.
+static int apply_q_wide(cyb_ctx_t ctx, const std::vector<BqrMat>& mats, const std::vector<BqrTarget>& targets)
+{
+    const int W = wide_width();
+    struct Tgt {
+        const BqrMat* q;
+        const BqrTarget* t;
+        int k_eff, ng; // reflector columns that are applied (the panels behind an early stop are the identity), groups
+        double* VT;    // V_S T_S of every group, laid out like V (element (i, c) at c * ld + i)
+        double* TS;    // ng images of W x W
+        double* G;     // Gram partials: per group n_gp images of W x W
+        std::vector<int> n_gp;
+    };
+    std::vector<Tgt> tg;
+    size_t bytes = 0;
+    int max_ng = 0;
+    for (const auto& t : targets) {
+        const BqrMat& q = mats[(size_t)t.mat];
+        const int npan = (q.k + NBK - 1) / NBK;
+        const int nf = t.n_pan >= 0 ? std::min(npan, (int)t.n_pan) : npan;
+        const int k_eff = std::min<int>(q.k, nf * NBK);
+        if (k_eff <= 0 || t.kc <= 0) continue;
+        Tgt g{&q, &t, k_eff, (k_eff + W - 1) / W, nullptr, nullptr, nullptr, {}};
+        CYB_REQUIRE((int64_t)w_split(q.m) * W * t.kc <= q.scr_total, "bqr_apply_q: target wider than the carved scratch");
+        for (int s = 0; s < g.ng; ++s) {
+            // row chunks of the group's Gram blocks: every block column keeps at least 256 rows per chunk
+            const int j0 = s * W, w = std::min(W, k_eff - j0);
+            const int min_rows = q.m - j0 - (w - 1) / NBK * NBK;
+            g.n_gp.push_back(std::max(1, std::min(4, min_rows / 256)));
+        }
+        max_ng = std::max(max_ng, g.ng);
+        tg.push_back(std::move(g));
+    }
+    if (tg.empty()) return CYB_OK;
+    std::vector<size_t> o_vt(tg.size()), o_ts(tg.size()), o_g(tg.size());
+    for (size_t i = 0; i < tg.size(); ++i) {
+        size_t n_g = 0;
+        for (int n : tg[i].n_gp) n_g += (size_t)n;
+        o_vt[i] = bytes;
+        bytes += al256(sizeof(double) * (size_t)tg[i].q->ld * (size_t)tg[i].k_eff);
+        o_ts[i] = bytes;
+        bytes += al256(sizeof(double) * (size_t)tg[i].ng * W * W);
+        o_g[i] = bytes;
+        bytes += al256(sizeof(double) * n_g * W * W);
+    }
+    void* ws = nullptr;
+    CYB_TRY(ctx->workspace(bytes, &ws, 5));
+    for (size_t i = 0; i < tg.size(); ++i) {
+        tg[i].VT = reinterpret_cast<double*>(static_cast<char*>(ws) + o_vt[i]);
+        tg[i].TS = reinterpret_cast<double*>(static_cast<char*>(ws) + o_ts[i]);
+        tg[i].G = reinterpret_cast<double*>(static_cast<char*>(ws) + o_g[i]);
+    }
+    std::vector<char> image;
+    // ---- merged factors of every group of every target
+    {
+        GemmBatch gg, gv;
+        std::vector<MergeDesc> md;
+        for (const Tgt& g : tg) {
+            const BqrMat& q = *g.q;
+            size_t gp0 = 0;
+            for (int s = 0; s < g.ng; ++s) {
+                const int j0 = s * W, w = std::min(W, g.k_eff - j0), n_gp = g.n_gp[(size_t)s];
+                const double* Vs = q.V + (size_t)j0 * q.ld + j0; // V_S: element (i, a) at a * ld + i, i < m - j0
+                double* Gs = g.G + gp0 * (size_t)W * W;
+                double* TSs = g.TS + (size_t)s * W * W;
+                for (int a = NBK; a < w; a += NBK) {
+                    // G[0:a, a:a+wb] = V_S[a:, 0:a]^T V_S[a:, a:a+wb]  (the columns from a on are zero above row a)
+                    const int wb = std::min(NBK, w - a);
+                    const int64_t rows = q.m - j0 - a, chunk = (rows + n_gp - 1) / n_gp;
+                    for (int p = 0; p < n_gp; ++p) {
+                        const int64_t r0 = a + chunk * p, kr = std::min(chunk, rows - chunk * p);
+                        gg.add(Gs + (size_t)p * W * W + a, a, wb, W, Vs + r0, q.ld, 1, Vs + (size_t)a * q.ld + r0, 1, q.ld, kr, 1.0, 0.0);
+                    }
+                }
+                md.push_back(MergeDesc{Gs, q.T + (size_t)(j0 / NBK) * NBK * NBK, TSs, (int64_t)W * W, w, W, n_gp, 0});
+                // VT_S^T (w x rows, row stride ld) = T_S^T V_S^T
+                gv.add(g.VT + (size_t)j0 * q.ld + j0, w, q.m - j0, q.ld, TSs, 1, W, Vs, q.ld, 1, w, 1.0, 0.0);
+                gp0 += (size_t)n_gp;
+            }
+        }
+        GemmStaged sg, sv;
+        CYB_TRY(gg.stage(ctx, image, sg));
+        CYB_TRY(gv.stage(ctx, image, sv));
+        const size_t off_md = (image.size() + 255) / 256 * 256;
+        image.resize(off_md + sizeof(MergeDesc) * md.size());
+        memcpy(image.data() + off_md, md.data(), sizeof(MergeDesc) * md.size());
+        void* d_image = nullptr;
+        CYB_TRY(ctx->upload(image.data(), image.size(), &d_image));
+        CYB_TRY(gemm_launch_staged(ctx, sg, d_image));
+        const MergeDesc* mdp = reinterpret_cast<const MergeDesc*>(static_cast<char*>(d_image) + off_md);
+        if (W <= 128) hipLaunchKernelGGL(merge_t_kernel<96>, dim3((unsigned)md.size()), dim3(MG_NT), 0, ctx->stream, mdp);
+        else hipLaunchKernelGGL(merge_t_kernel<224>, dim3((unsigned)md.size()), dim3(MG_NT), 0, ctx->stream, mdp);
+        CYB_HIP(hipGetLastError());
+        CYB_TRY(gemm_launch_staged(ctx, sv, d_image));
+    }
+    // ---- the groups, last first, staged in growing chunks (2, 6, 18, ... groups): the host lays out the next chunk while
+    //      the device runs the previous ones
+    struct Step {
+        GemmStaged s1, s2;
+        size_t off_sum = 0;
+        unsigned n_sum = 0;
+    };
+    std::vector<Step> steps;
+    int chunk = 2;
+    for (int c0 = max_ng - 1; c0 >= 0; c0 -= chunk, chunk *= 3) {
+        const int c1 = std::max(-1, c0 - chunk);
+        steps.clear();
+        image.clear();
+        for (int s = c0; s > c1; --s) {
+            GemmBatch g1, g2;
+            std::vector<SumDesc> sums;
+            for (const Tgt& g : tg) {
+                if (s >= g.ng) continue;
+                const BqrMat& q = *g.q;
+                const BqrTarget& t = *g.t;
+                const int j0 = s * W, w = std::min(W, g.k_eff - j0);
+                const int64_t mr = q.m - j0;
+                const double* Vs = q.V + (size_t)j0 * q.ld + j0;
+                const double* VTs = g.VT + (size_t)j0 * q.ld + j0;
+                double* Ct = t.C + j0; // rows j0.. of every column
+                const int ns = w_split(mr);
+                const int64_t rch = ((mr + ns - 1) / ns + 15) / 16 * 16;
+                const int64_t stride = (int64_t)W * t.kc;
+                int n_part = 0;
+                for (int sidx = 0; sidx < ns; ++sidx) {
+                    const int64_t r0 = rch * sidx, rows = std::min(rch, mr - r0);
+                    if (rows <= 0) break;
+                    // partial W1 (w x kc row-major) of this row chunk
+                    g1.add(q.scratch + (size_t)sidx * (size_t)stride, w, t.kc, t.kc, Vs + r0, q.ld, 1, Ct + r0, 1, t.ldc, rows, 1.0, 0.0);
+                    ++n_part;
+                }
+                if (n_part > 1) sums.push_back(SumDesc{q.scratch, (int64_t)w * t.kc, stride, n_part, 0});
+                // C^T (kc x mr, row stride ldc) -= W1^T VT_S^T
+                g2.add(Ct, t.kc, mr, t.ldc, q.scratch, 1, t.kc, VTs, q.ld, 1, w, -1.0, 1.0);
+            }
+            if (g1.empty()) continue;
+            Step st;
+            CYB_TRY(g1.stage(ctx, image, st.s1));
+            CYB_TRY(g2.stage(ctx, image, st.s2));
+            if (!sums.empty()) {
+                st.n_sum = (unsigned)sums.size();
+                st.off_sum = (image.size() + 255) / 256 * 256;
+                image.resize(st.off_sum + sizeof(SumDesc) * sums.size());
+                memcpy(image.data() + st.off_sum, sums.data(), sizeof(SumDesc) * sums.size());
+            }
+            steps.push_back(st);
+        }
+        if (steps.empty()) continue;
+        void* d_image = nullptr;
+        CYB_TRY(ctx->upload(image.data(), image.size(), &d_image));
+        for (const auto& st : steps) {
+            CYB_TRY(gemm_launch_staged(ctx, st.s1, d_image));
+            if (st.n_sum) {
+                hipLaunchKernelGGL(sum_partials_kernel, dim3(helper_grid_x(st.n_sum), st.n_sum), dim3(256), 0, ctx->stream,
+                                   reinterpret_cast<const SumDesc*>(static_cast<char*>(d_image) + st.off_sum));
+                CYB_HIP(hipGetLastError());
+            }
+            CYB_TRY(gemm_launch_staged(ctx, st.s2, d_image));
+        }
+    }
+    return CYB_OK;
+}
+
+int bqr_apply_q(cyb_ctx_t ctx, const std::vector<BqrMat>& mats, const std::vector<BqrTarget>& targets)
+{
+    // the two routes work on disjoint targets (and on the scratch of disjoint matrices)
+    std::vector<BqrTarget> narrow, wide;
+    for (const auto& t : targets) (wide_target(mats[(size_t)t.mat], t) ? wide : narrow).push_back(t);
+    int64_t cols = 0;
+    for (const auto& t : wide) cols += t.kc;
+    if (wide_mode() < 0 && cols < kWideMinCols) { // (see wide_target)
+        narrow = targets;
+        wide.clear();
+    }
+    if (!narrow.empty()) CYB_TRY(apply_q_strips(ctx, mats, narrow));
+    if (!wide.empty()) CYB_TRY(apply_q_wide(ctx, mats, wide));
     return CYB_OK;
 }
 

@@ -877,7 +877,9 @@ static int run_svd_qr(cyb_ctx_t ctx, int64_t nmat, const cyb_svd_desc* sd, int32
         bool tall;
         size_t Ac, aux, W, J, sig, rank, thr, nnull, Cq, Fc, aux2, Cn, idx, Wc, Jc;
         size_t bad, Wq, aux3, Cq2, sig2; // second (LQ) preconditioning step
-        size_t stop;                     // early stop of the first QR: [ctl (2 doubles) | squared norms of the strips of one step]
+        size_t stop;                     // early stop of the first QR: squared norms of the strips of one step
+        size_t ctl;                      // ... and its two control words, behind the flags: they ride in the same D2H copy as the row norms
+        int n_fac = -1;                  // panels the first QR factored before it stopped (-1: all), for the application of Q1
         size_t sigo;                     // singular values of an LQ block by full-size row (PostDesc::sig_lq)
         size_t dev;                      // max |J' J'^T - 1| of the recovered rotations (behind the flags: same D2H copy)
         bool lq = false;
@@ -912,6 +914,10 @@ static int run_svd_qr(cyb_ctx_t ctx, int64_t nmat, const cyb_svd_desc* sd, int32
         lay[(size_t)b].dev = off;
         off += sizeof(double);
     }
+    for (int64_t b = 0; b < nmat; ++b) {
+        lay[(size_t)b].ctl = off;
+        off += 2 * sizeof(double);
+    }
     const size_t sig_bytes = off - sig_begin;
     off = al(off);
     for (int64_t b = 0; b < nmat; ++b) {
@@ -923,7 +929,7 @@ static int run_svd_qr(cyb_ctx_t ctx, int64_t nmat, const cyb_svd_desc* sd, int32
         };
         l.Ac = take(sizeof(double) * (size_t)l.L * l.k);
         l.aux = take(bqr_aux_bytes(l.L, l.k, l.L, l.k));
-        l.stop = take(sizeof(double) * (size_t)(2 + (l.k + cyb::NBK - 1) / cyb::NBK * cyb::bqr_strip_slots(l.L)));
+        l.stop = take(sizeof(double) * (size_t)std::max(1, (l.k + cyb::NBK - 1) / cyb::NBK * cyb::bqr_strip_slots(l.L)));
         l.W = take(sizeof(double) * (size_t)l.kp * l.kp);
         l.J = take(sizeof(double) * (size_t)l.kp * l.kp);
         l.rank = take(sizeof(int32_t) * (size_t)l.kp);
@@ -972,8 +978,8 @@ static int run_svd_qr(cyb_ctx_t ctx, int64_t nmat, const cyb_svd_desc* sd, int32
         // a rank-deficient block (every block of a two-site theta = A.B) stops factoring once the trailing block is at the
         // level the up-front deflation below discards anyway: ||A[j:, j:]||_F <= L eps ||A||_F (numpy.linalg.matrix_rank's
         // threshold; the reference norm the kernels use is a lower bound of ||A||_F, so they stop no earlier than this)
-        q.ctl = dp(l.stop);
-        q.parts = dp(l.stop) + 2;
+        q.ctl = dp(l.ctl);
+        q.parts = dp(l.stop);
         q.stop_rel2 = ((double)l.L * 2.220446049250313e-16) * ((double)l.L * 2.220446049250313e-16);
         if (l.tall) // Ac (col-major m x n) <- A (row-major):  out(r = col, c = row) = A[c*lda + r]
             x_in.push_back(XposeDesc{sd[b].A, q.Ac, sd[b].lda, l.L, l.n, l.m, 0, 0, 0, 0});
@@ -1041,6 +1047,9 @@ static int run_svd_qr(cyb_ctx_t ctx, int64_t nmat, const cyb_svd_desc* sd, int32
         for (int64_t b = 0; b < nmat; ++b) {
             Lay& l = lay[(size_t)b];
             const double* sg = sig_of(l);
+            // (the factorisation is over: ctl[0] is 1 + the first panel step it skipped, or 0)
+            const double stopped = h_sig[(l.ctl - sig_begin) / sizeof(double)];
+            l.n_fac = stopped != 0.0 ? (int)stopped - 1 : -1;
             // numerical-rank threshold (numpy.linalg.matrix_rank's): ||A||_F * max(m,n) * eps, squared;
             // ||A||_F = ||R||_F comes from the row norms just read
             double fro2 = 0.0;
@@ -1414,7 +1423,7 @@ static int run_svd_qr(cyb_ctx_t ctx, int64_t nmat, const cyb_svd_desc* sd, int32
     for (int64_t b = 0; b < nmat; ++b) {
         const Lay& l = lay[(size_t)b];
         jc.push_back(JcqDesc{dp(l.J), reinterpret_cast<const int32_t*>(base + l.rank), dp(l.Cq), l.L, l.kp, l.k});
-        tg.push_back(BqrTarget{(int)b, dp(l.Cq), l.L, l.k});
+        tg.push_back(BqrTarget{(int)b, dp(l.Cq), l.L, l.k, l.n_fac >= 0 ? l.n_fac : (l.k + cyb::NBK - 1) / cyb::NBK});
         if (l.tall) // U (row-major m x k): out(r, c) = Cq[c*L + r]
             x_out.push_back(XposeDesc{dp(l.Cq), sd[b].U, l.L, sd[b].ldu, l.m, l.k, 0, 0, 0, 0});
         else        // Vh (row-major k x n): row r = column r of Cq
