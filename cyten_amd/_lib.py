@@ -18,6 +18,11 @@ CYB_SVD_EMBEDDED_COMPLEX = 2
 CYB_EIGH_EMBEDDED_COMPLEX = 2
 CYB_EXPM_SMALL_MAX_N_F64 = 96
 CYB_EXPM_SMALL_MAX_N_C128 = 64
+CYB_SEG_ABSENT, CYB_SEG_F64, CYB_SEG_C128, CYB_SEG_BOOL = range(4)
+SEG_BINARY_OPS = {name: i for i, name in enumerate(('add', 'sub', 'mul', 'div', 'lt', 'le', 'gt', 'ge', 'eq', 'ne', 'and', 'or', 'xor', 'not'))}
+SEG_REDUCE_OPS = {name: i for i, name in enumerate(('sum', 'max', 'min', 'count'))}
+SEG_PRE_MAPS = {name: i for i, name in enumerate((None, 'abs', 'square', 'xlogx', 'pow'))}
+SEG_LANES_MAX, SEG_WAVE_MAX, SEG_CHUNK = 64, 1024, 16384   # owner regimes of a segment (csrc/segment_ops.hip)
 
 CYB_OK, CYB_ERR_INVALID, CYB_ERR_HIP, CYB_ERR_NOCONV, CYB_ERR_NOMEM, CYB_ERR_UNSUPPORTED = range(6)
 
@@ -137,6 +142,11 @@ class OuterRec(C.Structure):
                 ('b_shape', C.c_int64 * CYB_MAX_NDIM), ('b_strides', C.c_int64 * CYB_MAX_NDIM)]
 
 
+class SegRec(C.Structure):
+    _fields_ = [('a', C.c_void_p), ('b', C.c_void_p), ('out', C.c_void_p), ('n', C.c_int64),
+                ('a_kind', C.c_int32), ('b_kind', C.c_int32), ('out_kind', C.c_int32), ('reserved', C.c_int32)]
+
+
 # numpy views of the descriptor structs (same layout: numpy derives the dtype from the ctypes Structure), for the
 # vectorised marshalling of long block lists
 import numpy as _np  # noqa: E402
@@ -157,6 +167,7 @@ TRACE_OUT_DTYPE = _np.dtype(TraceOut)
 TRACE_TERM_DTYPE = _np.dtype(TraceTerm)
 EXPM_DTYPE = _np.dtype(ExpmDesc)
 OUTER_DTYPE = _np.dtype(OuterRec)
+SEG_DTYPE = _np.dtype(SegRec)
 
 _P = C.POINTER
 _ctx = C.c_void_p
@@ -239,6 +250,9 @@ PROTOTYPES = {
     'cyb_norm1_batched_c128': [_ctx, _P(ExpmDesc), C.c_int64, _vp],
     'cyb_outer_grouped_f64': [_ctx, _P(OuterRec), C.c_int64],
     'cyb_outer_grouped_c128': [_ctx, _P(OuterRec), C.c_int64],
+    'cyb_seg_binary': [_ctx, _P(SegRec), C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double],
+    'cyb_seg_reduce': [_ctx, _P(SegRec), C.c_int64, C.c_int32, C.c_int32, C.c_double, _vp],
+    'cyb_seg_compact': [_ctx, _P(SegRec), C.c_int64, _vp, _vp],
     'cyb_truncate_select_f64': [_ctx, _P(VecDesc), C.c_int64, _P(TruncOpts), _vp, _vp, _vp],
     'cyb_truncate_select_weighted_f64': [_ctx, _P(VecDesc), C.c_int64, _vp, _P(TruncOpts), _vp, _vp, _vp],
     'cyb_random_uniform_f64': [_ctx, _vp, C.c_int64, C.c_uint64, C.c_double, C.c_double],

@@ -920,6 +920,17 @@ class Mask:
     small_leg: Leg
     blocks: list
     block_inds: np.ndarray
+    # device masks (``diagonal_to_mask``, ``mask_binary``, ``mask_unary``): `blocks` are boolean DEVICE blocks and
+    # ``tables[i]`` holds the ascending kept positions of block i in device memory (what ``seg_compact_many`` returns), so
+    # that ``mask_contract`` uploads nothing.  ``is_projection=False``: the dagger / transpose, an inclusion of the small leg
+    # into the large one, whose ``block_inds`` columns are (large, small).
+    tables: list | None = None
+    is_projection: bool = True
+
+    @property
+    def large_col(self) -> int:
+        """the column of ``block_inds`` that indexes the sectors of the large leg"""
+        return 1 if self.is_projection else 0
 
     @classmethod
     def from_flags(cls, large_leg: Leg, flags) -> 'Mask':
@@ -944,13 +955,24 @@ def mask_contract(bb, t: AbelianTensor, mask: Mask, leg_idx: int, large_leg: boo
     mask's large leg) onto the kept states, blocks of sectors without a kept state are dropped; ``False``: embed leg
     `leg_idx` (the small leg) into the large one, zeros elsewhere.  The reference loops ``apply_mask`` / ``enlarge_leg``
     over the common blocks; here the block table is matched on the host and ALL blocks go through one batched gather
-    (``mask_gather_many``) or one zero fill + one batched scatter (``enlarge_leg_many``)."""
+    (``mask_gather_many``) or one zero fill + one batched scatter (``enlarge_leg_many``).  A device mask hands its
+    position tables over as they are (``mask.tables``): no upload of index tables in either direction."""
+    items, rows, legs = _mask_contract_items(t, mask, leg_idx, large_leg)
+    if not items:
+        return AbelianTensor(t.symmetry, legs, [], np.zeros((0, t.nlegs), np.int64), t.num_codomain)
+    blocks = bb.mask_gather_many(items) if large_leg else bb.enlarge_leg_many(items)
+    return AbelianTensor(t.symmetry, legs, blocks, np.array(rows, dtype=np.int64), t.num_codomain).sorted()
+
+
+def _mask_contract_items(t: AbelianTensor, mask: Mask, leg_idx: int, large_leg: bool):
+    """the host side of :func:`mask_contract`: (items for ``mask_gather_many`` / ``enlarge_leg_many``, rows of the new
+    block table in the order of the items, new legs)"""
     leg_idx = int(leg_idx) % t.nlegs
     old_leg = t.legs[leg_idx]
     src_leg, dst_leg = (mask.large_leg, mask.small_leg) if large_leg else (mask.small_leg, mask.large_leg)
     if old_leg.nsec != src_leg.nsec or not np.array_equal(old_leg.sectors, src_leg.sectors) or not np.array_equal(old_leg.mults, src_leg.mults):
         raise ValueError('mask_contract: the leg of the tensor is not the leg of the mask')
-    src_col = 1 if large_leg else 0
+    src_col = mask.large_col if large_leg else 1 - mask.large_col
     by_sector = {int(r[src_col]): j for j, r in enumerate(mask.block_inds)}
     # (the reference lexsorts by the contracted column and merges the two sorted columns; the result is sorted afterwards)
     items, rows = [], []
@@ -961,13 +983,16 @@ def mask_contract(bb, t: AbelianTensor, mask: Mask, leg_idx: int, large_leg: boo
         new_row = row.copy()
         new_row[leg_idx] = mask.block_inds[j, 1 - src_col]
         rows.append(new_row)
-        items.append((blk, mask.blocks[j], leg_idx))
+        if mask.tables is None:
+            which = mask.blocks[j]
+        elif large_leg:
+            which = mask.tables[j]
+        else:
+            which = (mask.tables[j], int(mask.large_leg.mults[int(mask.block_inds[j, mask.large_col])]))
+        items.append((blk, which, leg_idx))
     legs = list(t.legs)
     legs[leg_idx] = Leg(dst_leg.symmetry, dst_leg.sectors, dst_leg.mults, old_leg.sign)
-    if not items:
-        return AbelianTensor(t.symmetry, legs, [], np.zeros((0, t.nlegs), np.int64), t.num_codomain)
-    blocks = bb.mask_gather_many(items) if large_leg else bb.enlarge_leg_many(items)
-    return AbelianTensor(t.symmetry, legs, blocks, np.array(rows, dtype=np.int64), t.num_codomain).sorted()
+    return items, rows, legs
 
 
 def _common_sectors(cod: Leg, dom: Leg):
@@ -1062,6 +1087,10 @@ def _is_complex_block(b) -> bool:
     return np.dtype(getattr(b, 'dtype', np.float64)).kind == 'c'
 
 
+def _is_bool_block(b) -> bool:
+    return np.dtype(getattr(b, 'dtype', np.float64)).kind == 'b'
+
+
 def conj(bb, t: AbelianTensor) -> AbelianTensor:
     """Complex conjugate in the same leg order: every leg becomes its dual (same sectors, opposite sign), so the charge
     rule holds for the same block table.  Real blocks are their own conjugate (no launch); the complex blocks of the tensor
@@ -1096,9 +1125,14 @@ class DiagonalTensor:
     leg: Leg
     blocks: list
     block_inds: np.ndarray
+    dtype: np.dtype | None = None     # of the blocks; it matters for a tensor without blocks (abelian.cpp:1622-1626)
 
     def __post_init__(self):
         self.block_inds = np.asarray(self.block_inds, dtype=np.int64).reshape(len(self.blocks))
+        if self.dtype is None:
+            kinds = {np.dtype(getattr(b, 'dtype', np.float64)).kind for b in self.blocks}
+            self.dtype = np.dtype(np.complex128 if 'c' in kinds else np.bool_ if kinds == {'b'} else np.float64)
+        self.dtype = np.dtype(self.dtype)
 
     @classmethod
     def from_numpy(cls, bb, leg: Leg, values) -> 'DiagonalTensor':
@@ -1112,7 +1146,8 @@ class DiagonalTensor:
     def to_numpy(self, bb) -> np.ndarray:
         """the full diagonal, zeros in the sectors without a block"""
         cplx = any(_is_complex_block(b) for b in self.blocks)
-        out = np.zeros(self.leg.dim, dtype=np.complex128 if cplx else np.float64)
+        dtype = np.bool_ if self.blocks and all(_is_bool_block(b) for b in self.blocks) else np.complex128 if cplx else np.float64
+        out = np.zeros(self.leg.dim, dtype=dtype)
         for blk, i in zip(self.blocks, self.block_inds):
             out[int(self.leg.slices[i]):int(self.leg.slices[i + 1])] = bb.to_numpy(blk)
         return out
@@ -2065,3 +2100,402 @@ def squeeze_legs(bb, t: AbelianTensor, idcs=None) -> AbelianTensor:
     blocks = [bb.squeeze_axes(b, idcs) for b in t.blocks] if idcs else list(t.blocks)
     return AbelianTensor(t.symmetry, [t.legs[k] for k in keep], blocks, t.block_inds[:, keep].reshape(len(blocks), len(keep)),
                          t.num_codomain - sum(1 for k in idcs if k < t.num_codomain), [t.labels[k] for k in keep] if len(t.labels) == n else [])
+
+
+# ---------------------------------------------------------------------------------------------
+# diagonal-tensor arithmetic, reductions and device-side masks
+# ---------------------------------------------------------------------------------------------
+
+_ARITH_OPS = ('add', 'sub', 'mul', 'div')
+_COMPARE_OPS = ('lt', 'le', 'gt', 'ge', 'eq', 'ne')
+_LOGICAL_OPS = ('and', 'or', 'xor')
+_PY_COMPARE = {'lt': lambda a, b: a < b, 'le': lambda a, b: a <= b, 'gt': lambda a, b: a > b, 'ge': lambda a, b: a >= b,
+               'eq': lambda a, b: a == b, 'ne': lambda a, b: a != b}
+
+
+def _by_sector(blocks, inds) -> dict:
+    return {int(i): b for i, b in zip(inds, blocks)}
+
+
+def _parse_index(leg: Leg, idx: int):
+    """(sector index, index within the sector) of basis state `idx` of `leg` (``Space.parse_index``)"""
+    idx = int(idx)
+    if idx < 0:
+        idx += leg.dim
+    if not 0 <= idx < leg.dim:
+        raise IndexError(f'index {idx} out of range for a leg of dimension {leg.dim}')
+    sec = int(np.searchsorted(np.asarray(leg.slices), idx, side='right')) - 1
+    return sec, idx - int(leg.slices[sec])
+
+
+def _binary_result_dtype(func: str, dtype_a, dtype_b) -> np.dtype:
+    """dtype of ``func(ones(dtype_a), ones(dtype_b))``: the reference's sample rule for a result without blocks
+    (abelian.cpp:1622-1626)"""
+    if func in _ARITH_OPS:
+        return np.dtype(np.complex128 if 'c' in (np.dtype(dtype_a).kind, np.dtype(dtype_b).kind) else np.float64)
+    return np.dtype(np.bool_)
+
+
+def diagonal_binary(bb, a: DiagonalTensor, b: DiagonalTensor, func: str, partial_zero_is_zero: bool) -> DiagonalTensor:
+    """``AbelianBackend::diagonal_elementwise_binary`` (abelian.cpp:1568-1633) for the functions the device serves by name:
+    add, sub, mul, div; lt, le, gt, ge, eq, ne; and, or, xor (boolean diagonals).  The merge over the sectors of the leg is
+    the reference's (:1596-1619): with `partial_zero_is_zero` a sector missing on either side is skipped; otherwise the
+    missing operand is the kernel's "absent" kind, read as zeros -- no zero block is allocated (:1605, :1615).  ALL sectors
+    are ONE ``seg_binary_many`` launch and no download, where the reference calls ``func`` per sector.  A result without
+    blocks gets its dtype from the sample rule (:1622-1626).  (Where `a` lacks a sector that `b` has, the reference skips the
+    sector without stepping over the block of `b` (:1602-1603) and then treats every later block of `b` as missing; the
+    stated rule is followed here, not that slip.)"""
+    if func not in _ARITH_OPS + _COMPARE_OPS + _LOGICAL_OPS:
+        raise ValueError(f'diagonal_binary: unknown function {func!r}')
+    if a.symmetry != b.symmetry or not _same_space(a.leg, b.leg):
+        raise ValueError('diagonal_binary: the two diagonals do not live on the same leg')
+    ha, hb = _by_sector(a.blocks, a.block_inds), _by_sector(b.blocks, b.block_inds)
+    items, inds = [], []
+    for i in range(a.leg.nsec):
+        blk_a, blk_b = ha.get(i), hb.get(i)
+        if partial_zero_is_zero and (blk_a is None or blk_b is None):
+            continue
+        items.append((blk_a, blk_b, int(a.leg.mults[i])))
+        inds.append(i)
+    dtype = _binary_result_dtype(func, a.dtype, b.dtype)
+    blocks = bb.seg_binary_many(items, func, complex_out=dtype.kind == 'c') if items else []
+    return DiagonalTensor(a.symmetry, a.leg, list(blocks), np.array(inds, dtype=np.int64), dtype)
+
+
+def diagonal_compare(bb, d: DiagonalTensor, op: str, scalar) -> DiagonalTensor:
+    """``d (op) scalar`` as a boolean DiagonalTensor (``DiagonalTensor._elementwise_binary`` with a number, through
+    abelian.cpp:743-782 with ``maps_zero_to_zero`` decided by ``0 (op) scalar``): a sector without a block compares as
+    zeros, so it gets an all-true block if ``0 (op) scalar`` holds and stays without a block (all false) otherwise -- the
+    absent kind again, no zero block.  ONE launch for all sectors, no download."""
+    if op not in _COMPARE_OPS:
+        raise ValueError(f'diagonal_compare: unknown comparison {op!r}')
+    if isinstance(scalar, complex) and op not in ('eq', 'ne'):
+        raise TypeError('diagonal_compare: complex numbers are not ordered')
+    have = _by_sector(d.blocks, d.block_inds)
+    fill = bool(_PY_COMPARE[op](0.0, scalar))
+    items, inds = [], []
+    for i in range(d.leg.nsec):
+        if i in have or fill:
+            items.append((have.get(i), None, int(d.leg.mults[i])))
+            inds.append(i)
+    blocks = bb.seg_binary_many(items, op, scalar=scalar) if items else []
+    return DiagonalTensor(d.symmetry, d.leg, list(blocks), np.array(inds, dtype=np.int64), np.bool_)
+
+
+def _counts(bb, d: DiagonalTensor) -> np.ndarray:
+    table = bb.seg_reduce_many(d.blocks, [int(d.leg.mults[i]) for i in d.block_inds], 'count')
+    return table[:, 0].astype(np.int64)
+
+
+def diagonal_all(bb, d: DiagonalTensor) -> bool:
+    """``AbelianBackend::diagonal_all`` (abelian.cpp:717-730): missing blocks are False (:724), the existing ones must be
+    all-true -- ONE counting launch and one download instead of ``all(block)`` per sector (:726-728)."""
+    if len(d.blocks) < d.leg.nsec:
+        return False
+    if not d.blocks:
+        return True
+    return bool(np.all(_counts(bb, d) == np.asarray(d.leg.mults)[d.block_inds]))
+
+
+def diagonal_any(bb, d: DiagonalTensor) -> bool:
+    """``AbelianBackend::diagonal_any`` (abelian.cpp:733-740): ONE counting launch instead of ``any(block)`` per sector."""
+    return bool(d.blocks) and bool(np.any(_counts(bb, d) > 0))
+
+
+_REDUCERS = {'sum': lambda xs: sum(xs[1:], xs[0]) if len(xs) else 0.0, 'max': max, 'min': min}
+
+
+def _numbers(table: np.ndarray, cplx: bool) -> list:
+    return [complex(re, im) for re, im in table] if cplx else [float(re) for re in table[:, 0]]
+
+
+def reduce_diagonal(bb, d: DiagonalTensor, block_func: str, func=None):
+    """``AbelianBackend::reduce_DiagonalTensor`` (abelian.cpp:3154-3175): `block_func` (sum, max, min) of EVERY sector of
+    the leg -- a sector without a block is reduced as zeros of its multiplicity (:3170), the absent kind -- by ONE
+    ``seg_reduce_many`` launch and one download of ``16 * n_sectors`` bytes, then ``func(numbers)`` on the host in ascending
+    sector order (:3174).  `func`: a callable on the list of numbers, or None for the reduction named by `block_func`."""
+    if block_func not in _REDUCERS:
+        raise ValueError(f'reduce_diagonal: unknown block function {block_func!r}')
+    if block_func != 'sum' and d.dtype.kind == 'c':
+        raise TypeError('reduce_diagonal: complex numbers are not ordered')
+    have = _by_sector(d.blocks, d.block_inds)
+    table = bb.seg_reduce_many([have.get(i) for i in range(d.leg.nsec)], [int(m) for m in d.leg.mults], block_func)
+    numbers = _numbers(table, d.dtype.kind == 'c')
+    return (_REDUCERS[block_func] if func is None else func)(numbers)
+
+
+def diagonal_trace_full(bb, d: DiagonalTensor):
+    """``AbelianBackend::diagonal_tensor_trace_full`` (abelian.cpp:966-973): the sum of ``sum_all`` over the blocks, in
+    block order, from ONE launch and one download instead of a launch and a synchronisation per block (:970-971)."""
+    total = 0j if d.dtype.kind == 'c' else 0.0
+    if d.blocks:
+        table = bb.seg_reduce_many(d.blocks, [int(d.leg.mults[i]) for i in d.block_inds], 'sum')
+        for x in _numbers(table, d.dtype.kind == 'c'):
+            total = total + x
+    return total
+
+
+def get_element_diagonal(bb, d: DiagonalTensor, idx: int):
+    """``AbelianBackend::get_element_diagonal`` (abelian.cpp:2118-2131); zero of the dtype if the sector has no block"""
+    sec, within = _parse_index(d.leg, idx)
+    blk = _by_sector(d.blocks, d.block_inds).get(sec)
+    if blk is None:
+        return d.dtype.type(0).item()
+    return np.asarray(bb.to_numpy(bb.get_item(blk, (slice(within, within + 1),)))).reshape(()).item()
+
+
+def _leg_slice(leg: Leg, i) -> slice:
+    return slice(int(leg.slices[int(i)]), int(leg.slices[int(i) + 1]))
+
+
+def diagonal_to_block(bb, d: DiagonalTensor):
+    """``AbelianBackend::diagonal_tensor_to_block`` (abelian.cpp:1679-1692): the full diagonal as ONE 1-D block -- one
+    memset plus one batched copy instead of ``res[slice] = block`` per sector (:1686-1690)."""
+    res = bb.zeros_many([(d.leg.dim,)], dtype=d.dtype)[0]
+    pairs = [(bb.get_item(res, (_leg_slice(d.leg, i),)), blk) for blk, i in zip(d.blocks, d.block_inds)]
+    if pairs:
+        bb.copy_many(pairs)
+    return res
+
+
+def _diagonal_block_inds(t: AbelianTensor, what: str) -> np.ndarray:
+    if t.nlegs != 2 or not _same_space(t.legs[0], t.legs[1]):
+        raise ValueError(f'{what}: a tensor with two legs over the same sectors and multiplicities is required')
+    if len(t.blocks) and not np.array_equal(t.block_inds[:, 0], t.block_inds[:, 1]):
+        raise ValueError(f'{what}: the tensor has blocks off the diagonal of its block table')
+    return t.block_inds[:, 0].copy() if len(t.blocks) else np.zeros(0, np.int64)
+
+
+def diagonal_from_full_tensor(bb, t: AbelianTensor, tol=None) -> DiagonalTensor:
+    """``AbelianBackend::diagonal_tensor_from_full_tensor`` (abelian.cpp:956-963): the diagonals of ALL blocks by ONE batched
+    strided copy (source stride ``s0 + s1``) where the reference calls ``get_diagonal`` per block (:960-961).  With `tol`
+    the off-diagonal entries of all blocks -- for a contiguous ``n x n`` block they are ONE ``(n - 1, n)`` view with strides
+    ``(n + 1, 1)`` -- go through one further grouped reduction and one download; ``ValueError('Not a diagonal block.')`` if
+    one of them exceeds `tol`, as ``get_diagonal`` raises per block."""
+    inds = _diagonal_block_inds(t, 'diagonal_from_full_tensor')
+    if tol is not None and t.blocks:
+        offs = [bb.off_diagonal_view(b) for b in bb.contiguous_many(list(t.blocks))]
+        if bb.max_abs_many([o for o in offs if o.size]) > tol:
+            raise ValueError('Not a diagonal block.')
+    cplx = any(_is_complex_block(b) for b in t.blocks)
+    outs = bb.empty_many([(int(t.legs[0].mults[i]),) for i in inds], dtype='complex128' if cplx else None) if len(inds) else []
+    if len(inds):
+        bb.copy_many([(o, bb.diagonal_view(b if not cplx or _is_complex_block(b) else bb.as_complex(b))) for o, b in zip(outs, t.blocks)])
+    return DiagonalTensor(t.symmetry, t.legs[0], list(outs), inds)
+
+
+def full_from_diagonal(bb, d: DiagonalTensor) -> AbelianTensor:
+    """``AbelianBackend::full_data_from_diagonal_tensor`` (abelian.cpp:936-943) as the tensor ``[leg, leg*]``: one zero fill
+    plus one batched strided copy onto the diagonals instead of ``block_from_diagonal`` per block (:940-941)."""
+    if d.dtype.kind == 'b':
+        raise TypeError('full_from_diagonal: convert a boolean diagonal with mask_to_diagonal / diagonal_binary first')
+    blocks = bb.zeros_many([(int(d.leg.mults[i]),) * 2 for i in d.block_inds], dtype='complex128' if d.dtype.kind == 'c' else None) if d.blocks else []
+    if d.blocks:
+        bb.copy_many([(bb.diagonal_view(o), b) for o, b in zip(blocks, d.blocks)])
+    inds = np.stack([d.block_inds, d.block_inds], axis=1).reshape(len(d.blocks), 2)
+    return AbelianTensor(d.symmetry, [d.leg, d.leg.dual()], list(blocks), inds, 1)
+
+
+def diagonal_transpose(bb, d: DiagonalTensor) -> DiagonalTensor:
+    """``AbelianBackend::diagonal_transpose`` (abelian.cpp:1009-1016): the same blocks on the dual leg -- metadata only
+    (blocks are values here, the reference's copy is not needed)."""
+    return DiagonalTensor(d.symmetry, d.leg.dual(), list(d.blocks), d.block_inds.copy(), d.dtype)
+
+
+# -- masks
+
+def _device_mask(large_leg: Leg, flag_blocks, large_inds, tables, counts, is_projection=True) -> Mask:
+    """the Mask of the sectors of `large_inds` that keep at least one state (abelian.cpp:1730-1755 / :2441-2468; there is no
+    basis permutation in this project)"""
+    keep = [k for k in range(len(flag_blocks)) if int(counts[k]) > 0]
+    sectors = large_leg.sectors[[int(large_inds[k]) for k in keep]].reshape(len(keep), large_leg.symmetry.n)
+    small = Leg(large_leg.symmetry, sectors, [int(counts[k]) for k in keep], large_leg.sign)
+    inds = np.array([[j, int(large_inds[k])] for j, k in enumerate(keep)], dtype=np.int64).reshape(len(keep), 2)
+    if not is_projection:
+        inds = inds[:, ::-1].copy()
+    return Mask(large_leg, small, [flag_blocks[k] for k in keep], inds, [tables[k] for k in keep], is_projection)
+
+
+def diagonal_to_mask(bb, d: DiagonalTensor) -> Mask:
+    """``AbelianBackend::diagonal_to_mask`` (abelian.cpp:1695-1756) for a boolean diagonal: ONE ``seg_compact_many`` over the
+    blocks of `d` writes the position table of every sector on the device; the host reads the kept counts (one download of
+    ``8 * n_blocks`` bytes), drops the all-false sectors and builds the small leg (:1707-1755).  The reference calls
+    ``any``, ``sum_all`` and ``to_numpy`` per sector (:1709-1728).  The flag blocks and the tables stay on the device."""
+    if d.dtype.kind != 'b':
+        raise TypeError('diagonal_to_mask: a boolean DiagonalTensor is required')
+    tables, counts = bb.seg_compact_many(list(d.blocks)) if d.blocks else ([], np.zeros(0, np.int64))
+    return _device_mask(d.leg, list(d.blocks), d.block_inds, tables, counts)
+
+
+def _mask_logic(bb, items, large_leg: Leg, func: str) -> Mask:
+    flags = bb.seg_binary_many(items, func) if items else []
+    tables, counts = bb.seg_compact_many(list(flags)) if flags else ([], np.zeros(0, np.int64))
+    return _device_mask(large_leg, list(flags), np.arange(large_leg.nsec), tables, counts)
+
+
+def mask_binary(bb, m1: Mask, m2: Mask, func: str) -> Mask:
+    """``AbelianBackend::mask_binary_operand`` (abelian.cpp:2385-2469), `func` one of and, or, xor: ONE ``seg_binary_many``
+    over ALL sectors of the large leg (a sector without a block is the absent kind, where the reference allocates zero blocks,
+    :2417, :2425), then ONE ``seg_compact_many`` whose counts -- the only download -- decide which sectors keep a block and
+    give the multiplicities of the small leg (the reference: ``sum_all`` per sector, :2428)."""
+    if func not in _LOGICAL_OPS:
+        raise ValueError(f'mask_binary: unknown function {func!r}')
+    if not (m1.is_projection and m2.is_projection):
+        raise ValueError('mask_binary: projections are required')
+    if m1.large_leg.symmetry != m2.large_leg.symmetry or not _same_space(m1.large_leg, m2.large_leg):
+        raise ValueError('mask_binary: the masks do not have the same large leg')
+    h1, h2 = _by_sector(m1.blocks, m1.block_inds[:, 1]), _by_sector(m2.blocks, m2.block_inds[:, 1])
+    leg = m1.large_leg
+    return _mask_logic(bb, [(_flag_block(bb, h1.get(i)), _flag_block(bb, h2.get(i)), int(leg.mults[i])) for i in range(leg.nsec)], leg, func)
+
+
+def mask_unary(bb, m: Mask, func: str = 'not') -> Mask:
+    """``AbelianBackend::mask_unary_operand`` (abelian.cpp:2686-2757) for ``logical_not``: as :func:`mask_binary`, two launches
+    and one download.  The sectors that have a block change: a sector the mask keeps whole loses its block, a sector the
+    mask drops whole (no block) gets an all-true one."""
+    if func != 'not':
+        raise ValueError(f'mask_unary: unknown function {func!r}')
+    if not m.is_projection:
+        raise ValueError('mask_unary: a projection is required')
+    have = _by_sector(m.blocks, m.block_inds[:, 1])
+    leg = m.large_leg
+    return _mask_logic(bb, [(_flag_block(bb, have.get(i)), None, int(leg.mults[i])) for i in range(leg.nsec)], leg, func)
+
+
+def _flag_block(bb, b):
+    """a mask block as the backend's boolean block (the blocks of ``Mask.from_flags`` are host vectors)"""
+    return b if b is None or bb.is_correct_block_type(b) else bb.as_block(np.asarray(b, dtype=bool))
+
+
+def mask_dagger(bb, m: Mask) -> Mask:
+    """``AbelianBackend::mask_dagger`` (abelian.cpp:976-985): the legs change places, i.e. the two columns of ``block_inds``
+    (both ascending, so the table stays sorted) and the projection flag; blocks and tables are shared."""
+    return Mask(m.large_leg, m.small_leg, list(m.blocks), m.block_inds[:, ::-1].copy(), m.tables, not m.is_projection)
+
+
+def mask_transpose(bb, m: Mask) -> Mask:
+    """``AbelianBackend::mask_transpose`` (abelian.cpp:2674-2683): as the dagger, on the dual legs"""
+    return Mask(m.large_leg.dual(), m.small_leg.dual(), list(m.blocks), m.block_inds[:, ::-1].copy(), m.tables, not m.is_projection)
+
+
+def get_element_mask(bb, m: Mask, idcs) -> bool:
+    """``AbelianBackend::get_element_mask`` (abelian.cpp:2133-2156): `idcs` in the leg order of the mask, (small, large) for a
+    projection and (large, small) for an inclusion"""
+    legs = [m.small_leg, m.large_leg] if m.is_projection else [m.large_leg, m.small_leg]
+    if len(idcs) != 2:
+        raise ValueError('get_element_mask: two indices are required')
+    pos = [_parse_index(l, i) for l, i in zip(legs, idcs)]
+    hit = [j for j, row in enumerate(m.block_inds) if (int(row[0]), int(row[1])) == (pos[0][0], pos[1][0])]
+    if not hit:
+        return False
+    small, large = (pos[0][1], pos[1][1]) if m.is_projection else (pos[1][1], pos[0][1])
+    flags = np.asarray(bb.to_numpy(m.blocks[hit[0]]) if bb.is_correct_block_type(m.blocks[hit[0]]) else m.blocks[hit[0]]).astype(bool)
+    return bool(flags[large]) and small == int(flags[:large].sum())
+
+
+def mask_to_block(bb, m: Mask):
+    """``AbelianBackend::mask_to_block`` (abelian.cpp:2641-2657): ONE boolean block over the large leg, one memset plus one
+    batched copy"""
+    res = bb.zeros_many([(m.large_leg.dim,)], dtype=bool)[0]
+    pairs = [(bb.get_item(res, (_leg_slice(m.large_leg, row[m.large_col]),)), _flag_block(bb, blk)) for blk, row in zip(m.blocks, m.block_inds)]
+    if pairs:
+        bb.copy_many(pairs)
+    return res
+
+
+def mask_to_diagonal(bb, m: Mask, dtype=np.float64) -> DiagonalTensor:
+    """``AbelianBackend::mask_to_diagonal`` (abelian.cpp:2659-2672): the flags as numbers on the large leg; the conversion of
+    all blocks is ONE launch (the flags times 1.0) instead of ``to_dtype`` per block (:2665-2666)."""
+    dtype = np.dtype(dtype)
+    inds = m.block_inds[:, m.large_col].copy()
+    blocks = [_flag_block(bb, b) for b in m.blocks]
+    if dtype.kind != 'b' and blocks:
+        blocks = bb.seg_binary_many([(b, None, int(m.large_leg.mults[i])) for b, i in zip(blocks, inds)], 'mul', scalar=1.0)
+        if dtype.kind == 'c':
+            blocks = [bb.as_complex(b) for b in blocks]
+    return DiagonalTensor(m.large_leg.symmetry, m.large_leg, list(blocks), inds, dtype)
+
+
+def full_from_mask(bb, m: Mask, dtype=np.float64) -> AbelianTensor:
+    """``AbelianBackend::full_data_from_mask`` (abelian.cpp:945-953): the mask as the tensor ``[small, large*]`` (or its
+    dagger), every block ``(k, n)`` with a single 1 per row at the kept positions.  Identity blocks (one zero fill, one
+    batched copy of ones onto the diagonals) are scattered along their columns by ONE ``enlarge_leg_many`` that reads the
+    position tables of a device mask in place; the reference calls ``block_from_mask`` per block (:950-951)."""
+    ks = [int(m.small_leg.mults[int(row[1 - m.large_col])]) for row in m.block_inds]
+    ns = [int(m.large_leg.mults[int(row[m.large_col])]) for row in m.block_inds]
+    blocks = []
+    if ks:
+        eyes = bb.zeros_many([(k, k) for k in ks])
+        ones = bb.seg_binary_many([(None, None, max(ks))], 'add', scalar=1.0)[0]
+        bb.copy_many([(bb.diagonal_view(e), bb.get_item(ones, (slice(0, k),))) for e, k in zip(eyes, ks)])
+        which = m.tables if m.tables is not None else [np.flatnonzero(np.asarray(b, dtype=bool)) for b in m.blocks]
+        blocks = bb.enlarge_leg_many([(e, (w, n), 1) for e, w, n in zip(eyes, which, ns)])
+        if not m.is_projection:
+            blocks = [bb.permute_axes(b, [1, 0]) for b in blocks]
+        if np.dtype(dtype).kind == 'c':
+            blocks = [bb.as_complex(b) for b in blocks]
+    legs = [m.small_leg, m.large_leg.dual()] if m.is_projection else [m.large_leg, m.small_leg.dual()]
+    return AbelianTensor(m.large_leg.symmetry, legs, list(blocks), m.block_inds.copy().reshape(len(ks), 2), 1)
+
+
+def apply_mask_to_diagonal(bb, d: DiagonalTensor, mask: Mask) -> DiagonalTensor:
+    """``AbelianBackend::apply_mask_to_DiagonalTensor`` (abelian.cpp:646-673): the sectors `d` and the mask share (:658-669)
+    go through ONE ``mask_gather_many`` instead of ``apply_mask`` per sector (:663-666); the result lives on the small leg."""
+    items, inds = _apply_mask_items(d, mask)
+    blocks = bb.mask_gather_many(items) if items else []
+    return DiagonalTensor(d.symmetry, mask.small_leg, list(blocks), np.array(inds, dtype=np.int64), d.dtype)
+
+
+def _apply_mask_items(d: DiagonalTensor, mask: Mask):
+    if not mask.is_projection:
+        raise ValueError('apply_mask_to_diagonal: a projection is required')
+    if d.symmetry != mask.large_leg.symmetry or not _same_space(d.leg, mask.large_leg):
+        raise ValueError('apply_mask_to_diagonal: the leg of the diagonal is not the large leg of the mask')
+    have = _by_sector(d.blocks, d.block_inds)
+    items, inds = [], []
+    for j, row in enumerate(mask.block_inds):
+        blk = have.get(int(row[1]))
+        if blk is not None:
+            items.append((blk, mask.tables[j] if mask.tables is not None else mask.blocks[j], 0))
+            inds.append(int(row[0]))
+    return items, inds
+
+
+def svd_apply_mask(bb, U: AbelianTensor, S: DiagonalTensor, Vh: AbelianTensor, mask: Mask):
+    """``svd_apply_mask`` (src/tensors/decompositions.cpp:620-631): project the new leg of ``U`` (its last leg), of ``S`` and
+    of ``Vh`` (its first leg) onto the states the mask keeps.  The reference composes U with the dagger of the mask, applies
+    the mask to S and composes it with Vh, each a loop over blocks; here the three block tables are matched on the host and
+    the blocks of all three go through ONE ``mask_gather_many`` call, which reads the position tables of a device mask in
+    place (no upload of index tables)."""
+    if not mask.is_projection:
+        raise ValueError('svd_apply_mask: a projection is required')
+    u_items, u_rows, u_legs = _mask_contract_items(U, mask, U.nlegs - 1, True)
+    s_items, s_inds = _apply_mask_items(S, mask)
+    v_items, v_rows, v_legs = _mask_contract_items(Vh, mask, 0, True)
+    items = u_items + s_items + v_items
+    out = bb.mask_gather_many(items) if items else []
+    nu, ns = len(u_items), len(s_items)
+    U2 = AbelianTensor(U.symmetry, u_legs, list(out[:nu]), np.array(u_rows, dtype=np.int64).reshape(nu, U.nlegs), U.num_codomain, list(U.labels)).sorted()
+    S2 = DiagonalTensor(S.symmetry, mask.small_leg, list(out[nu:nu + ns]), np.array(s_inds, dtype=np.int64), S.dtype)
+    V2 = AbelianTensor(Vh.symmetry, v_legs, list(out[nu + ns:]), np.array(v_rows, dtype=np.int64).reshape(len(v_items), Vh.nlegs), Vh.num_codomain,
+                       list(Vh.labels)).sorted()
+    return U2, S2, V2
+
+
+def entropy(bb, p: DiagonalTensor, n=1) -> float:
+    """``entropy`` of a real, normalised DiagonalTensor of probabilities (src/tensors/decompositions.cpp:427-450): von
+    Neumann ``-sum p log p`` for ``n = 1`` (``p * stable_log(p, 1e-30)`` then the trace, :439-441), ``-log max p`` for
+    ``n = inf`` (:444) and the Renyi entropy ``log(sum p^n) / (1 - n)`` otherwise (:446-449).  Each is ONE launch -- the
+    ``x log x`` / ``x^n`` pre-map is applied inside the reduction -- and one download of ``16 * n_sectors`` bytes, where the
+    reference makes an elementwise pass or two and then a ``sum_all`` per sector."""
+    if p.dtype.kind != 'f':
+        raise TypeError('entropy: a real DiagonalTensor is required')
+    lengths = [int(p.leg.mults[i]) for i in p.block_inds]
+    if n == 1:
+        table = bb.seg_reduce_many(p.blocks, lengths, 'sum', 'xlogx', 1e-30) if p.blocks else np.zeros((0, 2))
+        return -float(sum(_numbers(table, False), 0.0))
+    if n == np.inf:
+        return -float(np.log(reduce_diagonal(bb, p, 'max')))
+    n = float(n)
+    table = bb.seg_reduce_many(p.blocks, lengths, 'sum', 'pow', n) if p.blocks else np.zeros((0, 2))
+    return float(np.log(sum(_numbers(table, False), 0.0)) / (1.0 - n))

@@ -589,7 +589,11 @@ class HipBlockBackend:
 
     def zeros_many(self, shapes, dtype=None, device=None):
         """``zeros`` for a list of shapes (the result blocks of ``AbelianBackend::combine_legs``,
-        abelian.cpp:1200-1214): one buffer, one memset."""
+        abelian.cpp:1200-1214): one buffer, one memset.  Boolean blocks (``dtype=bool``) live in a byte buffer of their own."""
+        if dtype is not None and np.dtype(dtype).kind == 'b':
+            shapes = [tuple(int(x) for x in sh) for sh in shapes]
+            flat = self._new_bool_many([math.prod(sh) for sh in shapes], zero=True)
+            return [HipBlock._trusted(self, b.buf, b.offset, sh, _c_strides(sh), True) for b, sh in zip(flat, shapes)]
         return self._new_many(shapes, dtype is not None and np.dtype(dtype).kind == 'c', zero=True)
 
     # -- complex128 helpers (interleaved storage: a complex block IS a float64 block with a trailing axis of 2)
@@ -1156,7 +1160,8 @@ class HipBlockBackend:
         """``enlarge_leg`` (numpy.cpp:700-728) for a list of (block, mask, axis): ONE zero-filled allocation per dtype, one
         upload of all position tables and ONE scatter launch -- the per-block loop of ``AbelianBackend::_mask_contract``
         with ``large_leg=False`` (abelian.cpp:2550-2553).  `mask`: 1-D bool array / block, or the positions themselves
-        together with the large extent as ``(positions, n_large)``."""
+        together with the large extent as ``(positions, n_large)``; `positions` may be a :class:`DeviceIndex` (the table of a
+        device mask: nothing is uploaded for it)."""
         if not items:
             return []
         srcs = self.contiguous_many([it[0] for it in items])
@@ -1164,7 +1169,14 @@ class HipBlockBackend:
         idxs, geo = [], []
         for (_, mask, axis), a in zip(items, srcs):
             axis = axis % a.ndim
-            if isinstance(mask, tuple):
+            if isinstance(mask, tuple) and isinstance(mask[0], DeviceIndex):   # positions already on the device
+                idx, n_large = mask[0], int(mask[1])
+                if idx.n != a.shape[axis]:
+                    raise ValueError('mask does not match the axis to enlarge')
+                idxs.append(idx)
+                geo.append((axis, n_large, a.shape[:axis] + (n_large,) + a.shape[axis + 1:]))
+                continue
+            elif isinstance(mask, tuple):
                 idx, n_large = np.asarray(mask[0], dtype=np.int64), int(mask[1])
             else:
                 m = np.asarray(mask.to_numpy() if isinstance(mask, HipBlock) else mask).astype(bool)
@@ -1178,17 +1190,24 @@ class HipBlockBackend:
             sel = [i for i, a in enumerate(srcs) if a.is_complex == cplx]
             for i, o in zip(sel, self._new_many([geo[i][2] for i in sel], cplx, zero=True)):
                 outs[i] = o
-        offs = np.concatenate([[0], np.cumsum([len(x) for x in idxs])]).astype(np.int64)
+        host = [x for x in idxs if not isinstance(x, DeviceIndex)]
+        offs = np.concatenate([[0], np.cumsum([len(x) for x in host])]).astype(np.int64)
         didx = self.ctx.empty(max(int(offs[-1]), 1), 'int64')
         if offs[-1]:
-            self.ctx.h2d(didx, np.concatenate(idxs))
+            self.ctx.h2d(didx, np.concatenate(host))
         descs = (_lib.MaskDesc * len(items))()
+        h = 0
         for i, (a, out) in enumerate(zip(srcs, outs)):
             outer, _, inner = self._as_3d(a, geo[i][0])
             if a.is_complex:
                 inner *= 2
-            descs[i].x, descs[i].out, descs[i].idx = a.ptr, out.ptr, didx.data_ptr() + 8 * int(offs[i])
-            descs[i].outer, descs[i].axis, descs[i].inner, descs[i].n_keep = outer, geo[i][1], inner, len(idxs[i])
+            if isinstance(idxs[i], DeviceIndex):
+                table, n_keep = idxs[i].ptr, idxs[i].n
+            else:
+                table, n_keep = didx.data_ptr() + 8 * int(offs[h]), len(idxs[i])
+                h += 1
+            descs[i].x, descs[i].out, descs[i].idx = a.ptr, out.ptr, table
+            descs[i].outer, descs[i].axis, descs[i].inner, descs[i].n_keep = outer, geo[i][1], inner, n_keep
         self.ctx.sync_stream()
         _lib.check(self.lib.cyb_mask_scatter_batched_f64(self.ctx.handle, descs, len(items)))
         return outs
@@ -2802,6 +2821,143 @@ class HipBlockBackend:
             else:
                 _lib.check(self.lib.cyb_unary_batched_f64(self.ctx.handle, descs, len(sel), self._UNARY_OPS[op]))
         return outs
+
+    # ------------------------------------------------------------------ segment ops (csrc/segment_ops.hip)
+    @staticmethod
+    def _seg_kind(b) -> int:
+        if b is None:
+            return _lib.CYB_SEG_ABSENT
+        return _lib.CYB_SEG_BOOL if b.is_bool else _lib.CYB_SEG_C128 if b.is_complex else _lib.CYB_SEG_F64
+
+    def _seg_operand(self, b, n, what):
+        """the contiguous 1-D operand of a segment record (None: absent)"""
+        if b is None:
+            return None
+        if not isinstance(b, HipBlock) or b.ndim != 1 or b.shape[0] != n:
+            raise ValueError(f'{what}: every operand is a 1-D block of the length of its segment')
+        return b if b.is_contiguous() else self.contiguous(b)
+
+    def _new_bool_many(self, lengths, zero: bool = False):
+        """boolean 1-D blocks carved out of ONE byte buffer (16-byte aligned offsets); with `zero`, one memset"""
+        offs, tot = [], 0
+        for n in lengths:
+            offs.append(tot)
+            tot += (int(n) + 15) // 16 * 16
+        buf = self.ctx.empty(tot, 'bool')
+        if zero and tot:
+            self.ctx.sync_stream()
+            _lib.check(self.lib.cyb_memset(self.ctx.handle, C.c_void_p(buf.data_ptr()), 0, tot))
+        return [HipBlock._trusted(self, buf, o, (int(n),), (1,), True) for o, n in zip(offs, lengths)]
+
+    def diagonal_view(self, a: HipBlock) -> HipBlock:
+        """the diagonal of a 2-D block as a strided 1-D view (stride ``s0 + s1``): source or target of a batched copy"""
+        return HipBlock(self, a.buf, a.offset, (min(a.shape),), (a.strides[0] + a.strides[1],))
+
+    def off_diagonal_view(self, a: HipBlock) -> HipBlock:
+        """all off-diagonal entries of a contiguous square block as ONE strided view: the ``n`` entries after each of the
+        first ``n - 1`` diagonal entries, shape ``(n - 1, n)`` with strides ``(n + 1, 1)``"""
+        n = a.shape[0]
+        if a.ndim != 2 or a.shape[1] != n or not a.is_contiguous():
+            raise ValueError('off_diagonal_view: a contiguous square block is required')
+        return HipBlock(self, a.buf, a.offset + 1, (max(n - 1, 0), n), (n + 1, 1)) if n > 1 else HipBlock(self, a.buf, a.offset, (0, n), (n + 1, 1))
+
+    def seg_binary_many(self, items, op: str, scalar=None, complex_out: bool = False):
+        """``out = a (op) b`` for a list of 1-D segments ``(a, b, n)`` in ONE launch (``cyb_seg_binary``): `a` / `b` are
+        float64, complex128 or boolean blocks of length `n`, or None -- an absent operand reads as zeros, no zero block is
+        made.  `op`: add, sub, mul, div (float64 results, complex128 for the whole list if any operand is complex); lt, le,
+        gt, ge, eq, ne (boolean results; ordering comparisons reject complex operands); and, or, xor, not (boolean operands,
+        boolean results; `not` ignores b).  With `scalar` operand b of every segment is that number; `complex_out` asks for
+        complex128 results of an arithmetic op whatever the operands are (a complex diagonal whose blocks are all absent).
+        One descriptor upload, no download; the results are carved out of one pooled allocation."""
+        if op not in _lib.SEG_BINARY_OPS:
+            raise ValueError(f'seg_binary_many: unknown op {op!r}')
+        code = _lib.SEG_BINARY_OPS[op]
+        items = [(self._seg_operand(a, int(n), 'seg_binary_many'), None if scalar is not None else self._seg_operand(b, int(n), 'seg_binary_many'), int(n))
+                 for a, b, n in items]
+        if any(n < 0 for _, _, n in items):
+            raise ValueError('seg_binary_many: negative length')
+        s = complex(scalar) if scalar is not None else 0j
+        operands = [x for a, b, _ in items for x in (a, b) if x is not None]
+        cplx = any(x.is_complex for x in operands) or s.imag != 0.0 or (complex_out and op in ('add', 'sub', 'mul', 'div'))
+        logical = op in ('and', 'or', 'xor', 'not')
+        if logical and (scalar is not None or any(not x.is_bool for x in operands)):
+            raise TypeError(f'seg_binary_many: {op} takes boolean operands')
+        if op in ('lt', 'le', 'gt', 'ge') and cplx:
+            raise TypeError(f'seg_binary_many: complex numbers are not ordered ({op})')
+        lengths = [n for _, _, n in items]
+        if code <= _lib.SEG_BINARY_OPS['div']:
+            outs = self._new_many([(n,) for n in lengths], cplx)
+        else:
+            outs = self._new_bool_many(lengths)
+        if not items:
+            return []
+        arr = np.zeros(len(items), dtype=_lib.SEG_DTYPE)
+        arr['a'] = [0 if a is None else a.ptr for a, _, _ in items]
+        arr['b'] = [0 if b is None else b.ptr for _, b, _ in items]
+        arr['out'] = [o.ptr for o in outs]
+        arr['n'] = lengths
+        arr['a_kind'] = [self._seg_kind(a) for a, _, _ in items]
+        arr['b_kind'] = [self._seg_kind(b) for _, b, _ in items]
+        arr['out_kind'] = self._seg_kind(outs[0])
+        self.ctx.sync_stream()
+        _lib.check(self.lib.cyb_seg_binary(self.ctx.handle, arr.ctypes.data_as(C.POINTER(_lib.SegRec)), len(items), code,
+                                           0 if scalar is None else 1, s.real, s.imag))
+        return outs
+
+    def _seg_records(self, blocks, lengths, what):
+        blocks = [self._seg_operand(b, int(n), what) for b, n in zip(blocks, lengths)]
+        arr = np.zeros(max(len(blocks), 1), dtype=_lib.SEG_DTYPE)
+        if blocks:
+            arr['a'][:len(blocks)] = [0 if b is None else b.ptr for b in blocks]
+            arr['n'][:len(blocks)] = [int(n) for n in lengths]
+            arr['a_kind'][:len(blocks)] = [self._seg_kind(b) for b in blocks]
+        return blocks, arr
+
+    def seg_reduce_many(self, blocks, lengths, op: str, pre=None, param=None) -> np.ndarray:
+        """One number per 1-D segment in ONE launch and ONE download of ``16 * n`` bytes (``cyb_seg_reduce``): row s of the
+        returned ``(n, 2)`` table is (re, im) / (value, 0) of `op` (sum, max, min, count of non-zeros) over
+        ``blocks[s]`` (None: absent, reduced as ``lengths[s]`` zeros) after the elementwise pre-map `pre` (None, abs, square,
+        xlogx -- ``x log x`` where ``x > param``, else 0 --, pow -- ``x ** param``).  A zero-length segment gives 0 for sum
+        and count, -inf for max, +inf for min."""
+        if op not in _lib.SEG_REDUCE_OPS or pre not in _lib.SEG_PRE_MAPS:
+            raise ValueError(f'seg_reduce_many: unknown reduction {op!r} / pre-map {pre!r}')
+        if (pre in ('xlogx', 'pow')) != (param is not None):
+            raise ValueError(f'seg_reduce_many: pre-map {pre!r} and parameter {param!r} do not go together')
+        lengths = [int(n) for n in lengths]
+        if len(lengths) != len(blocks) or any(n < 0 for n in lengths):
+            raise ValueError('seg_reduce_many: one non-negative length per segment')
+        blocks, arr = self._seg_records(blocks, lengths, 'seg_reduce_many')
+        if any(b is not None and b.is_complex for b in blocks) and not (pre == 'abs' or (pre is None and op in ('sum', 'count'))):
+            raise TypeError(f'seg_reduce_many: {op} with pre-map {pre!r} takes real segments')
+        n = len(blocks)
+        if n == 0:
+            return np.zeros((0, 2))
+        res = self.ctx.empty(2 * n)
+        self.ctx.sync_stream()
+        _lib.check(self.lib.cyb_seg_reduce(self.ctx.handle, arr.ctypes.data_as(C.POINTER(_lib.SegRec)), n, _lib.SEG_REDUCE_OPS[op],
+                                           _lib.SEG_PRE_MAPS[pre], 0.0 if param is None else float(param), C.c_void_p(res.data_ptr())))
+        return self.ctx.d2h(res, 2 * n, np.float64).reshape(n, 2)
+
+    def seg_compact_many(self, flag_blocks):
+        """The ascending positions of the true (boolean) / non-zero (numeric) entries of every 1-D block of a list, in ONE
+        launch (``cyb_seg_compact``): returns (tables, counts) with ``tables[s]`` a :class:`DeviceIndex` -- the positions
+        stay on the device, ready for ``mask_gather_many`` / ``enlarge_leg_many`` -- and `counts` the kept counts, the ONE
+        download of ``8 * n`` bytes."""
+        lengths = [b.shape[0] if isinstance(b, HipBlock) and b.ndim == 1 else -1 for b in flag_blocks]
+        if any(n < 0 for n in lengths):
+            raise ValueError('seg_compact_many: every flag block is a 1-D block')
+        blocks, arr = self._seg_records(flag_blocks, lengths, 'seg_compact_many')
+        n = len(blocks)
+        if n == 0:
+            return [], np.zeros(0, dtype=np.int64)
+        offs = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+        idx = self.ctx.empty(max(int(offs[-1]), 1), 'int64')
+        cnt = self.ctx.empty(n, 'int64')
+        self.ctx.sync_stream()
+        _lib.check(self.lib.cyb_seg_compact(self.ctx.handle, arr.ctypes.data_as(C.POINTER(_lib.SegRec)), n, C.c_void_p(idx.data_ptr()),
+                                            C.c_void_p(cnt.data_ptr())))
+        counts = self.ctx.d2h(cnt, n, np.int64)
+        return [DeviceIndex(idx.data_ptr() + 8 * int(offs[s]), int(counts[s]), idx) for s in range(n)], counts
 
     def empty_many(self, shapes, dtype=None, device=None):
         """uninitialised blocks of the given shapes in one pooled allocation (destinations of a batched copy)"""

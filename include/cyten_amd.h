@@ -597,6 +597,61 @@ int cyb_truncate_select_f64(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t n_
 int cyb_truncate_select_weighted_f64(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t n_sectors, const double* sector_weights,
                                      const cyb_trunc_opts* opts, int64_t* keep_idx_dev, uint8_t* mask_dev, double* result_dev);
 
+/* ---- segment ops: arithmetic, reductions and compaction of lists of 1-D sector blocks ---------------------------------
+ * What a tensor-network code does with a DiagonalTensor (singular values) or a Mask after a decomposition, for ALL sectors
+ * in ONE launch per call (csrc/segment_ops.hip).  A *segment* is one contiguous 1-D sector block; a record names up to
+ * two operand segments and an output of the same length n.  Operand kinds: CYB_SEG_ABSENT (read as zeros: a sector
+ * without a block, no zero block is allocated), CYB_SEG_F64, CYB_SEG_C128 (interleaved) and CYB_SEG_BOOL (one byte per
+ * element).  Pointers are aligned to 8 bytes (numeric kinds); 16-byte accesses are used where a pointer allows them.
+ * n == 0, n == 1 and an empty list are valid.  All three entries are bit-identical from run to run and a segment's result
+ * depends on nothing but the segment: the owner of a segment (16 lanes for n <= 64, one wave for n <= 1024, one
+ * workgroup for n <= 16384, one workgroup per 16384-element chunk above) and the combination order are fixed by n alone; no
+ * float atomics (an integer ticket elects the workgroup that adds the chunk partials in chunk order).
+ *
+ * cyb_seg_binary: out = a (op) b elementwise.  Replaces the per-sector func(block_a, block_b) of
+ * AbelianBackend::diagonal_elementwise_binary (src/backends/abelian.cpp:1596-1619) and of mask_binary_operand /
+ * mask_unary_operand (:2410-2427, :2705-2714), and the zero blocks they allocate for missing sectors (:1605, :1615, :2417,
+ * :2425, :2712).  Arithmetic ops write out_kind F64 or C128 (a real operand next to a complex one is read in place);
+ * comparisons and logical ops write BOOL.  With use_scalar != 0 operand b of EVERY record is the scalar (re, im).  The
+ * ordering comparisons use the real parts (callers reject complex operands); logical ops read "non-zero" as true, NOT
+ * ignores b.
+ *
+ * cyb_seg_reduce: one number per segment (operand a; b and out are ignored), result_dev[2 s] / [2 s + 1] = (re, im) or
+ * (value, 0).  Replaces block_func(block) per sector of reduce_DiagonalTensor (:3163-3173), sum_all per sector of
+ * diagonal_tensor_trace_full (:970-971) and all / any per sector of diagonal_all / diagonal_any (:726-738), each of them a
+ * launch and a host synchronisation.  The pre-map is applied to every element on the fly (real segments; ABS also takes
+ * complex ones).  An absent segment is reduced as n zeros; n == 0 gives 0 (SUM, COUNT), -inf (MAX), +inf (MIN).  MAX / MIN
+ * compare real parts and skip NaN (fmax / fmin).
+ *
+ * cyb_seg_compact: per segment (operand a: the flags, BOOL or numeric with non-zero = keep) the ascending kept positions
+ * keep_idx_dev[off_s + j], off_s = sum of the n of the segments before s, and counts_dev[s] = number kept -- the table
+ * layout of cyb_truncate_select_f64, read by cyb_mask_gather_batched_f64 / cyb_mask_scatter_batched_f64.  Replaces any /
+ * sum_all / to_numpy per sector of diagonal_to_mask (:1707-1728) and sum_all per sector of mask_binary_operand (:2428) and
+ * mask_unary_operand (:2715).  A workgroup that owns a later chunk of a long segment recounts the flags before its chunk
+ * (quadratic in the number of chunks; bond dimensions stay far below that mattering). */
+#define CYB_SEG_ABSENT 0
+#define CYB_SEG_F64 1
+#define CYB_SEG_C128 2
+#define CYB_SEG_BOOL 3
+enum { CYB_SEG_ADD = 0, CYB_SEG_SUB, CYB_SEG_MUL, CYB_SEG_DIV, CYB_SEG_LT, CYB_SEG_LE, CYB_SEG_GT, CYB_SEG_GE, CYB_SEG_EQ,
+       CYB_SEG_NE, CYB_SEG_AND, CYB_SEG_OR, CYB_SEG_XOR, CYB_SEG_NOT, CYB_SEG_N_OPS };
+enum { CYB_SEG_SUM = 0, CYB_SEG_MAX, CYB_SEG_MIN, CYB_SEG_COUNT, CYB_SEG_N_REDUCE };
+enum { CYB_SEG_PRE_NONE = 0, CYB_SEG_PRE_ABS, CYB_SEG_PRE_SQUARE, CYB_SEG_PRE_XLOGX /* x log x for x > param, else 0 */,
+       CYB_SEG_PRE_POW /* x^param */, CYB_SEG_N_PRE };
+typedef struct {
+    const void* a;
+    const void* b;
+    void* out;
+    int64_t n;
+    int32_t a_kind, b_kind, out_kind;
+    int32_t reserved;
+} cyb_seg_rec;
+int cyb_seg_binary(cyb_ctx_t ctx, const cyb_seg_rec* recs, int64_t n_segs, int32_t op, int32_t use_scalar, double scalar_re,
+                   double scalar_im);
+int cyb_seg_reduce(cyb_ctx_t ctx, const cyb_seg_rec* recs, int64_t n_segs, int32_t op, int32_t pre, double param,
+                   double* result_dev);
+int cyb_seg_compact(cyb_ctx_t ctx, const cyb_seg_rec* recs, int64_t n_segs, int64_t* keep_idx_dev, int64_t* counts_dev);
+
 /* fill: out[i] = value (zeros / ones_block); eye: out (n x n, contiguous) = identity
  * (eye_matrix, numpy.cpp:1197-1207) */
 int cyb_fill_f64(cyb_ctx_t ctx, double* out, int64_t n, double value);
