@@ -72,6 +72,14 @@ def test_strided_operand_views(bb, rng):
     sub = bb.get_item(big, (slice(10, 80), slice(5, 50)))
     ref = bb.to_numpy(big)[10:80, 5:50] @ b
     assert np.abs(bb.to_numpy(bb.matrix_dot(sub, bb.as_block(b))) - ref).max() <= TOL * np.abs(ref).max()
+    frame = bb.as_block(np.full((90, 120), -7.5))
+    out = bb.get_item(frame, (slice(11, 81), slice(7, 98)))         # 70 x 91 at an odd offset, leading dimension 120
+    res = bb.matrix_dot_grouped([[(sub, bb.as_block(b))]], outs=[out])
+    assert res[0] is out
+    got = bb.to_numpy(frame)
+    assert np.abs(got[11:81, 7:98] - ref).max() <= TOL * np.abs(ref).max()
+    got[11:81, 7:98] = -7.5
+    assert np.array_equal(got, np.full((90, 120), -7.5))           # nothing next to the slice was written
     # a view with no unit stride at all falls back to one strided copy, still correct
     t3 = bb.as_block(rng.standard_normal((6, 7, 8)))
     v = bb.reshape(bb.permute_axes(t3, [1, 0, 2]), (7, 48))
