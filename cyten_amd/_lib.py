@@ -19,6 +19,7 @@ CYB_EIGH_EMBEDDED_COMPLEX = 2
 CYB_EXPM_SMALL_MAX_N_F64 = 96
 CYB_EXPM_SMALL_MAX_N_C128 = 64
 CYB_SEG_ABSENT, CYB_SEG_F64, CYB_SEG_C128, CYB_SEG_BOOL = range(4)
+TREE_AXIS_MODES = {'scale': 0, 'gather': 1, 'scatter': 2}   # CYB_TREE_SCALE / _GATHER / _SCATTER
 SEG_BINARY_OPS = {name: i for i, name in enumerate(('add', 'sub', 'mul', 'div', 'lt', 'le', 'gt', 'ge', 'eq', 'ne', 'and', 'or', 'xor', 'not'))}
 SEG_REDUCE_OPS = {name: i for i, name in enumerate(('sum', 'max', 'min', 'count'))}
 SEG_PRE_MAPS = {name: i for i, name in enumerate((None, 'abs', 'square', 'xlogx', 'pow'))}
@@ -142,6 +143,23 @@ class OuterRec(C.Structure):
                 ('b_shape', C.c_int64 * CYB_MAX_NDIM), ('b_strides', C.c_int64 * CYB_MAX_NDIM)]
 
 
+class TreeAxisRec(C.Structure):
+    _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p), ('table', C.c_void_p),
+                ('src_ts', C.c_int64), ('src_xs', C.c_int64), ('dst_ts', C.c_int64), ('dst_xs', C.c_int64),
+                ('src_start', C.c_int64), ('dst_start', C.c_int64), ('X', C.c_int64),
+                ('outer', C.c_int64), ('A', C.c_int64), ('A_dst', C.c_int64), ('inner', C.c_int64),
+                ('mode', C.c_int32), ('src_is_real', C.c_int32), ('table_is_complex', C.c_int32), ('reserved', C.c_int32)]
+
+
+class TreeFill(C.Structure):
+    _fields_ = [('ptr', C.c_void_p), ('bytes', C.c_int64)]
+
+
+class WDotDesc(C.Structure):
+    _fields_ = [('x', C.c_void_p), ('y', C.c_void_p), ('rows', C.c_int64), ('cols', C.c_int64),
+                ('x_rs', C.c_int64), ('x_cs', C.c_int64), ('y_rs', C.c_int64), ('y_cs', C.c_int64), ('w', C.c_double)]
+
+
 class SegRec(C.Structure):
     _fields_ = [('a', C.c_void_p), ('b', C.c_void_p), ('out', C.c_void_p), ('n', C.c_int64),
                 ('a_kind', C.c_int32), ('b_kind', C.c_int32), ('out_kind', C.c_int32), ('reserved', C.c_int32)]
@@ -168,6 +186,9 @@ TRACE_TERM_DTYPE = _np.dtype(TraceTerm)
 EXPM_DTYPE = _np.dtype(ExpmDesc)
 OUTER_DTYPE = _np.dtype(OuterRec)
 SEG_DTYPE = _np.dtype(SegRec)
+TREE_AXIS_DTYPE = _np.dtype(TreeAxisRec)
+TREE_FILL_DTYPE = _np.dtype(TreeFill)
+WDOT_DTYPE = _np.dtype(WDotDesc)
 
 _P = C.POINTER
 _ctx = C.c_void_p
@@ -250,6 +271,10 @@ PROTOTYPES = {
     'cyb_norm1_batched_c128': [_ctx, _P(ExpmDesc), C.c_int64, _vp],
     'cyb_outer_grouped_f64': [_ctx, _P(OuterRec), C.c_int64],
     'cyb_outer_grouped_c128': [_ctx, _P(OuterRec), C.c_int64],
+    'cyb_tree_axis_f64': [_ctx, _P(TreeAxisRec), C.c_int64, _P(TreeFill), C.c_int64],
+    'cyb_tree_axis_c128': [_ctx, _P(TreeAxisRec), C.c_int64, _P(TreeFill), C.c_int64],
+    'cyb_dot_weighted_f64': [_ctx, _P(WDotDesc), C.c_int64, _vp],
+    'cyb_dot_weighted_c128': [_ctx, _P(WDotDesc), C.c_int64, C.c_int32, _vp],
     'cyb_seg_binary': [_ctx, _P(SegRec), C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double],
     'cyb_seg_reduce': [_ctx, _P(SegRec), C.c_int64, C.c_int32, C.c_int32, C.c_double, _vp],
     'cyb_seg_compact': [_ctx, _P(SegRec), C.c_int64, _vp, _vp],

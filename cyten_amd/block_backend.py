@@ -1490,6 +1490,178 @@ class HipBlockBackend:
             return out
         return self.scale_axis_many([(block, factors, axis)])[0]
 
+    # ------------------------------------------------------------------ tree blocks of fusion-tree tensors
+    @staticmethod
+    def _tree_view(blk: HipBlock, side: int, what: str):
+        """(stride of the tree index, stride of the other index, extent of the other index) of a coupled block whose tree
+        blocks are row ranges (side 0, codomain) or column ranges (side 1, domain); a 1-D block is a one-column matrix"""
+        if blk.ndim == 1:
+            if side != 0:
+                raise ValueError(f'tree_axis_many: a 1-D {what} block has a codomain side only')
+            return blk.strides[0], 0, 1
+        if blk.ndim != 2:
+            raise ValueError(f'tree_axis_many: {what} blocks are coupled blocks (2-D) or diagonal blocks (1-D)')
+        return (blk.strides[0], blk.strides[1], blk.shape[1]) if side == 0 else (blk.strides[1], blk.strides[0], blk.shape[0])
+
+    def tree_axis_many(self, records, mode, fill=()):
+        """scale / gather / scatter along one leg of tree blocks, ONE launch for all `records` of a tensor operation
+        (``FusionTreeBackend::scale_axis`` fusion_tree_backend.cpp:3611-3639, ``::_mask_contract`` :2453-2494, which make five
+        block-backend calls per forest block).  A record has the fields of :class:`cyten_amd.fusion_tree.TreeAxisRecord`:
+        ``src`` / ``dst`` coupled blocks (any 2-D views, read and written in place), ``side`` 0 / 1 (tree blocks are row /
+        column ranges), ``src_start`` / ``dst_start``, ``outer`` / ``A`` / ``A_dst`` / ``inner`` (the multiplicities around
+        the acted leg) and ``table``: a 1-D block of A factors (`mode` 'scale'; real or complex) or the kept positions
+        ('gather' / 'scatter') as a host int64 array or a :class:`DeviceIndex`.  Host tables are uploaded once,
+        concatenated.  `fill`: blocks (contiguous) the launch sets to zero first.  The destinations decide the entry:
+        all float64, or all complex128 (a float64 source is then widened in the kernel)."""
+        if mode not in _lib.TREE_AXIS_MODES:
+            raise ValueError(f'tree_axis_many: unknown mode {mode!r}')
+        records, fill = list(records), list(fill)
+        self._numeric_only([r.src for r in records] + [r.dst for r in records] + fill, 'tree_axis_many')
+        kinds = {r.dst.is_complex for r in records} | {b.is_complex for b in fill}
+        if len(kinds) > 1:
+            raise ValueError('tree_axis_many: the destination blocks of one call share one dtype')
+        cplx = bool(kinds and kinds.pop())
+        n = len(records)
+        arr = np.zeros(max(n, 1), dtype=_lib.TREE_AXIS_DTYPE)
+        keep = []
+        if mode == 'scale':
+            tables = [None] * n
+            for i, r in enumerate(records):
+                f = r.table
+                if f.is_bool or f.ndim != 1 or f.shape[0] != r.A:
+                    raise ValueError('tree_axis_many: the factors of a record are a 1-D numeric block of A entries')
+                if f.is_complex and not cplx:
+                    raise ValueError('tree_axis_many: complex factors need complex destination blocks')
+                if f.strides[0] != 1 and f.shape[0] > 1:
+                    f = self.contiguous(f)
+                    keep.append(f)
+                tables[i] = (f.ptr, 1 if f.is_complex else 0)
+        else:
+            host = [np.ascontiguousarray(r.table, dtype=np.int64) for r in records if not isinstance(r.table, DeviceIndex)]
+            offs = np.concatenate([[0], np.cumsum([len(x) for x in host])]).astype(np.int64)
+            didx = None
+            if offs[-1]:     # (nothing is allocated or uploaded when every table already is on the device)
+                didx = self.ctx.empty(int(offs[-1]), 'int64')
+                self.ctx.h2d(didx, np.concatenate(host))
+                keep.append(didx)
+            base = didx.data_ptr() if didx is not None else 0
+            tables, h = [None] * n, 0
+            for i, r in enumerate(records):
+                if isinstance(r.table, DeviceIndex):
+                    ptr, cnt = r.table.ptr, r.table.n
+                else:
+                    ptr, cnt = (base + 8 * int(offs[h]) if len(host[h]) else 0), len(host[h])
+                    large = r.A if mode == 'gather' else r.A_dst
+                    if len(host[h]) and not (0 <= host[h].min() and host[h].max() < large):
+                        raise ValueError('tree_axis_many: a kept position lies outside the large leg')
+                    h += 1
+                if cnt != (r.A_dst if mode == 'gather' else r.A):
+                    raise ValueError('tree_axis_many: the table of a record does not match its small extent')
+                tables[i] = (ptr, 0)
+        for i, r in enumerate(records):
+            s_ts, s_xs, X = self._tree_view(r.src, r.side, 'source')
+            d_ts, d_xs, Xd = self._tree_view(r.dst, r.side, 'destination')
+            if X != Xd:
+                raise ValueError('tree_axis_many: source and destination differ in the extent of the other index')
+            if r.src.is_complex and not cplx:
+                raise ValueError('tree_axis_many: a complex source needs complex destination blocks')
+            ext_s, ext_d = r.outer * r.A * r.inner, r.outer * r.A_dst * r.inner
+            if min(r.src_start, r.dst_start, r.outer, r.A, r.A_dst, r.inner) >= 0 and (
+                    r.src_start + ext_s > r.src.shape[r.side if r.src.ndim == 2 else 0]
+                    or r.dst_start + ext_d > r.dst.shape[r.side if r.dst.ndim == 2 else 0]):
+                raise ValueError('tree_axis_many: a tree block reaches beyond its coupled block')
+            arr[i] = (r.src.ptr, r.dst.ptr, tables[i][0], s_ts, s_xs, d_ts, d_xs, r.src_start, r.dst_start, X, r.outer, r.A, r.A_dst,
+                      r.inner, _lib.TREE_AXIS_MODES[mode], 0 if r.src.is_complex else 1, tables[i][1], 0)
+        fills = np.zeros(max(len(fill), 1), dtype=_lib.TREE_FILL_DTYPE)
+        for i, b in enumerate(fill):
+            if not b.is_contiguous():
+                raise ValueError('tree_axis_many: only contiguous blocks can be zero-filled')
+            fills[i] = (b.ptr, b.size * (16 if b.is_complex else 8))
+        if not n and not fill:
+            return
+        fn = self.lib.cyb_tree_axis_c128 if cplx else self.lib.cyb_tree_axis_f64
+        self.ctx.sync_stream()
+        _lib.check(fn(self.ctx.handle, arr.ctypes.data_as(C.POINTER(_lib.TreeAxisRec)), n,
+                      fills.ctypes.data_as(C.POINTER(_lib.TreeFill)), len(fill)))
+        del keep
+
+    def _wdot(self, descs, cplx, conj):
+        """launch chain of the weighted reduction + the one read of its result"""
+        n = len(descs)
+        arr = np.zeros(max(n, 1), dtype=_lib.WDOT_DTYPE)
+        for i, d in enumerate(descs):
+            arr[i] = d
+        res = self.ctx.empty(2)
+        p = arr.ctypes.data_as(C.POINTER(_lib.WDotDesc))
+        self.ctx.sync_stream()
+        if cplx:
+            _lib.check(self.lib.cyb_dot_weighted_c128(self.ctx.handle, p, n, 1 if conj else 0, C.c_void_p(res.data_ptr())))
+            re, im = self.ctx.d2h(res, 2, np.float64)
+            return complex(float(re), float(im))
+        _lib.check(self.lib.cyb_dot_weighted_f64(self.ctx.handle, p, n, C.c_void_p(res.data_ptr())))
+        return float(self.ctx.d2h(res, 1, np.float64)[0])
+
+    @staticmethod
+    def _as_matrix(b: HipBlock):
+        """(rows, cols, row stride, column stride) of a 1-D or 2-D block"""
+        if b.ndim == 1:
+            return b.shape[0], 1, b.strides[0], 0
+        if b.ndim != 2:
+            raise ValueError('inner_weighted_many: blocks are 1-D or 2-D')
+        return b.shape[0], b.shape[1], b.strides[0], b.strides[1]
+
+    def inner_weighted_many(self, a_blocks, b_blocks, weights, do_dagger=False):
+        """``sum_n weights[n] * inner(a_n, b_n, do_dagger)`` over lists of 1-D / 2-D blocks: ONE launch chain and one read of
+        the result (the loops of ``FusionTreeBackend::inner`` fusion_tree_backend.cpp:1238-1259 and ``::norm`` :1280-1296 make a
+        reduction and a host wait per coupled sector).  ``do_dagger``: sum conj(a)[i, j] b[i, j]; else sum a[i, j] b[j, i] without
+        conjugation (numpy.cpp:815-842).  ``b_blocks=None``: the weighted square norm sum_n w_n |a_n|^2 (real).  The blocks are
+        read in place through their strides (transposed views included); a float64 block beside complex ones is promoted."""
+        a_blocks, weights = list(a_blocks), [float(w) for w in weights]
+        norm = b_blocks is None
+        b_blocks = a_blocks if norm else list(b_blocks)
+        if not (len(a_blocks) == len(b_blocks) == len(weights)):
+            raise ValueError('inner_weighted_many: one weight and one partner per block')
+        self._numeric_only(a_blocks + b_blocks, 'inner_weighted_many')
+        cplx = any(x.is_complex for x in a_blocks) or any(x.is_complex for x in b_blocks)
+        if cplx:
+            a_blocks = [self.as_complex(x) for x in a_blocks]
+            b_blocks = a_blocks if norm else [self.as_complex(x) for x in b_blocks]
+        descs = []
+        for x, y, w in zip(a_blocks, b_blocks, weights):
+            rows, cols, x_rs, x_cs = self._as_matrix(x)
+            yr, yc, y_rs, y_cs = self._as_matrix(y)
+            if not (do_dagger or norm):
+                if x.ndim != 2 or y.ndim != 2:
+                    raise ValueError('inner_weighted_many: do_dagger=False needs 2-D blocks')
+                yr, yc, y_rs, y_cs = yc, yr, y_cs, y_rs
+            if (rows, cols) != (yr, yc):
+                raise ValueError('inner: shape mismatch')
+            descs.append((x.ptr, 0 if norm else y.ptr, rows, cols, x_rs, x_cs, y_rs, y_cs, w))
+        res = self._wdot(descs, cplx, do_dagger or norm)
+        return res.real if norm and cplx else res
+
+    def trace_weighted_many(self, blocks, weights):
+        """``sum_n weights[n] * trace(block_n)`` over square blocks (``FusionTreeBackend::trace_full``,
+        fusion_tree_backend.cpp:1261-1278): the weighted reduction over the diagonals (element stride ld + 1) against a
+        constant one -- the same launch chain as :meth:`inner_weighted_many`."""
+        blocks, weights = list(blocks), list(weights)
+        if len(blocks) != len(weights):
+            raise ValueError('trace_weighted_many: one weight per block')
+        self._numeric_only(blocks, 'trace_weighted_many')
+        cplx = any(b.is_complex for b in blocks)
+        if cplx:
+            blocks = [self.as_complex(b) for b in blocks]
+        ones = self.__dict__.setdefault('_const_one', {})        # the constant one of either dtype, uploaded once
+        one = ones.get(cplx)
+        if one is None:
+            one = ones[cplx] = self.as_block(np.ones(1, dtype=np.complex128 if cplx else np.float64))
+        descs = []
+        for b, w in zip(blocks, weights):
+            if b.ndim != 2 or b.shape[0] != b.shape[1]:
+                raise ValueError('trace_weighted_many: blocks must be square matrices')
+            descs.append((b.ptr, one.ptr, b.shape[0], 1, b.strides[0] + b.strides[1], 0, 0, 0, float(w)))
+        return self._wdot(descs, cplx, False)
+
     def allclose(self, a, b, rtol=1e-5, atol=1e-8) -> bool:
         diff = self.linear_combination(1.0, a, -1.0, b)
         return self.max_abs(diff) <= atol + rtol * self.max_abs(b)

@@ -23,15 +23,28 @@ module mirrors is everything BETWEEN that layer and the block backend:
   symmetry layer as data; the loops over coupled sectors and tree pairs are the reference's, but instead of ``zeros`` +
   (``get_item``, ``mul``, ``operator+``) per term + ``permute_combined_matrix`` + ``set_item`` per tree pair they fill ONE
   descriptor list for ``HipBlockBackend.transform_blocks`` (one zero fill + one launch per tensor, complex coefficients).
+* :func:`inner` / :func:`trace_full` / :func:`norm`  <- ``::inner`` (:1238-1259), ``::trace_full`` (:1261-1278), ``::norm``
+  (:1280-1296): ONE quantum-dimension weighted reduction (``inner_weighted_many`` / ``trace_weighted_many``) instead of a
+  reduction and a host wait per coupled sector.  :func:`mul`, :func:`linear_combination`, :func:`dagger`,
+  :func:`almost_equal`  <- ``::mul`` (:1298-1314), ``::linear_combination`` (:1316-1360), ``::dagger`` (:717-729),
+  ``::almost_equal`` (:560-590).
+* :func:`scale_axis`  <- ``::scale_axis`` (:3521-3644), :func:`mask_contract`  <- ``::_mask_contract`` (:2372-2500): the loops
+  over forest blocks emit one :class:`TreeAxisRecord` per tree block; the arithmetic is ONE ``tree_axis_many`` launch.  Both are
+  defined PER TREE BLOCK (rows ``start:stop`` of a tree, reshaped to its multiplicities in C order), which is what
+  ``iter_tree_blocks`` and ``transform_tensor`` mean; the reference's ``_mask_contract`` reshapes a codomain forest to
+  ``(m..., -1)`` (:2471), which mixes the tree index into the columns when a forest holds several trees, and is not reproduced.
+* :func:`truncated_svd`: svd, truncation and the mask on U, S and Vh -- three launches after the SVD.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass, field
+from typing import NamedTuple
 
 import numpy as np
 
 __all__ = ['TreeBlock', 'TreeSpace', 'FusionTreeData', 'compose', 'svd', 'qr', 'lq', 'eigh', 'truncate_singular_values',
-           'transform_tensor', 'discard_zero_blocks', 'norm']
+           'transform_tensor', 'discard_zero_blocks', 'norm', 'inner', 'trace_full', 'mul', 'linear_combination', 'dagger',
+           'almost_equal', 'TreeAxisRecord', 'TreeMask', 'leg_keys', 'scale_axis', 'mask_contract', 'truncated_svd']
 
 
 @dataclass(frozen=True)
@@ -42,6 +55,7 @@ class TreeBlock:
     start: int
     stop: int
     multiplicities: tuple
+    uncoupled: tuple = ()  # one hashable sector key per flat leg (``TreeBlockInfo::uncoupled``); () where the caller has none
 
 
 @dataclass
@@ -75,20 +89,25 @@ class TreeSpace:
         tbs = self.tree_blocks[i]
         return tbs[-1].stop if tbs else 0
 
+    def has_tree(self, tree) -> bool:
+        return tree in self._where
+
     def tree_block_slice(self, tree):
         """(coupled sector index, TreeBlock) of a tree (``tree_block_slice`` + the tree's ``coupled``)"""
         return self._where[tree]
 
     @classmethod
-    def from_multiplicities(cls, sectors, tree_mults, qdims=None, num_legs=0, names=None):
-        """``tree_mults[i]``: list of multiplicity tuples of the trees of coupled sector i (block rows in that order)"""
+    def from_multiplicities(cls, sectors, tree_mults, qdims=None, num_legs=0, names=None, uncoupled=None):
+        """``tree_mults[i]``: list of multiplicity tuples of the trees of coupled sector i (block rows in that order);
+        ``uncoupled[i][t]``: the sector keys of the legs of tree t, where the caller has them"""
         blocks = []
         for i, lst in enumerate(tree_mults):
             off, tbs = 0, []
             for t, m in enumerate(lst):
                 m = tuple(int(x) for x in m)
                 sz = int(np.prod(m)) if m else 1
-                tbs.append(TreeBlock(names[i][t] if names is not None else (i, t), off, off + sz, m))
+                tbs.append(TreeBlock(names[i][t] if names is not None else (i, t), off, off + sz, m,
+                                     tuple(uncoupled[i][t]) if uncoupled is not None else ()))
                 off += sz
             blocks.append(tbs)
         q = np.ones(len(blocks)) if qdims is None else qdims
@@ -238,6 +257,12 @@ def truncate_singular_values(bb, S: FusionTreeData, domain: TreeSpace, **options
     has no block) weighted by ``sector_qdims[j]``.  Returns (mask_blocks, mask_block_inds, err, new_norm): boolean host
     vectors of the sectors that keep at least one value, rows (small index, large index j), as the reference builds its
     Mask.  The selection runs on the device when the backend offers it (weights are one number per sector)."""
+    return _truncate(bb, S, domain, **options)[:4]
+
+
+def _truncate(bb, S: FusionTreeData, domain: TreeSpace, **options):
+    """:func:`truncate_singular_values` + the kept positions per sector j as the device tables of ``truncate_select``
+    (``{j: DeviceIndex}``), or None where the selection ran on the host"""
     mults = [int(m) for m in domain.multiplicities]
     have = {int(i): n for n, i in enumerate(S.block_inds[:, 0])}
     absent = [j for j in range(len(mults)) if j not in have and mults[j] > 0]
@@ -250,9 +275,11 @@ def truncate_singular_values(bb, S: FusionTreeData, domain: TreeSpace, **options
     sec = [j for j, m in enumerate(mults) if m > 0]
     q = np.array([domain.qdims[j] for j in sec], dtype=np.float64)
     if hasattr(bb, 'truncate_select') and 0 < sum(mults) <= bb.TRUNCATE_MAX:
-        _, mask, err, new_norm = bb.truncate_select(blocks, qdims=q, **options)
+        tables, mask, err, new_norm = bb.truncate_select(blocks, qdims=q, **options)
         keep = bb.to_numpy(mask).astype(bool)
+        tables = dict(zip(sec, tables))
     else:
+        tables = None
         from . import abelian as ab
         S_np = np.concatenate([bb.to_numpy(b) for b in blocks]) if blocks else np.zeros(0)
         keep, err, new_norm = ab.truncation_selection(S_np, qdims=np.repeat(q, [mults[j] for j in sec]), **options)
@@ -263,16 +290,19 @@ def truncate_singular_values(bb, S: FusionTreeData, domain: TreeSpace, **options
         if blk.any():
             out_r.append((len(out_r), j))
             out_b.append(blk.copy())
-    return out_b, np.array(out_r, dtype=np.int64).reshape(len(out_r), 2), float(err), float(new_norm)
+    return out_b, np.array(out_r, dtype=np.int64).reshape(len(out_r), 2), float(err), float(new_norm), tables
 
 
 def norm(bb, a: FusionTreeData, codomain: TreeSpace) -> float:
-    """fusion_tree_backend.cpp:1283-1297: sqrt(sum_n qdim(coupled_n) |block_n|^2), one reduction per block list"""
+    """fusion_tree_backend.cpp:1283-1297: sqrt(sum_n qdim(coupled_n) |block_n|^2), one reduction per block list -- with
+    different quantum dimensions the weighted one, where the backend has it"""
     if not a.blocks:
         return 0.0
     q = codomain.qdims[a.block_inds[:, 0]]
     if np.all(q == q[0]):
         return float(np.sqrt(q[0]) * bb.norm_many(a.blocks))
+    if hasattr(bb, 'inner_weighted_many'):
+        return float(np.sqrt(bb.inner_weighted_many(a.blocks, None, q)))
     return float(np.sqrt(sum(float(qi) * bb.norm_many([b]) ** 2 for qi, b in zip(q, a.blocks))))
 
 
@@ -342,3 +372,310 @@ def discard_zero_blocks(bb, data: FusionTreeData, eps: float) -> FusionTreeData:
     if len(keep) == len(data.blocks):
         return data
     return FusionTreeData(data.block_inds[keep], [data.blocks[n] for n in keep])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# vector-space operations
+
+def _match(a_keys, b_keys):
+    """(n_a or None, n_b or None) over the union of two ascending duplicate-free key arrays, ascending
+    (``iter_common_noncommon_sorted_1d``)"""
+    ia = {int(k): n for n, k in enumerate(a_keys)}
+    ib = {int(k): n for n, k in enumerate(b_keys)}
+    return [(ia.get(k), ib.get(k)) for k in sorted(set(ia) | set(ib))]
+
+
+def inner(bb, a: FusionTreeData, b: FusionTreeData, codomain: TreeSpace, do_dagger: bool = False):
+    """fusion_tree_backend.cpp:1238-1259: sum over the common coupled sectors of qdim * inner(block_a, block_b, do_dagger) --
+    ``do_dagger``: <a|b> with b on the spaces of a; else trace(a b) with b's domain on a's codomain.  ONE weighted
+    reduction.  `codomain`: a's."""
+    col = 0 if do_dagger else 1
+    pairs = [(n, m) for n, m in _match(a.block_inds[:, 0], np.sort(b.block_inds[:, col])) if n is not None and m is not None]
+    if not pairs:
+        return 0.0
+    where = {int(k): m for m, k in enumerate(b.block_inds[:, col])}
+    xs = [a.blocks[n] for n, _ in pairs]
+    ys = [b.blocks[where[int(a.block_inds[n, 0])]] for n, _ in pairs]
+    return bb.inner_weighted_many(xs, ys, [codomain.qdims[a.block_inds[n, 0]] for n, _ in pairs], do_dagger=do_dagger)
+
+
+def trace_full(bb, a: FusionTreeData, codomain: TreeSpace):
+    """fusion_tree_backend.cpp:1261-1278: sum_n qdim(coupled_n) trace(block_n), ONE weighted reduction over the diagonals"""
+    if not a.blocks:
+        return 0.0
+    return bb.trace_weighted_many(a.blocks, codomain.qdims[a.block_inds[:, 0]])
+
+
+def mul(bb, scalar, a: FusionTreeData) -> FusionTreeData:
+    """fusion_tree_backend.cpp:1298-1314: a zero scalar gives the tensor without blocks"""
+    if scalar == 0 or not a.blocks:
+        return FusionTreeData(np.zeros((0, 2), np.int64), [])
+    return FusionTreeData(a.block_inds.copy(), bb.mul_many(scalar, a.blocks))
+
+
+def linear_combination(bb, a, v: FusionTreeData, b, w: FusionTreeData) -> FusionTreeData:
+    """fusion_tree_backend.cpp:1316-1360: a v + b w; a coupled sector only one of them holds gets a * block or b * block
+    (:1335-1356).  One batched call for the common blocks and one for each of the two one-sided lists."""
+    pairs = _match(v.block_inds[:, 0], w.block_inds[:, 0])
+    both = [(i, j) for i, j in pairs if i is not None and j is not None]
+    only_v = [i for i, j in pairs if j is None]
+    only_w = [j for i, j in pairs if i is None]
+    cplx = any(np.dtype(getattr(x, 'dtype', float)).kind == 'c' for x in v.blocks + w.blocks)
+    one = complex(1.0) if cplx else 1.0      # (the common dtype of :1324-1332: a one-sided block of a mixed pair is promoted too)
+    out = {}
+    if both:
+        res = bb.linear_combination_many(a, [v.blocks[i] for i, _ in both], b, [w.blocks[j] for _, j in both])
+        out.update({('v', i): r for (i, _), r in zip(both, res)})
+    if only_v:
+        out.update({('v', i): r for i, r in zip(only_v, bb.mul_many(a * one, [v.blocks[i] for i in only_v]))})
+    if only_w:
+        out.update({('w', j): r for j, r in zip(only_w, bb.mul_many(b * one, [w.blocks[j] for j in only_w]))})
+    rows, blocks = [], []
+    for i, j in pairs:
+        rows.append(v.block_inds[i] if i is not None else w.block_inds[j])
+        blocks.append(out[('v', i)] if i is not None else out[('w', j)])
+    return FusionTreeData(np.array(rows, dtype=np.int64).reshape(len(rows), 2), blocks)
+
+
+def dagger(bb, a: FusionTreeData) -> FusionTreeData:
+    """fusion_tree_backend.cpp:717-729: the columns of ``block_inds`` swap (codomain and domain have swapped), the rows are
+    sorted again, every block is the conjugate of its transposed view: a real block stays a view (the kernels read strides), the
+    complex blocks of the tensor are conjugated by ONE batched copy"""
+    views = [bb.permute_axes(blk, [1, 0]) for blk in a.blocks]
+    cplx = [n for n, blk in enumerate(a.blocks) if _is_complex(blk)]
+    if cplx:
+        outs = bb.empty_many([tuple(views[n].shape) for n in cplx], dtype=np.complex128)
+        bb.copy_many([(o, views[n]) for o, n in zip(outs, cplx)], conj=True)
+        for o, n in zip(outs, cplx):
+            views[n] = o
+    return FusionTreeData(a.block_inds[:, ::-1].copy(), views).sorted()
+
+
+def almost_equal(bb, a: FusionTreeData, b: FusionTreeData, rtol: float = 1e-5, atol: float = 1e-8) -> bool:
+    """fusion_tree_backend.cpp:560-590: blocks only one tensor holds must vanish within atol, common ones be allclose.  As in
+    the reference this is a reduction and a host wait per coupled sector, ending at the first sector that differs: a
+    comparison for tests and convergence checks, not part of an update step."""
+    for i, j in _match(a.block_inds[:, 0], b.block_inds[:, 0]):
+        if j is None:
+            ok = bb.max_abs(a.blocks[i]) <= atol
+        elif i is None:
+            ok = bb.max_abs(b.blocks[j]) <= atol
+        else:
+            ok = bb.allclose(a.blocks[i], b.blocks[j], rtol, atol)
+        if not ok:
+            return False
+    return True
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# axis operations on tree blocks
+
+class TreeAxisRecord(NamedTuple):
+    """one tree block of one coupled block on one side, as ``tree_axis_many`` reads it: tree position
+    ``t = (o * A + a) * inner + i`` counted from ``src_start`` / ``dst_start``"""
+    src: object        # coupled block (2-D) or diagonal block (1-D), read in place
+    dst: object        # result block, written in place
+    side: int          # 0: tree blocks are row ranges (codomain), 1: column ranges (domain)
+    src_start: int
+    dst_start: int
+    outer: int
+    A: int             # multiplicity of the acted leg in the source
+    A_dst: int         # ... in the destination
+    inner: int
+    table: object      # scale: 1-D block of A factors; gather / scatter: kept positions (host int64 array or DeviceIndex)
+
+
+@dataclass
+class TreeMask:
+    """A mask on one leg: per sector of the large leg (a hashable key, as in ``TreeBlock.uncoupled``) its multiplicity and the
+    ascending kept positions -- a host int64 array, a ``DeviceIndex`` (the table ``truncate_select`` left on the device) or
+    None (nothing kept; also the meaning of a sector the mask does not list)."""
+    sectors: list
+    large_mults: list
+    keep: list
+    _pos: dict = field(default_factory=dict, repr=False)
+
+    def __post_init__(self):
+        self._pos = {k: n for n, k in enumerate(self.sectors)}
+        self.keep = [None if t is None else (t if hasattr(t, 'ptr') else np.asarray(t, dtype=np.int64)) for t in self.keep]
+
+    def table(self, key):
+        n = self._pos.get(key)
+        return None if n is None else self.keep[n]
+
+    def small(self, key) -> int:
+        t = self.table(key)
+        return 0 if t is None else (t.n if hasattr(t, 'ptr') else len(t))
+
+    def large(self, key) -> int:
+        n = self._pos.get(key)
+        return 0 if n is None else int(self.large_mults[n])
+
+    @classmethod
+    def from_truncation(cls, mask_blocks, mask_block_inds, leg_space: TreeSpace, tables=None) -> 'TreeMask':
+        """the mask :func:`truncate_singular_values` returned (boolean host vectors, rows (small index, large index j)) on
+        the one-leg space it was computed for; `tables`: ``{j: DeviceIndex}`` to use instead of the host positions"""
+        keys = leg_keys(leg_space)
+        keep = [None] * len(keys)
+        for blk, (_, j) in zip(mask_blocks, np.asarray(mask_block_inds).reshape(-1, 2).tolist()):
+            keep[j] = tables[j] if tables is not None else np.flatnonzero(blk)
+        return cls(keys, [int(m) for m in leg_space.multiplicities], keep)
+
+
+def leg_keys(space: TreeSpace) -> list:
+    """sector key of every coupled sector of a one-leg space: the ``uncoupled`` key of its tree, else the sector itself"""
+    keys = []
+    for i, tbs in enumerate(space.tree_blocks):
+        if len(tbs) != 1 or len(tbs[0].multiplicities) != 1:
+            raise ValueError('a one-leg space has one tree with one multiplicity per sector')
+        keys.append(tbs[0].uncoupled[0] if tbs[0].uncoupled else tuple(space.sectors[i].tolist()))
+    return keys
+
+
+def _parse_leg(codomain: TreeSpace, domain: TreeSpace, leg: int):
+    """(side, index within the side) of a leg numbered as in :func:`transform_tensor`: the codomain legs, then the domain
+    legs counted from the end"""
+    J, N = codomain.num_legs, codomain.num_legs + domain.num_legs
+    if not 0 <= leg < N:
+        raise ValueError(f'leg {leg} outside [0, {N})')
+    return (0, leg) if leg < J else (1, N - 1 - leg)
+
+
+def _split(tb: TreeBlock, idx: int):
+    if len(tb.uncoupled) != len(tb.multiplicities) or idx >= len(tb.multiplicities):
+        raise ValueError('this operation needs the uncoupled sector keys of every tree (TreeBlock.uncoupled)')
+    m = tb.multiplicities
+    return int(np.prod(m[:idx], dtype=np.int64)), int(m[idx]), int(np.prod(m[idx + 1:], dtype=np.int64)), tb.uncoupled[idx]
+
+
+def _is_complex(blk) -> bool:
+    return np.dtype(getattr(blk, 'dtype', float)).kind == 'c'
+
+
+def scale_axis(bb, data: FusionTreeData, codomain: TreeSpace, domain: TreeSpace, diag: FusionTreeData, diag_space: TreeSpace,
+               leg: int) -> FusionTreeData:
+    """fusion_tree_backend.cpp:3521-3644: every tree block is multiplied along `leg` (numbered as in :func:`transform_tensor`)
+    with the diagonal block of its uncoupled sector there.  `diag`: 1-D blocks on the one-leg `diag_space`.  Tree blocks
+    whose sector has no diagonal block give zeros; a coupled block none of whose trees has one is absent (:3596-3605).  The
+    one-leg side (:3544-3568) is the general case with ``outer = inner = 1``.  ONE launch."""
+    side, idx = _parse_leg(codomain, domain, leg)
+    space = domain if side else codomain
+    keys = leg_keys(diag_space)
+    f_of = {keys[int(j)]: diag.blocks[n] for n, j in enumerate(diag.block_inds[:, 0])}
+    cplx = any(_is_complex(b) for b in data.blocks) or any(_is_complex(b) for b in diag.blocks)
+    plan, rows, shapes = [], [], []
+    for n, (i, j) in enumerate(data.block_inds.tolist()):
+        recs = []
+        for tb in space.tree_blocks[j if side else i]:
+            outer, A, inner, key = _split(tb, idx)
+            f = f_of.get(key)
+            if f is not None and tb.stop > tb.start:
+                recs.append((tb.start, outer, A, inner, f))
+        if not recs:
+            continue
+        covered = sum(o * A * i_ for _, o, A, i_, _ in recs) == space.block_size(j if side else i)
+        plan.append((n, recs, covered))
+        rows.append((i, j))
+        shapes.append(tuple(data.blocks[n].shape))
+    if not plan:
+        return FusionTreeData(np.zeros((0, 2), np.int64), [])
+    outs = bb.empty_many(shapes, dtype=np.complex128 if cplx else np.float64)
+    records = [TreeAxisRecord(data.blocks[n], out, side, start, start, outer, A, A, inner, f)
+               for (n, recs, _), out in zip(plan, outs) for start, outer, A, inner, f in recs]
+    bb.tree_axis_many(records, 'scale', fill=[out for (_, _, covered), out in zip(plan, outs) if not covered])
+    return FusionTreeData(np.array(rows, dtype=np.int64), outs)
+
+
+def _masked_space(space: TreeSpace, idx: int, mask: TreeMask, large_leg: bool) -> TreeSpace:
+    """the space with the multiplicity of leg `idx` replaced by the mask's small (`large_leg`) or large one: the same trees
+    in the same order, empty trees and then empty coupled sectors dropped"""
+    keep, blocks = [], []
+    for i, tbs in enumerate(space.tree_blocks):
+        off, new = 0, []
+        for tb in tbs:
+            _, _, _, key = _split(tb, idx)
+            m = list(tb.multiplicities)
+            m[idx] = mask.small(key) if large_leg else mask.large(key)
+            sz = int(np.prod(m, dtype=np.int64))
+            if sz:
+                new.append(TreeBlock(tb.tree, off, off + sz, tuple(m), tb.uncoupled))
+                off += sz
+        if new:
+            keep.append(i)
+            blocks.append(new)
+    return TreeSpace(space.sectors[keep], space.qdims[keep], blocks, space.num_legs)
+
+
+def mask_contract(bb, data: FusionTreeData, codomain: TreeSpace, domain: TreeSpace, mask: TreeMask, leg: int, large_leg: bool = True,
+                  target: TreeSpace = None, eps: float = 0.0, discard: bool = True):
+    """fusion_tree_backend.cpp:2372-2500: project `leg` (numbered as in :func:`transform_tensor`) with the mask
+    (``large_leg=True``: the leg is the mask's large leg, ``apply_mask`` per tree block) or embed it (``False``: the leg is the
+    small leg, ``enlarge_leg``).  Returns (data, new codomain, new domain).  `target`: the new space of that side; if not
+    given it is derived (:func:`_masked_space`, and ``block_inds`` re-indexed, :2424-2439).  ONE launch; the result goes
+    through :func:`discard_zero_blocks` with `eps` (the reference's ``fusion_tree_eps``) unless ``discard=False`` -- the switch
+    :func:`truncated_svd` uses, whose isometries have no zero blocks and which must not wait for the host per block.  Defined per tree block (the module docstring
+    names the difference to :2471)."""
+    side, idx = _parse_leg(codomain, domain, leg)
+    space = domain if side else codomain
+    new_space = target if target is not None else _masked_space(space, idx, mask, large_leg)
+    where = {tuple(s): k for k, s in enumerate(new_space.sectors.tolist())}
+    other = codomain if side else domain
+    plan, rows, shapes = [], [], []
+    for n, (i, j) in enumerate(data.block_inds.tolist()):
+        s = j if side else i
+        k = where.get(tuple(space.sectors[s].tolist()))
+        if k is None or new_space.block_size(k) == 0:
+            continue
+        recs, written = [], 0
+        for tb in space.tree_blocks[s]:
+            outer, A, inner, key = _split(tb, idx)
+            table = mask.table(key)
+            if table is None or not new_space.has_tree(tb.tree):
+                continue
+            k2, nb = new_space.tree_block_slice(tb.tree)
+            A_dst = int(nb.multiplicities[idx])
+            if k2 != k or A_dst != (mask.small(key) if large_leg else mask.large(key)) or A != (mask.large(key) if large_leg else mask.small(key)):
+                raise ValueError('mask_contract: the target space does not match the mask')
+            recs.append((tb.start, nb.start, outer, A, A_dst, inner, table))
+            written += nb.stop - nb.start
+        plan.append((n, recs, (not large_leg) or written != new_space.block_size(k)))
+        rows.append((i, k) if side else (k, j))
+        o = other.block_size(i if side else j)
+        blk = data.blocks[n]
+        shapes.append((new_space.block_size(k),) if len(blk.shape) == 1 else ((o, new_space.block_size(k)) if side else (new_space.block_size(k), o)))
+    new_cod, new_dom = (codomain, new_space) if side else (new_space, domain)
+    if not plan:
+        return FusionTreeData(np.zeros((0, 2), np.int64), []), new_cod, new_dom
+    cplx = any(_is_complex(b) for b in data.blocks)
+    outs = bb.empty_many(shapes, dtype=np.complex128 if cplx else np.float64)
+    records = [TreeAxisRecord(data.blocks[n], out, side, s0, d0, outer, A, A_dst, inner, table)
+               for (n, recs, _), out in zip(plan, outs) for s0, d0, outer, A, A_dst, inner, table in recs]
+    bb.tree_axis_many(records, 'gather' if large_leg else 'scatter', fill=[out for (_, _, z), out in zip(plan, outs) if z])
+    res = FusionTreeData(np.array(rows, dtype=np.int64), outs).sorted()
+    return (discard_zero_blocks(bb, res, eps) if discard else res), new_cod, new_dom
+
+
+def truncated_svd(bb, a: FusionTreeData, codomain: TreeSpace, domain: TreeSpace, factors=None, **options):
+    """:func:`svd`, :func:`truncate_singular_values`, and the mask applied to U's domain leg, to S and to Vh's codomain leg
+    (``TensorBackend::truncated_svd``).  Returns (U, S, Vh, new_leg_space, err, new_norm).  After the SVD: the selection
+    (its one download: the mask, err, new_norm) and three ``tree_axis_many`` launches reading the kept positions from the
+    tables the selection left on the device -- no per-block call, no further host wait.  `factors`: the (U, S, Vh) of
+    :func:`svd` of `a` where the caller already has them; they are truncated instead of decomposing again."""
+    algorithm = options.pop('algorithm', None)
+    common = common_sectors(codomain, domain)
+    cm, dm = codomain.multiplicities, domain.multiplicities
+    new_mults = [min(int(cm[i]), int(dm[j])) for i, j in common]
+    U, S, Vh = factors if factors is not None else svd(bb, a, codomain, domain, new_mults, algorithm)
+    sec = codomain.sectors[[i for i, _ in common]]
+    keys = [tuple(x) for x in sec.tolist()]
+    mid = TreeSpace.from_multiplicities(sec, [[(m,)] for m in new_mults], codomain.qdims[[i for i, _ in common]], 1,
+                                        [[('svd', k)] for k in keys], [[(k,)] for k in keys])
+    mask_blocks, mask_inds, err, new_norm, tables = _truncate(bb, S, mid, **options)
+    mask = TreeMask.from_truncation(mask_blocks, mask_inds, mid, tables)
+    J = codomain.num_legs
+    U2, _, new_leg = mask_contract(bb, U, codomain, mid, mask, J, True, discard=False)
+    Vh2, _, _ = mask_contract(bb, Vh, mid, domain, mask, 0, True, target=new_leg, discard=False)
+    S2, _, _ = mask_contract(bb, FusionTreeData(S.block_inds[:, :1].repeat(2, axis=1), S.blocks), mid, mid, mask, 0, True,
+                             target=new_leg, discard=False)
+    S2 = FusionTreeData(S2.block_inds[:, :1].repeat(2, axis=1), S2.blocks)
+    return U2, S2, Vh2, new_leg, err, new_norm

@@ -570,6 +570,64 @@ typedef struct {
 int cyb_outer_grouped_f64(cyb_ctx_t ctx, const cyb_outer_rec* recs, int64_t n);
 int cyb_outer_grouped_c128(cyb_ctx_t ctx, const cyb_outer_rec* recs, int64_t n);
 
+/* ---- axis operations on the tree blocks of fusion-tree tensors ---------------------------------------------------------
+ * FusionTreeBackend::scale_axis (src/backends/fusion_tree_backend.cpp:3521-3644) and FusionTreeBackend::_mask_contract
+ * (:2372-2500) in ONE launch per tensor operation: replaces, per forest block, get_item + reshape + BlockBackend::scale_axis
+ * (numpy.cpp:1373-1385) / apply_mask (:605-613) / enlarge_leg (:700-728) + reshape + set_item (:3611-3639, :2453-2494).
+ * A record is one tree block of one coupled block on one side.  With the tree position t = (o * A + a) * inner + i
+ * (o < outer, i < inner) counted from the start of the tree block and x < X the other matrix index, element (t, x) of the
+ * source is at src + (src_start + t) * src_ts + x * src_xs, of the destination at dst + (dst_start + t') * dst_ts + x * dst_xs
+ * (strides in elements of the operand's own type; a codomain record has ts = row stride, a domain record ts = column
+ * stride; every block keeps its own leading dimension).
+ *   CYB_TREE_SCALE   A_dst = A, dst(t, x) = table[a] * src(t, x); table: A float64 factors, or A interleaved complex ones
+ *                    with table_is_complex (c128 entry only)
+ *   CYB_TREE_GATHER  A_dst <= A, dst((o * A_dst + a') * inner + i, x) = src((o * A + table[a']) * inner + i, x)
+ *   CYB_TREE_SCATTER A <= A_dst, dst((o * A_dst + table[a]) * inner + i, x) = src((o * A + a) * inner + i, x)
+ * table of gather / scatter: int64 positions in DEVICE memory (A_dst resp. A entries, each below A resp. A_dst).
+ * `fills`: regions of device memory that are set to zero before the launch (the result blocks of a scatter, and of a scale
+ * whose diagonal lacks sectors: once per result block, not per record).  f64 entry: src, dst float64.  c128 entry: dst
+ * interleaved (re, im), 16-byte aligned; src complex, or float64 with src_is_real (read in place, widened in the kernel).
+ * Every record is validated before anything is enqueued (CYB_ERR_INVALID: negative extent, A_dst > A in a gather, NULL
+ * pointer with a non-zero size, misaligned pointer).  Records with a zero extent are skipped; an empty list is valid.
+ * Records of one call must not write overlapping elements. */
+enum { CYB_TREE_SCALE = 0, CYB_TREE_GATHER = 1, CYB_TREE_SCATTER = 2 };
+typedef struct {
+    const void* src;
+    void* dst;
+    const void* table;
+    int64_t src_ts, src_xs, dst_ts, dst_xs;
+    int64_t src_start, dst_start;
+    int64_t X;
+    int64_t outer, A, A_dst, inner;
+    int32_t mode;
+    int32_t src_is_real, table_is_complex;
+    int32_t reserved;
+} cyb_tree_axis_rec;
+typedef struct {
+    void* ptr;
+    int64_t bytes;
+} cyb_tree_fill;
+int cyb_tree_axis_f64(cyb_ctx_t ctx, const cyb_tree_axis_rec* recs, int64_t n, const cyb_tree_fill* fills, int64_t n_fills);
+int cyb_tree_axis_c128(cyb_ctx_t ctx, const cyb_tree_axis_rec* recs, int64_t n, const cyb_tree_fill* fills, int64_t n_fills);
+
+/* result_dev[0] = sum_n w_n sum_{r, c} x_n[r * x_rs + c * x_cs] * y_n[r * y_rs + c * y_cs] over a list of rows x cols views
+ * (strides in elements; y == NULL: x itself, the weighted square norm).  The weights travel in the descriptors, the result
+ * stays on the device, no host synchronisation.  Two stages in a fixed order, no floating-point atomics: bit-identical from
+ * run to run.  Replaces the loop over coupled sectors of FusionTreeBackend::inner (fusion_tree_backend.cpp:1238-1259:
+ * BlockBackend::inner per block, do_dagger = false is y read with swapped strides), ::norm (:1280-1296: BlockBackend::norm per
+ * block) and ::trace_full (:1261-1278: BlockBackend::trace_full per block -- here rows = n, cols = 1, x_rs = ld + 1 and y a
+ * constant one with strides 0), each of which is a reduction and a host wait per block.  c128 entry: x, y interleaved
+ * complex, 16-byte aligned, result_dev[0] / [1] = (re, im); conj_x != 0 conjugates x. */
+typedef struct {
+    const double* x;
+    const double* y;
+    int64_t rows, cols;
+    int64_t x_rs, x_cs, y_rs, y_cs;
+    double w;
+} cyb_wdot_desc;
+int cyb_dot_weighted_f64(cyb_ctx_t ctx, const cyb_wdot_desc* descs, int64_t n, double* result_dev);
+int cyb_dot_weighted_c128(cyb_ctx_t ctx, const cyb_wdot_desc* descs, int64_t n, int32_t conj_x, double* result_dev);
+
 /* ---- truncation of singular values on the device -----------------------------------------
  * TensorBackend::_truncate_singular_values_selection (src/backends/tensor_backend.cpp:139-242) applied to the
  * concatenation of the per-sector singular values WITHOUT the host round trip of
