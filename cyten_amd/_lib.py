@@ -258,6 +258,10 @@ PROTOTYPES = {
     'cyb_multi_axpy_c128': [_ctx, _vp, C.c_int64, _vp, C.c_double, C.c_double, _vp, C.c_int64],
     'cyb_gram_schmidt_f64': [_ctx, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, _vp],
     'cyb_gram_schmidt_c128': [_ctx, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, _vp],
+    'cyb_multi_dot_weighted_f64': [_ctx, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp],
+    'cyb_multi_dot_weighted_c128': [_ctx, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp],
+    'cyb_gram_schmidt_weighted_f64': [_ctx, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, _vp, _vp],
+    'cyb_gram_schmidt_weighted_c128': [_ctx, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, _vp, _vp],
     'cyb_fill_f64': [_ctx, _vp, C.c_int64, C.c_double],
     'cyb_eye_f64': [_ctx, _vp, C.c_int64],
     'cyb_random_normal_f64': [_ctx, _vp, C.c_int64, C.c_uint64, C.c_double],

@@ -185,6 +185,7 @@ namespace {
 constexpr int GS_MAX_M = 64;
 constexpr int GS_WAVES = 4;
 constexpr int GS_MAX_GRID = 2048;
+constexpr int GS_GRANULE = 256; // elements (doubles or complex numbers) per entry of a weight table
 
 struct BasisPtrs {
     const double* v[GS_MAX_M];
@@ -202,6 +203,8 @@ template <> struct GsT<false> {
     static __device__ __forceinline__ T scale(double are, double, T u) { return are * u; }
     static __device__ __forceinline__ double sq(T w) { return w * w; }
     static __device__ __forceinline__ T add(T a, T b) { return a + b; }
+    static __device__ __forceinline__ T wscale(double d, T w) { return d * w; }
+    static __device__ __forceinline__ double sqw(T wd, T w) { return wd * w; }
 };
 template <> struct GsT<true> {
     typedef d2v T;
@@ -219,14 +222,23 @@ template <> struct GsT<true> {
     static __device__ __forceinline__ T scale(double are, double aim, T u) { return T{are * u.x - aim * u.y, are * u.y + aim * u.x}; }
     static __device__ __forceinline__ double sq(T w) { return w.x * w.x + w.y * w.y; }
     static __device__ __forceinline__ T add(T a, T b) { return T{a.x + b.x, a.y + b.y}; }
+    static __device__ __forceinline__ T wscale(double d, T w) { return T{d * w.x, d * w.y}; }
+    static __device__ __forceinline__ double sqw(T wd, T w) { return wd.x * w.x + wd.y * w.y; }
 };
 
 // partial[(g * (m + 1) + j) * 2 + {0, 1}]: (re, im) of the workgroup's partial dot with V_j (j < m) or its partial |w|^2
 // (j == m).  coef: m (real) or 2m (interleaved complex) device doubles, scaled by alpha in the update.
-template <bool CPLX, int J, int MODE>
+//
+// WT: the reductions carry a weight per granule of GS_GRANULE elements (the quantum dimension of the coupled sector a
+// fusion-tree pool keeps there): h_j = sum_i d(i) conj(V_j[i]) w[i], |w|^2 = sum_i d(i) |w[i]|^2; the update is unweighted.
+// A tile is one granule (f64) or half of one (c128), so the weight is uniform per tile: it is read once per tile and
+// multiplied onto the tile's EL elements of w before they meet the J rows of V -- EL multiplications per lane and tile,
+// whatever J is, and the accumulation chain of every lane is the unweighted one term for term (a weight d = s^2 with s a
+// power of two therefore gives the bits of the unweighted kernel on (s V, s w)).
+template <bool CPLX, int J, int MODE, bool WT>
 __global__ void __launch_bounds__(64 * GS_WAVES) gs_sweep_kernel(BasisPtrs P, int m, double* __restrict__ w_, int64_t n, int64_t tpg,
                                                                 const double* __restrict__ coef, double are, double aim,
-                                                                double* __restrict__ partial)
+                                                                double* __restrict__ partial, const double* __restrict__ weights)
 {
     typedef GsT<CPLX> O;
     typedef typename O::T T;
@@ -286,6 +298,24 @@ __global__ void __launch_bounds__(64 * GS_WAVES) gs_sweep_kernel(BasisPtrs P, in
                 if (q == 0 && i < n) w[i] = wr[e];
             }
             __syncthreads(); // (red is refilled by the next tile)
+        }
+        if (WT) {
+            static_assert(GS_GRANULE % TS == 0, "a tile must not straddle a granule");
+            const double d = weights[t / (GS_GRANULE / TS)];
+            T wd[EL];
+#pragma unroll
+            for (int e = 0; e < EL; ++e) wd[e] = O::wscale(d, wr[e]);
+            if (DOT) {
+#pragma unroll
+                for (int jj = 0; jj < J; ++jj)
+#pragma unroll
+                    for (int e = 0; e < EL; ++e) O::cdot(vr[jj][e], wd[e], dre[jj], dim[jj]);
+            }
+            if (MODE == GS_UPD_NORM && q == 0) {
+#pragma unroll
+                for (int e = 0; e < EL; ++e) nrm += O::sqw(wd[e], wr[e]);
+            }
+            continue;
         }
         if (DOT) {
 #pragma unroll
@@ -378,13 +408,13 @@ static GsGrid gs_grid(int64_t n, bool cplx)
     return GsGrid{cdiv64(tiles, tpg), tpg};
 }
 
-template <bool CPLX, int MODE>
+template <bool CPLX, int MODE, bool WT>
 static void gs_launch_j(int J, const GsGrid& g, hipStream_t s, const BasisPtrs& P, int m, double* w, int64_t n, const double* coef,
-                        double are, double aim, double* partial)
+                        double are, double aim, double* partial, const double* weights)
 {
     const dim3 grid((unsigned)g.groups), block(64 * GS_WAVES);
 #define GS_CASE(JJ)                                                                                                    \
-    case JJ: hipLaunchKernelGGL((gs_sweep_kernel<CPLX, JJ, MODE>), grid, block, 0, s, P, m, w, n, g.tpg, coef, are, aim, partial); break;
+    case JJ: hipLaunchKernelGGL((gs_sweep_kernel<CPLX, JJ, MODE, WT>), grid, block, 0, s, P, m, w, n, g.tpg, coef, are, aim, partial, weights); break;
     switch (J) {
         GS_CASE(1)
         GS_CASE(2)
@@ -395,18 +425,27 @@ static void gs_launch_j(int J, const GsGrid& g, hipStream_t s, const BasisPtrs& 
 #undef GS_CASE
 }
 
+// `weights` (a granule table, or nullptr: the unweighted instantiations) only reaches the sweeps that reduce
 template <bool CPLX>
 static void gs_sweep(int mode, const GsGrid& g, hipStream_t s, const BasisPtrs& P, int m, double* w, int64_t n, const double* coef,
-                     double are, double aim, double* partial)
+                     double are, double aim, double* partial, const double* weights = nullptr)
 {
     if (g.groups == 0) return;
     int J = 1;
     while (J * GS_WAVES < m) J *= 2;
+    if (weights) {
+        switch (mode) {
+        case GS_DOT: gs_launch_j<CPLX, GS_DOT, true>(J, g, s, P, m, w, n, coef, are, aim, partial, weights); break;
+        case GS_UPD_DOT: gs_launch_j<CPLX, GS_UPD_DOT, true>(J, g, s, P, m, w, n, coef, are, aim, partial, weights); break;
+        default: gs_launch_j<CPLX, GS_UPD_NORM, true>(J, g, s, P, m, w, n, coef, are, aim, partial, weights); break;
+        }
+        return;
+    }
     switch (mode) {
-    case GS_DOT: gs_launch_j<CPLX, GS_DOT>(J, g, s, P, m, w, n, coef, are, aim, partial); break;
-    case GS_UPD_DOT: gs_launch_j<CPLX, GS_UPD_DOT>(J, g, s, P, m, w, n, coef, are, aim, partial); break;
-    case GS_UPD_NORM: gs_launch_j<CPLX, GS_UPD_NORM>(J, g, s, P, m, w, n, coef, are, aim, partial); break;
-    default: gs_launch_j<CPLX, GS_UPD>(J, g, s, P, m, w, n, coef, are, aim, partial); break;
+    case GS_DOT: gs_launch_j<CPLX, GS_DOT, false>(J, g, s, P, m, w, n, coef, are, aim, partial, nullptr); break;
+    case GS_UPD_DOT: gs_launch_j<CPLX, GS_UPD_DOT, false>(J, g, s, P, m, w, n, coef, are, aim, partial, nullptr); break;
+    case GS_UPD_NORM: gs_launch_j<CPLX, GS_UPD_NORM, false>(J, g, s, P, m, w, n, coef, are, aim, partial, nullptr); break;
+    default: gs_launch_j<CPLX, GS_UPD, false>(J, g, s, P, m, w, n, coef, are, aim, partial, nullptr); break;
     }
 }
 
@@ -428,6 +467,13 @@ static int gs_args(const char* fn, const double* const* basis, int64_t m, const 
     return CYB_OK;
 }
 
+// the granule table of a weighted entry: ceil(n / GS_GRANULE) device doubles
+static int gs_weights(const char* fn, bool weighted, const double* wt, int64_t n)
+{
+    CYB_REQUIRE(!weighted || n == 0 || (wt && (uintptr_t)wt % 8 == 0), "%s: NULL or misaligned weight table", fn);
+    return CYB_OK;
+}
+
 // partial table of one sweep + (for CGS2) the pass-1 and pass-2 coefficients, in workspace slot 0
 static int gs_workspace(cyb_ctx_t ctx, const GsGrid& g, int64_t m, double** partial, double** h1, double** h2)
 {
@@ -442,11 +488,12 @@ static int gs_workspace(cyb_ctx_t ctx, const GsGrid& g, int64_t m, double** part
 
 template <bool CPLX>
 static int gram_schmidt(const char* fn, cyb_ctx_t ctx, const double* const* basis, int64_t m, double* w, int64_t n, int32_t passes,
-                        double* out_dev)
+                        double* out_dev, bool weighted = false, const double* wt = nullptr)
 {
     CYB_REQUIRE(ctx && out_dev, "%s: NULL argument", fn);
     BasisPtrs P;
     CYB_TRY(gs_args(fn, basis, m, w, n, CPLX, &P));
+    CYB_TRY(gs_weights(fn, weighted, wt, n));
     CYB_REQUIRE(passes == 1 || passes == 2, "%s: passes must be 1 or 2, got %d", fn, (int)passes);
     const GsGrid g = gs_grid(n, CPLX);
     double *partial, *h1, *h2;
@@ -457,33 +504,35 @@ static int gram_schmidt(const char* fn, cyb_ctx_t ctx, const double* const* basi
     // pass 1: h1 = V^H w (straight into out_dev for one pass)
     double* hp1 = passes == 1 ? out_dev : h1;
     if (m > 0) {
-        gs_sweep<CPLX>(GS_DOT, g, s, P, mi, w, n, nullptr, 0.0, 0.0, partial);
+        gs_sweep<CPLX>(GS_DOT, g, s, P, mi, w, n, nullptr, 0.0, 0.0, partial, wt);
         hipLaunchKernelGGL(gs_reduce_kernel, dim3((unsigned)m), dim3(NT), 0, s, partial, g.groups, mi, c, 0, hp1, nullptr, nullptr, nullptr);
     }
     const double* last = hp1;
     if (passes == 2 && m > 0) { // w -= V h1, h2 = V^H w; out = h1 + h2
-        gs_sweep<CPLX>(GS_UPD_DOT, g, s, P, mi, w, n, hp1, -1.0, 0.0, partial);
+        gs_sweep<CPLX>(GS_UPD_DOT, g, s, P, mi, w, n, hp1, -1.0, 0.0, partial, wt);
         hipLaunchKernelGGL(gs_reduce_kernel, dim3((unsigned)m), dim3(NT), 0, s, partial, g.groups, mi, c, 0, h2, hp1, out_dev, nullptr);
         last = h2;
     }
     // w -= V h_last, |w|
-    gs_sweep<CPLX>(GS_UPD_NORM, g, s, P, mi, w, n, m > 0 ? last : nullptr, -1.0, 0.0, partial);
+    gs_sweep<CPLX>(GS_UPD_NORM, g, s, P, mi, w, n, m > 0 ? last : nullptr, -1.0, 0.0, partial, wt);
     hipLaunchKernelGGL(gs_reduce_kernel, dim3(1), dim3(NT), 0, s, partial, g.groups, mi, c, mi, nullptr, nullptr, nullptr, norm_out);
     CYB_HIP(hipGetLastError());
     return CYB_OK;
 }
 
 template <bool CPLX>
-static int multi_dot(const char* fn, cyb_ctx_t ctx, const double* const* basis, int64_t m, const double* w, int64_t n, double* h_dev)
+static int multi_dot(const char* fn, cyb_ctx_t ctx, const double* const* basis, int64_t m, const double* w, int64_t n, double* h_dev,
+                     bool weighted = false, const double* wt = nullptr)
 {
     CYB_REQUIRE(ctx && (m == 0 || h_dev), "%s: NULL argument", fn);
     BasisPtrs P;
     CYB_TRY(gs_args(fn, basis, m, w, n, CPLX, &P));
+    CYB_TRY(gs_weights(fn, weighted, wt, n));
     if (m == 0) return CYB_OK;
     const GsGrid g = gs_grid(n, CPLX);
     double *partial, *h1, *h2;
     CYB_TRY(gs_workspace(ctx, g, m, &partial, &h1, &h2));
-    gs_sweep<CPLX>(GS_DOT, g, ctx->stream, P, (int)m, const_cast<double*>(w), n, nullptr, 0.0, 0.0, partial);
+    gs_sweep<CPLX>(GS_DOT, g, ctx->stream, P, (int)m, const_cast<double*>(w), n, nullptr, 0.0, 0.0, partial, wt);
     hipLaunchKernelGGL(gs_reduce_kernel, dim3((unsigned)m), dim3(NT), 0, ctx->stream, partial, g.groups, (int)m, CPLX ? 1 : 0, 0, h_dev,
                        nullptr, nullptr, nullptr);
     CYB_HIP(hipGetLastError());
@@ -526,6 +575,30 @@ int cyb_multi_dot_f64(cyb_ctx_t ctx, const double* const* basis, int64_t m, cons
 int cyb_multi_dot_c128(cyb_ctx_t ctx, const double* const* basis, int64_t m, const double* w, int64_t n, double* h_dev)
 {
     return multi_dot<true>("cyb_multi_dot_c128", ctx, basis, m, w, n, h_dev);
+}
+
+int cyb_multi_dot_weighted_f64(cyb_ctx_t ctx, const double* const* basis, int64_t m, const double* w, int64_t n, const double* weights_dev,
+                               double* h_dev)
+{
+    return multi_dot<false>("cyb_multi_dot_weighted_f64", ctx, basis, m, w, n, h_dev, true, weights_dev);
+}
+
+int cyb_multi_dot_weighted_c128(cyb_ctx_t ctx, const double* const* basis, int64_t m, const double* w, int64_t n, const double* weights_dev,
+                                double* h_dev)
+{
+    return multi_dot<true>("cyb_multi_dot_weighted_c128", ctx, basis, m, w, n, h_dev, true, weights_dev);
+}
+
+int cyb_gram_schmidt_weighted_f64(cyb_ctx_t ctx, const double* const* basis, int64_t m, double* w, int64_t n, int32_t passes,
+                                  const double* weights_dev, double* out_dev)
+{
+    return gram_schmidt<false>("cyb_gram_schmidt_weighted_f64", ctx, basis, m, w, n, passes, out_dev, true, weights_dev);
+}
+
+int cyb_gram_schmidt_weighted_c128(cyb_ctx_t ctx, const double* const* basis, int64_t m, double* w, int64_t n, int32_t passes,
+                                   const double* weights_dev, double* out_dev)
+{
+    return gram_schmidt<true>("cyb_gram_schmidt_weighted_c128", ctx, basis, m, w, n, passes, out_dev, true, weights_dev);
 }
 
 int cyb_multi_axpy_f64(cyb_ctx_t ctx, const double* const* basis, int64_t m, const double* h_dev, double alpha, double* w, int64_t n)

@@ -34,6 +34,10 @@ module mirrors is everything BETWEEN that layer and the block backend:
   ``iter_tree_blocks`` and ``transform_tensor`` mean; the reference's ``_mask_contract`` reshapes a codomain forest to
   ``(m..., -1)`` (:2471), which mixes the tree index into the columns when a forest holds several trees, and is not reproduced.
 * :func:`truncated_svd`: svd, truncation and the mask on U, S and Vh -- three launches after the SVD.
+* :class:`TreeTensor`: data + codomain + domain, the vector the Krylov solvers and the operator wrappers take
+  (``cyten_amd.krylov``, ``cyten_amd.sparse``): the reference's Krylov code calls ``inner`` / ``norm`` /
+  ``linear_combination`` on whatever tensor it is given (src/tensors/krylov_based.cpp), and those need the quantum dimensions
+  of the codomain, which :class:`FusionTreeData` alone does not carry.
 """
 from __future__ import annotations
 
@@ -44,7 +48,8 @@ import numpy as np
 
 __all__ = ['TreeBlock', 'TreeSpace', 'FusionTreeData', 'compose', 'svd', 'qr', 'lq', 'eigh', 'truncate_singular_values',
            'transform_tensor', 'discard_zero_blocks', 'norm', 'inner', 'trace_full', 'mul', 'linear_combination', 'dagger',
-           'almost_equal', 'TreeAxisRecord', 'TreeMask', 'leg_keys', 'scale_axis', 'mask_contract', 'truncated_svd']
+           'almost_equal', 'TreeAxisRecord', 'TreeMask', 'leg_keys', 'scale_axis', 'mask_contract', 'truncated_svd', 'TreeTensor',
+           'same_space']
 
 
 @dataclass(frozen=True)
@@ -137,6 +142,32 @@ class FusionTreeData:
         """index of the block whose domain sector index is j (``block_ind_from_coupled``), or None"""
         hit = np.flatnonzero(self.block_inds[:, 1] == j)
         return int(hit[0]) if len(hit) else None
+
+
+@dataclass
+class TreeTensor:
+    """A fusion-tree tensor as a vector: its blocks and the two spaces that give them a meaning -- the quantum dimensions of
+    ``codomain`` weight :func:`inner` and :func:`norm`.  ``blocks`` / ``block_inds`` forward to ``data``."""
+    data: FusionTreeData
+    codomain: TreeSpace
+    domain: TreeSpace
+
+    @property
+    def blocks(self) -> list:
+        return self.data.blocks
+
+    @property
+    def block_inds(self) -> np.ndarray:
+        return self.data.block_inds
+
+    def like(self, data: FusionTreeData) -> 'TreeTensor':
+        """`data` on the spaces of this tensor"""
+        return TreeTensor(data, self.codomain, self.domain)
+
+
+def same_space(a: TreeSpace, b: TreeSpace) -> bool:
+    """the same coupled sectors with the same block sizes: blocks on `a` can be added to, or contracted with, blocks on `b`"""
+    return a is b or (np.array_equal(a.sectors, b.sectors) and np.array_equal(a.multiplicities, b.multiplicities))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -14,6 +14,9 @@
 * :class:`LanczosEvolution`, :class:`Arnoldi`, :class:`ArnoldiEvolution` -- exp(delta H) psi (the TDVP step) and the
   non-Hermitian eigensolver of the reference (krylov_based.cpp:532-800, 948-1019), on the same flat pools: float64 while the
   operator and the start vector are real, complex128 otherwise.
+* Every solver takes fusion-tree vectors (:class:`cyten_amd.fusion_tree.TreeTensor`) as well: the recurrences are the same
+  code, the vector operations are :class:`_TreeTensorOps` (tensors) or :class:`_FlatTreeOps` (pools whose reductions carry the
+  quantum dimension of the coupled sector); :class:`TreeChainOperator` is an operator to apply to them.
 
 Leg orders used here (signs: + ket-like, - dual):
     theta [vL, p0, p1, vR]
@@ -26,6 +29,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import abelian as ab
+from . import fusion_tree as ft
 
 
 def _is_complex_block(b) -> bool:
@@ -133,6 +137,67 @@ class HEffective:
         return x
 
 
+class TreeChainOperator:
+    """A linear map on fusion-tree vectors given as a chain of contractions and leg moves -- what a two-site H_eff on
+    fusion-tree tensors is made of (``compose`` and ``permute_legs`` -> ``TreePairMapping::transform_tensor`` in the
+    reference).  The symmetry layer stays out: as elsewhere in :mod:`cyten_amd.fusion_tree` its mappings arrive as data.
+
+    `steps`, applied in order to ``X`` on (`codomain`, `domain`):
+
+    * ``('compose_left', A)``: ``X <- A X``, `A` a :class:`fusion_tree.TreeTensor` whose domain is X's codomain;
+    * ``('compose_right', B)``: ``X <- X B``, `B` a TreeTensor whose codomain is X's domain;
+    * ``('transform', new_codomain, new_domain, codomain_idcs, domain_idcs, mapping)``: one ``ft.transform_tensor``.
+
+    ``matvec`` tracks the spaces through the chain; the constructor checks that every step fits the spaces the one before
+    leaves.  ``is_complex``: any operand block or mapping coefficient is complex.  This is host composition of the existing
+    launches (one grouped GEMM per compose, one ``transform_blocks`` per transform); recording and replaying the launch
+    sequence (:mod:`cyten_amd.replay`) is out of scope here."""
+
+    def __init__(self, bb, steps, codomain, domain):
+        self.bb, self.steps, self.codomain, self.domain = bb, [tuple(s) for s in steps], codomain, domain
+        cplx = False
+        cod, dom = codomain, domain
+        for n, st in enumerate(self.steps):
+            kind = st[0]
+            if kind in ('compose_left', 'compose_right'):
+                if len(st) != 2 or not isinstance(st[1], ft.TreeTensor):
+                    raise ValueError(f'step {n}: ({kind!r}, TreeTensor) expected')
+                op = st[1]
+                if kind == 'compose_left':
+                    if not ft.same_space(op.domain, cod):
+                        raise ValueError(f'step {n}: the domain of A is not the codomain of the vector')
+                    cod = op.codomain
+                else:
+                    if not ft.same_space(op.codomain, dom):
+                        raise ValueError(f'step {n}: the codomain of B is not the domain of the vector')
+                    dom = op.domain
+                cplx = cplx or any(_is_complex_block(b) for b in op.blocks)
+            elif kind == 'transform':
+                if len(st) != 6:
+                    raise ValueError(f'step {n}: (\'transform\', new_codomain, new_domain, codomain_idcs, domain_idcs, mapping) expected')
+                cod, dom = st[1], st[2]
+                cplx = cplx or any(isinstance(c, (complex, np.complexfloating)) and complex(c).imag != 0.0
+                                   for targets in st[5].values() for c in targets.values())
+            else:
+                raise ValueError(f'step {n}: unknown kind {kind!r}')
+        self.out_codomain, self.out_domain = cod, dom
+        self.is_complex = bool(cplx)
+
+    def matvec(self, x):
+        bb = self.bb
+        data, cod, dom = x.data, x.codomain, x.domain
+        for st in self.steps:
+            if st[0] == 'compose_left':
+                data, cod = ft.compose(bb, st[1].data, data), st[1].codomain
+            elif st[0] == 'compose_right':
+                data, dom = ft.compose(bb, data, st[1].data), st[1].domain
+            else:
+                _, new_cod, new_dom, codomain_idcs, domain_idcs, mapping = st
+                data = ft.transform_tensor(bb, data, cod, dom, new_cod, new_dom, codomain_idcs, domain_idcs, mapping)
+                cod, dom = new_cod, new_dom
+        return ft.TreeTensor(data, cod, dom)
+
+
 class _NotFlat(Exception):
     """The vector left the block structure the flat representation was built for (caught by the solvers' run)."""
 
@@ -185,6 +250,41 @@ class _TensorOps:
         return _mgs(self, basis, w)
 
 
+class _TreeTensorOps(_TensorOps):
+    """:class:`_TensorOps` on fusion-tree vectors (:class:`fusion_tree.TreeTensor`): the inner product and the norm carry the
+    quantum dimension of the coupled sector (``FusionTreeBackend::inner`` / ``::norm``); needs nothing of the backend beyond
+    what :mod:`cyten_amd.fusion_tree` calls, so it runs on a numpy stand-in."""
+
+    def norm(self, w):
+        return ft.norm(self.bb, w.data, w.codomain)
+
+    def inner(self, v, w):
+        return ft.inner(self.bb, v.data, w.data, v.codomain, do_dagger=True)
+
+    def scale(self, a, w):
+        return w.like(ft.mul(self.bb, a, w.data))
+
+    def lincomb(self, a, w, b, v):
+        return w.like(ft.linear_combination(self.bb, a, w.data, b, v.data))
+
+
+def tree_pool_layout(codomain, domain, granule=256):
+    """The pool of a fusion-tree vector on (codomain, domain): one block per pair of ``ft.common_sectors`` -- every block an
+    operator can create -- of shape ``(codomain.block_size(i), domain.block_size(j))``, each starting at a multiple of
+    `granule` elements.  Returns (block_inds, shapes, offsets, total, weights): `total` is a multiple of `granule` and
+    ``weights[g]`` = ``codomain.qdims[i]`` for every granule g of block (i, j) -- the table the weighted pool reductions read
+    (one entry per granule, so a tile of the kernel never sees two weights)."""
+    pairs = ft.common_sectors(codomain, domain)
+    shapes = [(int(codomain.block_size(i)), int(domain.block_size(j))) for i, j in pairs]
+    offs, weights, tot = [], [], 0
+    for (i, _), (r, c) in zip(pairs, shapes):
+        g = (r * c + granule - 1) // granule
+        offs.append(tot)
+        tot += g * granule
+        weights += [float(codomain.qdims[i])] * g
+    return (np.array(pairs, dtype=np.int64).reshape(len(pairs), 2), shapes, offs, tot, np.array(weights, dtype=np.float64))
+
+
 class _FlatOps:
     """The same operations on Krylov vectors kept as ONE contiguous pool each: the block offsets of
     the structure are computed once, every ``scale / axpy / inner / norm`` of the recurrences is a single-descriptor
@@ -202,11 +302,8 @@ class _FlatOps:
         """`template`: a tensor on the legs of the vectors; `block_inds` (default: the template's): the block table of the
         pool -- a superset of the template's when the operator creates blocks the start vector does not have.
         `cplx`: the Krylov vectors are complex128 pools."""
-        from .block_backend import HipBlock, _c_strides
-        from . import _lib
-        import ctypes
-        self.bb, self.H, self.t, self.cplx = bb, H, template, bool(cplx)
-        self._HipBlock, self._lib, self._C = HipBlock, _lib, ctypes
+        from .block_backend import _c_strides
+        self._bind(bb, H, template, cplx)
         self.block_inds = template.block_inds if block_inds is None else block_inds
         self.shapes = [template.block_shape(r) for r in self.block_inds]
         self.strides = [_c_strides(sh) for sh in self.shapes]
@@ -224,6 +321,13 @@ class _FlatOps:
         # the pool is laid out over every charge-allowed block, but the operator only ever sees -- and the result only carries --
         # this support, as the reference's tensors do (krylov_based.cpp works on tensors whose block tables grow the same way)
         self.support = set()
+
+    def _bind(self, bb, H, template, cplx):
+        from .block_backend import HipBlock
+        from . import _lib
+        import ctypes
+        self.bb, self.H, self.t, self.cplx = bb, H, template, bool(cplx)
+        self._HipBlock, self._lib, self._C = HipBlock, _lib, ctypes
 
     @staticmethod
     def usable(bb, t) -> bool:
@@ -476,6 +580,92 @@ class _FlatOps:
         return float(np.sqrt(bb.ctx.d2h(res, 1, np.float64)[0]))
 
 
+class _FlatTreeOps(_FlatOps):
+    """:class:`_FlatOps` for fusion-tree vectors.  The pool holds the blocks themselves -- ``leave`` stays a list of views and
+    the operator reads and writes plain blocks -- so the inner product sum_c d_c <X_c, Y_c> is not the plain one over the flat
+    range: the reductions (``inner``, ``norm``, the fused Gram-Schmidt step, the multi-dot) are the weighted entries of
+    krylov_vec.hip, which read the quantum dimension of a granule of 256 elements from a table built ONCE per structure and
+    kept on the device (:func:`tree_pool_layout`).  Everything linear (``scale``, ``lincomb``, ``combine``, the multi-axpy) is
+    inherited: it does not see the weights."""
+
+    GRANULE = 256
+
+    def __init__(self, bb, H, template, cplx=False):
+        from .block_backend import _c_strides
+        self._bind(bb, H, template, cplx)
+        self.block_inds, self.shapes, self.offs, self.total, self.weights = tree_pool_layout(template.codomain, template.domain,
+                                                                                             self.GRANULE)
+        self.strides = [_c_strides(sh) for sh in self.shapes]
+        self.key = self.block_inds.tobytes()
+        self.index = None
+        self.support = set()
+        self._wdev = bb.ctx.empty(max(len(self.weights), 1))
+        if len(self.weights):
+            bb.ctx.h2d(self._wdev, self.weights)
+
+    @staticmethod
+    def usable(bb, t) -> bool:
+        return _FlatOps.usable(bb, t) and tree_pool_layout(t.codomain, t.domain)[3] > 0
+
+    def leave(self, buf):
+        idx = None if len(self.support) == len(self.offs) else sorted(self.support)
+        rows = self.block_inds if idx is None else self.block_inds[idx]
+        return self.t.like(ft.FusionTreeData(rows.copy(), self._views(buf, idx)))
+
+    def _wptr(self):
+        return self._C.c_void_p(self._wdev.data_ptr())
+
+    def _gs(self, basis, w, passes, out, off=0):
+        bb = self.bb
+        fn = bb.lib.cyb_gram_schmidt_weighted_c128 if w.is_complex() else bb.lib.cyb_gram_schmidt_weighted_f64
+        bb.ctx.sync_stream()
+        self._lib.check(fn(bb.ctx.handle, self._ptrs(basis), len(basis), self._C.c_void_p(w.data_ptr()), self.total, int(passes),
+                           self._wptr(), self._C.c_void_p(out.data_ptr() + 8 * off)))
+
+    def _multi(self, kind, basis, w, h, off=0, alpha=1.0):
+        if kind != 'dot':
+            return super()._multi(kind, basis, w, h, off, alpha)
+        bb, C = self.bb, self._C
+        fn = bb.lib.cyb_multi_dot_weighted_c128 if w.is_complex() else bb.lib.cyb_multi_dot_weighted_f64
+        bb.ctx.sync_stream()
+        self._lib.check(fn(bb.ctx.handle, self._ptrs(basis), len(basis), C.c_void_p(w.data_ptr()), self.total, self._wptr(),
+                           C.c_void_p(h.data_ptr() + 8 * off)))
+
+    def inner(self, v, w):
+        """<v, w> = sum_c d_c sum conj(v_c) w_c: the weighted multi-dot with the basis [v]"""
+        cplx = v.is_complex() or w.is_complex()
+        if cplx:
+            v = v if v.is_complex() else self._promote(v)
+            w = w if w.is_complex() else self._promote(w)
+        k = 2 if cplx else 1
+        res = self.bb.ctx.empty(k)
+        self._multi('dot', [v], w, res)
+        r = self.bb.ctx.d2h(res, k, np.float64)
+        return complex(float(r[0]), float(r[1])) if cplx else float(r[0])
+
+    def norm(self, w):
+        return float(np.sqrt(max(np.real(self.inner(w, w)), 0.0)))
+
+
+def _is_tree(t) -> bool:
+    return isinstance(t, ft.TreeTensor)
+
+
+def _vector_ops(bb, H, template, mode):
+    """The vector operations of a run on vectors like `template`: pools (`mode` False / True: float64 / complex128) or
+    tensors (`mode` None), abelian or fusion-tree by the type of the template."""
+    if _is_tree(template):
+        return _FlatTreeOps(bb, H, template, mode) if mode is not None else _TreeTensorOps(bb, H)
+    if mode is None:
+        return _TensorOps(bb, H)
+    # pool structure: every block the charge rule allows on these legs (what an operator can create at most)
+    return _FlatOps(bb, H, template, ab.AbelianTensor.allowed_block_inds(template.symmetry, template.legs), mode)
+
+
+def _flat_usable(bb, t) -> bool:
+    return _FlatTreeOps.usable(bb, t) if _is_tree(t) else _FlatOps.usable(bb, t)
+
+
 def _mgs(V, basis, w):
     h = []
     for v in basis:
@@ -544,16 +734,14 @@ class LanczosGroundState:
         restarts the run on them); a vector that leaves the block structure of psi0 (an operator that creates blocks psi0
         does not have) restarts it on tensors."""
         psi_in = self.psi0
-        flat = bool(self.flat) and _FlatOps.usable(self.bb, psi_in)
-        # pool structure: every block the charge rule allows on these legs (what an operator can create at most)
-        allowed = ab.AbelianTensor.allowed_block_inds(psi_in.symmetry, psi_in.legs) if flat else None
+        flat = bool(self.flat) and _flat_usable(self.bb, psi_in)
         cplx = any(_is_complex_block(b) for b in psi_in.blocks) or bool(getattr(self.H, 'is_complex', False))
         modes = ([cplx] if cplx else [False, True]) if flat else []
         modes.append(None)   # tensors
         i = 0
         while True:
             mode = modes[i]
-            self.V = _FlatOps(self.bb, self.H, psi_in, allowed, mode) if mode is not None else _TensorOps(self.bb, self.H)
+            self.V = _vector_ops(self.bb, self.H, psi_in, mode)
             self._reset_krylov_state()
             try:
                 self.psi0 = self.V.enter(psi_in)
@@ -859,7 +1047,8 @@ class ArnoldiEvolution(Arnoldi):
         super().__init__(bb, H, psi0, options)
         self._result_norm = 1.0
         self.delta = None
-        self._psi0_norm = ab.norm(bb, psi0)     # (Arnoldi._build_krylov does not record it)
+        # (Arnoldi._build_krylov does not record it)
+        self._psi0_norm = ft.norm(bb, psi0.data, psi0.codomain) if _is_tree(psi0) else ab.norm(bb, psi0)
 
     def run(self, delta, normalize=None):
         if self.N_cache < self.N_max:
@@ -904,6 +1093,8 @@ class ArnoldiEvolution(Arnoldi):
 
 
 def _same_legs(a, b) -> bool:
+    if _is_tree(a) or _is_tree(b):
+        return (_is_tree(a) and _is_tree(b) and ft.same_space(a.codomain, b.codomain) and ft.same_space(a.domain, b.domain))
     return len(a.legs) == len(b.legs) and all(
         x.sign == y.sign and np.array_equal(x.sectors, y.sectors) and np.array_equal(x.mults, y.mults)
         for x, y in zip(a.legs, b.legs))
@@ -943,7 +1134,7 @@ class GMRES:
         self.restart = int(o.get('restart', 10))
         self.res = float(o.get('res', 1e-8))
         self.flat = o.get('flat', True)
-        flat = bool(self.flat) and _FlatOps.usable(bb, b)
+        flat = bool(self.flat) and _flat_usable(bb, b)
         cplx = (any(_is_complex_block(t) for v in (x, b) for t in v.blocks) or bool(getattr(A, 'is_complex', False)))
         self._modes = ([cplx] if cplx else [False, True]) if flat else []
         self._modes.append(None)   # tensors
@@ -964,8 +1155,7 @@ class GMRES:
 
     def _start(self, mode):
         bb = self.bb
-        self.V = (_FlatOps(bb, self.A, self.b_in, ab.AbelianTensor.allowed_block_inds(self.b_in.symmetry, self.b_in.legs), mode)
-                  if mode is not None else _TensorOps(bb, self.A))
+        self.V = _vector_ops(bb, self.A, self.b_in, mode)
         V = self.V
         self.x = V.enter(self.x_in)
         self.b = V.enter(self.b_in)

@@ -8,7 +8,8 @@
   is removed from the current vector in turn.  For orthonormal ortho vectors that is the projector above; for others it is
   what the reference computes (its docstring, py_sparse.cpp:322-324, promises a Gram-Schmidt the code does not do).
 
-Every wrapper acts on block-sparse tensors through ``.matvec(tensor)`` with the block backend of the wrapped operator (or the
+Every wrapper acts on block-sparse tensors -- abelian ones or fusion-tree ones (``fusion_tree.TreeTensor``, whose inner product
+carries the quantum dimensions) -- through ``.matvec(tensor)`` with the block backend of the wrapped operator (or the
 ``bb`` given), exposes ``is_complex`` as the solvers expect and has ``adjoint()`` where the wrapped operators have one.  On
 flat Krylov pools the solvers do not call these ``matvec``s: ``krylov._FlatOps`` recognises the wrappers and does their
 vector work on the pools.
@@ -18,6 +19,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import abelian as ab
+from . import fusion_tree as ft
 
 
 def _is_complex_op(op) -> bool:
@@ -26,6 +28,29 @@ def _is_complex_op(op) -> bool:
 
 def _is_complex_tensor(t) -> bool:
     return any(np.iscomplexobj(b) if isinstance(b, np.ndarray) else bool(b.is_complex) for b in t.blocks)
+
+
+def _inner(bb, a, b):
+    """<a|b> of two vectors of the kind the solvers take: abelian tensors, or fusion-tree tensors (weighted by the quantum
+    dimensions of the codomain)"""
+    if isinstance(a, ft.TreeTensor):
+        return ft.inner(bb, a.data, b.data, a.codomain, do_dagger=True)
+    return ab.inner(bb, a, b)
+
+
+def _lincomb(bb, a, v, b, w):
+    if isinstance(v, ft.TreeTensor):
+        return v.like(ft.linear_combination(bb, a, v.data, b, w.data))
+    return ab.linear_combination(bb, a, v, b, w)
+
+
+def _compatible(a, b) -> bool:
+    if isinstance(a, ft.TreeTensor) or isinstance(b, ft.TreeTensor):
+        return (isinstance(a, ft.TreeTensor) and isinstance(b, ft.TreeTensor) and ft.same_space(a.codomain, b.codomain)
+                and ft.same_space(a.domain, b.domain))
+    return len(a.legs) == len(b.legs) and all(
+        x.sign == y.sign and np.array_equal(x.sectors, y.sectors) and np.array_equal(x.mults, y.mults)
+        for x, y in zip(a.legs, b.legs))
 
 
 def _plain(c):
@@ -72,7 +97,7 @@ class SumLinearOperator(LinearOperatorWrapper):
     def matvec(self, vec):
         res = self.original_operator.matvec(vec)
         for op in self.more_operators:
-            res = ab.linear_combination(self.bb, 1.0, op.matvec(vec), 1.0, res)
+            res = _lincomb(self.bb, 1.0, op.matvec(vec), 1.0, res)
         return res
 
     def adjoint(self):
@@ -92,7 +117,7 @@ class ShiftedLinearOperator(LinearOperatorWrapper):
 
     def matvec(self, vec):
         res = self.original_operator.matvec(vec)
-        return ab.linear_combination(self.bb, _plain(self.shift), vec, 1.0, res)
+        return _lincomb(self.bb, _plain(self.shift), vec, 1.0, res)
 
     def adjoint(self):
         return ShiftedLinearOperator(self.original_operator.adjoint(), self.shift.conjugate(), self.bb)
@@ -109,9 +134,7 @@ class ProjectedLinearOperator(LinearOperatorWrapper):
         self.project_operator = bool(project_operator)
         self.penalty = None if penalty is None else complex(penalty)
         for v in self.ortho_vecs[1:]:
-            if len(v.legs) != len(self.ortho_vecs[0].legs) or not all(
-                    a.sign == b.sign and np.array_equal(a.sectors, b.sectors) and np.array_equal(a.mults, b.mults)
-                    for a, b in zip(v.legs, self.ortho_vecs[0].legs)):
+            if not _compatible(v, self.ortho_vecs[0]):
                 raise ValueError('All ortho_vecs must be mutually compatible')
 
     @property
@@ -129,19 +152,19 @@ class ProjectedLinearOperator(LinearOperatorWrapper):
         coeffs = []
         if self.project_operator:
             for o in self.ortho_vecs:
-                c = ab.inner(bb, o, res)
+                c = _inner(bb, o, res)
                 coeffs.append(c)
-                res = ab.linear_combination(bb, 1.0, res, _plain(-c), o)
+                res = _lincomb(bb, 1.0, res, _plain(-c), o)
         else:
-            coeffs = [ab.inner(bb, o, res) for o in self.ortho_vecs]
+            coeffs = [_inner(bb, o, res) for o in self.ortho_vecs]
         res = self.original_operator.matvec(res)
         if self.project_operator:
             for o in self.ortho_vecs:
-                c = ab.inner(bb, o, res)
-                res = ab.linear_combination(bb, 1.0, res, _plain(-c), o)
+                c = _inner(bb, o, res)
+                res = _lincomb(bb, 1.0, res, _plain(-c), o)
         if self.penalty is not None:
             for o, c in zip(self.ortho_vecs, coeffs):
-                res = ab.linear_combination(bb, 1.0, res, _plain(self.penalty * c), o)
+                res = _lincomb(bb, 1.0, res, _plain(self.penalty * c), o)
         return res
 
     def adjoint(self):

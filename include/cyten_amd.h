@@ -385,6 +385,20 @@ int cyb_multi_axpy_c128(cyb_ctx_t ctx, const double* const* basis, int64_t m, co
  * followed by |w| after the last update (one double). */
 int cyb_gram_schmidt_f64(cyb_ctx_t ctx, const double* const* basis, int64_t m, double* w, int64_t n, int32_t passes, double* out_dev);
 int cyb_gram_schmidt_c128(cyb_ctx_t ctx, const double* const* basis, int64_t m, double* w, int64_t n, int32_t passes, double* out_dev);
+/* The same reductions with a weight per granule of 256 elements (doubles in the f64 form, complex numbers in the c128 form):
+ * h_j = sum_i d(i) conj(V_j[i]) w[i] and |w| = sqrt(sum_i d(i) |w[i]|^2) with d(i) = weights_dev[i / 256]; the update
+ * w <- w - sum_j h_j V_j is unweighted.  weights_dev: ceil(n / 256) device doubles -- the quantum dimension of the coupled
+ * sector a fusion-tree pool keeps in that granule (FusionTreeBackend::inner / ::norm, fusion_tree_backend.cpp:1238-1296).
+ * Same work split, same summation order and same error rules as the unweighted entries; a NULL table with n > 0 is
+ * CYB_ERR_INVALID; m == 0 in the Gram-Schmidt step still writes the weighted norm. */
+int cyb_multi_dot_weighted_f64(cyb_ctx_t ctx, const double* const* basis, int64_t m, const double* w, int64_t n, const double* weights_dev,
+                               double* h_dev);
+int cyb_multi_dot_weighted_c128(cyb_ctx_t ctx, const double* const* basis, int64_t m, const double* w, int64_t n, const double* weights_dev,
+                                double* h_dev);
+int cyb_gram_schmidt_weighted_f64(cyb_ctx_t ctx, const double* const* basis, int64_t m, double* w, int64_t n, int32_t passes,
+                                  const double* weights_dev, double* out_dev);
+int cyb_gram_schmidt_weighted_c128(cyb_ctx_t ctx, const double* const* basis, int64_t m, double* w, int64_t n, int32_t passes,
+                                   const double* weights_dev, double* out_dev);
 
 /* ---- host-side sector matching of a contraction (no device work) ------------------------------------------------
  * The int64 bookkeeping of abelian_compose_worker (src/backends/abelian.cpp:1239-1469) in C++, as in the reference:
