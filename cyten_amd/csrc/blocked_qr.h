@@ -58,19 +58,29 @@ struct BqrTarget {
 };
 // C <- Q C for every target (asynchronous). At most one target per matrix per call (the targets
 // share the matrix' scratch), kc <= the kc the matrix was carved for.
-// Two routes, chosen per target from its shape alone (bqr_apply_wide): 32-column strips, panel by panel, or groups of
-// CYB_QR_APPLY_WIDTH reflector columns through the grouped GEMM (merged T factors, two GEMM launches per group).
+// Two routes: 32-column strips, panel by panel, or groups of CYB_QR_APPLY_WIDTH reflector columns through the grouped GEMM
+// (merged T factors, two GEMM launches per group).  A target qualifies for the wide route by its shape (wide_target); the
+// qualifying targets of ONE application take it only if their columns sum to kWideMinCols, otherwise the whole application
+// stays on strips (split_routes).  CYB_QR_TRACE_ROUTE: one line on stderr per application with the outcome.
 int bqr_apply_q(cyb_ctx_t ctx, const std::vector<BqrMat>& mats, const std::vector<BqrTarget>& targets);
+// Two applications that do not depend on each other in one call: targets[0 : n_first] and targets[n_first :] are each
+// routed exactly as a call of their own would route them (the shape rule sums the columns of ONE application), the strip
+// targets of each run as that call would run them, and the wide targets of both share their launches (one prelude,
+// every group launch carries both chains).  The rule above holds for the whole list: one target per matrix.
+int bqr_apply_q_pair(cyb_ctx_t ctx, const std::vector<BqrMat>& mats, const std::vector<BqrTarget>& targets, size_t n_first);
 
 // Batched tile transpose  out[r*ldo + c] = in[c*ldi + r]  for r < R, c < C  (row-major <-> col-major).
 // upper != 0: entries with r > c or r >= rlim are written as 0 (extraction of R).
 // plain != 0: no transpose, out[r*ldo + c] = in[r*ldi + c] (2-D copy with different leading dimensions).
+// idx != null: a permutation on the READ side, of the strided index of `in` -- out[r*ldo + c] = in[idx[c]*ldi + r], or
+// with plain out[r*ldo + c] = in[idx[r]*ldi + c]: the reads stay contiguous runs and the writes coalesced.
 struct XposeDesc {
     const double* in;
     double* out;
     int64_t ldi, ldo;
     int32_t R, C, upper, rlim;
     int32_t plain, pad;
+    const int32_t* idx = nullptr;
 };
 int xpose_batched(cyb_ctx_t ctx, const std::vector<XposeDesc>& descs);
 // C (col-major m x kc, ld) = first kc columns of the identity

@@ -1362,6 +1362,7 @@ inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
 __global__ void __launch_bounds__(256) xpose_kernel(const XposeDesc* __restrict__ descs)
 {
     __shared__ double tile[32][33];
+    __shared__ int cidx[32]; // source columns of a tile (XposeDesc::idx): one load per column, not one per element
     const XposeDesc d = descs[blockIdx.y];
     gcp in = (gcp)d.in;
     gp out = (gp)d.out;
@@ -1370,7 +1371,7 @@ __global__ void __launch_bounds__(256) xpose_kernel(const XposeDesc* __restrict_
         const int64_t tot = (int64_t)d.R * d.C;
         for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < tot; e += (int64_t)gridDim.x * 256) {
             const int64_t r = e / d.C, c = e % d.C;
-            out[r * d.ldo + c] = in[r * d.ldi + c];
+            out[r * d.ldo + c] = in[(d.idx ? (int64_t)d.idx[r] : r) * d.ldi + c];
         }
         return;
     }
@@ -1378,10 +1379,14 @@ __global__ void __launch_bounds__(256) xpose_kernel(const XposeDesc* __restrict_
     for (int t = blockIdx.x; t < tr * tc; t += gridDim.x) {
         const int r0 = (t / tc) * 32, c0 = (t % tc) * 32;
         __syncthreads();
+        if (d.idx) { // (uniform over the workgroup)
+            if (threadIdx.x < 32) cidx[threadIdx.x] = c0 + (int)threadIdx.x < d.C ? d.idx[c0 + threadIdx.x] : 0;
+            __syncthreads();
+        }
 #pragma unroll
         for (int q = 0; q < 4; ++q) { // read in[c*ldi + r]: r contiguous
             const int c = c0 + ty + 8 * q, r = r0 + tx;
-            tile[ty + 8 * q][tx] = (c < d.C && r < d.R) ? in[(int64_t)c * d.ldi + r] : 0.0;
+            tile[ty + 8 * q][tx] = (c < d.C && r < d.R) ? in[(int64_t)(d.idx ? cidx[ty + 8 * q] : c) * d.ldi + r] : 0.0;
         }
         __syncthreads();
 #pragma unroll
@@ -2291,18 +2296,47 @@ static int apply_q_wide(cyb_ctx_t ctx, const std::vector<BqrMat>& mats, const st
     return CYB_OK;
 }
 
+// the route of every target of ONE application (targets[begin : end]): see wide_target
+static void split_routes(const std::vector<BqrMat>& mats, const std::vector<BqrTarget>& targets, size_t begin, size_t end,
+                         std::vector<BqrTarget>& narrow, std::vector<BqrTarget>& wide)
+{
+    const size_t w0 = wide.size();
+    int64_t cols = 0;
+    for (size_t i = begin; i < end; ++i) {
+        const BqrTarget& t = targets[i];
+        if (wide_target(mats[(size_t)t.mat], t)) {
+            wide.push_back(t);
+            cols += t.kc;
+        } else narrow.push_back(t);
+    }
+    if (wide_mode() < 0 && cols < kWideMinCols) { // (see wide_target)
+        wide.resize(w0);
+        narrow.assign(targets.begin() + (std::ptrdiff_t)begin, targets.begin() + (std::ptrdiff_t)end);
+    }
+    static const bool trace = getenv("CYB_QR_TRACE_ROUTE") != nullptr; // (test hook: the route every application took)
+    if (trace)
+        fprintf(stderr, "[cyb] apply_q: %zu targets, %zu wide (%lld columns qualify), %zu on strips\n", end - begin, wide.size() - w0,
+                (long long)cols, narrow.size());
+}
+
 int bqr_apply_q(cyb_ctx_t ctx, const std::vector<BqrMat>& mats, const std::vector<BqrTarget>& targets)
 {
     // the two routes work on disjoint targets (and on the scratch of disjoint matrices)
     std::vector<BqrTarget> narrow, wide;
-    for (const auto& t : targets) (wide_target(mats[(size_t)t.mat], t) ? wide : narrow).push_back(t);
-    int64_t cols = 0;
-    for (const auto& t : wide) cols += t.kc;
-    if (wide_mode() < 0 && cols < kWideMinCols) { // (see wide_target)
-        narrow = targets;
-        wide.clear();
-    }
+    split_routes(mats, targets, 0, targets.size(), narrow, wide);
     if (!narrow.empty()) CYB_TRY(apply_q_strips(ctx, mats, narrow));
+    if (!wide.empty()) CYB_TRY(apply_q_wide(ctx, mats, wide));
+    return CYB_OK;
+}
+
+int bqr_apply_q_pair(cyb_ctx_t ctx, const std::vector<BqrMat>& mats, const std::vector<BqrTarget>& targets, size_t n_first)
+{
+    n_first = std::min(n_first, targets.size());
+    std::vector<BqrTarget> narrow_a, narrow_b, wide;
+    split_routes(mats, targets, 0, n_first, narrow_a, wide);
+    split_routes(mats, targets, n_first, targets.size(), narrow_b, wide);
+    if (!narrow_a.empty()) CYB_TRY(apply_q_strips(ctx, mats, narrow_a));
+    if (!narrow_b.empty()) CYB_TRY(apply_q_strips(ctx, mats, narrow_b));
     if (!wide.empty()) CYB_TRY(apply_q_wide(ctx, mats, wide));
     return CYB_OK;
 }

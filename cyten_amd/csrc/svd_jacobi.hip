@@ -132,6 +132,7 @@ struct PostDesc {
     // lq_unpack_kernel -- and replaces the norm of the row that kernel built from it (equal up to rounding, but dependent on
     // how J' was obtained: with this S is bit-identical with the rotations accumulated or recovered)
     const double* sig_lq = nullptr;
+    int32_t* inv = nullptr; // nv : inverse of rank (inv[rank[j]] = j), or null; pairs of an embedded complex block stay adjacent
 };
 
 // sig[j] = || W[j,:] ||, one wave per row.  grid.y = matrix
@@ -192,6 +193,7 @@ __global__ void __launch_bounds__(256) rank_kernel(const PostDesc* __restrict__ 
         }
         if (mine) {
             d.rank[j] = r;
+            if (d.inv) d.inv[r] = j;
             d.S[r] = (d.mode == 0) ? sj : sj - shift;
         }
     }
@@ -603,22 +605,37 @@ __global__ void __launch_bounds__(256) scatter_rows_kernel(const RowsDesc* __res
 }
 
 struct JcqDesc {
-    const double* J;
-    const int32_t* rank;
-    double* Cq; // col-major L x k
-    int64_t L;
-    int32_t kp, k;
+    const double* src;  // J (k x k, row stride lds), or the compact Jc (r0 x r0) of a block that iterated on r0 of its rows
+    const int32_t* idx; // compact: full-size row of compact row g (k entries: the r0 iterated rows, then the deflated ones); else null
+    double* Cq;         // col-major L x k
+    int64_t L, lds;
+    int64_t pos_off;    // compact: pos[pos_off + i] = compact row of full-size row i, or -1 for a deflated row
+    int32_t k, r0;
 };
-// Cq[:, rank[j]] = [ J[j, 0:k] ; 0 ]
-__global__ void __launch_bounds__(256) j_to_cq_kernel(const JcqDesc* __restrict__ descs)
+// Cq[:, j] = [ J[j, 0:k] ; 0 ], every one of the L rows written (the application of Q1 overwrites Cq in place, and a second
+// pass of the iteration rebuilds it).  The column order is the order of the rows of J: the descending order of S is imposed
+// where the factor is written out.  A compact block never scatters Jc into the full-size J: J[idx[g]][idx[h]] = Jc[g][h]
+// and the identity on the deflated rows are read off here.
+__global__ void __launch_bounds__(256) j_to_cq_kernel(const JcqDesc* __restrict__ descs, const int32_t* __restrict__ pos_all)
 {
     const JcqDesc d = descs[blockIdx.y];
-    gcp J = (gcp)d.J;
+    gcp src = (gcp)d.src;
     gp Cq = (gp)d.Cq;
+    const int32_t* pos = pos_all + d.pos_off;
     const int lane = threadIdx.x & 63;
-    for (int j = blockIdx.x * 4 + (threadIdx.x >> 6); j < d.k; j += gridDim.x * 4) {
-        const int r = d.rank[j];
-        for (int i = lane; i < d.k; i += 64) Cq[(int64_t)r * d.L + i] = J[(int64_t)j * d.kp + i];
+    for (int g = blockIdx.x * 4 + (threadIdx.x >> 6); g < d.k; g += gridDim.x * 4) {
+        const int j = d.idx ? d.idx[g] : g;
+        for (int64_t i = lane; i < d.L; i += 64) {
+            double v = 0.0;
+            if (i < d.k) {
+                if (!d.idx) v = src[(int64_t)g * d.lds + i];
+                else if (g < d.r0) {
+                    const int h = pos[i];
+                    if (h >= 0) v = src[(int64_t)g * d.lds + h];
+                } else v = (i == j) ? 1.0 : 0.0;
+            }
+            Cq[(int64_t)j * d.L + i] = v;
+        }
     }
 }
 
@@ -648,19 +665,6 @@ __global__ void __launch_bounds__(256) row_move_kernel(const RowMoveDesc* __rest
         }
     }
 }
-// J[idx[g]][idx[h]] = Jc[g][h]   (g, h < cnt)
-__global__ void __launch_bounds__(256) j_scatter_kernel(const RowMoveDesc* __restrict__ descs)
-{
-    const RowMoveDesc d = descs[blockIdx.y];
-    gcp src = (gcp)d.src;
-    gp dst = (gp)d.dst;
-    const int lane = threadIdx.x & 63;
-    for (int g = blockIdx.x * 4 + (threadIdx.x >> 6); g < d.cnt; g += gridDim.x * 4) {
-        const int j = d.idx[g];
-        for (int h = lane; h < d.cnt; h += 64) dst[(int64_t)j * d.ldd + d.idx[h]] = src[(int64_t)g * d.lds + h];
-    }
-}
-
 // ---- embedded complex rows: rows 2a = [x, -y] and 2a+1 = [y, x] (interleaved) of the iteration matrix are made EXACT
 //      partners before the first sweep (both copies averaged).  The QR steps leave them partners up to eps ||A|| -- for the
 //      small rows of a graded spectrum that is a large RELATIVE defect (1e-4 at sigma = 1e-12 sigma_max), the structured
@@ -848,15 +852,12 @@ __global__ void __launch_bounds__(256) lq_unpack_kernel(const LqDesc* __restrict
     }
 }
 
-static int launch_row_moves(cyb_ctx_t ctx, const std::vector<RowMoveDesc>& v, bool jscatter = false)
+static int launch_row_moves(cyb_ctx_t ctx, const std::vector<RowMoveDesc>& v)
 {
     if (v.empty()) return CYB_OK;
     void* d = nullptr;
     CYB_TRY(ctx->upload(v.data(), sizeof(RowMoveDesc) * v.size(), &d));
-    if (jscatter)
-        hipLaunchKernelGGL(j_scatter_kernel, dim3(64, (unsigned)v.size()), dim3(256), 0, ctx->stream, static_cast<const RowMoveDesc*>(d));
-    else
-        hipLaunchKernelGGL(row_move_kernel, dim3(helper_grid_x(v.size()), (unsigned)v.size()), dim3(256), 0, ctx->stream, static_cast<const RowMoveDesc*>(d));
+    hipLaunchKernelGGL(row_move_kernel, dim3(helper_grid_x(v.size()), (unsigned)v.size()), dim3(256), 0, ctx->stream, static_cast<const RowMoveDesc*>(d));
     CYB_HIP(hipGetLastError());
     return CYB_OK;
 }
@@ -875,7 +876,7 @@ static int run_svd_qr(cyb_ctx_t ctx, int64_t nmat, const cyb_svd_desc* sd, int32
     struct Lay {
         int m, n, k, L, kp;
         bool tall;
-        size_t Ac, aux, W, J, sig, rank, thr, nnull, Cq, Fc, aux2, Cn, idx, Wc, Jc;
+        size_t Ac, aux, W, J, sig, rank, inv, thr, nnull, Cq, Fc, aux2, Cn, idx, Wc, Jc;
         size_t bad, Wq, aux3, Cq2, sig2; // second (LQ) preconditioning step
         size_t stop;                     // early stop of the first QR: squared norms of the strips of one step
         size_t ctl;                      // ... and its two control words, behind the flags: they ride in the same D2H copy as the row norms
@@ -933,6 +934,7 @@ static int run_svd_qr(cyb_ctx_t ctx, int64_t nmat, const cyb_svd_desc* sd, int32
         l.W = take(sizeof(double) * (size_t)l.kp * l.kp);
         l.J = take(sizeof(double) * (size_t)l.kp * l.kp);
         l.rank = take(sizeof(int32_t) * (size_t)l.kp);
+        l.inv = take(sizeof(int32_t) * (size_t)l.kp);
         l.nnull = take(sizeof(int32_t));
         l.Cq = take(sizeof(double) * (size_t)l.L * l.k);
         l.Fc = take(sizeof(double) * (size_t)l.k * l.k);
@@ -1019,6 +1021,7 @@ static int run_svd_qr(cyb_ctx_t ctx, int64_t nmat, const cyb_svd_desc* sd, int32
         q.mode = 0;
         q.sig = dp(l.sig);
         q.rank = reinterpret_cast<int32_t*>(base + l.rank);
+        q.inv = reinterpret_cast<int32_t*>(base + l.inv);
         q.S = sd[b].S;
         q.U = l.tall ? nullptr : sd[b].U;
         q.ldu = sd[b].ldu;
@@ -1130,6 +1133,16 @@ static int run_svd_qr(cyb_ctx_t ctx, int64_t nmat, const cyb_svd_desc* sd, int32
         // (k entries per matrix, in the order of the lists in the workspace)
         CYB_HIP(hipMemcpyAsync(base + idx_begin, d_idx_v, sizeof(int32_t) * idx_all.size(), hipMemcpyDeviceToDevice, st));
     }
+    // compact row of every full-size row (-1: deflated up front), k entries per matrix: the J side is read off the compact
+    // rotations without a scatter into the full-size J (j_to_cq_kernel)
+    std::vector<int32_t> pos_all;
+    std::vector<int64_t> pos_off((size_t)nmat, 0);
+    for (int64_t b = 0; b < nmat; ++b) {
+        const Lay& l = lay[(size_t)b];
+        pos_off[(size_t)b] = (int64_t)pos_all.size();
+        pos_all.resize(pos_all.size() + (size_t)l.k, -1);
+        for (size_t g = 0; g < l.good0.size(); ++g) pos_all[(size_t)pos_off[(size_t)b] + (size_t)l.good0[g]] = (int32_t)g;
+    }
     const std::vector<JMat> jm0 = jm;
     std::vector<BqrMat> qm3; // the LQ factorisations (their Q2 also completes the deflated rows in step 5)
     std::vector<int> qm3_of((size_t)nmat, -1);
@@ -1143,11 +1156,20 @@ static int run_svd_qr(cyb_ctx_t ctx, int64_t nmat, const cyb_svd_desc* sd, int32
         std::vector<XposeDesc> x_r2;
         std::vector<LqDesc> lqd;
         std::vector<int> jrec_blocks; // rotation recovery: blocks that iterate without accumulation
-        std::vector<BqrTarget> tg3;
+        // the two applications after the sweeps share one call: Q1 on the J side (targets 0 .. nmat - 1, matrices qm) and
+        // Q2 on [J'^T 0; 0 I] of the LQ blocks (matrices qm3, behind qm in the joint list)
+        std::vector<BqrTarget> tg1, tg3;
+        std::vector<JcqDesc> jc;
         for (int64_t b = 0; b < nmat; ++b) {
             Lay& l = lay[(size_t)b];
             l.lq = l.lq && allow_lq;
-            if (l.r0 == l.k && !l.lq) continue;
+            tg1.push_back(BqrTarget{(int)b, dp(l.Cq), l.L, l.k, l.n_fac >= 0 ? l.n_fac : (l.k + cyb::NBK - 1) / cyb::NBK});
+            if (l.r0 == l.k && !l.lq) {
+                jc.push_back(JcqDesc{dp(l.J), nullptr, dp(l.Cq), l.L, l.kp, 0, l.k, l.r0});
+                continue;
+            }
+            jc.push_back(JcqDesc{dp(l.Jc), reinterpret_cast<const int32_t*>(base + l.idx), dp(l.Cq), l.L, std::max(round_up(l.r0, 64), 64),
+                                 pos_off[(size_t)b], l.k, l.r0});
             const int32_t* didx = reinterpret_cast<const int32_t*>(base + l.idx);
             const int rp = std::max(round_up(l.r0, 64), 64);
             gat.push_back(RowMoveDesc{dp(l.W), dp(l.Wc), didx, l.kp, l.kp, l.r0, l.kp, 0, 0});
@@ -1191,7 +1213,7 @@ static int run_svd_qr(cyb_ctx_t ctx, int64_t nmat, const cyb_svd_desc* sd, int32
                     x_r2.push_back(XposeDesc{dp(l.Wc), dp(l.Cn), l.kp, l.r0, l.r0, l.r0, 1, l.r0, 0, 0});
                     jrec_blocks.push_back((int)b);
                 }
-                tg3.push_back(BqrTarget{(int)qm3.size(), dp(l.Cq2), l.k, l.k});
+                tg3.push_back(BqrTarget{(int)(nmat + (int64_t)qm3.size()), dp(l.Cq2), l.k, l.k});
                 qm3_of[(size_t)b] = (int)qm3.size();
                 qm3.push_back(q);
             }
@@ -1248,8 +1270,24 @@ static int run_svd_qr(cyb_ctx_t ctx, int64_t nmat, const cyb_svd_desc* sd, int32
             // (its waves share the Gram rows of the flagged directions: a large graded block has hundreds -- 0.94 ms on 64 workgroups)
             hipLaunchKernelGGL(lq_check_kernel, dim3(helper_grid_x(lqd.size()), (unsigned)lqd.size()), dim3(256), 0, st, dl);
             CYB_HIP(hipGetLastError());
-            CYB_TRY(bqr_apply_q(ctx, qm3, tg3));
-            CYB_TRY(ctx->upload(lqd.data(), sizeof(LqDesc) * lqd.size(), &d)); // (slot may have been recycled)
+        }
+        {   // the J side, unsorted: column j of Cq is row j of J (Z^T of an LQ block, the accumulated rotations otherwise)
+            void *d = nullptr, *dpos = nullptr;
+            CYB_TRY(upload_packed(ctx, {{jc.data(), sizeof(JcqDesc) * jc.size(), &d}, {pos_all.data(), sizeof(int32_t) * pos_all.size(), &dpos}}));
+            hipLaunchKernelGGL(j_to_cq_kernel, dim3(helper_grid_x((size_t)nmat), (unsigned)nmat), dim3(256), 0, st, static_cast<const JcqDesc*>(d),
+                               static_cast<const int32_t*>(dpos));
+            CYB_HIP(hipGetLastError());
+        }
+        {
+            // Q2's targets are ordered behind Q1's; every target takes the route a call of its own application would give it
+            std::vector<BqrMat> qall(qm);
+            qall.insert(qall.end(), qm3.begin(), qm3.end());
+            tg1.insert(tg1.end(), tg3.begin(), tg3.end());
+            CYB_TRY(bqr_apply_q_pair(ctx, qall, tg1, (size_t)nmat));
+        }
+        if (!qm3.empty()) {
+            void* d = nullptr;
+            CYB_TRY(ctx->upload(lqd.data(), sizeof(LqDesc) * lqd.size(), &d));
             hipLaunchKernelGGL(lq_unpack_kernel, dim3(64, (unsigned)lqd.size()), dim3(256), 0, st, static_cast<const LqDesc*>(d));
             CYB_HIP(hipGetLastError());
         }
@@ -1293,18 +1331,15 @@ static int run_svd_qr(cyb_ctx_t ctx, int64_t nmat, const cyb_svd_desc* sd, int32
     if (info)
         for (int64_t b = 0; b < nmat; ++b) info[b] = sweeps[(size_t)b];
     if (jst != CYB_OK && jst != CYB_ERR_NOCONV) return jst;
-    {   // compact results back into the full-size W / J (J is still the identity there)
-        std::vector<RowMoveDesc> sw, sj;
+    {   // compact results back into the full-size W (the J side went from the compact rotations into Cq, see iterate())
+        std::vector<RowMoveDesc> sw;
         for (int64_t b = 0; b < nmat; ++b) {
             const Lay& l = lay[(size_t)b];
             if ((l.r0 == l.k && !l.lq) || l.r0 == 0) continue;
             const int32_t* didx = reinterpret_cast<const int32_t*>(base + l.idx);
-            const int rp = std::max(round_up(l.r0, 64), 64);
             sw.push_back(RowMoveDesc{dp(l.Wc), dp(l.W), didx, l.kp, l.kp, l.r0, l.kp, 1, 0});
-            sj.push_back(RowMoveDesc{dp(l.Jc), dp(l.J), didx, rp, l.kp, l.r0, l.r0, 0, 0});
         }
         CYB_TRY(launch_row_moves(ctx, sw));
-        CYB_TRY(launch_row_moves(ctx, sj, true));
     }
     // ---- 4. singular values (row norms) -> host, to find the deflated rows
     for (int64_t b = 0; b < nmat; ++b) post[(size_t)b].sig_lq = lay[(size_t)b].lq ? dp(lay[(size_t)b].sigo) : nullptr;
@@ -1411,31 +1446,22 @@ static int run_svd_qr(cyb_ctx_t ctx, int64_t nmat, const cyb_svd_desc* sd, int32
             CYB_HIP(hipGetLastError());
         }
     }
-    // ---- 6. sort, write the W side directly and the J side through the block reflectors of Q1
+    // ---- 6. sort, write the W side directly; the J side (Q1 applied in iterate(), columns in the order of the rows of J)
+    //         takes the descending order where it is written out: output column c is column inv[c] of Cq
     CYB_TRY(ctx->upload(post.data(), sizeof(PostDesc) * post.size(), &d_post)); // (slot may have been recycled)
     dpost = static_cast<const PostDesc*>(d_post);
     hipLaunchKernelGGL(rank_kernel, dim3(8, (unsigned)nmat), dim3(256), 0, st, dpost);
     hipLaunchKernelGGL(write_factors_kernel, dim3(helper_grid_x((size_t)nmat), (unsigned)nmat), dim3(256), 0, st, dpost);
     CYB_HIP(hipGetLastError());
-    std::vector<JcqDesc> jc;
-    std::vector<BqrTarget> tg;
     std::vector<XposeDesc> x_out;
     for (int64_t b = 0; b < nmat; ++b) {
         const Lay& l = lay[(size_t)b];
-        jc.push_back(JcqDesc{dp(l.J), reinterpret_cast<const int32_t*>(base + l.rank), dp(l.Cq), l.L, l.kp, l.k});
-        tg.push_back(BqrTarget{(int)b, dp(l.Cq), l.L, l.k, l.n_fac >= 0 ? l.n_fac : (l.k + cyb::NBK - 1) / cyb::NBK});
-        if (l.tall) // U (row-major m x k): out(r, c) = Cq[c*L + r]
-            x_out.push_back(XposeDesc{dp(l.Cq), sd[b].U, l.L, sd[b].ldu, l.m, l.k, 0, 0, 0, 0});
-        else        // Vh (row-major k x n): row r = column r of Cq
-            x_out.push_back(XposeDesc{dp(l.Cq), sd[b].Vh, l.L, sd[b].ldvh, l.k, l.n, 0, 0, 1, 0});
+        const int32_t* inv = reinterpret_cast<const int32_t*>(base + l.inv);
+        if (l.tall) // U (row-major m x k): out(r, c) = Cq[inv[c]*L + r]
+            x_out.push_back(XposeDesc{dp(l.Cq), sd[b].U, l.L, sd[b].ldu, l.m, l.k, 0, 0, 0, 0, inv});
+        else        // Vh (row-major k x n): row r = column inv[r] of Cq
+            x_out.push_back(XposeDesc{dp(l.Cq), sd[b].Vh, l.L, sd[b].ldvh, l.k, l.n, 0, 0, 1, 0, inv});
     }
-    {
-        void* d = nullptr;
-        CYB_TRY(ctx->upload(jc.data(), sizeof(JcqDesc) * jc.size(), &d));
-        hipLaunchKernelGGL(j_to_cq_kernel, dim3(helper_grid_x((size_t)nmat), (unsigned)nmat), dim3(256), 0, st, static_cast<const JcqDesc*>(d));
-        CYB_HIP(hipGetLastError());
-    }
-    CYB_TRY(bqr_apply_q(ctx, qm, tg));
     CYB_TRY(xpose_batched(ctx, x_out));
     if (info) CYB_HIP(hipStreamSynchronize(st));
     return jst;
