@@ -25,6 +25,7 @@ from typing import Sequence
 import numpy as np
 
 from . import _lib
+from . import decomp as _decomp
 from .runtime import Context, get_context
 
 __all__ = ['HipBlock', 'Scalar', 'HipBlockBackend', 'GemmPlan', 'DeviceIndex']
@@ -1887,540 +1888,47 @@ class HipBlockBackend:
         o = self.tdot(a, b, [], [])
         return self.reshape(self.permute_axes(o, [0, 2, 1, 3]), (a.shape[0] * b.shape[0], a.shape[1] * b.shape[1]))
 
-    # ------------------------------------------------------------------ the hot path: decompositions
-    def matrix_svd_batched(self, blocks, algorithm=None, return_info=False, outs=None, null_vectors=True, return_rank=False):
-        """Thin SVD of every 2-D block of a list in one batched call.
-        Returns [(U, S, Vh)], S descending (scipy.linalg.svd(full_matrices=False) conventions,
-        numpy.cpp:1247-1297). All reference algorithm names are accepted and map to the
-        block-Jacobi kernel."""
-        if algorithm is not None and algorithm not in self.svd_algorithms:
-            raise ValueError(f'SVD algorithm not supported: {algorithm}')
-        self._numeric_only(blocks, 'decomposition')
-        cplx = any(b.is_complex for b in blocks)
-        if cplx:  # the whole list in complex arithmetic (small blocks only: csrc/csvd_small.hip)
-            if outs is not None:
-                raise NotImplementedError('matrix_svd_batched: preallocated outputs are for float64 blocks')
-            blocks = [self.as_complex(b) for b in blocks]
-        n = len(blocks)
-        srcs = self.contiguous_many(blocks)
-        for a in srcs:
-            if a.ndim != 2:
-                raise ValueError('matrix_svd: block must be 2-D')
-        given = outs
-        if cplx and n:
-            # large blocks: the float64 block engine on the interleaved embedding (also the truncating caller's form: null
-            # vectors skipped, numerical ranks reported); small ones (and lists the engine refuses): the complex Jacobi
-            # kernels below, which always complete and report k
-            big = [i for i, a in enumerate(srcs) if min(a.shape) >= self.COMPLEX_SVD_EMBED_MIN]
-            got = self._complex_svd_embedded([srcs[i] for i in big], True, null_vectors) if big else None
-            if got is not None:
-                res_big, info_big, rank_big = got
-                rest = [i for i in range(n) if i not in set(big)]
-                res_all, info_all, rank_all = [None] * n, [0] * n, [min(a.shape) for a in srcs]
-                for i, r, f, rk in zip(big, res_big, info_big, rank_big):
-                    res_all[i], info_all[i], rank_all[i] = r, f, rk
-                if rest:
-                    rres, rinfo = self.matrix_svd_batched_complex_direct([srcs[i] for i in rest], True)
-                    for i, r, f in zip(rest, rres, rinfo):
-                        res_all[i], info_all[i] = r, f
-                out = (res_all,) + ((info_all,) if return_info else ()) + ((rank_all,) if return_rank else ())
-                return out if len(out) > 1 else res_all
-        if given is None and cplx:
-            cs, rs = [], []
-            for a in srcs:
-                m, nn = a.shape
-                k = min(m, nn)
-                cs += [(m, k), (k, nn)]
-                rs.append((k,))
-            cflat, rflat = self._new_many(cs, True), self._new_many(rs)
-            outs = [(cflat[2 * i], rflat[i], cflat[2 * i + 1]) for i in range(n)]
-        elif given is None:  # U, S, Vh of all blocks out of one buffer
-            shapes = []
-            for a in srcs:
-                m, nn = a.shape
-                k = min(m, nn)
-                shapes += [(m, k), (k,), (k, nn)]
-            flat = self._new_many(shapes)
-            outs = [tuple(flat[3 * i:3 * i + 3]) for i in range(n)]
-        else:
-            outs = []
-            for a, (U, S, Vh) in zip(srcs, given):
-                m, nn = a.shape
-                k = min(m, nn)
-                if U.shape != (m, k) or S.shape != (k,) or Vh.shape != (k, nn) or not (
-                        U.is_contiguous() and S.is_contiguous() and Vh.is_contiguous()):
-                    raise ValueError('matrix_svd_batched: outs[i] must be contiguous (m,k), (k,), (k,n) blocks')
-                outs.append((U, S, Vh))
-        arr = np.zeros(max(n, 1), dtype=_lib.SVD_DTYPE)
-        if n:
-            ms = np.array([a.shape[0] for a in srcs], dtype=np.int64)
-            ns = np.array([a.shape[1] for a in srcs], dtype=np.int64)
-            ks = np.minimum(ms, ns)
-            arr['A'][:n], arr['m'][:n], arr['n'][:n] = [a.ptr for a in srcs], ms, ns
-            arr['lda'][:n] = arr['ldvh'][:n] = np.maximum(ns, 1)
-            arr['ldu'][:n] = np.maximum(ks, 1)
-            arr['U'][:n], arr['S'][:n], arr['Vh'][:n] = ([o[0].ptr for o in outs], [o[1].ptr for o in outs], [o[2].ptr for o in outs])
-        descs = arr.ctypes.data_as(C.POINTER(_lib.SvdDesc))
-        info = (C.c_int32 * max(n, 1))()
-        rank = (C.c_int32 * max(n, 1))()
-        if n:
-            self.ctx.sync_stream()
-            if cplx or (null_vectors and not return_rank):
-                fn = self.lib.cyb_svd_batched_c128 if cplx else self.lib.cyb_svd_batched_f64
-                _lib.check(fn(self.ctx.handle, descs, n, info if return_info else None))
-                for i in range(n):
-                    rank[i] = min(srcs[i].shape)
-            else:   # the truncating caller's form: null vectors skipped and / or the numerical ranks reported
-                _lib.check(self.lib.cyb_svd_batched_ex_f64(self.ctx.handle, descs, n, info if return_info else None,
-                                                           0 if null_vectors else _lib.CYB_SVD_SKIP_NULL_VECTORS, rank))
-        res = (outs,)
-        if return_info:
-            res += (list(info)[:n],)
-        if return_rank:
-            res += (list(rank)[:n],)
-        return res if len(res) > 1 else outs
+    # ------------------------------------------------------------------ the hot path: decompositions (decomp.py)
+    # thresholds of the embedded complex routes: read from the backend on every call, so an instance may override them
+    COMPLEX_SVD_EMBED_MIN = _decomp.COMPLEX_SVD_EMBED_MIN
+    COMPLEX_QR_EMBED_MIN = _decomp.COMPLEX_QR_EMBED_MIN
+    COMPLEX_QR_EMBED_MAX_ROWS = _decomp.COMPLEX_QR_EMBED_MAX_ROWS
+    COMPLEX_EIGH_EMBED_MIN = _decomp.COMPLEX_EIGH_EMBED_MIN
 
-    def matrix_svd_batched_complex_direct(self, srcs, return_info=False):
-        """The complex Jacobi kernels (`cyb_svd_batched_c128`) on contiguous complex blocks, without the embedded route."""
-        keep = self.COMPLEX_SVD_EMBED_MIN
-        self.COMPLEX_SVD_EMBED_MIN = 1 << 62
-        try:
-            return self.matrix_svd_batched(srcs, return_info=return_info)
-        finally:
-            self.COMPLEX_SVD_EMBED_MIN = keep
+    def matrix_svd_batched(self, blocks, algorithm=None, return_info=False, outs=None, null_vectors=True, return_rank=False):
+        return _decomp.matrix_svd_batched(self, blocks, algorithm, return_info, outs, null_vectors, return_rank)
 
     def matrix_svd(self, a: HipBlock, algorithm=None):
         return self.matrix_svd_batched([a], algorithm)[0]
 
     def matrix_qr_batched(self, blocks, full=False):
-        """QR of every 2-D block (scipy.linalg.qr mode 'economic'/'full', numpy.cpp:1236-1245)."""
-        self._numeric_only(blocks, 'decomposition')
-        cplx = any(b.is_complex for b in blocks)
-        if cplx:
-            blocks = [self.as_complex(b) for b in blocks]
-        n = len(blocks)
-        srcs = self.contiguous_many(blocks)
-        if cplx and n:
-            # large blocks: the real MFMA block engine on the interleaved embedding, economic and full; blocks that route gives
-            # up (it verifies unitarity and reconstruction per block) and all small ones: complex Householder QR
-            # (csrc/cqr_house.hip), which is backward stable for every block
-            big = [i for i, a in enumerate(srcs) if a.ndim == 2 and min(a.shape) > 0
-                   and (min(a.shape) >= self.COMPLEX_QR_EMBED_MIN or max(a.shape) > 128) and a.shape[0] <= self.COMPLEX_QR_EMBED_MAX_ROWS]
-            if big:
-                got = self._complex_qr_embedded([srcs[i] for i in big], full)
-                done = {i: g for i, g in zip(big, got) if g is not None}
-                rest = [i for i in range(n) if i not in done]
-                if rest:
-                    rest_out = self.matrix_qr_batched_direct([srcs[i] for i in rest], full, True)
-                    done.update(dict(zip(rest, rest_out)))
-                return [done[i] for i in range(n)]
-        return self.matrix_qr_batched_direct(srcs, full, cplx)
-
-    def matrix_qr_batched_direct(self, srcs, full, cplx):
-        """The QR kernels of the C-ABI on contiguous 2-D blocks of one dtype (`cyb_qr_batched_f64` / `_c128`)."""
-        n = len(srcs)
-        shapes = []
-        for a in srcs:
-            if a.ndim != 2:
-                raise ValueError('matrix_qr: block must be 2-D')
-            m, nn = a.shape
-            kq = m if full else min(m, nn)
-            shapes += [(m, kq), (kq, nn)]
-        flat = self._new_many(shapes, cplx)
-        outs = [tuple(flat[2 * i:2 * i + 2]) for i in range(n)]
-        arr = np.zeros(max(n, 1), dtype=_lib.QR_DTYPE)
-        if n:
-            ms = np.array([a.shape[0] for a in srcs], dtype=np.int64)
-            ns = np.array([a.shape[1] for a in srcs], dtype=np.int64)
-            kqs = ms if full else np.minimum(ms, ns)
-            arr['A'][:n], arr['m'][:n], arr['n'][:n] = [a.ptr for a in srcs], ms, ns
-            arr['lda'][:n] = arr['ldr'][:n] = np.maximum(ns, 1)
-            arr['ldq'][:n] = np.maximum(kqs, 1)
-            arr['Q'][:n], arr['R'][:n] = [o[0].ptr for o in outs], [o[1].ptr for o in outs]
-            arr['full'][:n] = int(full)
-        descs = arr.ctypes.data_as(C.POINTER(_lib.QrDesc))
-        if n:
-            self.ctx.sync_stream()
-            _lib.check((self.lib.cyb_qr_batched_c128 if cplx else self.lib.cyb_qr_batched_f64)(self.ctx.handle, descs, n))
-        return outs
+        return _decomp.matrix_qr_batched(self, blocks, full)
 
     def matrix_qr(self, a: HipBlock, full: bool):
         return self.matrix_qr_batched([a], full)[0]
 
-    # complex blocks with min(m, n) at least this large take the embedded route of `_complex_qr_embedded`
-    COMPLEX_QR_EMBED_MIN = 48
-    # ... up to this many rows (the embedding has twice as many; beyond 1536 real rows the blocked QR spreads a panel over
-    # several workgroups, qr_panel_multi_kernel, which must all be resident: 256 CUs x 1536 rows)
-    COMPLEX_QR_EMBED_MAX_ROWS = 65536
-
-    def _embed_complex(self, srcs):
-        """Interleaved real embeddings M(A) (a + ib -> [[a, -b], [b, a]]; 2m x 2n float64) of contiguous complex 2-D blocks:
-        one buffer, ONE strided launch."""
-        Ms = self._new_many([(2 * a.shape[0], 2 * a.shape[1]) for a in srcs])
-        items = []
-        for a, M in zip(srcs, Ms):
-            m, nn = a.shape
-            if m * nn == 0:
-                continue
-            re, im = self._plane(a, 0), self._plane(a, 1)
-            for off, coeff, src in ((0, 1.0, re), (1, -1.0, im), (2 * nn, 1.0, im), (2 * nn + 1, 1.0, re)):
-                items.append((HipBlock(self, M.buf, M.offset + off, (m, nn), (4 * nn, 2)), [(coeff, src)], False))
-        self.lincomb_many(items)
-        return Ms
-
-    def _extract_complex_items(self, X, out, by_rows=False):
-        """lincomb items that read the complex matrix out of a structured embedding X into the complex block `out` (r x c):
-        from the even COLUMNS of X (real part rows 0::2, imaginary part rows 1::2 -- a real column of X is one complex
-        column), or with `by_rows` from the even ROWS (real part columns 0::2, imaginary part minus columns 1::2 -- a
-        real row of X is one complex row)."""
-        r, c = out.shape
-        if r * c == 0:
-            return []
-        ld = X.strides[0]
-        fo = self._fview(out)
-        items = []
-        for plane, off, coeff in (((0, 0, 1.0), (1, 1, -1.0)) if by_rows else ((0, 0, 1.0), (1, ld, 1.0))):
-            dst = HipBlock(self, fo.buf, fo.offset + plane, (r, c), (2 * c, 2))
-            src = HipBlock(self, X.buf, X.offset + off, (r, c), (2 * ld, 2))
-            items.append((dst, [(coeff, src)], False))
-        return items
-
-    # complex blocks with min(m, n) at least this large are decomposed on the float64 block engine through the embedding
-    # (measured: 96 -> 4.7 vs 4.7 ms, 192 -> 10.0 vs 11.3 ms, 1024 -> 111 vs 220 ms, sixteen 128-blocks -> 13.7 vs 21.3 ms)
-    COMPLEX_SVD_EMBED_MIN = 96
-    # defect |U^H U - 1| above which a factor of the embedded route is re-orthonormalised (full-rank, mildly graded blocks
-    # come out at 1e-14 ... 3e-13)
-    COMPLEX_SVD_ORTHO_TOL = 2e-12
-
-    def _complex_svd_embedded(self, srcs, return_info=False, null_vectors=True):
-        """Thin SVD of complex blocks on the float64 block engine: the pipeline of the real SVD --
-        blocked QR, LQ step, persistent block-Jacobi sweeps, completion from Q2 -- runs on the interleaved embeddings
-        with `CYB_SVD_EMBEDDED_COMPLEX`: its QR steps preserve the structure by uniqueness, its pivot solves by
-        construction (a complex 16 x 16 Hermitian Jacobi solve per pair), rows are deflated / ranked / completed as
-        pairs.  Returns ([(U, S, Vh)], info, ranks) in complex / float64 blocks (ranks: numerical ranks in complex rows;
-        with `null_vectors=False` the vectors beyond a block's rank are unspecified, CYB_SVD_SKIP_NULL_VECTORS), or None
-        if the engine refuses the list: the caller then uses the complex Jacobi kernels."""
-        n = len(srcs)
-        Ms = self._embed_complex(srcs)
-        shapes = []
-        for a in srcs:
-            m, nn = a.shape
-            k = min(m, nn)
-            shapes += [(2 * m, 2 * k), (2 * k,), (2 * k, 2 * nn)]
-        flat = self._new_many(shapes)
-        arr = np.zeros(n, dtype=_lib.SVD_DTYPE)
-        ms = np.array([2 * a.shape[0] for a in srcs], dtype=np.int64)
-        ns = np.array([2 * a.shape[1] for a in srcs], dtype=np.int64)
-        ks = np.minimum(ms, ns)
-        arr['A'], arr['m'], arr['n'] = [M.ptr for M in Ms], ms, ns
-        arr['lda'] = arr['ldvh'] = np.maximum(ns, 1)
-        arr['ldu'] = np.maximum(ks, 1)
-        arr['U'], arr['S'], arr['Vh'] = [flat[3 * i].ptr for i in range(n)], [flat[3 * i + 1].ptr for i in range(n)], [flat[3 * i + 2].ptr for i in range(n)]
-        info = (C.c_int32 * n)()
-        rank = (C.c_int32 * n)()
-        self.ctx.sync_stream()
-        st = self.lib.cyb_svd_batched_ex_f64(self.ctx.handle, arr.ctypes.data_as(C.POINTER(_lib.SvdDesc)), n, info,
-                                             _lib.CYB_SVD_EMBEDDED_COMPLEX | (0 if null_vectors else _lib.CYB_SVD_SKIP_NULL_VECTORS), rank)
-        if st == _lib.CYB_ERR_UNSUPPORTED:
-            return None
-        if st != _lib.CYB_ERR_NOCONV:   # (blocks that did not settle are caught by the reconstruction check below)
-            _lib.check(st)
-        cs, rs = [], []
-        for a in srcs:
-            m, nn = a.shape
-            k = min(m, nn)
-            cs += [(m, k), (k, nn)]
-            rs.append((k,))
-        cflat, rflat = self._new_many(cs, True), self._new_many(rs)
-        items, pairs = [], []
-        for i in range(n):
-            U, S, Vh = flat[3 * i], flat[3 * i + 1], flat[3 * i + 2]
-            # real column 2a of U and real row 2a of Vh are ONE real singular triplet: a complex triplet whatever the
-            # basis the engine left inside the two-dimensional real singular subspace
-            items += self._extract_complex_items(U, cflat[2 * i]) + self._extract_complex_items(Vh, cflat[2 * i + 1], by_rows=True)
-            k = rflat[i].shape[0]
-            if k:
-                pairs.append((rflat[i], HipBlock(self, S.buf, S.offset, (k,), (2,))))
-        self.lincomb_many(items)
-        self.copy_many(pairs)
-        # Orthonormality in the COMPLEX sense.  The even real columns of U (rows of Vh) are orthonormal as real vectors by
-        # construction; as complex vectors they are as long as the real factor is structured, and that is only as good as
-        # the structure of Q1's reflectors: the ones built from a trailing block near the rounding level of the matrix --
-        # the null space of a rank-deficient block, the small end of a spectrum graded over many decades -- have none
-        # (defect eps * sigma_max / sigma_j).  One grouped GEMM measures the defect; where it shows, a complex QR of the
-        # factor (columns in order of descending sigma) restores it: U = Q_u R_u with R_u = 1 + (terms that couple only
-        # columns of such small sigma_j), so Q_u S Vh is the same matrix to eps ||A||.
-        cranks = [int(rank[i]) // 2 for i in range(n)]
-        # (columns that count: all of them, or -- null vectors skipped -- the leading rank)
-        kk = [min(srcs[i].shape) if null_vectors else cranks[i] for i in range(n)]
-        todo = [i for i in range(n) if kk[i] > 0]
-        if todo:
-            us = [self.subblock(cflat[2 * i], 0, srcs[i].shape[0], 0, kk[i]) for i in todo]
-            vs = [self.subblock(cflat[2 * i + 1], 0, kk[i], 0, srcs[i].shape[1]) for i in todo]
-            uh = [self.conj(self.permute_axes(u, [1, 0])) for u in us]
-            vt = [self.conj(self.permute_axes(v, [1, 0])) for v in vs]
-            uc = self.contiguous_many(us)
-            grams = self.matrix_dot_grouped([[(uh[j], uc[j])] for j in range(len(todo))] + [[(vs[j], vt[j])] for j in range(len(todo))])
-            eyes = {}
-            bad_u, bad_v = [], []
-            for j, i in enumerate(todo):
-                k = kk[i]
-                if k not in eyes:
-                    eyes[k] = self.eye_matrix(k, dtype='complex128')
-                for g, lst in ((grams[j], bad_u), (grams[len(todo) + j], bad_v)):
-                    if self.max_abs(self.linear_combination(1.0, g, -1.0, eyes[k])) > self.COMPLEX_SVD_ORTHO_TOL:
-                        lst.append(j)
-            if bad_u or bad_v:
-                qs = [q for q, _ in self.matrix_qr_batched([uc[j] for j in bad_u] + [vt[j] for j in bad_v], False)]
-                self.copy_many([(us[j], qs[t]) for t, j in enumerate(bad_u)])
-                self.copy_many([(vs[j], self.permute_axes(qs[len(bad_u) + t], [1, 0])) for t, j in enumerate(bad_v)], conj=True)
-        res, info = [(cflat[2 * i], rflat[i], cflat[2 * i + 1]) for i in range(n)], list(info)
-        # Reconstruction check.  The route rests on the QR steps leaving R = M(R_c) structured, which needs the leading
-        # columns of the block to be independent: a numerically dependent column in the MIDDLE (zero columns, a product of
-        # block-sparse factors) gets an unstructured reflector pair and the rows of R after it are no partners any more
-        # (singular values off by 1e-3, or no convergence; scripts/svd_fuzz.py seeds 52 / 53).  One grouped GEMM per list
-        # finds those blocks; they go to the complex Jacobi kernels, which make no such assumption.
-        if todo:
-            us = [self.subblock(cflat[2 * i], 0, srcs[i].shape[0], 0, kk[i]) for i in todo]
-            vs = [self.subblock(cflat[2 * i + 1], 0, kk[i], 0, srcs[i].shape[1]) for i in todo]
-            ss = [HipBlock(self, rflat[i].buf, rflat[i].offset, (kk[i],), (1,)) for i in todo]
-            usc = self.scale_axis_many([(u, sv, 1) for u, sv in zip(us, ss)])
-            recon = self.matrix_dot_grouped([[(usc[j], vs[j])] for j in range(len(todo))])
-            diffs = self.linear_combination_many(1.0, recon, -1.0, [srcs[i] for i in todo])
-            failing = [i for j, i in enumerate(todo)
-                       if not self.max_abs(diffs[j]) <= self.COMPLEX_SVD_RECON_TOL * np.sqrt(max(srcs[i].shape)) * self.max_abs(srcs[i])]
-            if failing:
-                fres, finfo = self.matrix_svd_batched_complex_direct([srcs[i] for i in failing], True)
-                for i, r, f in zip(failing, fres, finfo):
-                    res[i], info[i], cranks[i] = r, f, min(srcs[i].shape)
-        elif st == _lib.CYB_ERR_NOCONV:
-            _lib.check(st)
-        return res, info, cranks
-
-    # |U S Vh - A|_max above this (times sqrt(max(m, n)) max|A|) sends a block of the embedded route to the complex kernels
-    # (structured blocks come out at 1e-15 ... 1e-14 on this scale)
-    COMPLEX_SVD_RECON_TOL = 1e-12
-
-    # unitarity defect |Q^H Q - 1| above which the factor of the embedded QR is re-orthonormalised
-    COMPLEX_QR_ORTHO_TOL = 1e-12
-
-    def _complex_qr_embedded(self, srcs, full=False, _depth=0):
-        """QR of complex blocks on the real block engine: the REAL blocked Householder QR of the
-        interleaved embedding M(A) -- entry a + ib -> [[a, -b], [b, a]], 2m x 2n -- IS the complex QR once the diagonal of
-        R is made positive (a QR with fixed diagonal signs is unique, and M(R_c) is upper triangular in the interleaved
-        column order), so the MFMA strip kernel and the register-resident panel kernels serve complex blocks unchanged.
-        Q_c is the even real columns of Q (real column 2a IS complex column a), R_c the even rows of R.
-
-        That argument needs full column rank.  Where the block is numerically rank deficient -- or only has a part at the
-        level eps |A| / sigma, e.g. a low-rank block plus noise -- the reflectors built from the trailing block carry no
-        (or only part of the) structure: the even columns are then still orthonormal as REAL vectors and A = Q R still holds,
-        but they are not orthonormal in the complex sense (defect eps |A| / sigma_j, up to O(1)).  One grouped GEMM measures
-        the defect; above `COMPLEX_QR_ORTHO_TOL` the factor is factored once more, Q_c = Q' S (a well-conditioned block:
-        its embedded QR is structured to rounding), and A = Q' (S R_c) with S R_c upper triangular -- "twice is enough".
-        `full`: the extra m - k columns are the even columns of the real full Q's trailing part, made orthonormal with the
-        rest by the same second pass.  `scripts/complex_embedding_model.py` is the numpy check of the argument."""
-        n = len(srcs)
-        Ms = self._embed_complex(srcs)
-        qrs = self.matrix_qr_batched(Ms, full)
-        # diagonal of every R to the host: signs for the uniqueness fix
-        diags = [self.contiguous(HipBlock(self, R.buf, R.offset, (min(R.shape),), (R.strides[0] + 1,))) if min(R.shape) else None
-                 for _, R in qrs]
-        fix_q, fix_r = [], []
-        for (Q, R), d in zip(qrs, diags):
-            sq = np.ones(Q.shape[1])
-            sr = np.ones(R.shape[0])
-            if d is not None:
-                dn = self.to_numpy(d)
-                sgn = np.where(dn < 0, -1.0, 1.0)
-                sq[:len(sgn)] = sgn
-                sr[:len(sgn)] = sgn
-            fix_q.append((Q, self.as_block(sq), 1))
-            fix_r.append((R, self.as_block(sr), 0))
-        Qs = self.scale_axis_many(fix_q)
-        Rs = self.scale_axis_many(fix_r)
-        shapes = []
-        for a in srcs:
-            m, nn = a.shape
-            kq = m if full else min(m, nn)
-            shapes += [(m, kq), (kq, nn)]
-        flat = self._new_many(shapes, True)
-        items = []
-        for i in range(n):
-            items += self._extract_complex_items(Qs[i], flat[2 * i]) + self._extract_complex_items(Rs[i], flat[2 * i + 1])
-        self.lincomb_many(items)
-        outs = [(flat[2 * i], flat[2 * i + 1]) for i in range(n)]
-        # ---- complex unitarity of the extracted factors; second pass where it is not there
-        todo = [i for i in range(n) if outs[i][0].shape[1] > 0 and outs[i][0].shape[0] > 0]
-        if todo and _depth < 2:
-            qh = [self.conj(self.permute_axes(outs[i][0], [1, 0])) for i in todo]
-            grams = self.matrix_dot_grouped([[(qh[j], outs[i][0])] for j, i in enumerate(todo)])
-            eyes = {}
-            diffs = []
-            for j, i in enumerate(todo):
-                k = outs[i][0].shape[1]
-                if k not in eyes:
-                    eyes[k] = self.eye_matrix(k, dtype='complex128')
-                diffs.append(self.linear_combination(1.0, grams[j], -1.0, eyes[k]))
-            bad = []
-            if self.max_abs_many(diffs) > self.COMPLEX_QR_ORTHO_TOL:   # (one read-back for the list; per block only if needed)
-                bad = [i for i, df in zip(todo, diffs) if self.max_abs(df) > self.COMPLEX_QR_ORTHO_TOL]
-            if bad:
-                second = self._complex_qr_embedded([outs[i][0] for i in bad], False, _depth + 1)
-                newr = self.matrix_dot_grouped([[(S, outs[i][1])] for i, (_, S) in zip(bad, second)])
-                for i, (Q2, _), R2 in zip(bad, second, newr):
-                    outs[i] = (Q2, R2)
-                if _depth == 0:   # the re-factored blocks are measured once more; what is still not unitary goes to Householder
-                    qh2 = [self.conj(self.permute_axes(outs[i][0], [1, 0])) for i in bad]
-                    grams2 = self.matrix_dot_grouped([[(qh2[j], outs[i][0])] for j, i in enumerate(bad)])
-                    for j, i in enumerate(bad):
-                        k = outs[i][0].shape[1]
-                        if not self.max_abs(self.linear_combination(1.0, grams2[j], -1.0, eyes[k])) <= 1e-11:
-                            outs[i] = None
-                    todo = [i for i in todo if outs[i] is not None]
-        if _depth == 0 and todo:
-            # The structure argument also fails when a numerically DEPENDENT column sits in the middle of the block (an
-            # unstructured reflector pair there leaves a complement that is not invariant either, and every later column pair
-            # inherits it): A = Q_c R_c then no longer holds.  One more grouped GEMM checks the reconstruction; such blocks go
-            # back to the caller (None), which uses the Gram-Schmidt kernels with their completion of dependent columns.
-            prods = self.matrix_dot_grouped([[(outs[i][0], outs[i][1])] for i in todo])
-            for j, i in enumerate(todo):
-                scale = self.max_abs(srcs[i])
-                if scale > 0.0 and self.max_abs(self.linear_combination(1.0, prods[j], -1.0, srcs[i])) > 1e-11 * scale * max(srcs[i].shape):
-                    outs[i] = None
-        return outs
-
     def matrix_lq_batched(self, blocks, full=False):
-        """block_backend.cpp:1033-1040: q, r = qr(a^T); return r^T, q^T (views)."""
-        qrs = self.matrix_qr_batched([self.permute_axes(a, [1, 0]) for a in blocks], full)
-        return [(self.permute_axes(r, [1, 0]), self.permute_axes(q, [1, 0])) for q, r in qrs]
+        return _decomp.matrix_lq_batched(self, blocks, full)
 
     def matrix_lq(self, a: HipBlock, full: bool):
         return self.matrix_lq_batched([a], full)[0]
 
-    def _argsort_perm(self, w: np.ndarray, sort):
-        """block_backend.cpp:759-781."""
-        if sort in ('m<', 'SM'):
-            key = np.abs(w)
-        elif sort in ('m>', 'LM'):
-            key = -np.abs(w)
-        elif sort in ('<', 'SR', 'SA'):
-            key = w
-        elif sort in ('>', 'LR', 'LA'):
-            key = -w
-        else:
-            raise ValueError(f"Unknown sort option: '{sort}'")
-        return np.argsort(key, kind='stable')
-
-    # complex Hermitian blocks at least this large are diagonalised on the float64 block engine through the embedding
-    # (measured: 128 -> 4.5 vs 5.5 ms, 448 -> 24 vs 40 ms, 1024 -> 85 vs 181 ms, sixteen 256-blocks -> 13 vs 68 ms; the in-LDS
-    #  kernel of csvd_small.hip serves n <= 64 in 1.6 ms)
-    COMPLEX_EIGH_EMBED_MIN = 96
-
-    def _complex_eigh_embedded(self, srcs, return_info=False):
-        """np.linalg.eigh of complex Hermitian blocks on the float64 block engine: the one-sided block-Jacobi iteration
-        of the real path on the rows of M(H) + shift (exactly structured: no QR step is involved) with the structured
-        pivot solves of `CYB_EIGH_EMBEDDED_COMPLEX`.  Every eigenvalue comes out twice; real column 2a of the
-        eigenvector matrix is complex eigenvector a.  Returns ([(w, V)], info), or None where the engine refuses the list."""
-        n = len(srcs)
-        Ms = self._embed_complex(srcs)
-        flat = self._new_many([sh for a in srcs for sh in ((2 * a.shape[0],), (2 * a.shape[0], 2 * a.shape[0]))])
-        arr = np.zeros(n, dtype=_lib.EIGH_DTYPE)
-        ks = np.array([2 * a.shape[0] for a in srcs], dtype=np.int64)
-        arr['A'], arr['n'] = [M.ptr for M in Ms], ks
-        arr['lda'] = arr['ldv'] = np.maximum(ks, 1)
-        arr['W'], arr['V'] = [flat[2 * i].ptr for i in range(n)], [flat[2 * i + 1].ptr for i in range(n)]
-        info = (C.c_int32 * n)()
-        self.ctx.sync_stream()
-        st = self.lib.cyb_eigh_batched_ex_f64(self.ctx.handle, arr.ctypes.data_as(C.POINTER(_lib.EighDesc)), n, info,
-                                              _lib.CYB_EIGH_EMBEDDED_COMPLEX)
-        if st == _lib.CYB_ERR_UNSUPPORTED:
-            return None
-        _lib.check(st)
-        wflat = self._new_many([(a.shape[0],) for a in srcs])
-        vflat = self._new_many([(a.shape[0], a.shape[0]) for a in srcs], True)
-        items, pairs = [], []
-        for i in range(n):
-            k = srcs[i].shape[0]
-            items += self._extract_complex_items(flat[2 * i + 1], vflat[i])
-            if k:
-                pairs.append((wflat[i], HipBlock(self, flat[2 * i].buf, flat[2 * i].offset, (k,), (2,))))
-        self.lincomb_many(items)
-        self.copy_many(pairs)
-        return list(zip(wflat, vflat)), list(info)
-
-    def eigh_batched(self, blocks, sort=None, vectors=True, return_info=False, _embed=True):
-        """Hermitian EVD of every block: [(w ascending, V)] (np.linalg.eigh, numpy.cpp:658-680)."""
-        self._numeric_only(blocks, 'decomposition')
-        cplx = any(b.is_complex for b in blocks)
-        want_vectors = vectors
-        if cplx:  # eigenvectors are always computed on the complex paths
-            blocks = [self.as_complex(b) for b in blocks]
-            vectors = True
-        n = len(blocks)
-        srcs = self.contiguous_many(blocks)
-        for a in srcs:
-            if a.ndim != 2 or a.shape[0] != a.shape[1]:
-                raise ValueError('eigh: block must be a square matrix')
-        if cplx and n and _embed:
-            # large blocks: the float64 block engine on the interleaved embedding; small ones (and lists the engine refuses):
-            # the complex Jacobi kernels (csrc/csvd_small.hip, csrc/csvd_large.hip)
-            big = [i for i, a in enumerate(srcs) if a.shape[0] >= self.COMPLEX_EIGH_EMBED_MIN]
-            got = self._complex_eigh_embedded([srcs[i] for i in big], True) if big else None
-            if got is not None:
-                outs, info_all = [None] * n, [0] * n
-                for i, r, f in zip(big, *got):
-                    outs[i], info_all[i] = r, f
-                rest = [i for i in range(n) if outs[i] is None]
-                if rest:
-                    rres, rinfo = self.eigh_batched([srcs[i] for i in rest], None, True, True, _embed=False)
-                    for i, r, f in zip(rest, rres, rinfo):
-                        outs[i], info_all[i] = r, f
-                return self._eigh_finish(outs, info_all, sort, want_vectors, return_info)
-        shapes = []
-        for a in srcs:
-            shapes += [(a.shape[0],), (a.shape[0], a.shape[0])] if (vectors and not cplx) else [(a.shape[0],)]
-        flat = self._new_many(shapes)
-        if cplx:
-            vflat = self._new_many([(a.shape[0], a.shape[0]) for a in srcs], True)
-            outs = list(zip(flat, vflat))
-        else:
-            outs = [(flat[2 * i], flat[2 * i + 1]) for i in range(n)] if vectors else [(w, None) for w in flat]
-        arr = np.zeros(max(n, 1), dtype=_lib.EIGH_DTYPE)
-        if n:
-            ks = np.array([a.shape[0] for a in srcs], dtype=np.int64)
-            arr['A'][:n], arr['n'][:n] = [a.ptr for a in srcs], ks
-            arr['lda'][:n] = arr['ldv'][:n] = np.maximum(ks, 1)
-            arr['W'][:n] = [o[0].ptr for o in outs]
-            if vectors:
-                arr['V'][:n] = [o[1].ptr for o in outs]
-        descs = arr.ctypes.data_as(C.POINTER(_lib.EighDesc))
-        info = (C.c_int32 * max(n, 1))()
-        if n:
-            self.ctx.sync_stream()
-            fn = self.lib.cyb_eigh_batched_c128 if cplx else self.lib.cyb_eigh_batched_f64
-            _lib.check(fn(self.ctx.handle, descs, n, info if return_info else None))
-        return self._eigh_finish(outs, list(info)[:n], sort, want_vectors or not cplx, return_info)
-
-    def _eigh_finish(self, outs, info, sort, want_vectors, return_info):
-        if not want_vectors:
-            outs = [(w, None) for w, _ in outs]
-        if sort is not None:
-            res = []
-            for W, V in outs:
-                perm = self._argsort_perm(self.to_numpy(W), sort)
-                W2 = self._gather_axis(W, perm, 0)
-                V2 = self._gather_axis(V, perm, 1) if V is not None else None
-                res.append((W2, V2))
-            outs = res
-        if return_info:
-            return outs, info
-        return outs
+    def eigh_batched(self, blocks, sort=None, vectors=True, return_info=False):
+        return _decomp.eigh_batched(self, blocks, sort, vectors, return_info)
 
     def eigh(self, block: HipBlock, sort=None):
         return self.eigh_batched([block], sort)[0]
 
     def eigvalsh(self, block: HipBlock, sort=None):
         return self.eigh_batched([block], sort, vectors=False)[0][0]
+
+    # the C-ABI kernels without the embedded routes in front, and the embedded routes themselves (contiguous blocks of one dtype)
+    matrix_svd_batched_complex_direct = _decomp.svd_complex_direct
+    matrix_qr_batched_direct = _decomp.qr_direct
+    eigh_batched_direct = _decomp.eigh_direct
+    _complex_svd_embedded = _decomp.complex_svd_embedded
+    _complex_qr_embedded = _decomp.complex_qr_embedded
+    _complex_eigh_embedded = _decomp.complex_eigh_embedded
 
     # ------------------------------------------------------------------ small helpers of the API
     def block_from_diagonal(self, diag: HipBlock) -> HipBlock:

@@ -42,7 +42,7 @@ for n in (256, 512, 1024):
     z = crandn((n, n)); h = z + z.conj().T
     H = bb.as_block(h)
     t, (w, v) = timed(lambda: bb.eigh(H))
-    t_old = timed(lambda: bb.eigh_batched([H], _embed=False))[0]
+    t_old = timed(lambda: bb.eigh_batched_direct([H]))[0]
     w, v = bb.to_numpy(w), bb.to_numpy(v)
     t0 = time.perf_counter(); wr = np.linalg.eigh(h)[0]; tc = time.perf_counter() - t0
     nrm = np.linalg.norm(h)

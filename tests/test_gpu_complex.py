@@ -458,7 +458,7 @@ def test_complex_eigh_embedded_route(bb, rng):
     srcs = bb.contiguous_many([bb.as_block(h) for h in mats])
     got = bb._complex_eigh_embedded(srcs, return_info=True)
     assert got is not None
-    direct = bb.eigh_batched(srcs, _embed=False)
+    direct = bb.eigh_batched_direct(srcs)
     for h, (w, v), (wd, _) in zip(mats, got[0], direct):
         w, v = bb.to_numpy(w), bb.to_numpy(v)
         sc = np.abs(h).max() or 1.0
