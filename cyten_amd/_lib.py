@@ -290,6 +290,7 @@ PROTOTYPES = {
     'cyb_convert_u8_f64': [_ctx, _vp, _vp, C.c_int64],
     'cyb_count_nonzero_u8': [_ctx, _vp, C.c_int64, _vp],
     'cyb_extremum_f64': [_ctx, _vp, C.c_int64, C.c_int32, _vp],
+    'cyb_allclose_count': [_ctx, _vp, _vp, C.c_int64, C.c_int32, C.c_double, C.c_double, _vp],
 }
 _NON_STATUS = {'cyb_version': C.c_int, 'cyb_last_error': C.c_char_p}
 

@@ -2275,7 +2275,7 @@ def diagonal_from_full_tensor(bb, t: AbelianTensor, tol=None) -> DiagonalTensor:
     inds = _diagonal_block_inds(t, 'diagonal_from_full_tensor')
     if tol is not None and t.blocks:
         offs = [bb.off_diagonal_view(b) for b in bb.contiguous_many(list(t.blocks))]
-        if bb.max_abs_many([o for o in offs if o.size]) > tol:
+        if not bb.max_abs_many([o for o in offs if o.size]) <= tol:
             raise ValueError('Not a diagonal block.')
     cplx = any(_is_complex_block(b) for b in t.blocks)
     outs = bb.empty_many([(int(t.legs[0].mults[i]),) for i in inds], dtype='complex128' if cplx else None) if len(inds) else []

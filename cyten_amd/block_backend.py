@@ -1664,8 +1664,22 @@ class HipBlockBackend:
         return self._wdot(descs, cplx, False)
 
     def allclose(self, a, b, rtol=1e-5, atol=1e-8) -> bool:
-        diff = self.linear_combination(1.0, a, -1.0, b)
-        return self.max_abs(diff) <= atol + rtol * self.max_abs(b)
+        """``np.allclose(a, b, rtol, atol)`` (numpy.cpp:578-585): the ELEMENTWISE test ``|a - b| <= atol + rtol * |b|``,
+        equal infinities pass, a NaN on either side fails.  One fused launch counts the violations, one 8-byte read."""
+        if a.shape != b.shape:
+            raise ValueError(f'allclose: shape mismatch {a.shape} vs {b.shape}')
+        self._numeric_only([a, b], 'allclose')
+        cplx = a.is_complex or b.is_complex
+        if cplx:
+            a, b = self.as_complex(a), self.as_complex(b)
+        if a.size == 0:
+            return True
+        x, y = self.contiguous_many([a, b])
+        res = self.ctx.empty(1, 'int64')
+        self.ctx.sync_stream()
+        _lib.check(self.lib.cyb_allclose_count(self.ctx.handle, C.c_void_p(x.ptr), C.c_void_p(y.ptr), x.size, int(cplx),
+                                               float(rtol), float(atol), C.c_void_p(res.data_ptr())))
+        return int(self.ctx.d2h(res, 1, np.int64)[0]) == 0
 
     # ------------------------------------------------------------------ the hot path: GEMM
     def _matrix_view(self, a: HipBlock):
@@ -1943,7 +1957,7 @@ class HipBlockBackend:
         view = HipBlock(self, a.buf, a.offset, (n,), (a.strides[0] + a.strides[1],))
         if tol is not None:
             off = self.linear_combination(1.0, a, -1.0, self.block_from_diagonal(view))
-            if self.max_abs(off) > tol:
+            if not self.max_abs(off) <= tol:
                 raise ValueError('Not a diagonal block.')
         return self.copy_block(view)
 

@@ -35,10 +35,12 @@ __device__ __forceinline__ double wave_sum(double v)
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
+// max that keeps a NaN of either side (fmax would return the other operand): np.max(np.abs(x)) is NaN when x holds one
+__device__ __forceinline__ double nan_max(double a, double b) { return (a > b || a != a) ? a : b; }
 __device__ __forceinline__ double wave_max(double v)
 {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    for (int o = 32; o > 0; o >>= 1) v = nan_max(v, __shfl_xor(v, o));
     return v;
 }
 
@@ -110,7 +112,7 @@ struct VecDev {
     int64_t n;
 };
 
-// mode 0: sum x*y (y null: x*x) ; mode 1: max |x|
+// mode 0: sum x*y (y null: x*x) ; mode 1: max |x|, NaN if any element is NaN
 __device__ __forceinline__ void reduce_stage1_body(const VecDev& d, const Item& it, double* __restrict__ partial, int mode)
 {
     __shared__ double red[NT / 64];
@@ -145,16 +147,16 @@ __device__ __forceinline__ void reduce_stage1_body(const VecDev& d, const Item& 
     } else {
         for (int64_t i = threadIdx.x; i < nv; i += NT) {
             const d2v a = xv[i];
-            acc = fmax(acc, fmax(fabs(a.x), fabs(a.y)));
+            acc = nan_max(acc, nan_max(fabs(a.x), fabs(a.y)));
         }
-        for (int64_t e = it.start + 2 * nv + threadIdx.x; e < e1; e += NT) acc = fmax(acc, fabs(x[e]));
+        for (int64_t e = it.start + 2 * nv + threadIdx.x; e < e1; e += NT) acc = nan_max(acc, fabs(x[e]));
         acc = wave_max(acc);
     }
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
         double r = red[0];
-        for (int q = 1; q < NT / 64; ++q) r = (mode == 0) ? r + red[q] : fmax(r, red[q]);
+        for (int q = 1; q < NT / 64; ++q) r = (mode == 0) ? r + red[q] : nan_max(r, red[q]);
         partial[blockIdx.x] = r;
     }
 }
@@ -179,13 +181,13 @@ __device__ __forceinline__ void reduce_stage2_body(const double* __restrict__ pa
 {
     __shared__ double red[NT / 64];
     double acc = 0.0;
-    for (int64_t e = s0 + threadIdx.x; e < s1; e += NT) acc = (mode == 0) ? acc + partial[e] : fmax(acc, partial[e]);
+    for (int64_t e = s0 + threadIdx.x; e < s1; e += NT) acc = (mode == 0) ? acc + partial[e] : nan_max(acc, partial[e]);
     acc = (mode == 0) ? wave_sum(acc) : wave_max(acc);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
         double r = red[0];
-        for (int q = 1; q < NT / 64; ++q) r = (mode == 0) ? r + red[q] : fmax(r, red[q]);
+        for (int q = 1; q < NT / 64; ++q) r = (mode == 0) ? r + red[q] : nan_max(r, red[q]);
         result[blockIdx.x] = r;
     }
 }
@@ -221,10 +223,176 @@ __global__ void __launch_bounds__(NT) axpby_c128_kernel(const VecDev* __restrict
     }
 }
 
-// complex elementwise: op 0 |z| (real out), 1 sqrt, 2 exp, 3 log, 4 angle (real out), 5 z*w, 6 z/w (Smith)
+// complex elementwise: op 0 |z| (real out), 1 sqrt, 2 exp, 3 log, 4 angle (real out), 5 z*w, 6 z/w (Smith).
+// Non-finite arguments, signed zeros and arguments near the ends of the double range follow numpy (C99 Annex G):
+// tests/special_value_cases.py holds the grid.
+typedef double cd2 __attribute__((ext_vector_type(2)));
+#define CYB_DBL_MAX 1.7976931348623157e308
+
+// a product rounded on its own: the empty asm keeps -ffp-contract=fast from fusing it into the add that follows
+__device__ __forceinline__ double mul_rn(double a, double b)
+{
+    double p = a * b;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(p));
+#endif
+    return p;
+}
+
+// principal square root.  sqrt((|z| + |x|) / 2) with the operands scaled by a power of four where |z| + |x| would overflow
+// (1.5e308 + 1e308 i) or where the parts are denormal (the quotient y / 2t would lose its bits)
+__device__ __forceinline__ cd2 csqrt_c128(cd2 z)
+{
+    double x = z.x, y = z.y;
+    if (x == 0.0 && y == 0.0) return cd2{0.0, y};
+    if (fabs(y) == INFINITY) return cd2{INFINITY, y};          // also for a NaN real part
+    if (x != x) return cd2{x, __builtin_nan("")};
+    if (fabs(x) == INFINITY) {
+        if (x > 0.0) return cd2{x, y != y ? y : copysign(0.0, y)};
+        return cd2{y != y ? y : 0.0, copysign(INFINITY, y)};
+    }
+    if (y != y) return cd2{y, y};
+    const double hi = fmax(fabs(x), fabs(y));
+    double back = 1.0;
+    if (hi > 4e307) {
+        x *= 0.25, y *= 0.25, back = 2.0;
+    } else if (hi < 1e-290) {
+        x *= 0x1p108, y *= 0x1p108, back = 0x1p-54;
+    }
+    const double t = sqrt(0.5 * (hypot(x, y) + fabs(x)));
+    const cd2 r = x >= 0.0 ? cd2{t, y / (2.0 * t)} : cd2{fabs(y) / (2.0 * t), copysign(t, y)};
+    return cd2{r.x * back, r.y * back};
+}
+
+// sin and cos of an argument of 2^30 and beyond.  The device library's reduction for such arguments came out wrong by about
+// |x| 2^-55 on the MI355X (sincos(1.5e12) off by 3e-5, measured against mpmath; below 2^30 it is accurate), so exp of a complex
+// number with a large imaginary part reduces the argument itself: Payne-Hanek in integer arithmetic -- the 192 bits of 2 / pi
+// that decide the quadrant and the fraction of |x| = m 2^e, times the 53-bit integer m.  64 zero bits (the integer part), then
+// the first 1344 bits of 2 / pi:
+__device__ const unsigned long long kTwoOverPi[22] = {
+    0x0000000000000000ull, 0xa2f9836e4e441529ull, 0xfc2757d1f534ddc0ull, 0xdb6295993c439041ull,
+    0xfe5163abdebbc561ull, 0xb7246e3a424dd2e0ull, 0x06492eea09d1921cull, 0xfe1deb1cb129a73eull,
+    0xe88235f52ebb4484ull, 0xe99c7026b45f7e41ull, 0x3991d639835339f4ull, 0x9c845f8bbdf9283bull,
+    0x1ff897ffde05980full, 0xef2f118b5a0a6d1full, 0x6d367ecf27cb09b7ull, 0x4f463f669e5fea2dull,
+    0x7527bac7ebe5f17bull, 0x3d0739f78a5292eaull, 0x6bfb5fb11f8d5d08ull, 0x56033046fc7b6babull,
+    0xf0cfbc209af4361dull, 0xa9e391615ee61b08ull
+};
+__device__ __forceinline__ void sincos_large(double x, double* sn, double* cs)
+{
+    int E;
+    const double fr = frexp(fabs(x), &E);                       // |x| = fr 2^E = m 2^e, m a 53-bit integer
+    const unsigned long long m = (unsigned long long)ldexp(fr, 53);
+    const int i0 = 62 + (E - 53);                               // first bit of 2/pi (after 64 zero integer bits) whose product with m is below 4
+    const int wi = i0 >> 6, bo = i0 & 63;
+    unsigned long long v[3];
+    for (int k = 0; k < 3; ++k)
+        v[k] = bo ? (kTwoOverPi[wi + k] << bo) | (kTwoOverPi[wi + k + 1] >> (64 - bo)) : kTwoOverPi[wi + k];
+    // m * (v[0] : v[1] : v[2]) as four 64-bit limbs r3 : r2 : r1 : r0; bit 190 has weight one quadrant
+    const unsigned __int128 p0 = (unsigned __int128)m * v[2];
+    const unsigned __int128 p1 = (unsigned __int128)m * v[1] + (unsigned long long)(p0 >> 64);
+    const unsigned __int128 p2 = (unsigned __int128)m * v[0] + (unsigned long long)(p1 >> 64);
+    const unsigned long long r0 = (unsigned long long)p0, r1 = (unsigned long long)p1, r2 = (unsigned long long)p2;
+    int q = (int)(r2 >> 62) & 3;
+    unsigned long long fh = (r2 << 2) | (r1 >> 62), fl = (r1 << 2) | (r0 >> 62); // the fraction of a quadrant, 128 bits
+    double sign = 1.0;
+    if (fh >> 63) { // beyond half a quadrant: the next one, from above
+        q = (q + 1) & 3;
+        fl = ~fl + 1ull;
+        fh = ~fh + (fl == 0ull ? 1ull : 0ull);
+        sign = -1.0;
+    }
+    int lz = 0;
+    if (fh == 0ull) {
+        fh = fl;
+        fl = 0ull;
+        lz = 64;
+    }
+    if (fh != 0ull) {
+        const int z = __builtin_clzll(fh);
+        if (z) fh = (fh << z) | (fl >> (64 - z));
+        lz += z;
+    }
+    // fraction = fh 2^-(64 + lz): its upper 53 bits and the 11 below them, times pi / 2 = hi + lo
+    const double f1 = ldexp((double)(fh & ~0x7FFull), -(64 + lz)), f2 = ldexp((double)(fh & 0x7FFull), -(64 + lz));
+    const double pio2_hi = 1.5707963267948966, pio2_lo = 6.123233995736766e-17;
+    const double rh = f1 * pio2_hi;
+    const double r = sign * (rh + (fma(f1, pio2_hi, -rh) + (f1 * pio2_lo + f2 * pio2_hi)));
+    double s, c;
+    sincos(r, &s, &c);
+    if (q & 1) {
+        const double t = s;
+        s = c;
+        c = -t;
+    }
+    if (q & 2) s = -s, c = -c;
+    *sn = x < 0.0 ? -s : s;
+    *cs = c;
+}
+
+// exp(x) (cos y + i sin y).  A zero imaginary part stays a zero of its sign (inf * sin(0) would be NaN); exp(x) beyond the
+// double range is applied in two factors so that exp(x) sin(y) can stay finite (710 + 1e-3 i); an infinite or NaN
+// imaginary part gives C99's results: 0 for x = -inf, (inf, NaN) for x = +inf, NaN otherwise
+__device__ __forceinline__ cd2 cexp_c128(cd2 z)
+{
+    const double x = z.x, y = z.y;
+    if (y == 0.0) return cd2{exp(x), y};
+    if (!(fabs(y) <= CYB_DBL_MAX)) {
+        if (x == -INFINITY) return cd2{0.0, copysign(0.0, y)};
+        if (x == INFINITY) return cd2{x, __builtin_nan("")};
+        return cd2{__builtin_nan(""), __builtin_nan("")};
+    }
+    double sn, cs;
+    if (fabs(y) >= 0x1p30) sincos_large(y, &sn, &cs);
+    else sincos(y, &sn, &cs);
+    if (x > 709.0 && x < INFINITY) {
+        const double e1 = exp(709.0), e2 = exp(x - 709.0);
+        return cd2{(cs * e1) * e2, (sn * e1) * e2};
+    }
+    const double ex = exp(x);
+    return cd2{ex * cs, ex * sn};
+}
+
+// log|z| + i arg z.  |z| near 1: log1p of |z|^2 - 1, summed without cancellation error (the squares with their FMA
+// remainders), so that the real part keeps a RELATIVE accuracy (log(hypot) returns 0 for 1 + 1e-9 i, the value is 5e-19).
+// Parts beyond 1e154 or below 1e-150 are scaled by 2^-+600 before the hypot.
+__device__ __forceinline__ cd2 clog_c128(cd2 z)
+{
+    const double ax = fabs(z.x), ay = fabs(z.y);
+    const double im = atan2(z.y, z.x);
+    if (ax != ax || ay != ay) return cd2{(ax == INFINITY || ay == INFINITY) ? INFINITY : __builtin_nan(""), im};
+    const double hi = fmax(ax, ay), lo = fmin(ax, ay);
+    if (hi == INFINITY) return cd2{hi, im};
+    if (hi == 0.0) return cd2{-INFINITY, im};
+    const double ln2_600 = 600.0 * 0.6931471805599453;
+    if (hi > 1e154) return cd2{log(hypot(hi * 0x1p-600, lo * 0x1p-600)) + ln2_600, im};
+    if (hi < 1e-150) return cd2{log(hypot(hi * 0x1p600, lo * 0x1p600)) - ln2_600, im};
+    if (hi >= 0.5 && hi <= 2.0) {
+        // |z|^2 - 1 = 2 d + d^2 + lo^2 with d = hi - 1 (exact): the two squares as (product, FMA remainder) pairs
+        const double d = hi - 1.0;
+        const double p1 = mul_rn(d, d), e1 = fma(d, d, -p1);
+        const double p2 = mul_rn(lo, lo), e2 = fma(lo, lo, -p2);
+        const double s1 = p1 + p2, b1 = s1 - p1, r1 = (p1 - (s1 - b1)) + (p2 - b1);
+        const double a = 2.0 * d, s2 = a + s1, b2 = s2 - a, r2 = (a - (s2 - b2)) + (s1 - b2);
+        return cd2{0.5 * log1p(s2 + (r2 + r1 + e1 + e2)), im};
+    }
+    return cd2{log(hypot(hi, lo)), im};
+}
+
+// Smith's division.  A zero divisor divides each part by +0 (numpy's rule: inf / NaN per component)
+__device__ __forceinline__ cd2 cdiv_c128(cd2 z, cd2 w)
+{
+    if (w.x == 0.0 && w.y == 0.0) return cd2{z.x / 0.0, z.y / 0.0};
+    if (fabs(w.x) >= fabs(w.y)) {
+        const double q = w.y / w.x, den = w.x + w.y * q;
+        return cd2{(z.x + z.y * q) / den, (z.y - z.x * q) / den};
+    }
+    const double q = w.x / w.y, den = w.x * q + w.y;
+    return cd2{(z.x * q + z.y) / den, (z.y * q - z.x) / den};
+}
+
 __global__ void __launch_bounds__(NT) celementwise_kernel(const VecDev* __restrict__ descs, const Item* __restrict__ items, int op)
 {
-    typedef double d2v __attribute__((ext_vector_type(2)));
+    typedef cd2 d2v;
     const Item it = items[blockIdx.x];
     const VecDev d = descs[it.desc];
     const GLOBAL_AS d2v* x = (const GLOBAL_AS d2v*)d.x;
@@ -243,40 +411,17 @@ __global__ void __launch_bounds__(NT) celementwise_kernel(const VecDev* __restri
         }
         d2v r;
         switch (op) {
-        case 1: { // principal square root
-            const double m = hypot(z.x, z.y);
-            if (m == 0.0) {
-                r = d2v{0.0, z.y};
-            } else {
-                const double t = sqrt(0.5 * (m + fabs(z.x)));
-                r = z.x >= 0.0 ? d2v{t, z.y / (2.0 * t)} : d2v{fabs(z.y) / (2.0 * t), copysign(t, z.y)};
-            }
-            break;
-        }
-        case 2: {
-            const double ex = exp(z.x);
-            double sn, cs;
-            sincos(z.y, &sn, &cs);
-            r = d2v{ex * cs, ex * sn};
-            break;
-        }
-        case 3: r = d2v{log(hypot(z.x, z.y)), atan2(z.y, z.x)}; break;
+        case 1: r = csqrt_c128(z); break;
+        case 2: r = cexp_c128(z); break;
+        case 3: r = clog_c128(z); break;
         case 5: {
+            // numpy's vectorised loop (fmaddsub): the products with z.y are rounded, those with z.x fused into the sum --
+            // which part overflows to Inf and which to NaN depends on it, so the contraction is spelled out
             const d2v w = y[e];
-            r = d2v{z.x * w.x - z.y * w.y, z.x * w.y + z.y * w.x};
+            r = d2v{fma(z.x, w.x, -mul_rn(z.y, w.y)), fma(z.x, w.y, mul_rn(z.y, w.x))};
             break;
         }
-        default: {
-            const d2v w = y[e];
-            if (fabs(w.x) >= fabs(w.y)) {
-                const double q = w.y / w.x, den = w.x + w.y * q;
-                r = d2v{(z.x + z.y * q) / den, (z.y - z.x * q) / den};
-            } else {
-                const double q = w.x / w.y, den = w.x * q + w.y;
-                r = d2v{(z.x * q + z.y) / den, (z.y * q - z.x) / den};
-            }
-            break;
-        }
+        default: r = cdiv_c128(z, y[e]); break;
         }
         outc[e] = r;
     }
@@ -290,16 +435,28 @@ __global__ void __launch_bounds__(NT) celementwise_kernel(const VecDev* __restri
 // size go through exponentiation by squaring (every partial product exact in the representable cases).
 __device__ __forceinline__ double pow_exactish(double x, double y)
 {
+    // x ** 0.5 is a correctly rounded square root in numpy; the device pow() was 5 ulp off at 1e10 ** 0.5.  pow's own edge
+    // cases: (-0) ** 0.5 = +0, (-inf) ** 0.5 = +inf
+    if (y == 0.5) return x == -INFINITY ? INFINITY : sqrt(x) + 0.0;
     const double yi = rint(y);
     if (yi == y && fabs(y) <= 4096.0) {
         unsigned int n = (unsigned int)fabs(yi);
+        const bool n_odd = n & 1u;
         double base = x, r = 1.0;
         while (n) {
             if (n & 1u) r *= base;
             base *= base;
             n >>= 1;
         }
-        return yi < 0.0 ? 1.0 / r : r;
+        // every partial product was exact or rounded once while r stayed a normal number
+        if (fabs(r) >= 2.2250738585072014e-308 && fabs(r) <= 1.7976931348623157e308) return yi < 0.0 ? 1.0 / r : r;
+        // r overflowed (2.0 ** -1074 is 5e-324, not 1 / inf), is denormal, zero or NaN: a power of two exactly by ldexp,
+        // everything else by pow()
+        int ex;
+        if (frexp(fabs(x), &ex) == 0.5) {
+            const double mag = ldexp(1.0, (int)((double)(ex - 1) * yi));
+            return (x < 0.0 && (n_odd)) ? -mag : mag;
+        }
     }
     return pow(x, y);
 }
@@ -584,14 +741,44 @@ __global__ void __launch_bounds__(NT) count_nonzero_kernel(const uint8_t* __rest
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(result, c); // integer atomics: order-independent, deterministic
 }
 
-// extremum with its flat index (ties: lowest index, like np.argmax / np.argmin): mode 0 max, 1 min, 2 max |x|
+// np.allclose as a count of violations: an element passes when x == y (equal infinities) or when both are finite and
+// |x - y| <= atol + rtol * |y|; a NaN on either side fails.  cplx: interleaved (re, im) elements, |.| the complex modulus.
+__global__ void __launch_bounds__(NT) allclose_count_kernel(const double* __restrict__ x_, const double* __restrict__ y_, int64_t n, int cplx,
+                                                            double rtol, double atol, unsigned long long* __restrict__ result)
+{
+    typedef double d2v __attribute__((ext_vector_type(2)));
+    gcp x = (gcp)x_;
+    gcp y = (gcp)y_;
+    const double big = 1.7976931348623157e308;
+    unsigned long long c = 0;
+    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += (int64_t)gridDim.x * NT) {
+        bool ok;
+        if (cplx) {
+            const d2v a = ((const GLOBAL_AS d2v*)x)[e], b = ((const GLOBAL_AS d2v*)y)[e];
+            const bool fin = fabs(a.x) <= big && fabs(a.y) <= big && fabs(b.x) <= big && fabs(b.y) <= big;
+            ok = (a.x == b.x && a.y == b.y) || (fin && hypot(a.x - b.x, a.y - b.y) <= atol + rtol * hypot(b.x, b.y));
+        } else {
+            const double a = x[e], b = y[e];
+            ok = a == b || (fabs(a) <= big && fabs(b) <= big && fabs(a - b) <= atol + rtol * fabs(b));
+        }
+        c += ok ? 0 : 1;
+    }
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(result, c); // integer atomics: order-independent, deterministic
+}
+
+// extremum with its flat index (ties: lowest index, like np.argmax / np.argmin): mode 0 max, 1 min, 2 max |x|.
+// NaN: the key is NaN and the index that of the first NaN, in every mode (np.max / np.min / np.argmax / np.argmin)
 struct Ext {
     double v;
     long long i;
 };
 __device__ __forceinline__ bool ext_better(double v, long long i, double bv, long long bi)
 {
-    return bi < 0 || v > bv || (v == bv && i < bi);
+    if (bi < 0) return true;
+    const bool vn = v != v, bn = bv != bv; // a NaN key ranks above every number (np.max / np.argmax), the first one wins
+    if (vn || bn) return vn && (!bn || i < bi);
+    return v > bv || (v == bv && i < bi);
 }
 __device__ __forceinline__ void ext_wave(double& v, long long& i)
 {
@@ -962,6 +1149,19 @@ int cyb_count_nonzero_u8(cyb_ctx_t ctx, const uint8_t* x, int64_t n, uint64_t* r
     if (n == 0) return CYB_OK;
     const unsigned grid = (unsigned)std::min<int64_t>(cdiv64(n, NT * 16), 2048);
     hipLaunchKernelGGL(count_nonzero_kernel, dim3(grid), dim3(NT), 0, ctx->stream, x, n,
+                       reinterpret_cast<unsigned long long*>(result_dev));
+    CYB_HIP(hipGetLastError());
+    return CYB_OK;
+}
+
+int cyb_allclose_count(cyb_ctx_t ctx, const double* x, const double* y, int64_t n, int32_t is_complex, double rtol, double atol,
+                       uint64_t* result_dev)
+{
+    CYB_REQUIRE(ctx && result_dev && n >= 0 && (n == 0 || (x && y)), "cyb_allclose_count: bad argument");
+    CYB_HIP(hipMemsetAsync(result_dev, 0, sizeof(uint64_t), ctx->stream));
+    if (n == 0) return CYB_OK;
+    const unsigned grid = (unsigned)std::min<int64_t>(cdiv64(n, NT * 8), 2048);
+    hipLaunchKernelGGL(allclose_count_kernel, dim3(grid), dim3(NT), 0, ctx->stream, x, y, n, is_complex ? 1 : 0, rtol, atol,
                        reinterpret_cast<unsigned long long*>(result_dev));
     CYB_HIP(hipGetLastError());
     return CYB_OK;

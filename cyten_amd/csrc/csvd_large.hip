@@ -195,7 +195,12 @@ __global__ void __launch_bounds__(NT) cl_round_kernel(const Jac* __restrict__ pr
     const double null2 = d.V ? d.stat[3] : 0.0;
     const double ag = sqrt(gr * gr + gi * gi);
     const double den = sqrt(app) * sqrt(aqq);
-    if (!(app > null2 && aqq > null2 && ag > 1e-15 * den)) return;
+    if (!(app > null2 && aqq > null2 && ag > 1e-15 * den)) {
+        // a NaN or Inf among them (a non-finite entry of the block) fails every test: that is no convergence -- the measure
+        // becomes +inf, the block stays active and the sweep budget reports it
+        if (tid == 0 && !(app + aqq + ag + null2 < __builtin_huge_val())) atomicMax(d.off, 0x7f800000u);
+        return;
+    }
     if (tid == 0) atomicMax(d.off, __float_as_uint((float)fmin(ag / den, 1.0)));
     const d2 ph = d2{gr / ag, -gi / ag}; // e^{-i arg g}
     const double zeta = (aqq - app) / (2.0 * ag);
@@ -413,6 +418,7 @@ int jacobi_sweeps(cyb_ctx_t ctx, std::vector<Jac>& jac, uint32_t* d_off, std::ve
     const int np = (int)jac.size();
     std::vector<uint32_t> off((size_t)np);
     std::vector<float> prev((size_t)np, 2.0f);
+    bool nonfinite = false;
     for (int sweep = 0; sweep < MAX_SWEEPS; ++sweep) {
         int base = 0, rounds = 0;
         for (Jac& j : jac) {
@@ -422,7 +428,7 @@ int jacobi_sweeps(cyb_ctx_t ctx, std::vector<Jac>& jac, uint32_t* d_off, std::ve
                 rounds = std::max(rounds, j.ncol - 1);
             }
         }
-        if (base == 0) return CYB_OK;
+        if (base == 0) break;
         void* d_jac = nullptr;
         CYB_TRY(ctx->upload(jac.data(), sizeof(Jac) * jac.size(), &d_jac));
         CYB_HIP(hipMemsetAsync(d_off, 0, sizeof(uint32_t) * (size_t)np, ctx->stream));
@@ -436,6 +442,12 @@ int jacobi_sweeps(cyb_ctx_t ctx, std::vector<Jac>& jac, uint32_t* d_off, std::ve
             ++sweeps[(size_t)i];
             float f;
             std::memcpy(&f, &off[(size_t)i], sizeof(float));
+            if (!(f <= 1.0f)) { // +inf: the block holds NaN or Inf (cl_round_kernel) -- further sweeps cannot change that
+                jac[(size_t)i].active = 0;
+                sweeps[(size_t)i] = -1;
+                nonfinite = true;
+                continue;
+            }
             // the measure was taken BEFORE each pair's rotation: at 1e-10 the rotations just applied leave the columns
             // orthogonal to rounding -- IF the iteration is in its quadratic regime, which a multiple singular value spoils
             // (rotations inside the cluster pass the couplings to the other columns on instead of annihilating them: the
@@ -446,7 +458,7 @@ int jacobi_sweeps(cyb_ctx_t ctx, std::vector<Jac>& jac, uint32_t* d_off, std::ve
             prev[(size_t)i] = f;
         }
     }
-    int st = CYB_OK;
+    int st = nonfinite ? CYB_ERR_NOCONV : CYB_OK;
     for (size_t i = 0; i < jac.size(); ++i)
         if (jac[i].active) {
             sweeps[i] = -1;

@@ -193,7 +193,8 @@ __global__ void __launch_bounds__(NT) csvd_small_kernel(const CDesc* __restrict_
         converged = (flag == 0);
         __syncthreads();
     }
-    if (tid == 0) sweeps_out[blockIdx.x] = converged ? sweeps : -1;
+    // a NaN or Inf entry makes every test above false (no rotation, "converged" after one sweep): report it as not converged
+    if (tid == 0) sweeps_out[blockIdx.x] = (converged && fro2 < __builtin_huge_val()) ? sweeps : -1;
     // ---- singular values and their descending order
     for (int c = grp; c < Np; c += NT / 8) {
         double s2 = 0.0;

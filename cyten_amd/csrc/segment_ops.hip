@@ -239,7 +239,9 @@ __device__ inline d2 red_term(d2 v, int kind, int op, int pre, double param)
     case CYB_SEG_PRE_ABS: v = d2{kind == CYB_SEG_C128 ? hypot(v.x, v.y) : fabs(v.x), 0.0}; break;
     case CYB_SEG_PRE_SQUARE: v = d2{v.x * v.x, 0.0}; break;
     case CYB_SEG_PRE_XLOGX: v = d2{v.x > param ? v.x * log(v.x) : 0.0, 0.0}; break;
-    case CYB_SEG_PRE_POW: v = d2{pow(v.x, param), 0.0}; break;
+    case CYB_SEG_PRE_POW: // (x ** 0.5 as Block::pow computes it: a correctly rounded square root, blockops.hip pow_exactish)
+        v = d2{param == 0.5 ? (v.x == -INFINITY ? INFINITY : sqrt(v.x) + 0.0) : pow(v.x, param), 0.0};
+        break;
     default: break;
     }
     if (op == CYB_SEG_COUNT) return d2{(v.x != 0.0 || v.y != 0.0) ? 1.0 : 0.0, 0.0};

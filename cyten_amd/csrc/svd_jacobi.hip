@@ -1591,6 +1591,40 @@ static int svd_batched_ranged(cyb_ctx_t ctx, const cyb_svd_desc* descs, int64_t 
         }
     std::vector<double> amax;
     CYB_TRY(cyb::matrix_amax(ctx, refs, amax));
+    // A block with a NaN or Inf entry (matrix_amax reports NaN for it) has no decomposition: np.linalg.svd raises
+    // LinAlgError.  Its Jacobi iteration would not say so -- every comparison with a NaN is false, so no pair is rotated
+    // and the sweep counts as converged.  Such blocks are left out, the others are decomposed as usual, and the call
+    // reports CYB_ERR_NOCONV with info = -1 for them.
+    std::vector<int64_t> bad;
+    for (size_t k = 0; k < refs.size(); ++k)
+        if (amax[k] != amax[k]) bad.push_back(which[k]);
+    if (!bad.empty()) {
+        std::vector<cyb_svd_desc> good;
+        std::vector<int64_t> good_idx;
+        for (int64_t b = 0, nb = 0; b < n; ++b) {
+            if (nb < (int64_t)bad.size() && bad[(size_t)nb] == b) {
+                ++nb;
+                continue;
+            }
+            good.push_back(descs[b]);
+            good_idx.push_back(b);
+        }
+        std::vector<int32_t> ginfo(good.size() + 1, 0), grank(good.size() + 1, 0);
+        const int st = good.empty() ? CYB_OK : svd_batched_ranged(ctx, good.data(), (int64_t)good.size(), info ? ginfo.data() : nullptr, flags,
+                                                                  rank ? grank.data() : nullptr);
+        if (st != CYB_OK && st != CYB_ERR_NOCONV) return st;
+        if (rank) CYB_HIP(hipStreamSynchronize(ctx->stream));
+        for (size_t g = 0; g < good.size(); ++g) {
+            if (info) info[good_idx[g]] = ginfo[g];
+            if (rank) rank[good_idx[g]] = grank[g];
+        }
+        for (int64_t b : bad) {
+            if (info) info[b] = -1;
+            if (rank) rank[b] = 0;
+        }
+        cyb::set_error("svd: %zu block(s) hold NaN or Inf entries (first: block %lld)", bad.size(), (long long)bad[0]);
+        return CYB_ERR_NOCONV;
+    }
     std::vector<cyb_svd_desc> mod;
     std::vector<void*> temps;
     std::vector<cyb::ScaleJob> pre, post;
@@ -1652,6 +1686,31 @@ static int eigh_batched_ranged(cyb_ctx_t ctx, const cyb_eigh_desc* descs, int64_
         }
     std::vector<double> amax;
     CYB_TRY(cyb::matrix_amax(ctx, refs, amax));
+    // (blocks with NaN or Inf entries: as in svd_batched_ranged)
+    std::vector<int64_t> bad;
+    for (size_t k = 0; k < refs.size(); ++k)
+        if (amax[k] != amax[k]) bad.push_back(which[k]);
+    if (!bad.empty()) {
+        std::vector<cyb_eigh_desc> good;
+        std::vector<int64_t> good_idx;
+        for (int64_t b = 0, nb = 0; b < n; ++b) {
+            if (nb < (int64_t)bad.size() && bad[(size_t)nb] == b) {
+                ++nb;
+                continue;
+            }
+            good.push_back(descs[b]);
+            good_idx.push_back(b);
+        }
+        std::vector<int32_t> ginfo(good.size() + 1, 0);
+        const int st = good.empty() ? CYB_OK : eigh_batched_ranged(ctx, good.data(), (int64_t)good.size(), info ? ginfo.data() : nullptr, flags);
+        if (st != CYB_OK && st != CYB_ERR_NOCONV) return st;
+        for (size_t g = 0; g < good.size(); ++g)
+            if (info) info[good_idx[g]] = ginfo[g];
+        for (int64_t b : bad)
+            if (info) info[b] = -1;
+        cyb::set_error("eigh: %zu block(s) hold NaN or Inf entries (first: block %lld)", bad.size(), (long long)bad[0]);
+        return CYB_ERR_NOCONV;
+    }
     std::vector<cyb_eigh_desc> mod;
     std::vector<void*> temps;
     std::vector<cyb::ScaleJob> pre, post;

@@ -225,8 +225,20 @@ def complex_svd_embedded(bb, srcs, return_info=False, null_vectors=True):
     cranks = [int(r) // 2 for r in rank]
     # (columns that count: all of them, or -- null vectors skipped -- the leading rank)
     kk = [min(srcs[i].shape) if null_vectors else cranks[i] for i in range(n)]
-    todo = [i for i in range(n) if kk[i] > 0]
+    # (info < 0 with rank 0: a block the engine left out because it holds NaN or Inf -- nothing was written for it, the
+    #  complex Jacobi kernels below get it and report the failure)
+    left_out = [i for i in range(n) if info[i] < 0 and int(rank[i]) == 0 and min(srcs[i].shape) > 0]
+    todo = [i for i in range(n) if kk[i] > 0 and i not in left_out]
+
+    def redo(failing):
+        fres, finfo = bb.matrix_svd_batched_complex_direct([srcs[i] for i in failing], True)
+        for i, r, f in zip(failing, fres, finfo):
+            res[i], info[i], cranks[i] = r, f, min(srcs[i].shape)
+        return res, info, cranks
+
     if not todo:
+        if left_out:
+            return redo(left_out)
         _lib.check(st)   # (no convergence, and no block to check)
         return res, info, cranks
     # Orthonormality in the COMPLEX sense ("Read-off"): the even real columns of U (rows of Vh) are
@@ -243,7 +255,7 @@ def complex_svd_embedded(bb, srcs, return_info=False, null_vectors=True):
     bad_u, bad_v = [], []
     for j in range(len(todo)):
         for g, lst in ((grams[j], bad_u), (grams[len(todo) + j], bad_v)):
-            if bb.max_abs(_gram_defect(bb, g, eyes)) > COMPLEX_SVD_ORTHO_TOL:
+            if not bb.max_abs(_gram_defect(bb, g, eyes)) <= COMPLEX_SVD_ORTHO_TOL:
                 lst.append(j)
     if bad_u or bad_v:
         qs = [q for q, _ in bb.matrix_qr_batched([uc[j] for j in bad_u] + [vt[j] for j in bad_v], False)]
@@ -259,11 +271,8 @@ def complex_svd_embedded(bb, srcs, return_info=False, null_vectors=True):
     diffs = bb.linear_combination_many(1.0, recon, -1.0, [srcs[i] for i in todo])
     failing = [i for j, i in enumerate(todo)
                if not bb.max_abs(diffs[j]) <= COMPLEX_SVD_RECON_TOL * np.sqrt(max(srcs[i].shape)) * bb.max_abs(srcs[i])]
-    if failing:
-        fres, finfo = bb.matrix_svd_batched_complex_direct([srcs[i] for i in failing], True)
-        for i, r, f in zip(failing, fres, finfo):
-            res[i], info[i], cranks[i] = r, f, min(srcs[i].shape)
-    return res, info, cranks
+    failing = sorted(failing + left_out)
+    return redo(failing) if failing else (res, info, cranks)
 
 
 # ---- QR / LQ
@@ -356,8 +365,8 @@ def complex_qr_embedded(bb, srcs, full=False, _depth=0):
         qs = [outs[i][0] for i in todo]
         diffs = [_gram_defect(bb, g, eyes) for g in _products(bb, [bb.dagger(q) for q in qs], qs)]
         bad = []
-        if bb.max_abs_many(diffs) > COMPLEX_QR_ORTHO_TOL:   # (one read-back for the list; per block only if needed)
-            bad = [i for i, df in zip(todo, diffs) if bb.max_abs(df) > COMPLEX_QR_ORTHO_TOL]
+        if not bb.max_abs_many(diffs) <= COMPLEX_QR_ORTHO_TOL:   # (one read-back for the list; per block only if needed)
+            bad = [i for i, df in zip(todo, diffs) if not bb.max_abs(df) <= COMPLEX_QR_ORTHO_TOL]
         if bad:
             second = bb._complex_qr_embedded([outs[i][0] for i in bad], False, _depth + 1)
             newr = _products(bb, [S for _, S in second], [outs[i][1] for i in bad])
@@ -377,7 +386,7 @@ def complex_qr_embedded(bb, srcs, full=False, _depth=0):
         prods = _products(bb, [outs[i][0] for i in todo], [outs[i][1] for i in todo])
         for j, i in enumerate(todo):
             scale = bb.max_abs(srcs[i])
-            if scale > 0.0 and bb.max_abs(bb.linear_combination(1.0, prods[j], -1.0, srcs[i])) > COMPLEX_QR_RECON_TOL * scale * max(srcs[i].shape):
+            if scale != 0.0 and not bb.max_abs(bb.linear_combination(1.0, prods[j], -1.0, srcs[i])) <= COMPLEX_QR_RECON_TOL * scale * max(srcs[i].shape):
                 outs[i] = None
     return outs
 

@@ -399,7 +399,7 @@ def discard_zero_blocks(bb, data: FusionTreeData, eps: float) -> FusionTreeData:
     largest entry is at most `eps` are dropped -- ONE batched reduction decides for the whole tensor when the backend has one"""
     if not data.blocks:
         return data
-    keep = [n for n, b in enumerate(data.blocks) if bb.max_abs(b) > eps]
+    keep = [n for n, b in enumerate(data.blocks) if not bb.max_abs(b) <= eps]
     if len(keep) == len(data.blocks):
         return data
     return FusionTreeData(data.block_inds[keep], [data.blocks[n] for n in keep])

@@ -291,7 +291,8 @@ int cyb_dot_batched_f64(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t n, dou
 int cyb_dot_each_f64(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t n, double* result_dev);
 /* out = a*x + b*y  for every entry (y may be NULL with b ignored) */
 int cyb_axpby_batched_f64(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t n, double a, double b);
-/* result_dev[0] = max_i |x_i| over the whole list */
+/* result_dev[0] = max_i |x_i| over the whole list; NaN if any element of any entry is NaN (np.max(np.abs(x))), 0 for an
+ * empty list */
 int cyb_maxabs_batched_f64(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t n, double* result_dev);
 /* elementwise binary op on contiguous lists: out = x (op) y; op: 0 add, 1 sub, 2 mul, 3 div, 4 pow (Block::pow(Block), numpy.cpp power) */
 int cyb_binary_batched_f64(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t n, int32_t op);
@@ -313,8 +314,16 @@ int cyb_convert_u8_f64(cyb_ctx_t ctx, const uint8_t* x, double* out, int64_t n);
 int cyb_count_nonzero_u8(cyb_ctx_t ctx, const uint8_t* x, int64_t n, uint64_t* result_dev);
 /* extremum of a contiguous vector together with its flat index, ties resolved to the lowest index like np.argmax /
  * np.argmin: mode 0 max (numpy.cpp:871-878), 1 min (:889-896, argmin :552-566), 2 max |x| (abs_argmax :533-550).
- * result_dev[0] = the maximised key (x, -x or |x|), result_dev[1] = the index as an int64 bit pattern. */
+ * result_dev[0] = the maximised key (x, -x or |x|), result_dev[1] = the index as an int64 bit pattern.
+ * NaN rule (np.max / np.min / np.argmax / np.argmin): a NaN ranks above every number in every mode -- if the vector
+ * holds one, the key is NaN and the index is that of the first NaN.  -0.0 and 0.0 compare equal (lowest index wins). */
 int cyb_extremum_f64(cyb_ctx_t ctx, const double* x, int64_t n, int32_t mode, double* result_dev);
+/* result_dev[0] = number of elements that FAIL np.isclose(x, y, rtol, atol): an element passes when x == y (equal
+ * infinities included) or when both are finite and |x - y| <= atol + rtol * |y|.  NaN rule: a NaN on either side fails
+ * (equal_nan=False).  is_complex: n interleaved (re, im) elements, |.| the modulus, finite = both parts finite.
+ * np.allclose is `result == 0` (numpy.cpp:578-585).  Contiguous operands. */
+int cyb_allclose_count(cyb_ctx_t ctx, const double* x, const double* y, int64_t n, int32_t is_complex, double rtol, double atol,
+                       uint64_t* result_dev);
 
 /* out[i, j, k] = x[i, j, k] * f[j]  for a block viewed as (outer, axis, inner), contiguous.
  * Replaces scale_axis (numpy.cpp:1373-1385). */
@@ -356,7 +365,10 @@ int cyb_complex_expand_batched_f64(cyb_ctx_t ctx, const cyb_cexpand_desc* descs,
  * linear_combination for complex128 (numpy.cpp:1358-1365) */
 /* elementwise functions of complex vectors (desc.n complex elements; x, y interleaved complex): op 0 |z| and
  * 4 angle write desc.n doubles to out; 1 sqrt, 2 exp, 3 log, 5 z*w, 6 z/w write complex
- * (abs / sqrt / exp / log / angle numpy.cpp:449-456,1066-1073,730-737,862-869,587-594; Block::operator* /  :217-227) */
+ * (abs / sqrt / exp / log / angle numpy.cpp:449-456,1066-1073,730-737,862-869,587-594; Block::operator* /  :217-227).
+ * NaN, Inf, signed zeros and arguments near the ends of the double range give numpy's results (C99 Annex G for sqrt /
+ * exp / log; z*w rounds the products with Im z and fuses those with Re z like numpy's vectorised loop; z/0 divides each
+ * part by +0).  A quotient by a non-zero divisor whose parts are both denormal is computed directly (numpy overflows). */
 int cyb_elementwise_batched_c128(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t n, int32_t op);
 int cyb_axpby_batched_c128(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t n,
                            double a_re, double a_im, double b_re, double b_im);
