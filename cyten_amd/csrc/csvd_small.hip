@@ -345,21 +345,42 @@ int launch(cyb_ctx_t ctx, std::vector<CDesc>& hd, size_t lds, int32_t* info)
 int finish(cyb_ctx_t ctx, std::vector<CDesc>& hd, const std::vector<int64_t>& idx, size_t lds, const std::vector<cyb_clarge::Req>& big,
            const std::vector<int64_t>& big_idx, int32_t* info)
 {
+    // A block without a decomposition (NaN or Inf entries, no convergence of its sweeps) makes the call CYB_ERR_NOCONV with
+    // info < 0 for that block; every other block of the list is still decomposed, as in the float64 entries.
+    int result = CYB_OK;
     if (!hd.empty()) {
         std::vector<int32_t> inf(hd.size());
         const int st = launch(ctx, hd, lds, inf.data());
         if (info)
             for (size_t k = 0; k < idx.size(); ++k) info[idx[k]] = inf[k];
-        if (st != CYB_OK) return st;
+        if (st != CYB_OK && st != CYB_ERR_NOCONV) return st;
+        result = st;
     }
     if (!big.empty()) {
         std::vector<int32_t> inf(big.size());
-        const int st = cyb_clarge::run(ctx, big, inf.data());
+        int st = cyb_clarge::run(ctx, big, inf.data());
+        if (st == CYB_ERR_NOCONV) {
+            // run() ends for the whole list when a block fails, before any factor is written: the others run again without it
+            const std::string msg = cyb_last_error();
+            std::vector<cyb_clarge::Req> good;
+            std::vector<size_t> good_at;
+            for (size_t k = 0; k < big.size(); ++k)
+                if (inf[k] >= 0) good.push_back(big[k]), good_at.push_back(k);
+            // (a failure that marks no block -- no convergence while completing null vectors -- would only repeat itself)
+            if (!good.empty() && good.size() < big.size()) {
+                std::vector<int32_t> ginf(good.size());
+                const int st2 = cyb_clarge::run(ctx, good, ginf.data());
+                if (st2 != CYB_OK && st2 != CYB_ERR_NOCONV) st = st2;
+                for (size_t g = 0; g < good.size(); ++g) inf[good_at[g]] = ginf[g];
+                if (st2 == CYB_OK) cyb::set_error("%s", msg.c_str());
+            }
+        }
         if (info)
             for (size_t k = 0; k < big_idx.size(); ++k) info[big_idx[k]] = inf[k];
-        if (st != CYB_OK) return st;
+        if (st != CYB_OK && st != CYB_ERR_NOCONV) return st;
+        if (st != CYB_OK) result = st;
     }
-    return CYB_OK;
+    return result;
 }
 
 } // namespace

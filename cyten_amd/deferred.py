@@ -62,6 +62,8 @@ class LazyBlock(HipBlock):
                 self._real = blk
             elif self._queued:
                 bb.flush()
+                if self._real is None:   # still pending: an operand is the output of a decomposition that failed
+                    raise RuntimeError('deferred queue: an operand of this product comes from a decomposition that failed')
             else:   # an addend that was folded into a longer chain and is read after all: its own launch
                 bb._run_products([self])
         return self._real
@@ -103,6 +105,7 @@ class _DecompNode:
 
     def __init__(self, kind, block, arg):
         self.kind, self.block, self.arg, self.outs = kind, block, arg, []
+        self.error = None   # the LinAlgError of a run that failed: the node has left the queue, forcing an output runs it again
 
 
 class LazyOut(HipBlock):
@@ -118,7 +121,15 @@ class LazyOut(HipBlock):
 
     def _force(self) -> HipBlock:
         if self._real is None:
-            self.backend.flush()
+            node = self._node
+            if node.error is None:
+                self.backend.flush()
+                if self._real is None and node.error is not None:
+                    raise node.error
+                if self._real is None:   # still pending: its input waits for the output of a decomposition that failed
+                    raise RuntimeError('deferred queue: the input of this decomposition comes from a decomposition that failed')
+            else:   # failed in an earlier flush and left the queue: only its own outputs run it again (and raise again)
+                self.backend._retry_decomp(node)
         return self._real
 
     buf = property(lambda self: self._force().buf)
@@ -250,17 +261,57 @@ class DeferredBlockBackend(HipBlockBackend):
                     for lazy, real in zip(n.outs, outs):
                         lazy._real = real
 
+    def _run_decomps_isolating(self, nodes):
+        """``_run_decomps`` with a LinAlgError confined to the blocks that cause it: a batched call that raises is repeated
+        block by block, and a block that fails alone keeps the exception on its node and leaves the queue -- forcing one of
+        its outputs raises it (``LazyOut._force``), nothing else does."""
+        from ._lib import LinAlgError
+        try:
+            self._run_decomps(nodes)
+            return
+        except LinAlgError as exc:
+            if len(nodes) == 1:
+                nodes[0].error = exc
+                return
+        for n in nodes:
+            if all(o._real is not None for o in n.outs):
+                continue
+            try:
+                self._run_decomps([n])
+            except LinAlgError as exc:
+                n.error = exc
+
+    def _retry_decomp(self, node):
+        """a node that failed before, on behalf of one of its outputs: alone, after whatever its input still waits for"""
+        if not self._is_resolved(node.block):
+            self.flush()
+        self._run_decomps([node])   # (raises again if the block is still bad)
+        node.error = None
+
+    @classmethod
+    def _blocked(cls, x) -> bool:
+        """does `x` wait for the output of a decomposition that failed?"""
+        if isinstance(x, LazyOut):   # of a node that failed, or of one whose own input waits for such a node
+            return x._real is None and (x._node.error is not None or cls._blocked(x._node.block))
+        if isinstance(x, LazyBlock):
+            root = x._root
+            return root._real is None and any(cls._blocked(y) for seg in root._segments for y in seg)
+        return False
+
     def flush(self):
         """Topological rounds over BOTH kinds of pending work: every product whose operands exist runs in one grouped
         launch, then every decomposition whose input exists runs in one batched call per kind, and so on -- a chain
         ``matrix_dot -> matrix_qr of that product -> matrix_dot with Q`` (tdot -> qr -> tdot on 2-leg tensors) needs three
         rounds, the reference's contraction / SVD loops one each.  No nested flush: operands are only marshalled once
-        everything they depend on has been materialised."""
+        everything they depend on has been materialised.  A block without a decomposition (LinAlgError: NaN entries, no
+        convergence) does not make flush() raise: the error stays with that block's outputs, the other blocks of its batch
+        are decomposed one by one, and work that depends on the failed outputs stays queued."""
         if self._flushing:
             raise RuntimeError('deferred queue: flush() re-entered (an operand was read before its producer ran)')
         self._flushing = True
         products, self._pending = [p for p in self._pending if p._real is None], []
         decomps, self._pending_decomp = self._pending_decomp, []
+        stalled_p, stalled_d = [], []   # work behind a failed decomposition: stays queued, runs once a retry of that node succeeds
         try:
             while products or decomps:
                 batch = [p for p in products if all(self._is_resolved(x) for seg in p._segments for x in seg)]
@@ -272,8 +323,12 @@ class DeferredBlockBackend(HipBlockBackend):
                 ready = [n for n in decomps if self._is_resolved(n.block)]
                 if ready:
                     ids = {id(n) for n in ready}
-                    self._run_decomps(ready)
                     decomps = [n for n in decomps if id(n) not in ids]
+                    try:
+                        self._run_decomps_isolating(ready)
+                    except BaseException:
+                        decomps = ready + decomps
+                        raise
                     continue
                 # nothing is ready: an operand may be an addend that `+` folded into a longer chain (it left the queue, so no
                 # round above will ever produce it) -- or a view of one.  Run those products on their own, then look again.
@@ -286,14 +341,25 @@ class DeferredBlockBackend(HipBlockBackend):
                 if orphans:
                     self._run_products(list(orphans.values()))
                     continue
+                held_p = [p for p in products if self._blocked(p)]
+                held_d = [n for n in decomps if self._blocked(n.block)]
+                if held_p or held_d:
+                    ids = {id(x) for x in held_p + held_d}
+                    stalled_p += held_p
+                    stalled_d += held_d
+                    products = [p for p in products if id(p) not in ids]
+                    decomps = [n for n in decomps if id(n) not in ids]
+                    continue
                 raise RuntimeError('deferred queue: cyclic dependency between pending products / decompositions')
         except BaseException:
-            # a launch failed (e.g. LinAlgError of a decomposition): what has not run goes back on the queues, so that the
-            # surviving lazy blocks stay materialisable (or raise the same error again) instead of reading None
+            # a launch failed for another reason than a block without a decomposition (a HIP error, an interrupt): what has not
+            # run goes back on the queues, so that the surviving lazy blocks stay materialisable instead of reading None
             self._pending = [p for p in products if p._real is None] + self._pending
-            self._pending_decomp = [n for n in decomps if any(o._real is None for o in n.outs)] + self._pending_decomp
+            self._pending_decomp = [n for n in decomps if n.error is None and any(o._real is None for o in n.outs)] + self._pending_decomp
             raise
         finally:
+            self._pending = stalled_p + self._pending
+            self._pending_decomp = stalled_d + self._pending_decomp
             self._flushing = False
 
     def synchronize(self):

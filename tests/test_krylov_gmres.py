@@ -349,9 +349,10 @@ def test_gpu_projection_kernels(bb, cplx):
     sfx = 'c128' if cplx else 'f64'
     rng = np.random.default_rng(21)
     k = 2 if cplx else 1
-    for n in (0, 1, 31, 4097, 300001):
-        for m in (1, 2, 7, 21, 64):
-            if n > 5000 and m in (2, 7):
+    two_tiles = 2048 * 256 + 257   # float64 sweeps: gs_grid gives a workgroup two tiles above 2048 * 256 elements
+    for n in (0, 1, 31, 4097, 300001, two_tiles):
+        for m in (1, 5) if n == two_tiles else (1, 2, 7, 21, 64):
+            if (n > 5000 and m in (2, 7)) or (n == two_tiles and cplx):
                 continue
             V = rng.standard_normal((m, n)) + (1j * rng.standard_normal((m, n)) if cplx else 0)
             w0 = rng.standard_normal(n) + (1j * rng.standard_normal(n) if cplx else 0)
