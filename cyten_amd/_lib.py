@@ -131,6 +131,17 @@ class TraceTerm(C.Structure):
                 ('pair_extent', C.c_int64 * CYB_TRACE_MAX_PAIRS), ('pair_stride', C.c_int64 * CYB_TRACE_MAX_PAIRS)]
 
 
+class TraceWeightedOut(C.Structure):
+    _fields_ = [('dst', C.c_void_p), ('ndim', C.c_int32), ('reserved', C.c_int32), ('first_term', C.c_int64), ('n_terms', C.c_int64),
+                ('shape', C.c_int64 * CYB_MAX_NDIM), ('dst_strides', C.c_int64 * CYB_MAX_NDIM)]
+
+
+class TraceWeightedTerm(C.Structure):
+    _fields_ = [('src', C.c_void_p), ('coeff_re', C.c_double), ('coeff_im', C.c_double), ('src_real', C.c_int32), ('n_pairs', C.c_int32),
+                ('rem_strides', C.c_int64 * CYB_MAX_NDIM), ('pair_extent', C.c_int64 * CYB_TRACE_MAX_PAIRS),
+                ('pair_stride', C.c_int64 * CYB_TRACE_MAX_PAIRS)]
+
+
 class ExpmDesc(C.Structure):
     _fields_ = [('A', C.c_void_p), ('lda', C.c_int64), ('n', C.c_int64), ('a_is_real', C.c_int32), ('reserved', C.c_int32),
                 ('E', C.c_void_p), ('lde', C.c_int64)]
@@ -183,6 +194,8 @@ LINTERM_C128_DTYPE = _np.dtype(LincombTermC128)
 CEXPAND_DTYPE = _np.dtype(CExpandDesc)
 TRACE_OUT_DTYPE = _np.dtype(TraceOut)
 TRACE_TERM_DTYPE = _np.dtype(TraceTerm)
+TRACE_WEIGHTED_OUT_DTYPE = _np.dtype(TraceWeightedOut)
+TRACE_WEIGHTED_TERM_DTYPE = _np.dtype(TraceWeightedTerm)
 EXPM_DTYPE = _np.dtype(ExpmDesc)
 OUTER_DTYPE = _np.dtype(OuterRec)
 SEG_DTYPE = _np.dtype(SegRec)
@@ -269,6 +282,8 @@ PROTOTYPES = {
     'cyb_lincomb_strided_batched_c128': [_ctx, _P(LincombDesc), C.c_int64, _P(LincombTermC128), C.c_int64],
     'cyb_trace_grouped_f64': [_ctx, _P(TraceOut), C.c_int64, _P(TraceTerm), C.c_int64],
     'cyb_trace_grouped_c128': [_ctx, _P(TraceOut), C.c_int64, _P(TraceTerm), C.c_int64],
+    'cyb_trace_weighted_f64': [_ctx, _P(TraceWeightedOut), C.c_int64, _P(TraceWeightedTerm), C.c_int64],
+    'cyb_trace_weighted_c128': [_ctx, _P(TraceWeightedOut), C.c_int64, _P(TraceWeightedTerm), C.c_int64],
     'cyb_expm_small_batched_f64': [_ctx, _P(ExpmDesc), C.c_int64, C.c_double],
     'cyb_expm_small_batched_c128': [_ctx, _P(ExpmDesc), C.c_int64, C.c_double, C.c_double],
     'cyb_norm1_batched_f64': [_ctx, _P(ExpmDesc), C.c_int64, _vp],

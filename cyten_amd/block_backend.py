@@ -1586,6 +1586,77 @@ class HipBlockBackend:
                       fills.ctypes.data_as(C.POINTER(_lib.TreeFill)), len(fill)))
         del keep
 
+    def tree_trace_many(self, outputs):
+        """Weighted partial traces into strided tiles, ONE descriptor upload and ONE launch for all result blocks of a
+        fusion-tree partial trace (``FusionTreeBackend::partial_trace`` step 2, fusion_tree_backend.cpp:3092-3159: seven
+        block-backend calls per tree pair).  `outputs`: a list of ``(dst_view, terms)``; ``dst_view`` is any strided N-d view
+        of the remaining shape, written in place (the views of one call must not overlap); ``terms`` a list of
+        ``(src_view, idcs1, idcs2, remaining_idcs, coeff)`` in the argument meaning of `trace_partial_grouped` (axis
+        ``idcs1[k]`` of the source is traced against ``idcs2[k]``), and ``dst = sum_terms coeff * trace(src)``, zeros without a
+        term.  The destinations decide the entry: all float64 (real sources, real coefficients) or all complex128 (a float64
+        source is then read as it stands, no promotion pass).  More than ``CYB_MAX_NDIM`` source axes or more than
+        ``CYB_TRACE_MAX_PAIRS`` pairs: ValueError.  Fixed summation order, bit-identical from run to run
+        (csrc/tree_trace.hip)."""
+        outputs = [(dst, list(terms)) for dst, terms in outputs]
+        if not outputs:
+            return
+        dsts = [dst for dst, _ in outputs]
+        srcs = [tm[0] for _, terms in outputs for tm in terms]
+        self._numeric_only(dsts + srcs, 'tree_trace_many')
+        kinds = {d.is_complex for d in dsts}
+        if len(kinds) > 1:
+            raise ValueError('tree_trace_many: the destination views of one call share one dtype')
+        cplx = kinds.pop()
+        nd_max, np_max = _lib.CYB_MAX_NDIM, _lib.CYB_TRACE_MAX_PAIRS
+        zeros_nd, zeros_np = (0,) * nd_max, (0,) * np_max
+        o_first, o_n, o_shape, o_str = [], [], [], []
+        t_re, t_im, t_real, t_pairs, t_rem, t_ext, t_str = [], [], [], [], [], [], []
+        for dst, terms in outputs:
+            shape = dst.shape
+            if len(shape) > nd_max:
+                raise ValueError(f'tree_trace_many: a destination view with more than {nd_max} axes')
+            o_first.append(len(t_pairs))
+            o_n.append(len(terms))
+            o_shape.append((shape + zeros_nd)[:nd_max])
+            o_str.append((dst.strides + zeros_nd)[:nd_max])
+            for a, idcs1, idcs2, remaining, coeff in terms:
+                nd = a.ndim
+                if len(idcs1) > np_max:
+                    raise ValueError(f'tree_trace_many: more than {np_max} traced pairs')
+                if nd > nd_max:
+                    raise ValueError(f'tree_trace_many: a source view with more than {nd_max} axes')
+                idcs1, idcs2, remaining = [i % nd for i in idcs1], [i % nd for i in idcs2], [i % nd for i in remaining]
+                if len(idcs1) != len(idcs2) or sorted(idcs1 + idcs2 + remaining) != list(range(nd)):
+                    raise ValueError('tree_trace_many: idcs1, idcs2 and remaining_idcs must list every axis once, in pairs')
+                sh, st = a.shape, a.strides
+                if any(sh[p] != sh[q] for p, q in zip(idcs1, idcs2)):
+                    raise ValueError('tree_trace_many: traced legs do not match')
+                if tuple(sh[k] for k in remaining) != shape:
+                    raise ValueError(f'tree_trace_many: remaining axes {tuple(sh[k] for k in remaining)} of a term do not have the '
+                                     f'shape {shape} of its destination view')
+                coeff = complex(coeff)
+                if not cplx and (a.is_complex or coeff.imag != 0):
+                    raise ValueError('tree_trace_many: a complex source or coefficient needs complex destination views')
+                t_re.append(coeff.real)
+                t_im.append(coeff.imag)
+                t_real.append(0 if a.is_complex or not cplx else 1)
+                t_pairs.append(len(idcs1))
+                t_rem.append((tuple(st[k] for k in remaining) + zeros_nd)[:nd_max])
+                t_ext.append((tuple(sh[p] for p in idcs1) + zeros_np)[:np_max])
+                t_str.append((tuple(st[p] + st[q] for p, q in zip(idcs1, idcs2)) + zeros_np)[:np_max])
+        oarr = np.zeros(len(outputs), dtype=_lib.TRACE_WEIGHTED_OUT_DTYPE)
+        oarr['dst'], oarr['ndim'] = [d.ptr for d in dsts], [d.ndim for d in dsts]
+        oarr['first_term'], oarr['n_terms'], oarr['shape'], oarr['dst_strides'] = o_first, o_n, o_shape, o_str
+        n_t = len(srcs)
+        tarr = np.zeros(max(n_t, 1), dtype=_lib.TRACE_WEIGHTED_TERM_DTYPE)
+        if n_t:
+            tarr['src'], tarr['coeff_re'], tarr['coeff_im'], tarr['src_real'] = [a.ptr for a in srcs], t_re, t_im, t_real
+            tarr['n_pairs'], tarr['rem_strides'], tarr['pair_extent'], tarr['pair_stride'] = t_pairs, t_rem, t_ext, t_str
+        fn = self.lib.cyb_trace_weighted_c128 if cplx else self.lib.cyb_trace_weighted_f64
+        self.ctx.sync_stream()
+        _lib.check(fn(self.ctx.handle, oarr.ctypes.data_as(C.POINTER(_lib.TraceWeightedOut)), len(outputs),
+                      tarr.ctypes.data_as(C.POINTER(_lib.TraceWeightedTerm)), n_t))
+
     def _wdot(self, descs, cplx, conj):
         """launch chain of the weighted reduction + the one read of its result"""
         n = len(descs)

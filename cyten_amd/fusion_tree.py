@@ -34,6 +34,10 @@ module mirrors is everything BETWEEN that layer and the block backend:
   ``iter_tree_blocks`` and ``transform_tensor`` mean; the reference's ``_mask_contract`` reshapes a codomain forest to
   ``(m..., -1)`` (:2471), which mixes the tree index into the columns when a forest holds several trees, and is not reproduced.
 * :func:`truncated_svd`: svd, truncation and the mask on U, S and Vh -- three launches after the SVD.
+* :func:`partial_trace`  <- ``::partial_trace`` (:2883-3183): step 1 is :func:`transform_tensor`; the loops of step 2
+  (:3092-3159, seven block-backend calls per tree pair) emit one output record per tile of the result blocks and one weighted
+  term per contributing old tree pair; the arithmetic is ONE ``tree_trace_many`` launch.  The per-tree data of the symmetry
+  layer (``partial_trace_helper`` :2557-2604, the new trees) comes in as a :class:`TreeTrace`.
 * :class:`TreeTensor`: data + codomain + domain, the vector the Krylov solvers and the operator wrappers take
   (``cyten_amd.krylov``, ``cyten_amd.sparse``): the reference's Krylov code calls ``inner`` / ``norm`` /
   ``linear_combination`` on whatever tensor it is given (src/tensors/krylov_based.cpp), and those need the quantum dimensions
@@ -49,7 +53,7 @@ import numpy as np
 __all__ = ['TreeBlock', 'TreeSpace', 'FusionTreeData', 'compose', 'svd', 'qr', 'lq', 'eigh', 'truncate_singular_values',
            'transform_tensor', 'discard_zero_blocks', 'norm', 'inner', 'trace_full', 'mul', 'linear_combination', 'dagger',
            'almost_equal', 'TreeAxisRecord', 'TreeMask', 'leg_keys', 'scale_axis', 'mask_contract', 'truncated_svd', 'TreeTensor',
-           'same_space']
+           'same_space', 'TreeTrace', 'partial_trace']
 
 
 @dataclass(frozen=True)
@@ -403,6 +407,125 @@ def discard_zero_blocks(bb, data: FusionTreeData, eps: float) -> FusionTreeData:
     if len(keep) == len(data.blocks):
         return data
     return FusionTreeData(data.block_inds[keep], [data.blocks[n] for n in keep])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# partial trace
+
+class TreeTrace(NamedTuple):
+    """What the symmetry layer knows about tracing adjacent leg pairs of ONE side (codomain or domain), as data:
+    ``partial_trace_helper`` (fusion_tree_backend.cpp:2557-2604: the ``on_diag`` flag and the product of conjugated B symbols and
+    Frobenius-Schur signs) and the ``FusionTree`` constructions at :3109 / :3136, per tree."""
+    positions: tuple   # ascending k, non-overlapping: legs (k, k+1) of THIS side (codomain order / domain order) are one traced pair
+    table: dict        # old tree key -> (new tree key, factor); a tree that is absent is off the diagonal (on_diag == False)
+
+
+def _traced_tree(space: TreeSpace, new_space: TreeSpace, trace, i_old: int, tb: TreeBlock, what: str):
+    """(new TreeBlock, factor) of an old tree of a surviving coupled sector, or None if it is off the diagonal"""
+    m = tb.multiplicities
+    if trace is None:
+        key, factor, positions = tb.tree, 1.0, ()
+    else:
+        positions = trace.positions
+        if len(m) != space.num_legs or len(tb.uncoupled) != len(m) or any(k + 1 >= len(m) for k in positions):
+            raise ValueError(f'partial_trace: a {what} tree lacks the uncoupled sector keys or the multiplicities of its legs '
+                             '(TreeBlock.uncoupled, TreeBlock.multiplicities)')
+        hit = trace.table.get(tb.tree)
+        if hit is None:
+            return None
+        key, factor = hit
+        for k in positions:
+            if m[k] != m[k + 1]:
+                raise ValueError(f'partial_trace: the legs {k} and {k + 1} of a {what} tree on the diagonal have the multiplicities '
+                                 f'{m[k]} and {m[k + 1]}')
+    if not new_space.has_tree(key):
+        raise ValueError(f'partial_trace: the new {what} has no tree {key!r}')
+    i_new, nb = new_space.tree_block_slice(key)
+    dropped = {k for p in positions for k in (p, p + 1)}
+    if tuple(nb.multiplicities) != tuple(x for a, x in enumerate(m) if a not in dropped):
+        raise ValueError(f'partial_trace: the multiplicities {tuple(nb.multiplicities)} of a new {what} tree are not the old ones {tuple(m)} '
+                         f'without the traced legs')
+    if new_space.sectors[i_new].tolist() != space.sectors[i_old].tolist():
+        raise ValueError(f'partial_trace: a new {what} tree lies in another coupled sector than the old one')
+    return nb, factor
+
+
+def partial_trace(bb, data: FusionTreeData, codomain: TreeSpace, domain: TreeSpace, new_codomain: TreeSpace, new_domain: TreeSpace,
+                  cod_trace: TreeTrace = None, dom_trace: TreeTrace = None, eps: float = 0.0, discard: bool = True, move=None) -> FusionTreeData:
+    """``FusionTreeBackend::partial_trace`` (fusion_tree_backend.cpp:2883-3183).  `cod_trace` / `dom_trace`: which adjacent leg
+    pairs of the codomain / domain are traced and what the symmetry layer says per tree (:class:`TreeTrace`); a side with None
+    is not traced (factor 1, the same trees).  `new_codomain` / `new_domain`: the spaces after tracing (:2934-2948).
+
+    `move = (mid_codomain, mid_domain, codomain_idcs, domain_idcs, mapping)` first runs :func:`transform_tensor` -- step 1
+    (:2908-3025), which bends and braids the legs until every traced pair is adjacent on one side; the traces then refer to
+    the mid spaces.  Two launches and a zero fill in total.
+
+    Step 2 has the reference's loops -- a coupled sector of the data survives if both new spaces hold it (:3027-3047); old
+    codomain trees on the diagonal, then old domain trees on the diagonal (:3092-3159) -- but what they emit is one output
+    record per (new codomain tree, new domain tree) tile of every result block, tiles without a term included (they are
+    written as zeros, so the result blocks need no zero fill), and one term record per contributing old tree pair with the
+    coefficient ``f_cod * conj(f_dom)`` (:3149), ordered by ascending old codomain tree, then old domain tree.  The tile of
+    an old tree pair is read in place, reshaped to (codomain multiplicities..., domain multiplicities...) (:3121-3142).  ONE
+    ``tree_trace_many`` call.  Result blocks exist for the surviving sectors only (the reference allocates every common
+    sector of the new spaces as zeros and discards them again, :3037, :3160); the result goes through
+    :func:`discard_zero_blocks` with `eps` unless ``discard=False``, and is complex if the data or a factor is.
+
+    With zero remaining legs on both sides (new spaces of zero legs: one coupled sector, one tree without multiplicities, block
+    size 1) the result always is the single 1 x 1 block with ``block_inds`` (0, 0) and is not discarded (:3162-3181): the caller
+    reads the scalar with ``bb.to_numpy(result.blocks[0])[0, 0]`` (one download; float64 or complex128 as the result is).  It
+    equals :func:`trace_full` when the factors carry the quantum dimensions, as the B symbols do."""
+    if move is not None:
+        mid_codomain, mid_domain, codomain_idcs, domain_idcs, mapping = move
+        data = transform_tensor(bb, data, codomain, domain, mid_codomain, mid_domain, codomain_idcs, domain_idcs, mapping)
+        codomain, domain = mid_codomain, mid_domain
+    for trace in (cod_trace, dom_trace):
+        if trace is not None and any(b - a < 2 for a, b in zip(trace.positions, trace.positions[1:])):
+            raise ValueError('partial_trace: the traced positions of a side are ascending and do not overlap')
+    J = codomain.num_legs
+    idcs1 = list(cod_trace.positions if cod_trace is not None else ()) + [J + k for k in (dom_trace.positions if dom_trace is not None else ())]
+    idcs2 = [k + 1 for k in idcs1]
+    remaining = [k for k in range(J + domain.num_legs) if k not in idcs1 and k not in idcs2]
+    scalar = new_codomain.num_legs == 0 and new_domain.num_legs == 0
+    where_cod = {tuple(s): k for k, s in enumerate(new_codomain.sectors.tolist())}
+    where_dom = {tuple(s): k for k, s in enumerate(new_domain.sectors.tolist())}
+    factors = [f for tr in (cod_trace, dom_trace) if tr is not None for _, f in tr.table.values()]
+    cplx = any(_is_complex(b) for b in data.blocks) or any(complex(f).imag != 0.0 for f in factors)
+    # (new codomain sector, new domain sector) -> the old block that feeds it (None: the scalar of a tensor without that block)
+    feeds = {k: None for k in common_sectors(new_codomain, new_domain)} if scalar else {}
+    for n, (_, j) in enumerate(data.block_inds.tolist()):
+        s = tuple(domain.sectors[j].tolist())
+        if s in where_cod and s in where_dom:
+            feeds[(where_cod[s], where_dom[s])] = n
+    rows = sorted(feeds)
+    if not rows:
+        return FusionTreeData(np.zeros((0, 2), np.int64), [])
+    outs = bb.empty_many([(new_codomain.block_size(i), new_domain.block_size(j)) for i, j in rows], dtype=np.complex128 if cplx else np.float64)
+    outputs = []
+    for (i_new, j_new), out in zip(rows, outs):
+        tiles = {(xb.tree, yb.tree): (xb, yb, []) for xb in new_codomain.tree_blocks[i_new] for yb in new_domain.tree_blocks[j_new]}
+        n = feeds[(i_new, j_new)]
+        if n is not None:
+            i_old, j_old = data.block_inds[n].tolist()
+            dom_side = [(yb, _traced_tree(domain, new_domain, dom_trace, j_old, yb, 'domain')) for yb in domain.tree_blocks[j_old]]
+            for xb in codomain.tree_blocks[i_old]:
+                hit = _traced_tree(codomain, new_codomain, cod_trace, i_old, xb, 'codomain')
+                if hit is None:
+                    continue
+                nx, f_cod = hit
+                for yb, hit2 in dom_side:
+                    if hit2 is None:
+                        continue
+                    ny, f_dom = hit2
+                    tile = bb.get_item(data.blocks[n], (slice(xb.start, xb.stop), slice(yb.start, yb.stop)))
+                    src = bb.reshape(tile, list(xb.multiplicities) + list(yb.multiplicities))
+                    coeff = f_cod * np.conj(f_dom)
+                    tiles[(nx.tree, ny.tree)][2].append((src, idcs1, idcs2, remaining, coeff if cplx else float(np.real(coeff))))
+        for xb, yb, terms in tiles.values():
+            dst = bb.get_item(out, (slice(xb.start, xb.stop), slice(yb.start, yb.stop)))
+            outputs.append((bb.reshape(dst, list(xb.multiplicities) + list(yb.multiplicities)), terms))
+    bb.tree_trace_many(outputs)
+    res = FusionTreeData(np.array(rows, dtype=np.int64), outs)
+    return discard_zero_blocks(bb, res, eps) if discard and not scalar else res
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

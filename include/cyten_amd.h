@@ -535,6 +535,53 @@ typedef struct {
 int cyb_trace_grouped_f64(cyb_ctx_t ctx, const cyb_trace_out* outs, int64_t n_outs, const cyb_trace_term* terms, int64_t n_terms);
 int cyb_trace_grouped_c128(cyb_ctx_t ctx, const cyb_trace_out* outs, int64_t n_outs, const cyb_trace_term* terms, int64_t n_terms);
 
+/* ---- weighted partial trace into strided tiles ------------------------------------------------------------------
+ * Every result block of FusionTreeBackend::partial_trace (src/backends/fusion_tree_backend.cpp:2883-3183) in ONE launch:
+ * step 2 of it (:3092-3159) makes, per pair of tree blocks, get_item, reshape, trace_partial, reshape, mul by the B-symbol
+ * factor (:3149), get_item of the destination tile, operator+ and set_item.  Here an output record is one destination tile
+ * and a term record one contributing old tree pair:
+ *   out[r] = sum_{t in [first_term, first_term + n_terms)} c_t * ( sum_tau src_t[r . rem_strides_t + tau . pair_stride_t] )
+ *   written to dst + r . dst_strides, r over `shape` (ndim remaining axes), tau over the pair extents of term t.
+ * The destination is a strided N-d view: in practice a tile rows x cols of a coupled block, the row range split into the
+ * remaining codomain multiplicities, the column range into the remaining domain ones, with the block's leading dimension.
+ * pair_stride[p] is the SUM of the two source strides of traced pair p (walking it walks the diagonal), ndim + 2 * n_pairs
+ * <= CYB_MAX_NDIM, entries beyond ndim / n_pairs are ignored -- the meanings of cyb_trace_term.  c_t = coeff_re + i coeff_im.
+ *   * Every output element has exactly one owner, which adds its terms in ascending order (tau with pair 0 fastest, tree
+ *     shapes fixed): no float atomics, no zero fill, no second pass; results are bit-identical from run to run.
+ *   * An output with no terms is written as zeros: a tile nothing contributes to is zeroed without a memset.
+ *   * The coefficient multiplies a term's sum once per output element, not once per addend.
+ *   * Sources are read in place and may overlap each other.  Destination tiles of one call must not overlap; the caller
+ *     vouches for that.  Zero extents and empty lists are valid.
+ *   * src_real != 0 (c128 entry only; the f64 entry ignores it): the source is float64 data read in place, strides in
+ *     doubles -- a real tensor under complex B symbols needs no promotion pass (as cyb_lincomb_term_c128).  The c128 entry
+ *     reads and writes interleaved (re, im) storage otherwise, strides counted in complex elements.
+ *   * The f64 entry requires coeff_im == 0 of every term: else CYB_ERR_INVALID, nothing is launched.
+ *   * Everything is validated on the host before anything is uploaded or launched: ndim, pair counts, term ranges,
+ *     negative extents, NULL pointers of non-empty outputs / terms.  A refused call leaves the context as it found it.
+ * The owner -- one lane, one wave or one workgroup -- is chosen per output record from its element count and its number of
+ * addends (csrc/tree_trace.hip). */
+typedef struct {
+    double* dst;
+    int32_t ndim;     /* number of remaining axes */
+    int32_t reserved;
+    int64_t first_term, n_terms;
+    int64_t shape[CYB_MAX_NDIM];
+    int64_t dst_strides[CYB_MAX_NDIM];
+} cyb_trace_weighted_out;
+typedef struct {
+    const double* src;
+    double coeff_re, coeff_im;
+    int32_t src_real;
+    int32_t n_pairs;
+    int64_t rem_strides[CYB_MAX_NDIM];
+    int64_t pair_extent[CYB_TRACE_MAX_PAIRS];
+    int64_t pair_stride[CYB_TRACE_MAX_PAIRS];
+} cyb_trace_weighted_term;
+int cyb_trace_weighted_f64(cyb_ctx_t ctx, const cyb_trace_weighted_out* outs, int64_t n_outs, const cyb_trace_weighted_term* terms,
+                           int64_t n_terms);
+int cyb_trace_weighted_c128(cyb_ctx_t ctx, const cyb_trace_weighted_out* outs, int64_t n_outs, const cyb_trace_weighted_term* terms,
+                            int64_t n_terms);
+
 /* ---- grouped matrix exponential of small blocks ---------------------------------------------------------------------
  * E = exp(alpha * A) for every listed square matrix in ONE launch, one workgroup per matrix, the whole computation in LDS
  * (csrc/expm_small.hip).  Replaces NumpyBlockBackend::matrix_exp = scipy.linalg.expm (src/block_backend/numpy.cpp:1227-1234),
