@@ -1657,6 +1657,69 @@ class HipBlockBackend:
         _lib.check(fn(self.ctx.handle, oarr.ctypes.data_as(C.POINTER(_lib.TraceWeightedOut)), len(outputs),
                       tarr.ctypes.data_as(C.POINTER(_lib.TraceWeightedTerm)), n_t))
 
+    def tree_outer_many(self, outputs):
+        """Weighted Kronecker products into strided tiles, ONE descriptor upload and ONE launch for all result blocks of a
+        fusion-tree outer (``FusionTreeBackend::outer``, fusion_tree_backend.cpp:2609-2667: outer, permute_axes, combine_legs
+        per pair of tree-block pairs and get_item, mul, operator+, set_item per new tree pair).  `outputs`: a list of
+        ``(dst_view, terms)``; ``dst_view`` is a 2-D view with unit column stride (a tile of a coupled block), written in place
+        (the views of one call must not overlap); ``terms`` a list of ``(a_view, b_view, coeff)`` of 2-D views read in place
+        through their strides, all of one shape ``(ha, wa)`` / ``(hb, wb)`` per output, and
+        ``dst[ra * hb + rb, ca * wb + cb] = sum_terms coeff * a[ra, ca] * b[rb, cb]``, zeros without a term.  The destinations
+        decide the entry: all float64 (real sources, real coefficients) or all complex128 (a float64 source is then read as
+        it stands, no promotion pass).  Fixed summation order, bit-identical from run to run (csrc/tree_outer.hip)."""
+        outputs = [(dst, list(terms)) for dst, terms in outputs]
+        if not outputs:
+            return
+        dsts = [dst for dst, _ in outputs]
+        a_srcs = [tm[0] for _, terms in outputs for tm in terms]
+        b_srcs = [tm[1] for _, terms in outputs for tm in terms]
+        self._numeric_only(dsts + a_srcs + b_srcs, 'tree_outer_many')
+        if any(x.ndim != 2 for x in dsts + a_srcs + b_srcs):
+            raise ValueError('tree_outer_many: destinations and sources are 2-D views')
+        kinds = {d.is_complex for d in dsts}
+        if len(kinds) > 1:
+            raise ValueError('tree_outer_many: the destination views of one call share one dtype')
+        cplx = kinds.pop()
+        o_ext, o_ldd, o_first, o_n, t_re, t_im = [], [], [], [], [], []
+        for dst, terms in outputs:
+            H, W = dst.shape
+            if dst.strides[1] != 1 and W > 1:
+                raise ValueError('tree_outer_many: a destination view needs the column stride 1')
+            ext = (H, 1, 1, W)          # (an output without terms: zeros, whatever the factorisation)
+            for k, (a, b, coeff) in enumerate(terms):
+                e = (a.shape[0], b.shape[0], a.shape[1], b.shape[1])
+                if k and e != ext:
+                    raise ValueError(f'tree_outer_many: the terms of one output differ in their extents, {ext} and {e}')
+                ext = e
+                if (e[0] * e[1], e[2] * e[3]) != (H, W):
+                    raise ValueError(f'tree_outer_many: a destination view of shape {(H, W)} for sources of the shapes '
+                                     f'{tuple(a.shape)} and {tuple(b.shape)}')
+                coeff = complex(coeff)
+                if not cplx and (a.is_complex or b.is_complex or coeff.imag != 0):
+                    raise ValueError('tree_outer_many: a complex source or coefficient needs complex destination views')
+                t_re.append(coeff.real)
+                t_im.append(coeff.imag)
+            o_first.append(len(t_re) - len(terms))
+            o_n.append(len(terms))
+            o_ext.append(ext)
+            o_ldd.append(dst.strides[0] if H > 1 else W)
+        oarr = np.zeros(len(outputs), dtype=_lib.OUTER_WEIGHTED_OUT_DTYPE)
+        ext = np.array(o_ext, dtype=np.int64).reshape(len(outputs), 4)
+        oarr['dst'], oarr['ha'], oarr['hb'], oarr['wa'], oarr['wb'] = [d.ptr for d in dsts], ext[:, 0], ext[:, 1], ext[:, 2], ext[:, 3]
+        oarr['ldd'], oarr['first_term'], oarr['n_terms'] = o_ldd, o_first, o_n
+        n_t = len(a_srcs)
+        tarr = np.zeros(max(n_t, 1), dtype=_lib.OUTER_WEIGHTED_TERM_DTYPE)
+        if n_t:
+            tarr['a'], tarr['b'], tarr['coeff_re'], tarr['coeff_im'] = [a.ptr for a in a_srcs], [b.ptr for b in b_srcs], t_re, t_im
+            tarr['a_real'] = [0 if a.is_complex or not cplx else 1 for a in a_srcs]
+            tarr['b_real'] = [0 if b.is_complex or not cplx else 1 for b in b_srcs]
+            tarr['a_rs'], tarr['a_cs'] = [a.strides[0] for a in a_srcs], [a.strides[1] for a in a_srcs]
+            tarr['b_rs'], tarr['b_cs'] = [b.strides[0] for b in b_srcs], [b.strides[1] for b in b_srcs]
+        fn = self.lib.cyb_outer_weighted_c128 if cplx else self.lib.cyb_outer_weighted_f64
+        self.ctx.sync_stream()
+        _lib.check(fn(self.ctx.handle, oarr.ctypes.data_as(C.POINTER(_lib.OuterWeightedOut)), len(outputs),
+                      tarr.ctypes.data_as(C.POINTER(_lib.OuterWeightedTerm)), n_t))
+
     def _wdot(self, descs, cplx, conj):
         """launch chain of the weighted reduction + the one read of its result"""
         n = len(descs)

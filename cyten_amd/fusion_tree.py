@@ -38,6 +38,9 @@ module mirrors is everything BETWEEN that layer and the block backend:
   (:3092-3159, seven block-backend calls per tree pair) emit one output record per tile of the result blocks and one weighted
   term per contributing old tree pair; the arithmetic is ONE ``tree_trace_many`` launch.  The per-tree data of the symmetry
   layer (``partial_trace_helper`` :2557-2604, the new trees) comes in as a :class:`TreeTrace`.
+* :func:`outer`  <- ``::outer`` (:2609-2667): the double loop over the tree-block pairs of a and of b emits one output record
+  per tile of the result blocks and one weighted term per contributing (a tree pair, b tree pair); the arithmetic is ONE
+  ``tree_outer_many`` launch.  What ``FusionTree::outer`` says per pair of trees comes in as a :class:`TreeOuter`.
 * :class:`TreeTensor`: data + codomain + domain, the vector the Krylov solvers and the operator wrappers take
   (``cyten_amd.krylov``, ``cyten_amd.sparse``): the reference's Krylov code calls ``inner`` / ``norm`` /
   ``linear_combination`` on whatever tensor it is given (src/tensors/krylov_based.cpp), and those need the quantum dimensions
@@ -53,7 +56,7 @@ import numpy as np
 __all__ = ['TreeBlock', 'TreeSpace', 'FusionTreeData', 'compose', 'svd', 'qr', 'lq', 'eigh', 'truncate_singular_values',
            'transform_tensor', 'discard_zero_blocks', 'norm', 'inner', 'trace_full', 'mul', 'linear_combination', 'dagger',
            'almost_equal', 'TreeAxisRecord', 'TreeMask', 'leg_keys', 'scale_axis', 'mask_contract', 'truncated_svd', 'TreeTensor',
-           'same_space', 'TreeTrace', 'partial_trace']
+           'same_space', 'TreeTrace', 'partial_trace', 'TreeOuter', 'outer']
 
 
 @dataclass(frozen=True)
@@ -526,6 +529,98 @@ def partial_trace(bb, data: FusionTreeData, codomain: TreeSpace, domain: TreeSpa
     bb.tree_trace_many(outputs)
     res = FusionTreeData(np.array(rows, dtype=np.int64), outs)
     return discard_zero_blocks(bb, res, eps) if discard and not scalar else res
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# outer
+
+class TreeOuter(NamedTuple):
+    """What the symmetry layer knows about the tensor product of the trees of ONE side (codomain or domain), as data:
+    ``FusionTree::outer`` (src/symmetries/trees.cpp:1354-1393, F symbols through ``insert_at``), per pair of trees."""
+    table: dict        # (a tree key, b tree key) -> [(new tree key, amplitude), ...]; an empty list is allowed, a missing pair is not
+
+
+def _outer_trees(new_space: TreeSpace, outer_table, seen: dict, xa: TreeBlock, xb: TreeBlock, what: str):
+    """[(coupled sector, its index, new TreeBlock, amplitude)] of a pair of trees of one side, checked once per pair"""
+    res = seen.get((xa.tree, xb.tree))
+    if res is not None:
+        return res
+    hit = outer_table.table.get((xa.tree, xb.tree))
+    if hit is None:
+        raise ValueError(f'outer: the {what} table has no entry for the trees {xa.tree!r} and {xb.tree!r}')
+    res = []
+    for key, amp in hit:
+        if not new_space.has_tree(key):
+            raise ValueError(f'outer: the new {what} has no tree {key!r}')
+        i_new, nb = new_space.tree_block_slice(key)
+        if tuple(nb.multiplicities) != tuple(xa.multiplicities) + tuple(xb.multiplicities):
+            raise ValueError(f'outer: the multiplicities {tuple(nb.multiplicities)} of a new {what} tree are not those of its factors, '
+                             f'{tuple(xa.multiplicities)} followed by {tuple(xb.multiplicities)}')
+        res.append((tuple(new_space.sectors[i_new].tolist()), i_new, nb, amp))
+    seen[(xa.tree, xb.tree)] = res
+    return res
+
+
+def outer(bb, a: FusionTreeData, a_codomain: TreeSpace, a_domain: TreeSpace, b: FusionTreeData, b_codomain: TreeSpace, b_domain: TreeSpace,
+          new_codomain: TreeSpace, new_domain: TreeSpace, cod_outer: TreeOuter, dom_outer: TreeOuter, eps: float = 0.0,
+          discard: bool = True) -> FusionTreeData:
+    """``FusionTreeBackend::outer`` (fusion_tree_backend.cpp:2609-2667): the tensor product of `a` and `b` on the spaces
+    ``new_codomain = a_codomain (x) b_codomain``, ``new_domain = a_domain (x) b_domain`` (:2618-2623).  `cod_outer` /
+    `dom_outer`: what ``FusionTree::outer`` says per pair of codomain / domain trees (:class:`TreeOuter`).
+
+    The reference's loops -- tree-block pairs of a (:2626-2630) times tree-block pairs of b (:2631-2635), then the new domain
+    trees and the new codomain trees of the same coupled sector (:2642-2650) -- emit one term record per contributing
+    (a tree pair, b tree pair) with the coefficient ``conj(u_cod) * v_dom`` (:2653), both tiles read in place, instead of
+    outer, permute_axes, combine_legs, get_item, mul, operator+ and set_item.  Every result block that receives at least one
+    term gets one output record per (new codomain tree, new domain tree) tile, tiles without a term included (they are
+    written as zeros, so the result needs no zero fill); result blocks that receive no term are absent (the reference
+    allocates them as zeros and discards them, :2625, :2665).  ONE ``tree_outer_many`` call.
+
+    Order of the terms of a tile: a's blocks ascending, a's codomain trees, a's domain trees, then b's blocks, b's codomain
+    trees, b's domain trees (``iter_tree_blocks`` order each); the tiles of a result block are ordered by new codomain tree,
+    then new domain tree.  The result is complex if an operand or an amplitude is, sorted by ``block_inds``, and goes through
+    :func:`discard_zero_blocks` with `eps` unless ``discard=False``.  A zero-leg operand (a space with one coupled sector,
+    one tree without multiplicities, block size 1) is an ordinary 1 x 1 tile."""
+    amps = [amp for tb in (cod_outer, dom_outer) for lst in tb.table.values() for _, amp in lst]
+    cplx = any(_is_complex(blk) for blk in a.blocks + b.blocks) or any(complex(x).imag != 0.0 for x in amps)
+    seen_cod, seen_dom = {}, {}
+    b_pairs = []
+    for m, (ib, jb) in enumerate(b.block_inds.tolist()):
+        for xb in b_codomain.tree_blocks[ib]:
+            for yb in b_domain.tree_blocks[jb]:
+                b_pairs.append((xb, yb, bb.get_item(b.blocks[m], (slice(xb.start, xb.stop), slice(yb.start, yb.stop)))))
+    terms_of: dict = {}      # (i_new, j_new) -> {(new codomain tree, new domain tree): [(A, B, coeff)]}
+    for n, (ia, ja) in enumerate(a.block_inds.tolist()):
+        for xa in a_codomain.tree_blocks[ia]:
+            for ya in a_domain.tree_blocks[ja]:
+                A = None
+                for xb, yb, B in b_pairs:
+                    cods = _outer_trees(new_codomain, cod_outer, seen_cod, xa, xb, 'codomain')
+                    doms = _outer_trees(new_domain, dom_outer, seen_dom, ya, yb, 'domain')
+                    for sec_d, j_new, ny, v in doms:
+                        for sec_c, i_new, nx, u in cods:
+                            if sec_c != sec_d:
+                                continue                     # (:2649)
+                            if A is None:
+                                A = bb.get_item(a.blocks[n], (slice(xa.start, xa.stop), slice(ya.start, ya.stop)))
+                            coeff = np.conj(u) * v           # (:2653)
+                            terms_of.setdefault((i_new, j_new), {}).setdefault((nx.tree, ny.tree), []).append(
+                                (A, B, complex(coeff) if cplx else float(np.real(coeff))))
+    rows = sorted(terms_of)
+    if not rows:
+        return FusionTreeData(np.zeros((0, 2), np.int64), [])
+    outs = bb.empty_many([(new_codomain.block_size(i), new_domain.block_size(j)) for i, j in rows], dtype=np.complex128 if cplx else np.float64)
+    outputs = []
+    for (i_new, j_new), out in zip(rows, outs):
+        tiles = terms_of[(i_new, j_new)]
+        for nx in new_codomain.tree_blocks[i_new]:
+            for ny in new_domain.tree_blocks[j_new]:
+                if nx.stop > nx.start and ny.stop > ny.start:
+                    dst = bb.get_item(out, (slice(nx.start, nx.stop), slice(ny.start, ny.stop)))
+                    outputs.append((dst, tiles.get((nx.tree, ny.tree), [])))
+    bb.tree_outer_many(outputs)
+    res = FusionTreeData(np.array(rows, dtype=np.int64), outs)
+    return discard_zero_blocks(bb, res, eps) if discard else res
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

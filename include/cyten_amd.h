@@ -582,6 +582,49 @@ int cyb_trace_weighted_f64(cyb_ctx_t ctx, const cyb_trace_weighted_out* outs, in
 int cyb_trace_weighted_c128(cyb_ctx_t ctx, const cyb_trace_weighted_out* outs, int64_t n_outs, const cyb_trace_weighted_term* terms,
                             int64_t n_terms);
 
+/* ---- weighted Kronecker products into strided tiles ---------------------------------------------------------------
+ * Every result block of FusionTreeBackend::outer (src/backends/fusion_tree_backend.cpp:2609-2667) in ONE launch: the
+ * reference makes, per (tree pair of a, tree pair of b), outer, permute_axes, combine_legs and then get_item, mul, operator+
+ * and set_item per (new codomain tree, new domain tree) into a zero-filled result.  Here an output record is one destination
+ * tile of ha * hb rows and wa * wb columns and a term record one contributing (tree pair of a, tree pair of b):
+ *   dst[(ra * hb + rb) * ldd + ca * wb + cb] = sum_{t in [first_term, first_term + n_terms)} c_t * A_t[ra * a_rs + ca * a_cs]
+ *                                                                                              * B_t[rb * b_rs + cb * b_cs]
+ * ra < ha, rb < hb, ca < wa, cb < wb (the axes (a.cod, b.cod | a.dom, b.dom) in C order, :2636-2639), c_t = coeff_re + i coeff_im.
+ * The destination tile has unit column stride; ldd is the leading dimension of the coupled block it lies in.  a_rs, a_cs,
+ * b_rs, b_cs are row and column strides in elements of the operand's own type: views and transposed views are read in
+ * place.  All terms of an output share its four extents.
+ *   * Every destination element has exactly one owner, which adds its terms in ascending order as (c_t * A_t) * B_t: no
+ *     float atomics, no zero fill, no second pass; results are bit-identical from run to run.
+ *   * An output with no terms is written as zeros: a tile nothing contributes to is zeroed without a memset.
+ *   * Zero extents and empty lists are valid.
+ *   * Sources are read in place and may overlap each other.  Destination tiles of one call must not overlap; the caller
+ *     vouches for that.
+ *   * a_real / b_real != 0 (c128 entry only; the f64 entry ignores them): the operand is float64 data read in place, strides
+ *     in doubles -- a real operand beside a complex one, or under complex amplitudes, needs no promotion pass.  The c128
+ *     entry reads and writes interleaved (re, im) storage otherwise, strides and ldd counted in complex elements.
+ *   * The f64 entry requires coeff_im == 0 of every term: else CYB_ERR_INVALID, nothing is launched.
+ *   * Everything is validated on the host before anything is uploaded or launched: negative extents (and extents beyond
+ *     2^30), term ranges, ldd < wa * wb of a tile of more than one row, NULL dst / a / b of a non-empty output.  A refused
+ *     call returns CYB_ERR_INVALID with a message and leaves the context as it found it.
+ * One wave owns a work item of a record, lanes along the columns, 16-byte stores (csrc/tree_outer.hip). */
+typedef struct {
+    double* dst;
+    int64_t ha, hb, wa, wb;
+    int64_t ldd;
+    int64_t first_term, n_terms;
+} cyb_outer_weighted_out;
+typedef struct {
+    const double* a;
+    const double* b;
+    double coeff_re, coeff_im;
+    int32_t a_real, b_real;
+    int64_t a_rs, a_cs, b_rs, b_cs;
+} cyb_outer_weighted_term;
+int cyb_outer_weighted_f64(cyb_ctx_t ctx, const cyb_outer_weighted_out* outs, int64_t n_outs, const cyb_outer_weighted_term* terms,
+                           int64_t n_terms);
+int cyb_outer_weighted_c128(cyb_ctx_t ctx, const cyb_outer_weighted_out* outs, int64_t n_outs, const cyb_outer_weighted_term* terms,
+                            int64_t n_terms);
+
 /* ---- grouped matrix exponential of small blocks ---------------------------------------------------------------------
  * E = exp(alpha * A) for every listed square matrix in ONE launch, one workgroup per matrix, the whole computation in LDS
  * (csrc/expm_small.hip).  Replaces NumpyBlockBackend::matrix_exp = scipy.linalg.expm (src/block_backend/numpy.cpp:1227-1234),
