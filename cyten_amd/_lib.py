@@ -152,6 +152,16 @@ class OuterWeightedTerm(C.Structure):
                 ('b_real', C.c_int32), ('a_rs', C.c_int64), ('a_cs', C.c_int64), ('b_rs', C.c_int64), ('b_cs', C.c_int64)]
 
 
+class ComposeWeightedOut(C.Structure):
+    _fields_ = [('dst', C.c_void_p), ('ext', C.c_int64 * 4), ('sd', C.c_int64 * 4), ('axis', C.c_int32), ('reserved', C.c_int32),
+                ('first_term', C.c_int64), ('n_terms', C.c_int64)]
+
+
+class ComposeWeightedTerm(C.Structure):
+    _fields_ = [('a', C.c_void_p), ('b', C.c_void_p), ('coeff_re', C.c_double), ('coeff_im', C.c_double), ('a_real', C.c_int32),
+                ('b_real', C.c_int32), ('K', C.c_int64), ('sa', C.c_int64 * 4), ('b_ns', C.c_int64), ('b_ks', C.c_int64)]
+
+
 class ExpmDesc(C.Structure):
     _fields_ = [('A', C.c_void_p), ('lda', C.c_int64), ('n', C.c_int64), ('a_is_real', C.c_int32), ('reserved', C.c_int32),
                 ('E', C.c_void_p), ('lde', C.c_int64)]
@@ -208,6 +218,8 @@ TRACE_WEIGHTED_OUT_DTYPE = _np.dtype(TraceWeightedOut)
 TRACE_WEIGHTED_TERM_DTYPE = _np.dtype(TraceWeightedTerm)
 OUTER_WEIGHTED_OUT_DTYPE = _np.dtype(OuterWeightedOut)
 OUTER_WEIGHTED_TERM_DTYPE = _np.dtype(OuterWeightedTerm)
+COMPOSE_WEIGHTED_OUT_DTYPE = _np.dtype(ComposeWeightedOut)
+COMPOSE_WEIGHTED_TERM_DTYPE = _np.dtype(ComposeWeightedTerm)
 EXPM_DTYPE = _np.dtype(ExpmDesc)
 OUTER_DTYPE = _np.dtype(OuterRec)
 SEG_DTYPE = _np.dtype(SegRec)
@@ -298,6 +310,8 @@ PROTOTYPES = {
     'cyb_trace_weighted_c128': [_ctx, _P(TraceWeightedOut), C.c_int64, _P(TraceWeightedTerm), C.c_int64],
     'cyb_outer_weighted_f64': [_ctx, _P(OuterWeightedOut), C.c_int64, _P(OuterWeightedTerm), C.c_int64],
     'cyb_outer_weighted_c128': [_ctx, _P(OuterWeightedOut), C.c_int64, _P(OuterWeightedTerm), C.c_int64],
+    'cyb_compose_weighted_f64': [_ctx, _P(ComposeWeightedOut), C.c_int64, _P(ComposeWeightedTerm), C.c_int64],
+    'cyb_compose_weighted_c128': [_ctx, _P(ComposeWeightedOut), C.c_int64, _P(ComposeWeightedTerm), C.c_int64],
     'cyb_expm_small_batched_f64': [_ctx, _P(ExpmDesc), C.c_int64, C.c_double],
     'cyb_expm_small_batched_c128': [_ctx, _P(ExpmDesc), C.c_int64, C.c_double, C.c_double],
     'cyb_norm1_batched_f64': [_ctx, _P(ExpmDesc), C.c_int64, _vp],

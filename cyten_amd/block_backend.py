@@ -1720,6 +1720,83 @@ class HipBlockBackend:
         _lib.check(fn(self.ctx.handle, oarr.ctypes.data_as(C.POINTER(_lib.OuterWeightedOut)), len(outputs),
                       tarr.ctypes.data_as(C.POINTER(_lib.OuterWeightedTerm)), n_t))
 
+    def tree_compose_many(self, outputs):
+        """Weighted short contractions into strided tiles, ONE descriptor upload and ONE launch for all result blocks of a
+        fusion-tree partial_compose (``FusionTreeBackend::partial_compose``, fusion_tree_backend.cpp:2670-2880: get_item,
+        reshape, tdot, permute_axes, reshape, as_scalar, get_item, mul, operator+ and set_item per innermost iteration).
+        `outputs`: a list of ``(dst_view, side, m0, m2, terms)``; ``terms`` a list of ``(a_view, b_view, coeff)``; all views are
+        2-D and read or written in place through their strides (the destination views of one call must not overlap, and have
+        the column stride 1).  ``side == 'domain'``: dst ``(R, m0 N m2)``, a ``(R, m0 K m2)``, b ``(K, N)`` and
+        ``dst[r, (i0, n, i2)] = sum_terms coeff * sum_k a[r, (i0, k, i2)] * b[k, n]``; ``side == 'codomain'``: dst ``(m0 N m2, C)``,
+        a ``(m0 K m2, C)``, b ``(N, K)`` and ``dst[(i0, n, i2), c] = sum_terms coeff * sum_k b[n, k] * a[(i0, k, i2), c]``.  K may
+        differ from term to term; an output without terms becomes zeros.  The destinations decide the entry: all float64 (real
+        sources, real coefficients) or all complex128 (a float64 source is then read as it stands, no promotion pass).  Fixed
+        summation order, bit-identical from run to run (csrc/tree_compose.hip)."""
+        outputs = [(dst, side, int(m0), int(m2), list(terms)) for dst, side, m0, m2, terms in outputs]
+        if not outputs:
+            return
+        dsts = [o[0] for o in outputs]
+        a_srcs = [tm[0] for o in outputs for tm in o[4]]
+        b_srcs = [tm[1] for o in outputs for tm in o[4]]
+        self._numeric_only(dsts + a_srcs + b_srcs, 'tree_compose_many')
+        if any(x.ndim != 2 for x in dsts + a_srcs + b_srcs):
+            raise ValueError('tree_compose_many: destinations and sources are 2-D views')
+        kinds = {d.is_complex for d in dsts}
+        if len(kinds) > 1:
+            raise ValueError('tree_compose_many: the destination views of one call share one dtype')
+        cplx = kinds.pop()
+        o_ext, o_sd, o_axis, o_first, o_n = [], [], [], [], []
+        t_re, t_im, t_K, t_sa, t_bn, t_bk = [], [], [], [], [], []
+        for dst, side, m0, m2, terms in outputs:
+            if side not in ('domain', 'codomain'):
+                raise ValueError(f"tree_compose_many: side is 'domain' or 'codomain', not {side!r}")
+            dom = side == 'domain'
+            H, W = dst.shape
+            if dst.strides[1] != 1 and W > 1:
+                raise ValueError('tree_compose_many: a destination view needs the column stride 1')
+            other, mine = (H, W) if dom else (W, H)          # the untouched extent, the extent m0 * N * m2
+            N = mine // (m0 * m2) if m0 > 0 and m2 > 0 else 0
+            if m0 < 0 or m2 < 0 or m0 * N * m2 != mine:
+                raise ValueError(f'tree_compose_many: a destination view of shape {(H, W)} does not factor as m0 * N * m2 with '
+                                 f'm0 = {m0}, m2 = {m2} in the {side}')
+            ldd = dst.strides[0]
+            for a, b, coeff in terms:
+                K = b.shape[0] if dom else b.shape[1]
+                want_a = (other, m0 * K * m2) if dom else (m0 * K * m2, other)
+                want_b = (K, N) if dom else (N, K)
+                if tuple(a.shape) != want_a or tuple(b.shape) != want_b:
+                    raise ValueError(f'tree_compose_many: a destination view of shape {(H, W)} with m0 = {m0}, m2 = {m2} in the {side} '
+                                     f'for sources of the shapes {tuple(a.shape)} and {tuple(b.shape)}')
+                coeff = complex(coeff)
+                if not cplx and (a.is_complex or b.is_complex or coeff.imag != 0):
+                    raise ValueError('tree_compose_many: a complex source or coefficient needs complex destination views')
+                ars, acs = a.strides
+                t_re.append(coeff.real)
+                t_im.append(coeff.imag)
+                t_K.append(K)
+                t_sa.append((ars, K * m2 * acs, m2 * acs, acs) if dom else (K * m2 * ars, m2 * ars, ars, acs))
+                t_bn.append(b.strides[1] if dom else b.strides[0])
+                t_bk.append(b.strides[0] if dom else b.strides[1])
+            o_first.append(len(t_re) - len(terms))
+            o_n.append(len(terms))
+            o_ext.append((other, m0, N, m2) if dom else (m0, N, m2, other))
+            o_sd.append((ldd, N * m2, m2, 1) if dom else (N * m2 * ldd, m2 * ldd, ldd, 1))
+            o_axis.append(2 if dom else 1)
+        oarr = np.zeros(len(outputs), dtype=_lib.COMPOSE_WEIGHTED_OUT_DTYPE)
+        oarr['dst'], oarr['ext'], oarr['sd'], oarr['axis'] = [d.ptr for d in dsts], o_ext, o_sd, o_axis
+        oarr['first_term'], oarr['n_terms'] = o_first, o_n
+        n_t = len(a_srcs)
+        tarr = np.zeros(max(n_t, 1), dtype=_lib.COMPOSE_WEIGHTED_TERM_DTYPE)
+        if n_t:
+            tarr['a'], tarr['b'], tarr['coeff_re'], tarr['coeff_im'] = [a.ptr for a in a_srcs], [b.ptr for b in b_srcs], t_re, t_im
+            tarr['a_real'] = [0 if a.is_complex or not cplx else 1 for a in a_srcs]
+            tarr['b_real'] = [0 if b.is_complex or not cplx else 1 for b in b_srcs]
+            tarr['K'], tarr['sa'], tarr['b_ns'], tarr['b_ks'] = t_K, t_sa, t_bn, t_bk
+        fn = self.lib.cyb_compose_weighted_c128 if cplx else self.lib.cyb_compose_weighted_f64
+        self.ctx.sync_stream()
+        _lib.check(fn(self.ctx.handle, oarr.ctypes.data_as(C.POINTER(_lib.ComposeWeightedOut)), len(outputs),
+                      tarr.ctypes.data_as(C.POINTER(_lib.ComposeWeightedTerm)), n_t))
+
     def _wdot(self, descs, cplx, conj):
         """launch chain of the weighted reduction + the one read of its result"""
         n = len(descs)

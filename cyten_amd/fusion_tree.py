@@ -41,6 +41,10 @@ module mirrors is everything BETWEEN that layer and the block backend:
 * :func:`outer`  <- ``::outer`` (:2609-2667): the double loop over the tree-block pairs of a and of b emits one output record
   per tile of the result blocks and one weighted term per contributing (a tree pair, b tree pair); the arithmetic is ONE
   ``tree_outer_many`` launch.  What ``FusionTree::outer`` says per pair of trees comes in as a :class:`TreeOuter`.
+* :func:`partial_compose`  <- ``::partial_compose`` (:2670-2880): the five-deep loop over outer trees, b's codomain trees, b's
+  domain trees, old trees and new trees emits one output record per new tree of the contracted side (a strip of a result
+  block) and one weighted term per innermost iteration; the arithmetic is ONE ``tree_compose_many`` launch.  What
+  ``FusionTree::insert_at`` says per (outer tree, tree of b) comes in as a :class:`TreeInsert`.
 * :class:`TreeTensor`: data + codomain + domain, the vector the Krylov solvers and the operator wrappers take
   (``cyten_amd.krylov``, ``cyten_amd.sparse``): the reference's Krylov code calls ``inner`` / ``norm`` /
   ``linear_combination`` on whatever tensor it is given (src/tensors/krylov_based.cpp), and those need the quantum dimensions
@@ -56,7 +60,7 @@ import numpy as np
 __all__ = ['TreeBlock', 'TreeSpace', 'FusionTreeData', 'compose', 'svd', 'qr', 'lq', 'eigh', 'truncate_singular_values',
            'transform_tensor', 'discard_zero_blocks', 'norm', 'inner', 'trace_full', 'mul', 'linear_combination', 'dagger',
            'almost_equal', 'TreeAxisRecord', 'TreeMask', 'leg_keys', 'scale_axis', 'mask_contract', 'truncated_svd', 'TreeTensor',
-           'same_space', 'TreeTrace', 'partial_trace', 'TreeOuter', 'outer']
+           'same_space', 'TreeTrace', 'partial_trace', 'TreeOuter', 'outer', 'TreeInsert', 'partial_compose']
 
 
 @dataclass(frozen=True)
@@ -620,6 +624,158 @@ def outer(bb, a: FusionTreeData, a_codomain: TreeSpace, a_domain: TreeSpace, b: 
                     outputs.append((dst, tiles.get((nx.tree, ny.tree), [])))
     bb.tree_outer_many(outputs)
     res = FusionTreeData(np.array(rows, dtype=np.int64), outs)
+    return discard_zero_blocks(bb, res, eps) if discard else res
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# partial_compose
+
+class TreeInsert(NamedTuple):
+    """what the symmetry layer knows about inserting b's trees into one leg of the outer trees (FusionTree::insert_at,
+    src/symmetries/trees.cpp:1218-1351; the iter_space of fusion_tree_backend.cpp:2697-2747), as data"""
+    side: str           # 'codomain' | 'domain': the side of a that is contracted
+    leg: int            # leg_idx: position of the inserted leg among the legs of that side, in that side's own order
+    outer_trees: dict   # coupled sector (tuple) -> [(outer tree key, b's coupled sector (tuple), m_before, m_after), ...] in iter_tree_blocks order
+    table: dict         # (outer tree key, b tree key) -> [(tree key, amplitude), ...]; looked up with b's codomain trees AND b's domain trees
+
+
+def _inserted_trees(space: TreeSpace, insert: TreeInsert, seen: dict, outer_key, b_key, what: str):
+    """[(coupled sector, TreeBlock, amplitude)] of ``outer tree.insert_at(leg, b tree)`` in `space`, checked once per pair"""
+    res = seen.get((outer_key, b_key))
+    if res is not None:
+        return res
+    hit = insert.table.get((outer_key, b_key))
+    if hit is None:
+        raise ValueError(f'partial_compose: the table has no entry for the outer tree {outer_key!r} and the tree {b_key!r} of b')
+    res = []
+    for key, amp in hit:
+        if not space.has_tree(key):
+            raise ValueError(f'partial_compose: the {what} has no tree {key!r}')
+        i, tb = space.tree_block_slice(key)
+        res.append((tuple(space.sectors[i].tolist()), tb, amp))
+    seen[(outer_key, b_key)] = res
+    return res
+
+
+def partial_compose(bb, a: FusionTreeData, a_codomain: TreeSpace, a_domain: TreeSpace, b: FusionTreeData, b_codomain: TreeSpace,
+                    b_domain: TreeSpace, new_codomain: TreeSpace, new_domain: TreeSpace, insert: TreeInsert, eps: float = 0.0,
+                    discard: bool = True) -> FusionTreeData:
+    """``FusionTreeBackend::partial_compose`` (fusion_tree_backend.cpp:2670-2880): ALL legs of one side of `b` are contracted
+    with a contiguous run of legs of one side of `a` -- b's codomain with legs of a's domain (``insert.side == 'domain'``), or
+    b's domain with legs of a's codomain (``'codomain'``) -- without bending and braiding `a` first.  `new_codomain` /
+    `new_domain`: the spaces of the result; the side that is not contracted keeps a's space.  `insert`: the outer ("dummy")
+    trees of every coupled sector (the ``iter_space`` of :2697-2747, in which the contracted legs are one leg that carries
+    b's coupled sectors) and what ``insert_at`` says per (outer tree, tree of b), as data (:class:`TreeInsert`).
+
+    The loops are the reference's.  A block of `a` gives a result block if its coupled sector is in both new spaces
+    (:2756-2768).  For every outer tree of that sector (:2771; its b-sector must have a block in `b`, :2775), every codomain
+    tree ``xb`` and every domain tree ``yb`` of that block of b (:2787-2794):
+
+    * ``'domain'`` (:2797-2827): old trees (in a's domain) from ``table[(tree, xb)]``, new trees (in the new domain) from
+      ``table[(tree, yb)]``, factor ``amp_old * conj(amp_new)`` (:2817); the tree block of b is K x N;
+    * ``'codomain'`` (:2828-2857): old trees (in a's codomain) from ``table[(tree, yb)]``, new trees (in the new codomain) from
+      ``table[(tree, xb)]``, factor ``conj(amp_old) * amp_new`` (:2847); the tree block of b is N x K.
+
+    The placement of the conjugate is the reference's in both cases; its own TODO at :2687 asks whether the domain case
+    should conjugate as the codomain case does, which only a symmetry with complex F symbols can decide.  It is kept as it
+    is, not "fixed".
+
+    Instead of get_item, reshape, tdot, permute_axes, reshape, as_scalar, get_item, mul, operator+ and set_item per innermost
+    iteration, every result block gets one output record per new tree of the contracted side in tree-block order -- a
+    full-height column strip (domain) or a full-width row strip (codomain), strips without a term included (they are written
+    as zeros, so the result needs no zero fill) -- and every contributing (outer tree, xb, yb, old tree, new tree) gives one
+    term record, in exactly that loop order, with the old strip of a and the tree block of b read in place.  ONE
+    ``tree_compose_many`` call for the whole tensor.  The result is complex if `a`, `b` or an amplitude is, sorted by
+    ``block_inds``, and goes through :func:`discard_zero_blocks` with `eps` unless ``discard=False`` (:2878).  An empty `a` or
+    `b` gives empty data (:2694).
+
+    The kernel behind it is shaped for SMALL contracted extents K and surviving extents N -- the multiplicities of physical
+    and MPO legs, a short register loop per result element.  A large K (contracting over a bond leg of dimension chi) is
+    still correct but runs at no GEMM rate: bend the legs with :func:`transform_tensor` and use :func:`compose` there."""
+    if insert.side not in ('codomain', 'domain'):
+        raise ValueError(f"partial_compose: insert.side is 'codomain' or 'domain', not {insert.side!r}")
+    if not a.blocks or not b.blocks:
+        return FusionTreeData(np.zeros((0, 2), np.int64), [])
+    dom = insert.side == 'domain'
+    old_space, new_space = (a_domain, new_domain) if dom else (a_codomain, new_codomain)
+    amps = [amp for lst in insert.table.values() for _, amp in lst]
+    cplx = any(_is_complex(blk) for blk in a.blocks + b.blocks) or any(complex(x).imag != 0.0 for x in amps)
+    where_cod = {tuple(s): k for k, s in enumerate(new_codomain.sectors.tolist())}
+    where_dom = {tuple(s): k for k, s in enumerate(new_domain.sectors.tolist())}
+    where_b = {tuple(s): k for k, s in enumerate(b_domain.sectors.tolist())}
+    seen_old, seen_new = {}, {}
+    b_tiles: dict = {}                 # (block of b, xb tree, yb tree) -> view
+    rows, shapes, plans = [], [], []
+    for n, (i, j) in enumerate(a.block_inds.tolist()):
+        coupled = tuple(a_codomain.sectors[i].tolist())
+        if coupled not in where_cod or coupled not in where_dom:
+            continue                                                     # (:2762)
+        i_new, j_new = where_cod[coupled], where_dom[coupled]
+        shape = (new_codomain.block_size(i_new), new_domain.block_size(j_new))
+        kept, kept_old = (shape[0], a_codomain.block_size(i)) if dom else (shape[1], a_domain.block_size(j))
+        if kept != kept_old:
+            raise ValueError(f'partial_compose: the result block of the coupled sector {coupled} has {kept} '
+                             f'{"rows" if dom else "columns"}, the block of a {kept_old}: the side that is not contracted keeps its space')
+        strips = {nb.tree: [nb, None, []] for nb in new_space.tree_blocks[j_new if dom else i_new]}   # tree -> [block, (m0, m2), terms]
+        a_strips: dict = {}
+        for tree, b_sector, m0, m2 in insert.outer_trees.get(coupled, ()):                            # (:2771)
+            jb = where_b.get(tuple(b_sector))
+            nb_ = b.block_ind_from_domain_sector(jb) if jb is not None else None
+            if nb_ is None:
+                raise ValueError(f'partial_compose: b has no block in the coupled sector {tuple(b_sector)} of the outer tree {tree!r}')   # (:2775)
+            ib = int(b.block_inds[nb_, 0])
+            m0, m2 = int(m0), int(m2)
+            for xb in b_codomain.tree_blocks[ib]:                                                     # (:2787)
+                for yb in b_domain.tree_blocks[jb]:                                                   # (:2789)
+                    kb, sb = (xb, yb) if dom else (yb, xb)          # the tree of b's contracted side, of its surviving side
+                    olds = _inserted_trees(old_space, insert, seen_old, tree, kb.tree, f'{insert.side} of a')
+                    news = _inserted_trees(new_space, insert, seen_new, tree, sb.tree, f'new {insert.side}')
+                    K, N = kb.stop - kb.start, sb.stop - sb.start
+                    B = None
+                    for sec_old, ob, amp_old in olds:                                                 # (:2799 / :2829)
+                        if sec_old != coupled:
+                            raise ValueError(f'partial_compose: the old tree {ob.tree!r} lies in the coupled sector {sec_old}, not in {coupled}')
+                        if ob.stop - ob.start != m0 * K * m2:
+                            raise ValueError(f'partial_compose: the old tree {ob.tree!r} has the size {ob.stop - ob.start}, not m_before * K * '
+                                             f'm_after = {m0} * {K} * {m2}')
+                        for sec_new, nb, amp_new in news:                                             # (:2807 / :2837)
+                            if sec_new != coupled:
+                                raise ValueError(f'partial_compose: the new tree {nb.tree!r} lies in the coupled sector {sec_new}, not in {coupled}')
+                            if nb.stop - nb.start != m0 * N * m2:
+                                raise ValueError(f'partial_compose: the new tree {nb.tree!r} has the size {nb.stop - nb.start}, not m_before * N * '
+                                                 f'm_after = {m0} * {N} * {m2}')
+                            strip = strips[nb.tree]
+                            if strip[1] is None:
+                                strip[1] = (m0, m2)
+                            elif strip[1] != (m0, m2):
+                                raise ValueError(f'partial_compose: the outer trees that feed the new tree {nb.tree!r} differ in (m_before, m_after): '
+                                                 f'{strip[1]} and {(m0, m2)}')
+                            A = a_strips.get(ob.tree)
+                            if A is None:
+                                sl = slice(ob.start, ob.stop)
+                                A = a_strips[ob.tree] = bb.get_item(a.blocks[n], (slice(None), sl) if dom else (sl, slice(None)))
+                            if B is None:
+                                B = b_tiles.get((nb_, xb.tree, yb.tree))
+                                if B is None:
+                                    B = b_tiles[(nb_, xb.tree, yb.tree)] = bb.get_item(
+                                        b.blocks[nb_], (slice(xb.start, xb.stop), slice(yb.start, yb.stop)))
+                            coeff = amp_old * np.conj(amp_new) if dom else np.conj(amp_old) * amp_new   # (:2817 / :2847)
+                            strip[2].append((A, B, complex(coeff) if cplx else float(np.real(coeff))))
+        rows.append((i_new, j_new))
+        shapes.append(shape)
+        plans.append(strips)
+    if not rows:
+        return FusionTreeData(np.zeros((0, 2), np.int64), [])
+    outs = bb.empty_many(shapes, dtype=np.complex128 if cplx else np.float64)
+    outputs = []
+    for out, shape, strips in zip(outs, shapes, plans):
+        for nb, mm, terms in strips.values():
+            if nb.stop > nb.start and shape[0] > 0 and shape[1] > 0:
+                sl = slice(nb.start, nb.stop)
+                dst = bb.get_item(out, (slice(None), sl) if dom else (sl, slice(None)))
+                outputs.append((dst, insert.side, *(mm or (1, 1)), terms))
+    bb.tree_compose_many(outputs)
+    res = FusionTreeData(np.array(rows, dtype=np.int64), outs).sorted()
     return discard_zero_blocks(bb, res, eps) if discard else res
 
 

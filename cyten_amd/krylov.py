@@ -146,10 +146,13 @@ class TreeChainOperator:
 
     * ``('compose_left', A)``: ``X <- A X``, `A` a :class:`fusion_tree.TreeTensor` whose domain is X's codomain;
     * ``('compose_right', B)``: ``X <- X B``, `B` a TreeTensor whose codomain is X's domain;
-    * ``('transform', new_codomain, new_domain, codomain_idcs, domain_idcs, mapping)``: one ``ft.transform_tensor``.
+    * ``('transform', new_codomain, new_domain, codomain_idcs, domain_idcs, mapping)``: one ``ft.transform_tensor``;
+    * ``('partial_compose', B, b_codomain, b_domain, new_codomain, new_domain, insert)``: one ``ft.partial_compose`` of X with
+      the blocks `B` (a :class:`fusion_tree.FusionTreeData`) on (`b_codomain`, `b_domain`), `insert` a
+      :class:`fusion_tree.TreeInsert` -- a site operator or a gate applied to some legs of one side of X.
 
     ``matvec`` tracks the spaces through the chain; the constructor checks that every step fits the spaces the one before
-    leaves.  ``is_complex``: any operand block or mapping coefficient is complex.  This is host composition of the existing
+    leaves.  ``is_complex``: any operand block, mapping coefficient or insert amplitude is complex.  This is host composition of the existing
     launches (one grouped GEMM per compose, one ``transform_blocks`` per transform); recording and replaying the launch
     sequence (:mod:`cyten_amd.replay`) is out of scope here."""
 
@@ -178,6 +181,13 @@ class TreeChainOperator:
                 cod, dom = st[1], st[2]
                 cplx = cplx or any(isinstance(c, (complex, np.complexfloating)) and complex(c).imag != 0.0
                                    for targets in st[5].values() for c in targets.values())
+            elif kind == 'partial_compose':
+                if len(st) != 7 or not isinstance(st[1], ft.FusionTreeData) or not isinstance(st[6], ft.TreeInsert):
+                    raise ValueError(f'step {n}: (\'partial_compose\', FusionTreeData, b_codomain, b_domain, new_codomain, new_domain, '
+                                     'TreeInsert) expected')
+                cod, dom = st[4], st[5]
+                cplx = cplx or any(_is_complex_block(b) for b in st[1].blocks) or any(
+                    complex(amp).imag != 0.0 for lst in st[6].table.values() for _, amp in lst)
             else:
                 raise ValueError(f'step {n}: unknown kind {kind!r}')
         self.out_codomain, self.out_domain = cod, dom
@@ -191,6 +201,10 @@ class TreeChainOperator:
                 data, cod = ft.compose(bb, st[1].data, data), st[1].codomain
             elif st[0] == 'compose_right':
                 data, dom = ft.compose(bb, data, st[1].data), st[1].domain
+            elif st[0] == 'partial_compose':
+                _, B, b_cod, b_dom, new_cod, new_dom, insert = st
+                data = ft.partial_compose(bb, data, cod, dom, B, b_cod, b_dom, new_cod, new_dom, insert)
+                cod, dom = new_cod, new_dom
             else:
                 _, new_cod, new_dom, codomain_idcs, domain_idcs, mapping = st
                 data = ft.transform_tensor(bb, data, cod, dom, new_cod, new_dom, codomain_idcs, domain_idcs, mapping)

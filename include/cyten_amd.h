@@ -625,6 +625,63 @@ int cyb_outer_weighted_f64(cyb_ctx_t ctx, const cyb_outer_weighted_out* outs, in
 int cyb_outer_weighted_c128(cyb_ctx_t ctx, const cyb_outer_weighted_out* outs, int64_t n_outs, const cyb_outer_weighted_term* terms,
                             int64_t n_terms);
 
+/* ---- weighted short contractions into strided tiles ---------------------------------------------------------------
+ * Every result block of FusionTreeBackend::partial_compose (src/backends/fusion_tree_backend.cpp:2670-2880) in ONE launch:
+ * the reference makes, per (outer tree, b codomain tree, b domain tree, old tree, new tree), get_item, reshape, tdot,
+ * permute_axes, reshape, as_scalar, get_item, mul, operator+ and set_item into a zero-filled result.  Here an output record
+ * is one destination tile seen as the 4-level index space (x0, x1, x2, x3) in C order, x_l < ext[l], with the destination
+ * strides sd[4]; the level `axis` (1 or 2) carries the surviving index n of b.  A term record is one contributing (old tree,
+ * b tree pair) with its own contracted extent K:
+ *   dst[sum_l x_l * sd[l]] = sum_{t in [first_term, first_term + n_terms)} c_t * sum_{k < K_t}
+ *                                A_t[sum_{l != axis} x_l * sa[l] + k * sa[axis]] * B_t[x_axis * b_ns + k * b_ks]
+ * c_t = coeff_re + i coeff_im.  All strides count elements of the operand's own type: views and transposed views are read in
+ * place.  The two cases of the reference, with m0 / m2 the products of the multiplicities before / after the inserted leg,
+ * N = ext[axis], lda / ldd the leading dimensions of the coupled blocks:
+ *   contraction in a's domain (:2797-2827): levels (r, i0, n, i2), axis = 2, sd = (ldd, N m2, m2, 1), sa = (lda, K m2, m2, 1),
+ *       B the K x N tree block (b_ks its row stride, b_ns its column stride);
+ *   contraction in a's codomain (:2828-2857): levels (i0, n, i2, col), axis = 1, sd = (N m2 ldd, m2 ldd, ldd, 1),
+ *       sa = (K m2 lda, m2 lda, lda, 1), B the N x K tree block (b_ns its row stride, b_ks its column stride).
+ *   * Every destination element has exactly one owner.  Within a term it sums k ascending, then adds c_t * that sum, terms
+ *     ascending: no float atomics, no zero fill, no second pass; results are bit-identical from run to run.
+ *   * An output with no terms is written as zeros.
+ *   * Zero extents, K == 0 (the term adds nothing; its a and b are not read and may be NULL) and empty lists are valid.
+ *   * Sources are read in place and may overlap each other.  Destination tiles of one call must not overlap; the caller
+ *     vouches for that.
+ *   * a_real / b_real != 0 (c128 entry only; the f64 entry ignores them): the operand is float64 data read in place, strides
+ *     in doubles -- a real operand beside a complex one needs no promotion pass.  The c128 entry reads and writes
+ *     interleaved (re, im) storage otherwise, strides counted in complex elements.
+ *   * The f64 entry requires coeff_im == 0 of every term: else CYB_ERR_INVALID, nothing is launched.
+ *   * Everything is validated on the host before anything is uploaded or launched: negative extents, extents or K beyond
+ *     2^30 (or negative K), axis outside {1, 2}, term ranges, sd[3] != 1 where ext[3] > 1, NULL dst of a non-empty output,
+ *     NULL a / b of a term with K > 0 of a non-empty output.  A refused call returns CYB_ERR_INVALID with a message and leaves
+ *     the context as it found it.
+ * One wave owns a work item of a record, lanes along the flat order of the levels.  16-byte stores: one complex, or a pair
+ * of doubles (x_p, x_p + 1) along the last level p whose extent is above 1, iff sd[p] == 1, ext[p] is even, sd[l] is even for
+ * every l < p with ext[l] > 1, and dst is 16-byte aligned; else one double per lane.  Iff p != axis, n runs in the registers of a
+ * lane (four values at a time, A loaded once per k for all of them) instead of in the lanes (csrc/tree_compose.hip).  The kernel is
+ * shaped for small K and N (multiplicities of physical / MPO legs); a large K is correct but runs at no GEMM rate. */
+typedef struct {
+    double* dst;
+    int64_t ext[4];
+    int64_t sd[4];
+    int32_t axis;     /* 1 or 2: the level of b's surviving index n */
+    int32_t reserved;
+    int64_t first_term, n_terms;
+} cyb_compose_weighted_out;
+typedef struct {
+    const double* a;
+    const double* b;
+    double coeff_re, coeff_im;
+    int32_t a_real, b_real;
+    int64_t K;
+    int64_t sa[4];
+    int64_t b_ns, b_ks;
+} cyb_compose_weighted_term;
+int cyb_compose_weighted_f64(cyb_ctx_t ctx, const cyb_compose_weighted_out* outs, int64_t n_outs, const cyb_compose_weighted_term* terms,
+                             int64_t n_terms);
+int cyb_compose_weighted_c128(cyb_ctx_t ctx, const cyb_compose_weighted_out* outs, int64_t n_outs, const cyb_compose_weighted_term* terms,
+                              int64_t n_terms);
+
 /* ---- grouped matrix exponential of small blocks ---------------------------------------------------------------------
  * E = exp(alpha * A) for every listed square matrix in ONE launch, one workgroup per matrix, the whole computation in LDS
  * (csrc/expm_small.hip).  Replaces NumpyBlockBackend::matrix_exp = scipy.linalg.expm (src/block_backend/numpy.cpp:1227-1234),
