@@ -13,6 +13,8 @@ LIB_PATH = PKG_DIR / 'lib' / 'libcyten_amd.so'
 
 CYB_MAX_NDIM = 8
 CYB_TRACE_MAX_PAIRS = 4
+CYB_TREE_DENSE_MAX_LEGS = 6
+CYB_TREE_DENSE_MAX_LEVELS = 12
 CYB_SVD_SKIP_NULL_VECTORS = 1
 CYB_SVD_EMBEDDED_COMPLEX = 2
 CYB_EIGH_EMBEDDED_COMPLEX = 2
@@ -162,6 +164,29 @@ class ComposeWeightedTerm(C.Structure):
                 ('b_real', C.c_int32), ('K', C.c_int64), ('sa', C.c_int64 * 4), ('b_ns', C.c_int64), ('b_ks', C.c_int64)]
 
 
+class TreeToDenseOut(C.Structure):
+    _fields_ = [('dst', C.c_void_p), ('n_levels', C.c_int32), ('reserved', C.c_int32), ('ext', C.c_int64 * CYB_TREE_DENSE_MAX_LEVELS),
+                ('sd', C.c_int64 * CYB_TREE_DENSE_MAX_LEVELS), ('ss', C.c_int64 * CYB_TREE_DENSE_MAX_LEVELS),
+                ('sr', C.c_int64 * CYB_TREE_DENSE_MAX_LEVELS), ('sc', C.c_int64 * CYB_TREE_DENSE_MAX_LEVELS), ('first_term', C.c_int64),
+                ('n_terms', C.c_int64)]
+
+
+class TreeToDenseTerm(C.Structure):
+    _fields_ = [('block', C.c_void_p), ('first_row', C.c_int64), ('first_col', C.c_int64), ('rs', C.c_int64), ('cs', C.c_int64), ('s_off', C.c_int64),
+                ('block_real', C.c_int32), ('s_real', C.c_int32)]
+
+
+class TreeFromDenseOut(C.Structure):
+    _fields_ = [('dst', C.c_void_p), ('n_levels', C.c_int32), ('n_k', C.c_int32), ('ext', C.c_int64 * CYB_TREE_DENSE_MAX_LEGS),
+                ('sd', C.c_int64 * CYB_TREE_DENSE_MAX_LEGS), ('ss', C.c_int64 * CYB_TREE_DENSE_MAX_LEGS),
+                ('kext', C.c_int64 * CYB_TREE_DENSE_MAX_LEGS), ('ks', C.c_int64 * CYB_TREE_DENSE_MAX_LEGS), ('divisor', C.c_double),
+                ('first_term', C.c_int64), ('n_terms', C.c_int64)]
+
+
+class TreeFromDenseTerm(C.Structure):
+    _fields_ = [('src', C.c_void_p), ('s_off', C.c_int64), ('src_real', C.c_int32), ('s_real', C.c_int32)]
+
+
 class ExpmDesc(C.Structure):
     _fields_ = [('A', C.c_void_p), ('lda', C.c_int64), ('n', C.c_int64), ('a_is_real', C.c_int32), ('reserved', C.c_int32),
                 ('E', C.c_void_p), ('lde', C.c_int64)]
@@ -220,6 +245,10 @@ OUTER_WEIGHTED_OUT_DTYPE = _np.dtype(OuterWeightedOut)
 OUTER_WEIGHTED_TERM_DTYPE = _np.dtype(OuterWeightedTerm)
 COMPOSE_WEIGHTED_OUT_DTYPE = _np.dtype(ComposeWeightedOut)
 COMPOSE_WEIGHTED_TERM_DTYPE = _np.dtype(ComposeWeightedTerm)
+TREE_TO_DENSE_OUT_DTYPE = _np.dtype(TreeToDenseOut)
+TREE_TO_DENSE_TERM_DTYPE = _np.dtype(TreeToDenseTerm)
+TREE_FROM_DENSE_OUT_DTYPE = _np.dtype(TreeFromDenseOut)
+TREE_FROM_DENSE_TERM_DTYPE = _np.dtype(TreeFromDenseTerm)
 EXPM_DTYPE = _np.dtype(ExpmDesc)
 OUTER_DTYPE = _np.dtype(OuterRec)
 SEG_DTYPE = _np.dtype(SegRec)
@@ -312,6 +341,10 @@ PROTOTYPES = {
     'cyb_outer_weighted_c128': [_ctx, _P(OuterWeightedOut), C.c_int64, _P(OuterWeightedTerm), C.c_int64],
     'cyb_compose_weighted_f64': [_ctx, _P(ComposeWeightedOut), C.c_int64, _P(ComposeWeightedTerm), C.c_int64],
     'cyb_compose_weighted_c128': [_ctx, _P(ComposeWeightedOut), C.c_int64, _P(ComposeWeightedTerm), C.c_int64],
+    'cyb_tree_to_dense_f64': [_ctx, _P(TreeToDenseOut), C.c_int64, _P(TreeToDenseTerm), C.c_int64, C.c_void_p],
+    'cyb_tree_to_dense_c128': [_ctx, _P(TreeToDenseOut), C.c_int64, _P(TreeToDenseTerm), C.c_int64, C.c_void_p],
+    'cyb_tree_from_dense_f64': [_ctx, _P(TreeFromDenseOut), C.c_int64, _P(TreeFromDenseTerm), C.c_int64, C.c_void_p],
+    'cyb_tree_from_dense_c128': [_ctx, _P(TreeFromDenseOut), C.c_int64, _P(TreeFromDenseTerm), C.c_int64, C.c_void_p],
     'cyb_expm_small_batched_f64': [_ctx, _P(ExpmDesc), C.c_int64, C.c_double],
     'cyb_expm_small_batched_c128': [_ctx, _P(ExpmDesc), C.c_int64, C.c_double, C.c_double],
     'cyb_norm1_batched_f64': [_ctx, _P(ExpmDesc), C.c_int64, _vp],

@@ -1797,6 +1797,153 @@ class HipBlockBackend:
         _lib.check(fn(self.ctx.handle, oarr.ctypes.data_as(C.POINTER(_lib.ComposeWeightedOut)), len(outputs),
                       tarr.ctypes.data_as(C.POINTER(_lib.ComposeWeightedTerm)), n_t))
 
+    def _tree_pair_table(self, tensors):
+        """the tree-pair tensors of one call (host arrays, each once) as ONE device table: (table block or None, offset of
+        every tensor by id, whether the table is complex)"""
+        uniq, offs, tot = [], {}, 0
+        for s in tensors:
+            if id(s) not in offs:
+                offs[id(s)] = tot
+                tot += s.size
+                uniq.append(s)
+        cplx = any(np.iscomplexobj(s) for s in uniq)
+        if not tot:
+            return None, offs, cplx
+        flat = np.concatenate([np.asarray(s, dtype=np.complex128 if cplx else np.float64).ravel() for s in uniq])
+        return self.block_from_numpy(flat), offs, cplx
+
+    @staticmethod
+    def _tree_dense_region(what, view, starts, dims, mults, J):
+        """checks one region of a dense view (axes in leg order) and returns its element offset inside the view"""
+        L = view.ndim
+        if not (len(starts) == len(dims) == len(mults) == L and 0 <= J <= L):
+            raise ValueError(f'{what}: a region names {len(starts)} starts, {len(dims)} dimensions and {len(mults)} multiplicities for a view of {L} axes')
+        if any(d < 1 or m < 0 or s < 0 or s + d * m > n for s, d, m, n in zip(starts, dims, mults, view.shape)):
+            raise ValueError(f'{what}: the region at {tuple(starts)} with the dimensions {tuple(dims)} and multiplicities {tuple(mults)} leaves the '
+                             f'view of shape {view.shape}')
+        return sum(s * st for s, st in zip(starts, view.strides))
+
+    def tree_to_dense_many(self, dst_view, regions):
+        """Every region of a dense tensor from the coupled blocks of a fusion-tree tensor, ONE table upload, ONE descriptor
+        upload and ONE launch (``FusionTreeBackend::to_dense_block``, fusion_tree_backend.cpp:1856-1973: per pair of trees of
+        every forest pair zeros, two to_dense_block of trees, tdot, get_item, reshape, outer, operator+, then permute_axes,
+        reshape and an accumulating set_item into a zero-filled result).  `dst_view`: the dense tensor as any strided view
+        whose axes are the flat legs in (codomain..., domain...) order, at most ``CYB_TREE_DENSE_MAX_LEGS`` of them, written in
+        place.  `regions`: a list of ``(starts, dims, mults, J, terms)`` -- per leg the first position of its sector on that
+        axis, the sector's dimension d and multiplicity m (the region spans d * m positions, index ``k * m + mu``); the first `J`
+        legs index the rows of a block, the others its columns; ``terms`` a list of ``(block, first_row, first_col, S)`` with a
+        2-D block view read in place through its strides and a host array ``S`` of shape `dims`:
+        ``region[(k_1, m_1), ..] = sum_terms S[k_1, ..] * block[first_row + (m_1 .. m_J), first_col + (n_1 .. n_K)]`` (C order),
+        zeros without a term.  The regions of one call must not overlap; what no region covers stays as it is.  The destination
+        decides the entry: float64 (real blocks, real S) or complex128 (a float64 block or a real table is then read as it
+        stands, no promotion pass).  Fixed summation order, bit-identical from run to run (csrc/tree_dense.hip)."""
+        what = 'tree_to_dense_many'
+        regions = [(tuple(st), tuple(d), tuple(m), int(J), list(terms)) for st, d, m, J, terms in regions]
+        if not regions:
+            return
+        blocks = [tm[0] for r in regions for tm in r[4]]
+        self._numeric_only([dst_view] + blocks, what)
+        L, cplx = dst_view.ndim, dst_view.is_complex
+        if L > _lib.CYB_TREE_DENSE_MAX_LEGS:
+            raise ValueError(f'{what}: a destination view with more than {_lib.CYB_TREE_DENSE_MAX_LEGS} axes')
+        if any(b.ndim != 2 for b in blocks):
+            raise ValueError(f'{what}: blocks are 2-D views')
+        table, s_offs, s_cplx = self._tree_pair_table([tm[3] for r in regions for tm in r[4]])
+        if not cplx and (s_cplx or any(b.is_complex for b in blocks)):
+            raise ValueError(f'{what}: a complex block or tree tensor needs a complex destination view')
+        order = sorted(range(L), key=lambda l: -abs(dst_view.strides[l]))       # the last level: the contiguous run of the destination
+        nl = _lib.CYB_TREE_DENSE_MAX_LEVELS
+        oarr = np.zeros(len(regions), dtype=_lib.TREE_TO_DENSE_OUT_DTYPE)
+        tarr = np.zeros(max(len(blocks), 1), dtype=_lib.TREE_TO_DENSE_TERM_DTYPE)
+        es, t = (16 if cplx else 8), 0
+        for i, (starts, dims, mults, J, terms) in enumerate(regions):
+            off = self._tree_dense_region(what, dst_view, starts, dims, mults, J)
+            s_str = _c_strides(dims)
+            r_str, c_str = _c_strides(mults[:J]), _c_strides(mults[J:])
+            ext, sd, ss, sr, sc = [], [], [], [], []
+            for l in order:
+                ext += [dims[l], mults[l]]
+                sd += [mults[l] * dst_view.strides[l], dst_view.strides[l]]
+                ss += [s_str[l], 0]
+                sr += [0, r_str[l] if l < J else 0]
+                sc += [0, c_str[l - J] if l >= J else 0]
+            pad = (0,) * (nl - 2 * L)
+            H, W = math.prod(mults[:J]), math.prod(mults[J:])
+            for blk, r0, c0, S in terms:
+                if tuple(S.shape) != dims:
+                    raise ValueError(f'{what}: a tree tensor pair of shape {tuple(S.shape)} for the sector dimensions {dims}')
+                if r0 < 0 or c0 < 0 or r0 + H > blk.shape[0] or c0 + W > blk.shape[1]:
+                    raise ValueError(f'{what}: the tile at ({r0}, {c0}) of {H} x {W} elements leaves its block of shape {blk.shape}')
+                tarr[t] = (blk.ptr, r0, c0, blk.strides[0], blk.strides[1], s_offs[id(S)], 0 if blk.is_complex or not cplx else 1,
+                           0 if s_cplx or not cplx else 1)
+                t += 1
+            oarr[i] = (dst_view.ptr + es * off, 2 * L, 0, tuple(ext) + pad, tuple(sd) + pad, tuple(ss) + pad, tuple(sr) + pad, tuple(sc) + pad,
+                       t - len(terms), len(terms))
+        fn = self.lib.cyb_tree_to_dense_c128 if cplx else self.lib.cyb_tree_to_dense_f64
+        self.ctx.sync_stream()
+        _lib.check(fn(self.ctx.handle, oarr.ctypes.data_as(C.POINTER(_lib.TreeToDenseOut)), len(regions),
+                      tarr.ctypes.data_as(C.POINTER(_lib.TreeToDenseTerm)), t, C.c_void_p(table.ptr if table is not None else 0)))
+
+    def tree_from_dense_many(self, outputs):
+        """Every tile of the coupled blocks of a fusion-tree tensor from a dense tensor, ONE table upload, ONE descriptor upload
+        and ONE launch (``FusionTreeBackend::from_dense_block``, fusion_tree_backend.cpp:1680-1853: per pair of trees two tdot,
+        trace_partial, a division, reshape and set_item).  `outputs`: a list of ``(dst_view, divisor, dims, mults, J, terms)``;
+        ``dst_view`` is a 2-D view (a tile of a coupled block: rows ``(m_1 .. m_J)``, columns ``(n_1 .. n_K)`` in C order), written
+        in place (the views of one call must not overlap); ``terms`` a list of ``(src_view, starts, S)`` with the dense tensor as
+        a strided view whose axes are the flat legs in (codomain..., domain...) order, read in place, the first position of the
+        region on every axis, and a host array ``S`` of shape `dims`:
+        ``dst[(m..), (n..)] = (sum_terms sum_k conj(S[k_1, ..]) * src[starts + (k_1 * m_1 + mu_1, ..)]) / divisor``, zeros without a term.
+        The destinations decide the entry: all float64 (real source, real S) or all complex128 (a float64 source or a real table
+        is then read as it stands).  Fixed summation order, bit-identical from run to run (csrc/tree_dense.hip)."""
+        what = 'tree_from_dense_many'
+        outputs = [(dst, float(div), tuple(d), tuple(m), int(J), list(terms)) for dst, div, d, m, J, terms in outputs]
+        if not outputs:
+            return
+        dsts = [o[0] for o in outputs]
+        srcs = [tm[0] for o in outputs for tm in o[5]]
+        self._numeric_only(dsts + srcs, what)
+        if any(d.ndim != 2 for d in dsts):
+            raise ValueError(f'{what}: destinations are 2-D views')
+        kinds = {d.is_complex for d in dsts}
+        if len(kinds) > 1:
+            raise ValueError(f'{what}: the destination views of one call share one dtype')
+        cplx = kinds.pop()
+        table, s_offs, s_cplx = self._tree_pair_table([tm[2] for o in outputs for tm in o[5]])
+        if not cplx and (s_cplx or any(a.is_complex for a in srcs)):
+            raise ValueError(f'{what}: a complex source or tree tensor needs complex destination views')
+        nk = _lib.CYB_TREE_DENSE_MAX_LEGS
+        oarr = np.zeros(len(outputs), dtype=_lib.TREE_FROM_DENSE_OUT_DTYPE)
+        tarr = np.zeros(max(len(srcs), 1), dtype=_lib.TREE_FROM_DENSE_TERM_DTYPE)
+        t = 0
+        for i, (dst, div, dims, mults, J, terms) in enumerate(outputs):
+            L = len(dims)
+            if L > nk or len(mults) != L or not 0 <= J <= L:
+                raise ValueError(f'{what}: {len(dims)} dimensions and {len(mults)} multiplicities, at most {nk} legs')
+            if dst.shape != (math.prod(mults[:J]), math.prod(mults[J:])):
+                raise ValueError(f'{what}: a destination view of shape {dst.shape} for the multiplicities {mults[:J]} and {mults[J:]}')
+            if div == 0.0 or div != div:
+                raise ValueError(f'{what}: the divisor is zero or NaN')
+            a_str = terms[0][0].strides if terms else (0,) * L
+            for a, starts, S in terms:
+                off = self._tree_dense_region(what, a, starts, dims, mults, J)
+                if a.strides != a_str:
+                    raise ValueError(f'{what}: the source views of one output share their strides')
+                if tuple(S.shape) != dims:
+                    raise ValueError(f'{what}: a tree tensor pair of shape {tuple(S.shape)} for the sector dimensions {dims}')
+                tarr[t] = (a.ptr + (16 if a.is_complex else 8) * off, s_offs[id(S)], 0 if a.is_complex or not cplx else 1,
+                           0 if s_cplx or not cplx else 1)
+                t += 1
+            order = sorted(range(L), key=lambda l: -abs(a_str[l]))              # the last level: the contiguous run of the source
+            d_str = [x * dst.strides[0] for x in _c_strides(mults[:J])] + [x * dst.strides[1] for x in _c_strides(mults[J:])]
+            pad = (0,) * (nk - L)
+            oarr[i] = (dst.ptr, L, L, tuple(mults[l] for l in order) + pad, tuple(d_str[l] for l in order) + pad,
+                       tuple(a_str[l] for l in order) + pad, dims + pad, tuple(m * s for m, s in zip(mults, a_str)) + pad, div,
+                       t - len(terms), len(terms))
+        fn = self.lib.cyb_tree_from_dense_c128 if cplx else self.lib.cyb_tree_from_dense_f64
+        self.ctx.sync_stream()
+        _lib.check(fn(self.ctx.handle, oarr.ctypes.data_as(C.POINTER(_lib.TreeFromDenseOut)), len(outputs),
+                      tarr.ctypes.data_as(C.POINTER(_lib.TreeFromDenseTerm)), t, C.c_void_p(table.ptr if table is not None else 0)))
+
     def _wdot(self, descs, cplx, conj):
         """launch chain of the weighted reduction + the one read of its result"""
         n = len(descs)

@@ -45,6 +45,14 @@ module mirrors is everything BETWEEN that layer and the block backend:
   domain trees, old trees and new trees emits one output record per new tree of the contracted side (a strip of a result
   block) and one weighted term per innermost iteration; the arithmetic is ONE ``tree_compose_many`` launch.  What
   ``FusionTree::insert_at`` says per (outer tree, tree of b) comes in as a :class:`TreeInsert`.
+* :func:`to_dense_block`  <- ``::to_dense_block`` (:1856-1973) with ``_get_forest_block_contribution`` (:1532-1604): the loops over
+  blocks, forest pairs and tree pairs emit one region record per combination of leg sectors (the regions partition the dense
+  tensor, so nothing is zero-filled) and one term per (block, tree, tree) whose weight is a small tensor, the contracted pair
+  of tree tensors; the arithmetic is ONE ``tree_to_dense_many`` launch.  What ``FusionTree::to_dense_block`` and
+  ``batch_sector_dim`` say per tree and per sector comes in as a :class:`TreeDense`.
+* :func:`from_dense_block`  <- ``::from_dense_block`` (:1680-1853) with ``_add_forest_block_entries`` (:1606-1677): one output
+  record per (tree, tree) tile of every common coupled sector, the dense block read in place; the projection is ONE
+  ``tree_from_dense_many`` launch, the tolerance check one weighted :func:`norm` and one norm of the dense block.
 * :class:`TreeTensor`: data + codomain + domain, the vector the Krylov solvers and the operator wrappers take
   (``cyten_amd.krylov``, ``cyten_amd.sparse``): the reference's Krylov code calls ``inner`` / ``norm`` /
   ``linear_combination`` on whatever tensor it is given (src/tensors/krylov_based.cpp), and those need the quantum dimensions
@@ -52,6 +60,7 @@ module mirrors is everything BETWEEN that layer and the block backend:
 """
 from __future__ import annotations
 
+import itertools
 from dataclasses import dataclass, field
 from typing import NamedTuple
 
@@ -60,7 +69,8 @@ import numpy as np
 __all__ = ['TreeBlock', 'TreeSpace', 'FusionTreeData', 'compose', 'svd', 'qr', 'lq', 'eigh', 'truncate_singular_values',
            'transform_tensor', 'discard_zero_blocks', 'norm', 'inner', 'trace_full', 'mul', 'linear_combination', 'dagger',
            'almost_equal', 'TreeAxisRecord', 'TreeMask', 'leg_keys', 'scale_axis', 'mask_contract', 'truncated_svd', 'TreeTensor',
-           'same_space', 'TreeTrace', 'partial_trace', 'TreeOuter', 'outer', 'TreeInsert', 'partial_compose']
+           'same_space', 'TreeTrace', 'partial_trace', 'TreeOuter', 'outer', 'TreeInsert', 'partial_compose',
+           'TreeDense', 'to_dense_block', 'from_dense_block']
 
 
 @dataclass(frozen=True)
@@ -777,6 +787,168 @@ def partial_compose(bb, a: FusionTreeData, a_codomain: TreeSpace, a_domain: Tree
     bb.tree_compose_many(outputs)
     res = FusionTreeData(np.array(rows, dtype=np.int64), outs).sorted()
     return discard_zero_blocks(bb, res, eps) if discard else res
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# dense conversion
+
+class TreeDense(NamedTuple):
+    """What the symmetry layer knows about the dense form of ONE side (codomain or domain), as data: the internal basis of
+    every flat leg, ``Symmetry::batch_sector_dim`` and ``FusionTree::to_dense_block(bb, nullopt, true)`` per tree."""
+    legs: tuple         # per flat leg of this side, in leg order: [(sector key, multiplicity), ...] in the leg's internal basis
+                        # order (sorted sectors, each contiguous)
+    sector_dims: dict   # sector key -> int dimension
+    tensors: dict       # tree -> ndarray of shape (d_a1, ..., d_aJ, d_c), float64 or complex128
+
+
+MAX_DENSE_LEGS = 6      # flat legs of both sides together (twelve levels (k, m) of the kernel's index space)
+_NORM_ROUNDING = 32 * 2.0 ** -53     # relative rounding allowance of the difference of two squared norms (from_dense_block)
+
+
+def _dense_side(space: TreeSpace, dense: TreeDense, what: str, name: str):
+    """-> (per leg {sector key: (start, dimension, multiplicity)}, dimension of every dense axis, per coupled sector the forests
+    {uncoupled: [TreeBlock, ...]}, per coupled sector its dimension d_c or None), everything checked"""
+    n = space.num_legs
+    if len(dense.legs) != n:
+        raise ValueError(f'{name}: the {what} has {n} flat legs, its TreeDense lists {len(dense.legs)}')
+    where, dims = [], []
+    for leg in dense.legs:
+        pos, off = {}, 0
+        for key, m in leg:
+            if key not in dense.sector_dims:
+                raise ValueError(f'{name}: no dimension for the sector {key!r} of a {what} leg')
+            d = int(dense.sector_dims[key])
+            pos[key] = (off, d, int(m))
+            off += d * int(m)
+        where.append(pos)
+        dims.append(off)
+    forests, dcs = [], []
+    for tbs in space.tree_blocks:
+        fs, dc = {}, None
+        for tb in tbs:
+            if len(tb.uncoupled) != n or len(tb.multiplicities) != n:
+                raise ValueError(f'{name}: a {what} tree lacks the uncoupled sector keys of its legs (TreeBlock.uncoupled)')
+            if tb.tree not in dense.tensors:
+                raise ValueError(f'{name}: the {what} TreeDense has no tensor for the tree {tb.tree!r}')
+            for j, (key, m) in enumerate(zip(tb.uncoupled, tb.multiplicities)):
+                if key not in where[j] or where[j][key][2] != m:
+                    raise ValueError(f'{name}: the multiplicity {m} of leg {j} of the {what} tree {tb.tree!r} is not that of the sector '
+                                     f'{key!r} in TreeDense.legs')
+            X = np.asarray(dense.tensors[tb.tree])
+            want = tuple(where[j][key][1] for j, key in enumerate(tb.uncoupled))
+            if X.ndim != n + 1 or X.shape[:-1] != want or (dc is not None and X.shape[-1] != dc):
+                raise ValueError(f'{name}: the tensor of the {what} tree {tb.tree!r} has the shape {X.shape}, not {want} and the dimension of '
+                                 'its coupled sector')
+            dc = X.shape[-1]
+            fs.setdefault(tuple(tb.uncoupled), []).append(tb)
+        forests.append(fs)
+        dcs.append(dc)
+    return where, dims, forests, dcs
+
+
+def _dense_setup(name, codomain: TreeSpace, domain: TreeSpace, cod_dense: TreeDense, dom_dense: TreeDense):
+    if codomain.num_legs + domain.num_legs > MAX_DENSE_LEGS:
+        raise ValueError(f'{name}: {codomain.num_legs + domain.num_legs} flat legs, at most {MAX_DENSE_LEGS}')
+    cod = _dense_side(codomain, cod_dense, 'codomain', name)
+    dom = _dense_side(domain, dom_dense, 'domain', name)
+    for i, j in common_sectors(codomain, domain):
+        if cod[3][i] is not None and dom[3][j] is not None and cod[3][i] != dom[3][j]:
+            raise ValueError(f'{name}: the tree tensors of the coupled sector {codomain.sectors[i].tolist()} have the dimension {cod[3][i]} in the '
+                             f'codomain and {dom[3][j]} in the domain')
+    pairs: dict = {}
+
+    def pair(xa: TreeBlock, yb: TreeBlock):
+        """S[k_a..., k_b...] = sum_kc conj(X_alpha[k_a..., kc]) X_beta[k_b..., kc] (:1582-1586), once per pair of trees"""
+        S = pairs.get((xa.tree, yb.tree))
+        if S is None:
+            S = np.ascontiguousarray(np.tensordot(np.conj(cod_dense.tensors[xa.tree]), dom_dense.tensors[yb.tree], ([-1], [-1])))
+            pairs[(xa.tree, yb.tree)] = S
+        return S
+
+    cplx = any(np.iscomplexobj(X) for td in (cod_dense, dom_dense) for X in td.tensors.values())
+    return cod, dom, pair, cplx
+
+
+def to_dense_block(bb, data: FusionTreeData, codomain: TreeSpace, domain: TreeSpace, cod_dense: TreeDense, dom_dense: TreeDense):
+    """``FusionTreeBackend::to_dense_block`` (fusion_tree_backend.cpp:1856-1973 with ``_get_forest_block_contribution``
+    :1532-1604) for flat legs, in the internal basis order, for a symmetry that can be dropped: the N-d block with the axes
+    (codomain legs..., domain legs reversed) (:1944-1950; the reversal is strides, not a pass).  `cod_dense` / `dom_dense`: what
+    the symmetry layer says per leg and per tree (:class:`TreeDense`); the spaces carry ``TreeBlock.uncoupled``.
+
+    Trees of one coupled sector with the same uncoupled sectors form a forest.  On leg j the sector a_j takes d * m positions
+    of the dense axis, index ``k * m + mu`` (:1926-1930).  The region of the uncoupled sectors (a..., b...) is
+    ``sum_c sum_{alpha, beta} S_{alpha beta} (x) T_{alpha beta}`` over ALL coupled sectors the tuple fuses to (the reference
+    accumulates into the same slice, :1937), with S the contracted pair of tree tensors (:1582-1586, built on the host, all of
+    a call uploaded as one table) and T the tile of block c at the rows of alpha and the columns of beta.  The reference's
+    loops -- blocks (:1881), domain forests (:1885), codomain forests (:1890), trees (:1581-1584) -- emit one region record per
+    combination of leg sectors, combinations nothing fuses to included (written as zeros: the regions partition the dense
+    tensor, so nothing is zero-filled first), and one term per (block, alpha, beta), ordered by block, then alpha, then beta.
+    ONE ``tree_to_dense_many`` call.  complex128 if the data or any tree tensor is complex, else float64."""
+    name = 'to_dense_block'
+    J, K = codomain.num_legs, domain.num_legs
+    (cw, cdims, cfor, _), (dw, ddims, dfor, _), pair, cplx = _dense_setup(name, codomain, domain, cod_dense, dom_dense)
+    cplx = cplx or any(_is_complex(blk) for blk in data.blocks)
+    terms_of: dict = {}
+    for n, (i, j) in enumerate(data.block_inds.tolist()):
+        for a_key, alphas in cfor[i].items():
+            for b_key, betas in dfor[j].items():
+                lst = terms_of.setdefault((a_key, b_key), [])
+                for xa in alphas:
+                    for yb in betas:
+                        lst.append((data.blocks[n], xa.start, yb.start, pair(xa, yb)))
+    res = bb.empty_many([tuple(cdims) + tuple(ddims[::-1])], dtype=np.complex128 if cplx else np.float64)[0]
+    view = bb.permute_axes(res, list(range(J)) + list(range(J + K - 1, J - 1, -1)))
+    regions = []
+    for combo in itertools.product(*[list(w.items()) for w in cw + dw]):
+        keys = tuple(k for k, _ in combo)
+        regions.append((tuple(v[0] for _, v in combo), tuple(v[1] for _, v in combo), tuple(v[2] for _, v in combo), J,
+                        terms_of.get((keys[:J], keys[J:]), [])))
+    bb.tree_to_dense_many(view, regions)
+    return res
+
+
+def from_dense_block(bb, a, codomain: TreeSpace, domain: TreeSpace, cod_dense: TreeDense, dom_dense: TreeDense, tol: float = 1e-8,
+                     discard: bool = True) -> FusionTreeData:
+    """``FusionTreeBackend::from_dense_block`` (fusion_tree_backend.cpp:1680-1853 with ``_add_forest_block_entries``
+    :1606-1677) for flat legs, in the internal basis order: the projection of the N-d block `a` (axes: codomain legs...,
+    domain legs reversed, :1752) onto the symmetric tensors.  Every tile (tree alpha, tree beta) of every common coupled sector
+    is ``T[m..., n...] = (1 / d_c) sum_{k_a, k_b} conj(S_{alpha beta}[k_a..., k_b...]) a_region[(k_a, m), (k_b, n)]`` (:1656-1662,
+    divided after the sum) -- one output record per tile, read from `a` in place; ONE ``tree_from_dense_many`` call, no zero
+    fill (the tiles partition the blocks).  One block per common coupled sector; with `discard` those of magnitude <= 1e-14
+    are dropped (:1827-1829, :func:`discard_zero_blocks`).  With ``tol != 0``: ValueError if
+    ``|a|^2 - sum_c d_c |block_c|^2 > tol^2 |a|^2`` (:1834-1838; the weighted :func:`norm` and the block backend's norm).  The two
+    squared norms are float64 reductions in different orders, each within a few 2^-53 relative, and the default ``tol^2 = 1e-16``
+    is 2^-53 itself: the comparison allows ``_NORM_ROUNDING = 32 * 2^-53`` on top of ``tol^2``, without which a block that is
+    symmetric to the last bit raises whenever the two reductions round differently."""
+    name = 'from_dense_block'
+    J, K = codomain.num_legs, domain.num_legs
+    (cw, cdims, _, cdc), (dw, ddims, _, ddc), pair, cplx = _dense_setup(name, codomain, domain, cod_dense, dom_dense)
+    if tuple(a.shape) != tuple(cdims) + tuple(ddims[::-1]):
+        raise ValueError(f'{name}: a dense block of shape {tuple(a.shape)} for legs of the dimensions {tuple(cdims) + tuple(ddims[::-1])}')
+    cplx = cplx or _is_complex(a)
+    view = bb.permute_axes(a, list(range(J)) + list(range(J + K - 1, J - 1, -1)))
+    rows = common_sectors(codomain, domain)
+    if not rows:
+        res = FusionTreeData(np.zeros((0, 2), np.int64), [])
+    else:
+        outs = bb.empty_many([(codomain.block_size(i), domain.block_size(j)) for i, j in rows], dtype=np.complex128 if cplx else np.float64)
+        outputs = []
+        for (i, j), out in zip(rows, outs):
+            for xa in codomain.tree_blocks[i]:
+                for yb in domain.tree_blocks[j]:
+                    if xa.stop == xa.start or yb.stop == yb.start:
+                        continue
+                    at = [cw[l][key] for l, key in enumerate(xa.uncoupled)] + [dw[l][key] for l, key in enumerate(yb.uncoupled)]
+                    dst = bb.get_item(out, (slice(xa.start, xa.stop), slice(yb.start, yb.stop)))
+                    outputs.append((dst, float(cdc[i]), tuple(v[1] for v in at), tuple(v[2] for v in at), J,
+                                    [(view, tuple(v[0] for v in at), pair(xa, yb))]))
+        bb.tree_from_dense_many(outputs)
+        res = FusionTreeData(np.array(rows, dtype=np.int64), outs)
+    if tol != 0.0:
+        a_norm_sq = float(bb.norm(a)) ** 2
+        if a_norm_sq - norm(bb, res, codomain) ** 2 > (tol * tol + _NORM_ROUNDING) * a_norm_sq:
+            raise ValueError(f'{name}: the block is not symmetric up to tolerance')
+    return discard_zero_blocks(bb, res, 1e-14) if discard else res
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -682,6 +682,86 @@ int cyb_compose_weighted_f64(cyb_ctx_t ctx, const cyb_compose_weighted_out* outs
 int cyb_compose_weighted_c128(cyb_ctx_t ctx, const cyb_compose_weighted_out* outs, int64_t n_outs, const cyb_compose_weighted_term* terms,
                               int64_t n_terms);
 
+/* ---- fusion-tree tensors <-> dense arrays ---------------------------------------------------------------------------
+ * FusionTreeBackend::to_dense_block (src/backends/fusion_tree_backend.cpp:1856-1973 with _get_forest_block_contribution
+ * :1532-1604) and ::from_dense_block (:1680-1853 with _add_forest_block_entries :1606-1677) in ONE launch each: the reference
+ * makes, per pair of trees of every forest pair, zeros, two to_dense_block of trees, tdot, get_item, reshape, outer and
+ * operator+, then permute_axes, reshape and an accumulating set_item into a zero-filled dense tensor (forward), and two
+ * tdot, trace_partial, a division, reshape and set_item (backward).
+ *
+ * to_dense: an output record is one region of the dense tensor (the positions of one combination of uncoupled sectors),
+ * seen as the index space of n_levels <= CYB_TREE_DENSE_MAX_LEVELS levels x_l < ext[l] in C order (the last level is the
+ * fastest; the lanes of a wave run along it) -- one (k, m) pair per leg, k inside the sector's dimension, m inside its
+ * multiplicity, in whatever order makes the last level the contiguous run of the destination.  A term record is one
+ * contributing (coupled block, tree alpha, tree beta):
+ *   dst[sum_l x_l sd[l]] = sum_{t in [first_term, first_term + n_terms)} S[s_off_t + sum_l x_l ss[l]]
+ *                              * B_t[(first_row_t + sum_l x_l sr[l]) * rs_t + (first_col_t + sum_l x_l sc[l]) * cs_t]
+ * S = s_table is ONE device table that holds the contracted tree-tensor pairs S_{alpha beta}[k_a..., k_b...] of the call (a
+ * small tensor per term, not a scalar); ss is nonzero on the k levels, sr / sc on the m levels of the codomain / domain legs.
+ * from_dense: an output record is one tile (tree alpha, tree beta) of a coupled block with n_levels <= CYB_TREE_DENSE_MAX_LEGS
+ * levels (m..., n...), in whatever order makes the last level the contiguous run of the source; a term is one dense region:
+ *   dst[sum_l x_l sd[l]] = (sum_t sum_{k} conj(S[s_off_t + k]) * A_t[sum_l x_l ss[l] + sum_j k_j ks[j]]) / divisor
+ * k = (k_0, .., k_{n_k - 1}), k_j < kext[j], counted in C order; summed k ascending inside the lane, divided after the sum.
+ *   * Every destination element has exactly one owner, which adds its terms in ascending order in registers: no float
+ *     atomics, no zero fill, no second pass; results are bit-identical from run to run.
+ *   * An output with no terms is written as zeros.  Zero extents and empty lists are valid.
+ *   * All strides count elements of the operand's own type and may be negative or zero; blocks, regions and the table are read in place
+ *     and may overlap each other.  Destinations of one call must not overlap; the caller vouches for that, and for
+ *     every address the strides reach.
+ *   * block_real / src_real / s_real != 0 (c128 entries only; the f64 entries ignore them): the operand is float64 data read
+ *     as it stands, offsets in doubles -- a real block under complex tree tensors (or the reverse) needs no promotion pass.
+ *     The c128 entries read and write interleaved (re, im) storage otherwise.
+ *   * Everything is validated on the host before anything is uploaded or launched: level counts, negative extents (and
+ *     extents beyond 2^30), term ranges, negative first_row / first_col / s_off, a zero or NaN divisor, NULL dst / block /
+ *     src / s_table of a non-empty output.  A refused call returns CYB_ERR_INVALID with a message and leaves the context as it
+ *     found it.
+ * One wave owns a work item of a record; a lane holds one element (csrc/tree_dense.hip). */
+#define CYB_TREE_DENSE_MAX_LEGS 6
+#define CYB_TREE_DENSE_MAX_LEVELS 12
+typedef struct {
+    double* dst;
+    int32_t n_levels;
+    int32_t reserved;
+    int64_t ext[CYB_TREE_DENSE_MAX_LEVELS];
+    int64_t sd[CYB_TREE_DENSE_MAX_LEVELS]; /* destination stride */
+    int64_t ss[CYB_TREE_DENSE_MAX_LEVELS]; /* stride into S */
+    int64_t sr[CYB_TREE_DENSE_MAX_LEVELS]; /* what the level adds to the row index of the block */
+    int64_t sc[CYB_TREE_DENSE_MAX_LEVELS]; /* ... to the column index */
+    int64_t first_term, n_terms;
+} cyb_tree_to_dense_out;
+typedef struct {
+    const double* block;
+    int64_t first_row, first_col;
+    int64_t rs, cs; /* row and column stride of the block: (ld, 1), or (1, ld) of a transposed view */
+    int64_t s_off;
+    int32_t block_real, s_real;
+} cyb_tree_to_dense_term;
+typedef struct {
+    double* dst;
+    int32_t n_levels;
+    int32_t n_k;
+    int64_t ext[CYB_TREE_DENSE_MAX_LEGS];
+    int64_t sd[CYB_TREE_DENSE_MAX_LEGS];   /* destination stride */
+    int64_t ss[CYB_TREE_DENSE_MAX_LEGS];   /* source stride of the same level */
+    int64_t kext[CYB_TREE_DENSE_MAX_LEGS]; /* the contracted levels */
+    int64_t ks[CYB_TREE_DENSE_MAX_LEGS];   /* their source strides */
+    double divisor;
+    int64_t first_term, n_terms;
+} cyb_tree_from_dense_out;
+typedef struct {
+    const double* src; /* the first element of the region */
+    int64_t s_off;
+    int32_t src_real, s_real;
+} cyb_tree_from_dense_term;
+int cyb_tree_to_dense_f64(cyb_ctx_t ctx, const cyb_tree_to_dense_out* outs, int64_t n_outs, const cyb_tree_to_dense_term* terms, int64_t n_terms,
+                          const double* s_table);
+int cyb_tree_to_dense_c128(cyb_ctx_t ctx, const cyb_tree_to_dense_out* outs, int64_t n_outs, const cyb_tree_to_dense_term* terms, int64_t n_terms,
+                           const double* s_table);
+int cyb_tree_from_dense_f64(cyb_ctx_t ctx, const cyb_tree_from_dense_out* outs, int64_t n_outs, const cyb_tree_from_dense_term* terms,
+                            int64_t n_terms, const double* s_table);
+int cyb_tree_from_dense_c128(cyb_ctx_t ctx, const cyb_tree_from_dense_out* outs, int64_t n_outs, const cyb_tree_from_dense_term* terms,
+                             int64_t n_terms, const double* s_table);
+
 /* ---- grouped matrix exponential of small blocks ---------------------------------------------------------------------
  * E = exp(alpha * A) for every listed square matrix in ONE launch, one workgroup per matrix, the whole computation in LDS
  * (csrc/expm_small.hip).  Replaces NumpyBlockBackend::matrix_exp = scipy.linalg.expm (src/block_backend/numpy.cpp:1227-1234),
