@@ -15,6 +15,7 @@ CYB_MAX_NDIM = 8
 CYB_TRACE_MAX_PAIRS = 4
 CYB_TREE_DENSE_MAX_LEGS = 6
 CYB_TREE_DENSE_MAX_LEVELS = 12
+CYB_TREE_PLACE_MAX_LEVELS = 6
 CYB_SVD_SKIP_NULL_VECTORS = 1
 CYB_SVD_EMBEDDED_COMPLEX = 2
 CYB_EIGH_EMBEDDED_COMPLEX = 2
@@ -187,6 +188,14 @@ class TreeFromDenseTerm(C.Structure):
     _fields_ = [('src', C.c_void_p), ('s_off', C.c_int64), ('src_real', C.c_int32), ('s_real', C.c_int32)]
 
 
+class TreePlaceRec(C.Structure):
+    _fields_ = [('dst', C.c_void_p), ('src', C.c_void_p), ('h', C.c_int64), ('nq', C.c_int64), ('wn', C.c_int64), ('cp', C.c_int64),
+                ('ldd', C.c_int64), ('n_row_levels', C.c_int32), ('n_col_levels', C.c_int32),
+                ('rext', C.c_int64 * CYB_TREE_PLACE_MAX_LEVELS), ('rs', C.c_int64 * CYB_TREE_PLACE_MAX_LEVELS),
+                ('cext', C.c_int64 * CYB_TREE_PLACE_MAX_LEVELS), ('cs', C.c_int64 * CYB_TREE_PLACE_MAX_LEVELS),
+                ('coeff_re', C.c_double), ('coeff_im', C.c_double), ('src_real', C.c_int32), ('reserved', C.c_int32)]
+
+
 class ExpmDesc(C.Structure):
     _fields_ = [('A', C.c_void_p), ('lda', C.c_int64), ('n', C.c_int64), ('a_is_real', C.c_int32), ('reserved', C.c_int32),
                 ('E', C.c_void_p), ('lde', C.c_int64)]
@@ -249,6 +258,7 @@ TREE_TO_DENSE_OUT_DTYPE = _np.dtype(TreeToDenseOut)
 TREE_TO_DENSE_TERM_DTYPE = _np.dtype(TreeToDenseTerm)
 TREE_FROM_DENSE_OUT_DTYPE = _np.dtype(TreeFromDenseOut)
 TREE_FROM_DENSE_TERM_DTYPE = _np.dtype(TreeFromDenseTerm)
+TREE_PLACE_DTYPE = _np.dtype(TreePlaceRec)
 EXPM_DTYPE = _np.dtype(ExpmDesc)
 OUTER_DTYPE = _np.dtype(OuterRec)
 SEG_DTYPE = _np.dtype(SegRec)
@@ -345,6 +355,8 @@ PROTOTYPES = {
     'cyb_tree_to_dense_c128': [_ctx, _P(TreeToDenseOut), C.c_int64, _P(TreeToDenseTerm), C.c_int64, C.c_void_p],
     'cyb_tree_from_dense_f64': [_ctx, _P(TreeFromDenseOut), C.c_int64, _P(TreeFromDenseTerm), C.c_int64, C.c_void_p],
     'cyb_tree_from_dense_c128': [_ctx, _P(TreeFromDenseOut), C.c_int64, _P(TreeFromDenseTerm), C.c_int64, C.c_void_p],
+    'cyb_tree_place_f64': [_ctx, _P(TreePlaceRec), C.c_int64],
+    'cyb_tree_place_c128': [_ctx, _P(TreePlaceRec), C.c_int64],
     'cyb_expm_small_batched_f64': [_ctx, _P(ExpmDesc), C.c_int64, C.c_double],
     'cyb_expm_small_batched_c128': [_ctx, _P(ExpmDesc), C.c_int64, C.c_double, C.c_double],
     'cyb_norm1_batched_f64': [_ctx, _P(ExpmDesc), C.c_int64, _vp],

@@ -1797,6 +1797,55 @@ class HipBlockBackend:
         _lib.check(fn(self.ctx.handle, oarr.ctypes.data_as(C.POINTER(_lib.ComposeWeightedOut)), len(outputs),
                       tarr.ctypes.data_as(C.POINTER(_lib.ComposeWeightedTerm)), n_t))
 
+    def tree_place_many(self, records):
+        """Weighted strided window copies, ONE descriptor upload and ONE launch for all result blocks of a fusion-tree
+        ``from_grid`` or ``from_tree_pairs`` (``FusionTreeBackend::from_grid``, fusion_tree_backend.cpp:3375-3518: nine
+        block-backend calls per (grid entry, codomain forest, domain forest) into a zero-filled result; ``::from_tree_pairs``
+        :3186-3263).  `records`: a list of ``(dst_view, src_view, n_row, coeff)``; ``dst_view`` is a 3-D view ``(h, nq, wn)`` of a
+        coupled block with unit stride on its last axis -- h rows, nq runs of wn columns -- written in place (the views of one
+        call must not overlap); ``src_view`` any strided view read in place whose first `n_row` axes (at most
+        ``CYB_TREE_PLACE_MAX_LEVELS``) multiply to h and whose other axes (at most as many) to nq * wn, both in C order:
+        ``dst[r, q, w] = coeff * src.reshape(h, nq, wn)[r, q, w]`` without the reshape ever being made.  ``src_view is None``:
+        the window becomes zeros.  The destinations decide the entry: all float64 (real sources, real coefficients) or all
+        complex128 (a float64 source is then read as it stands, no promotion pass).  ``coeff == 1`` copies bits; every element
+        has one owner, bit-identical from run to run (csrc/tree_place.hip)."""
+        what = 'tree_place_many'
+        records = [(dst, src, int(n_row), complex(coeff)) for dst, src, n_row, coeff in records]
+        if not records:
+            return
+        dsts = [r[0] for r in records]
+        self._numeric_only(dsts + [r[1] for r in records if r[1] is not None], what)
+        if any(d.ndim != 3 for d in dsts):
+            raise ValueError(f'{what}: destinations are 3-D views (rows, runs, columns of a run)')
+        kinds = {d.is_complex for d in dsts}
+        if len(kinds) > 1:
+            raise ValueError(f'{what}: the destination views of one call share one dtype')
+        cplx = kinds.pop()
+        nl = _lib.CYB_TREE_PLACE_MAX_LEVELS
+        pad = (0,) * nl
+        arr = np.zeros(len(records), dtype=_lib.TREE_PLACE_DTYPE)
+        for i, (dst, src, n_row, coeff) in enumerate(records):
+            h, nq, wn = dst.shape
+            if dst.strides[2] != 1 and wn > 1:
+                raise ValueError(f'{what}: a destination view needs the stride 1 on its last axis')
+            if src is None:
+                arr[i] = (dst.ptr, 0, h, nq, wn, dst.strides[1], dst.strides[0], 0, 0, pad, pad, pad, pad, 0.0, 0.0, 0, 0)
+                continue
+            n_col = src.ndim - n_row
+            if not (0 <= n_row <= nl and 0 <= n_col <= nl):
+                raise ValueError(f'{what}: a source view with {n_row} row axes and {n_col} column axes, at most {nl} each')
+            if (math.prod(src.shape[:n_row]), math.prod(src.shape[n_row:])) != (h, nq * wn):
+                raise ValueError(f'{what}: a source view of shape {tuple(src.shape)} with {n_row} row axes for a window of {h} rows and '
+                                 f'{nq} x {wn} columns')
+            if not cplx and (src.is_complex or coeff.imag != 0):
+                raise ValueError(f'{what}: a complex source or coefficient needs complex destination views')
+            arr[i] = (dst.ptr, src.ptr, h, nq, wn, dst.strides[1], dst.strides[0], n_row, n_col,
+                      (src.shape[:n_row] + pad)[:nl], (src.strides[:n_row] + pad)[:nl], (src.shape[n_row:] + pad)[:nl],
+                      (src.strides[n_row:] + pad)[:nl], coeff.real, coeff.imag, 0 if src.is_complex or not cplx else 1, 0)
+        fn = self.lib.cyb_tree_place_c128 if cplx else self.lib.cyb_tree_place_f64
+        self.ctx.sync_stream()
+        _lib.check(fn(self.ctx.handle, arr.ctypes.data_as(C.POINTER(_lib.TreePlaceRec)), len(records)))
+
     def _tree_pair_table(self, tensors):
         """the tree-pair tensors of one call (host arrays, each once) as ONE device table: (table block or None, offset of
         every tensor by id, whether the table is complex)"""

@@ -53,6 +53,15 @@ module mirrors is everything BETWEEN that layer and the block backend:
 * :func:`from_dense_block`  <- ``::from_dense_block`` (:1680-1853) with ``_add_forest_block_entries`` (:1606-1677): one output
   record per (tree, tree) tile of every common coupled sector, the dense block read in place; the projection is ONE
   ``tree_from_dense_many`` launch, the tolerance check one weighted :func:`norm` and one norm of the dense block.
+* :func:`from_grid`  <- ``::from_grid`` (:3375-3518, under ``tensor_from_grid``): the direct sum of a grid of tree tensors along
+  ``codomain[0]`` (rows) and ``domain[-1]`` (columns) -- an MPO tensor from operators, the sum of two MPS, a subspace expansion.
+  Every (new codomain tree, new domain tree) tile is partitioned into the cells of the grid; a cell an entry feeds is one copy
+  record of the entry's own tile read in place under the cell's factor, every other cell a record of zeros; the arithmetic is
+  ONE ``tree_place_many`` launch that writes every element of the result once (no zero fill, no promotion pass, no ``mul``
+  per factor).  The new spaces and the cumulative multiplicity tables come in as data; trees are matched by key.
+* :func:`from_tree_pairs`  <- ``::from_tree_pairs`` (:3186-3263): blocks ``(m_1 .. m_J, n_K .. n_1)`` per pair of trees into their
+  tiles, the permutation and the reshape done by the strides of ONE ``tree_place_many`` launch.  :func:`eye`  <- ``::eye_data``
+  (:1180-1192).
 * :class:`TreeTensor`: data + codomain + domain, the vector the Krylov solvers and the operator wrappers take
   (``cyten_amd.krylov``, ``cyten_amd.sparse``): the reference's Krylov code calls ``inner`` / ``norm`` /
   ``linear_combination`` on whatever tensor it is given (src/tensors/krylov_based.cpp), and those need the quantum dimensions
@@ -70,7 +79,7 @@ __all__ = ['TreeBlock', 'TreeSpace', 'FusionTreeData', 'compose', 'svd', 'qr', '
            'transform_tensor', 'discard_zero_blocks', 'norm', 'inner', 'trace_full', 'mul', 'linear_combination', 'dagger',
            'almost_equal', 'TreeAxisRecord', 'TreeMask', 'leg_keys', 'scale_axis', 'mask_contract', 'truncated_svd', 'TreeTensor',
            'same_space', 'TreeTrace', 'partial_trace', 'TreeOuter', 'outer', 'TreeInsert', 'partial_compose',
-           'TreeDense', 'to_dense_block', 'from_dense_block']
+           'TreeDense', 'to_dense_block', 'from_dense_block', 'from_grid', 'from_tree_pairs', 'eye']
 
 
 @dataclass(frozen=True)
@@ -949,6 +958,283 @@ def from_dense_block(bb, a, codomain: TreeSpace, domain: TreeSpace, cod_dense: T
         if a_norm_sq - norm(bb, res, codomain) ** 2 > (tol * tol + _NORM_ROUNDING) * a_norm_sq:
             raise ValueError(f'{name}: the block is not symmetric up to tolerance')
     return discard_zero_blocks(bb, res, 1e-14) if discard else res
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# constructors: from_grid, from_tree_pairs, eye
+
+MAX_PLACE_LEGS = 6      # flat legs of one side of a from_tree_pairs block (the levels of one side of a window's source)
+
+
+class _Window(NamedTuple):
+    """one window of a result block: rows ``r0 : r0 + h`` and columns ``c0 : c0 + wn`` of every one of the `nq` runs of the tile
+    ``(x0 : x1, y0 : y1)`` of block `n`, fed by ``coeff * src`` (a view whose first `n_row` axes are the rows) or by zeros"""
+    n: int
+    x0: int
+    x1: int
+    y0: int
+    y1: int
+    nq: int
+    r0: int
+    h: int
+    c0: int
+    wn: int
+    src: object
+    n_row: int
+    coeff: object
+
+
+def _place_windows(bb, shapes, cplx, windows):
+    """the result blocks of the given shapes with every window written: ONE ``tree_place_many`` call into blocks that are not
+    zero-filled (the windows of a block partition it); a backend without that call takes ``zeros_many`` and, per window with a
+    source, get_item / reshape / set_item as the reference does"""
+    dtype = np.complex128 if cplx else np.float64
+    windows = [w for w in windows if w.h > 0 and w.nq > 0 and w.wn > 0]
+    fused = hasattr(bb, 'tree_place_many')
+    outs = bb.empty_many(shapes, dtype=dtype) if fused else bb.zeros_many(shapes, dtype=dtype)
+    if fused:
+        tiles, records = {}, []
+        for w in windows:
+            t3 = tiles.get((w.n, w.x0, w.y0))
+            if t3 is None:
+                tile = bb.get_item(outs[w.n], (slice(w.x0, w.x1), slice(w.y0, w.y1)))
+                t3 = tiles[(w.n, w.x0, w.y0)] = bb.reshape(tile, (w.x1 - w.x0, w.nq, (w.y1 - w.y0) // w.nq))
+            dst = bb.get_item(t3, (slice(w.r0, w.r0 + w.h), slice(None), slice(w.c0, w.c0 + w.wn)))
+            records.append((dst, w.src, w.n_row, w.coeff))
+        bb.tree_place_many(records)
+        return outs
+    for w in windows:
+        if w.src is None:
+            continue
+        value = bb.reshape(w.src, (w.h, w.nq, w.wn))
+        if w.coeff != 1:
+            value = bb.mul(w.coeff, value)
+        key = (slice(w.x0, w.x1), slice(w.y0, w.y1))
+        t3 = bb.reshape(bb.get_item(outs[w.n], key), (w.x1 - w.x0, w.nq, (w.y1 - w.y0) // w.nq))
+        bb.set_item(t3, (slice(w.r0, w.r0 + w.h), slice(None), slice(w.c0, w.c0 + w.wn)), value)
+        bb.set_item(outs[w.n], key, bb.reshape(t3, (w.x1 - w.x0, w.y1 - w.y0)))
+    return outs
+
+
+def _grid_slices(table, key, n, total, what):
+    """the cumulative multiplicity table of the sector `key` of a stacked leg: n + 1 ascending entries from 0 to `total`"""
+    try:
+        s = [int(v) for v in table[key]]
+    except (KeyError, IndexError, TypeError):
+        raise ValueError(f'from_grid: {what} has no entry for the sector {key!r}') from None
+    if len(s) != n + 1 or s[0] != 0 or any(b < a for a, b in zip(s, s[1:])):
+        raise ValueError(f'from_grid: {what}[{key!r}] = {s} is no ascending table of {n + 1} entries that starts at 0')
+    if s[-1] != total:
+        raise ValueError(f'from_grid: {what}[{key!r}] ends at {s[-1]}, the multiplicity of that sector in the new space is {total}')
+    return s
+
+
+def _zero_windows(zero):
+    """maximal rectangles (i0, i1, j0, j1) of a boolean cell matrix: runs of zero cells along every row, equal runs of
+    consecutive rows merged"""
+    runs = []
+    for row in zero:
+        rr, j = [], 0
+        while j < len(row):
+            if row[j]:
+                j0 = j
+                while j < len(row) and row[j]:
+                    j += 1
+                rr.append((j0, j))
+            else:
+                j += 1
+        runs.append(rr)
+    out, open_ = [], {}          # open_: (j0, j1) -> first row of the rectangle that still grows
+    for i, rr in enumerate(runs + [[]]):
+        for key in [k for k in open_ if k not in rr]:
+            out.append((open_.pop(key), i, key[0], key[1]))
+        for key in rr:
+            open_.setdefault(key, i)
+    return sorted(out)
+
+
+def from_grid(bb, grid, new_codomain: TreeSpace, new_domain: TreeSpace, left_slices, right_slices, factors=None, eps: float = 0.0,
+              discard: bool = True) -> FusionTreeData:
+    """``FusionTreeBackend::from_grid`` (fusion_tree_backend.cpp:3375-3518, under ``tensor_from_grid``): the tensor whose
+    ``codomain[0]`` is the direct sum of that leg over the rows of `grid` and whose ``domain[-1]`` the direct sum over its
+    columns; every other leg is the same in all entries.  `grid`: a list of rows of :class:`TreeTensor` or None.
+    `new_codomain` / `new_domain` and the cumulative multiplicity tables come from the symmetry layer as data:
+    ``left_slices[a][i] : left_slices[a][i + 1]`` are the positions row i takes inside the multiplicity of sector ``a`` of the
+    stacked codomain leg, ``right_slices[b][j] : right_slices[b][j + 1]`` those of column j inside sector ``b`` of the stacked
+    domain leg; ``a`` / ``b`` is the first / last entry of ``TreeBlock.uncoupled``.  `factors`: a coefficient per cell
+    (``factors[i][j]``, default 1; that of an empty cell is not read).
+
+    A tree of an entry is found in the new space by its ``tree`` key: the trees of a forest depend on the uncoupled sectors,
+    the coupled sector and the dualities, not on the multiplicities, so an entry's tree IS a tree of the new space (the
+    reference matches them by their position inside the forest, :3424-3433).
+
+    For every coupled sector common to the new spaces and every (new codomain tree x, new domain tree y) the tile is
+    partitioned into cells (i, j) of positive width.  With Rc the product of x's multiplicities after the first, Rd that of
+    y's before the last and n' y's last multiplicity, cell (i, j) is the window of the rows ``left_slices[a][i] * Rc`` onward,
+    ``m0 * Rc`` of them, and of Rd runs of ``right_slices[b][j + 1] - right_slices[b][j]`` columns from column
+    ``right_slices[b][j]`` on, one run every n' columns -- the six-axis reshape of :3456-3506 per tree.  A cell whose entry
+    holds that block is a copy record of the entry's own tile, read in place through its strides (a :func:`dagger` view as it
+    stands) under the cell's factor; every other cell is a record of zeros, adjacent ones merged.  ONE ``tree_place_many``
+    call: every element of the result is written once, nothing is zero-filled first, a float64 entry beside complex ones is
+    read as it stands.
+
+    Result blocks that receive no copy record are absent (the reference allocates all of them as zeros and discards them,
+    :3391, :3516); the others go through :func:`discard_zero_blocks` with `eps` unless ``discard=False``.  Sorted by
+    ``block_inds``; complex if an entry or a factor is.  ValueError: an empty or ragged grid, a row or column without an entry,
+    a slice table without a sector's key or at odds with the multiplicities, an entry whose tree is missing from the new space
+    or differs from it in a multiplicity other than the stacked one."""
+    grid = [list(row) for row in grid]
+    if not grid or not grid[0]:
+        raise ValueError('from_grid: an empty grid')
+    nr, nc = len(grid), len(grid[0])
+    if any(len(row) != nc for row in grid):
+        raise ValueError('from_grid: the rows of the grid differ in their length')
+    for i, row in enumerate(grid):
+        if all(op is None for op in row):
+            raise ValueError(f'from_grid: row {i} of the grid has no entry')
+    for j in range(nc):
+        if all(row[j] is None for row in grid):
+            raise ValueError(f'from_grid: column {j} of the grid has no entry')
+    if factors is not None:
+        factors = [list(row) for row in factors]
+        if len(factors) != nr or any(len(row) != nc for row in factors):
+            raise ValueError(f'from_grid: factors for a grid of {nr} x {nc} cells are {nr} rows of {nc} numbers')
+    if new_codomain.num_legs < 1 or new_domain.num_legs < 1:
+        raise ValueError('from_grid: the rows stack on codomain[0] and the columns on domain[-1]: both sides need a leg')
+    coeff_of = lambda i, j: 1.0 if factors is None else factors[i][j]                    # noqa: E731
+    entries = [(i, j, op) for i, row in enumerate(grid) for j, op in enumerate(row) if op is not None]
+    cplx = any(_is_complex(b) for _, _, op in entries for b in op.blocks) or any(complex(coeff_of(i, j)).imag != 0.0 for i, j, _ in entries)
+    where_cod = {tuple(s): k for k, s in enumerate(new_codomain.sectors.tolist())}
+    where_dom = {tuple(s): k for k, s in enumerate(new_domain.sectors.tolist())}
+    J, K = new_codomain.num_legs, new_domain.num_legs
+    feeds: dict = {}         # (i_new, j_new) -> {(x tree, y tree): {(i, j): (block, xe, ye)}}
+    for i, j, op in entries:
+        for n, (ic, jd) in enumerate(op.block_inds.tolist()):
+            coupled = tuple(op.domain.sectors[jd].tolist())
+            if coupled not in where_cod or coupled not in where_dom:
+                continue                                                     # (:3411-3413)
+            rc = (where_cod[coupled], where_dom[coupled])
+            new_of = []
+            for tbs, space, legs, stacked, table, pos, what in ((op.codomain.tree_blocks[ic], new_codomain, J, 0, left_slices, i, 'codomain'),
+                                                                 (op.domain.tree_blocks[jd], new_domain, K, -1, right_slices, j, 'domain')):
+                side = []
+                for te in tbs:
+                    if len(te.uncoupled) != legs or len(te.multiplicities) != legs:
+                        raise ValueError(f'from_grid: a {what} tree of entry ({i}, {j}) lacks the uncoupled sector keys or the multiplicities of '
+                                         f'its {legs} legs (TreeBlock.uncoupled, TreeBlock.multiplicities)')
+                    if not space.has_tree(te.tree):
+                        raise ValueError(f'from_grid: the new {what} has no tree {te.tree!r} of entry ({i}, {j})')
+                    k_new, tn = space.tree_block_slice(te.tree)
+                    if k_new != rc[0 if what == 'codomain' else 1]:
+                        raise ValueError(f'from_grid: the tree {te.tree!r} of entry ({i}, {j}) lies in another coupled sector of the new {what}')
+                    me, mn = list(te.multiplicities), list(tn.multiplicities)
+                    del me[stacked], mn[stacked]
+                    if me != mn:
+                        raise ValueError(f'from_grid: the multiplicities {tuple(te.multiplicities)} of the {what} tree {te.tree!r} of entry '
+                                         f'({i}, {j}) differ from {tuple(tn.multiplicities)} in a leg other than the stacked one')
+                    s = _grid_slices(table, te.uncoupled[stacked], nr if what == 'codomain' else nc, tn.multiplicities[stacked],
+                                     'left_slices' if what == 'codomain' else 'right_slices')
+                    if s[pos + 1] - s[pos] != te.multiplicities[stacked]:
+                        raise ValueError(f'from_grid: entry ({i}, {j}) has the multiplicity {te.multiplicities[stacked]} in the sector '
+                                         f'{te.uncoupled[stacked]!r} of its stacked {what} leg, its slice is {s[pos]}:{s[pos + 1]}')
+                    side.append((te, tn))
+                new_of.append(side)
+            for xe, xn in new_of[0]:
+                for ye, yn in new_of[1]:
+                    if xe.stop > xe.start and ye.stop > ye.start:
+                        feeds.setdefault(rc, {}).setdefault((xn.tree, yn.tree), {})[(i, j)] = (op.blocks[n], xe, ye)
+    rows = sorted(feeds)
+    if not rows:
+        return FusionTreeData(np.zeros((0, 2), np.int64), [])
+    windows = []
+    for n, (i_new, j_new) in enumerate(rows):
+        tiles = feeds[(i_new, j_new)]
+        for x in new_codomain.tree_blocks[i_new]:
+            for y in new_domain.tree_blocks[j_new]:
+                if x.stop == x.start or y.stop == y.start:
+                    continue
+                if len(x.uncoupled) != J or len(x.multiplicities) != J or len(y.uncoupled) != K or len(y.multiplicities) != K:
+                    raise ValueError('from_grid: a tree of the new spaces lacks the uncoupled sector keys or the multiplicities of its legs '
+                                     '(TreeBlock.uncoupled, TreeBlock.multiplicities)')
+                L = _grid_slices(left_slices, x.uncoupled[0], nr, x.multiplicities[0], 'left_slices')
+                R = _grid_slices(right_slices, y.uncoupled[-1], nc, y.multiplicities[-1], 'right_slices')
+                Rc, Rd = int(np.prod(x.multiplicities[1:], dtype=np.int64)), int(np.prod(y.multiplicities[:-1], dtype=np.int64))
+                ri = [i for i in range(nr) if L[i + 1] > L[i]]
+                cj = [j for j in range(nc) if R[j + 1] > R[j]]
+                cells = tiles.get((x.tree, y.tree), {})
+                for i in ri:
+                    for j in cj:
+                        hit = cells.get((i, j))
+                        if hit is not None:
+                            blk, xe, ye = hit
+                            src = bb.get_item(blk, (slice(xe.start, xe.stop), slice(ye.start, ye.stop)))
+                            c = coeff_of(i, j)
+                            windows.append(_Window(n, x.start, x.stop, y.start, y.stop, Rd, L[i] * Rc, (L[i + 1] - L[i]) * Rc, R[j], R[j + 1] - R[j],
+                                                   src, 1, complex(c) if cplx else float(np.real(c))))
+                for a0, a1, b0, b1 in _zero_windows([[(i, j) not in cells for j in cj] for i in ri]):
+                    # (rows and columns of positive width are adjacent in the tile: what lies between them has the width 0)
+                    r0, r1, c0, c1 = L[ri[a0]], L[ri[a1 - 1] + 1], R[cj[b0]], R[cj[b1 - 1] + 1]
+                    windows.append(_Window(n, x.start, x.stop, y.start, y.stop, Rd, r0 * Rc, (r1 - r0) * Rc, c0, c1 - c0, None, 0, 0.0))
+    shapes = [(new_codomain.block_size(i), new_domain.block_size(j)) for i, j in rows]
+    outs = _place_windows(bb, shapes, cplx, windows)
+    res = FusionTreeData(np.array(rows, dtype=np.int64), outs)
+    return discard_zero_blocks(bb, res, eps) if discard else res
+
+
+def from_tree_pairs(bb, trees: dict, codomain: TreeSpace, domain: TreeSpace, dtype=None) -> FusionTreeData:
+    """``FusionTreeBackend::from_tree_pairs`` (fusion_tree_backend.cpp:3186-3263).  `trees`: ``{(codomain tree key, domain tree
+    key): block}`` with a block of the shape ``(m_1 .. m_J, n_K .. n_1)`` -- the multiplicities of the codomain tree followed by
+    those of the domain tree reversed.  Every block is ONE copy record into its tile: the row levels are ``m_1 .. m_J`` with
+    the block's own strides, the column levels ``n_1 .. n_K`` with the strides of its axes ``J + K - 1 .. J``; the permutation and
+    the reshape of :3226-3233 are never made, a block that is a view is read in place.  Tiles without an entry inside a coupled
+    block that holds at least one are records of zeros; coupled sectors without an entry are absent (:3242).  ONE
+    ``tree_place_many`` call.  complex128 if `dtype` or a block is complex.  ValueError: a key that no tile takes (the
+    reference's "uncovered tree pair", :3247-3249), a block of the wrong shape, more than six legs on a side, a complex block
+    under a real `dtype`."""
+    J, K = codomain.num_legs, domain.num_legs
+    if J > MAX_PLACE_LEGS or K > MAX_PLACE_LEGS:
+        raise ValueError(f'from_tree_pairs: {J} codomain legs and {K} domain legs, at most {MAX_PLACE_LEGS} on a side')
+    data_cplx = any(_is_complex(b) for b in trees.values())
+    cplx = data_cplx if dtype is None else np.dtype(dtype).kind == 'c'
+    if data_cplx and not cplx:
+        raise ValueError(f'from_tree_pairs: a complex block under the dtype {np.dtype(dtype)}')
+    perm = list(range(J)) + list(range(J + K - 1, J - 1, -1))
+    rows, shapes, windows, covered = [], [], [], set()
+    for i, j in common_sectors(codomain, domain):
+        tiles = []
+        for xb in codomain.tree_blocks[i]:
+            for yb in domain.tree_blocks[j]:
+                blk = trees.get((xb.tree, yb.tree))
+                if blk is not None:
+                    want = tuple(xb.multiplicities) + tuple(yb.multiplicities)[::-1]
+                    if len(xb.multiplicities) != J or len(yb.multiplicities) != K or tuple(blk.shape) != want:
+                        raise ValueError(f'from_tree_pairs: the block of the trees {xb.tree!r} and {yb.tree!r} has the shape {tuple(blk.shape)}, '
+                                         f'not {want}')
+                    covered.add((xb.tree, yb.tree))
+                tiles.append((xb, yb, blk))
+        if all(blk is None for _, _, blk in tiles):
+            continue                                                         # (is_zero_block, :3242)
+        for xb, yb, blk in tiles:
+            src = bb.permute_axes(blk, perm) if blk is not None else None
+            windows.append(_Window(len(rows), xb.start, xb.stop, yb.start, yb.stop, 1, 0, xb.stop - xb.start, 0, yb.stop - yb.start,
+                                   src, J if blk is not None else 0, 1.0))
+        rows.append((i, j))
+        shapes.append((codomain.block_size(i), domain.block_size(j)))
+    missing = [k for k in trees if k not in covered]
+    if missing:
+        raise ValueError(f'from_tree_pairs: uncovered tree pair {missing[0]!r}: no tile of a common coupled sector takes it')
+    if not rows:
+        return FusionTreeData(np.zeros((0, 2), np.int64), [])
+    return FusionTreeData(np.array(rows, dtype=np.int64), _place_windows(bb, shapes, cplx, windows))
+
+
+def eye(bb, space: TreeSpace, dtype=None) -> FusionTreeData:
+    """``FusionTreeBackend::eye_data`` (fusion_tree_backend.cpp:1180-1192): the identity block of every coupled sector of
+    `space`, ``block_inds`` (i, i).  The identity has the same matrix elements in every orthonormal basis, so the trees play no
+    role.  What most cells of an MPO grid hold."""
+    n = space.num_sectors
+    return FusionTreeData(np.array([(i, i) for i in range(n)], dtype=np.int64).reshape(n, 2),
+                          [bb.eye_matrix(space.block_size(i), dtype=dtype) for i in range(n)])
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -762,6 +762,49 @@ int cyb_tree_from_dense_f64(cyb_ctx_t ctx, const cyb_tree_from_dense_out* outs, 
 int cyb_tree_from_dense_c128(cyb_ctx_t ctx, const cyb_tree_from_dense_out* outs, int64_t n_outs, const cyb_tree_from_dense_term* terms,
                              int64_t n_terms, const double* s_table);
 
+/* ---- grouped, weighted, strided window copies -----------------------------------------------------------------------
+ * Every window of every result block of FusionTreeBackend::from_grid (src/backends/fusion_tree_backend.cpp:3375-3518) or
+ * ::from_tree_pairs (:3186-3263) in ONE launch: the reference makes get_item, reshape, copy_block, reshape, get_item,
+ * operator+, set_item, reshape and set_item per (grid entry, codomain forest, domain forest) into a zero-filled result
+ * (from_grid), and permute_axes, reshape and set_item per tree pair into zeros (from_tree_pairs).  A record is one window of
+ * a coupled block: h consecutive rows, nq runs of wn consecutive columns, one run every cp columns, in a block with the
+ * leading dimension ldd; dst addresses its first element:
+ *   dst[r * ldd + q * cp + w] = c * src[sum_l r_l * rs[l] + sum_l x_l * cs[l]]          r < h, q < nq, w < wn
+ * r is counted in C order over the n_row_levels levels rext[] (their product is h), x = q * wn + w in C order over the
+ * n_col_levels levels cext[] (their product is nq * wn); c = coeff_re + i coeff_im.
+ *   * src == NULL: the window is written as zeros (levels, strides and the coefficient's value are not read) -- the cells of
+ *     a result that nothing feeds are filled without a memset.
+ *   * Source strides count elements of the source's own type and may be zero or negative.  Sources are read in place,
+ *     transposed (dagger) views included, and may overlap each other.  The caller vouches for every address the strides reach.
+ *   * src_real != 0 (c128 entry only; the f64 entry ignores it): the source is float64 data read as it stands, strides in
+ *     doubles -- a real entry beside a complex one, or under a complex coefficient, needs no promotion pass.  The c128 entry
+ *     reads and writes interleaved (re, im) storage otherwise; cp and ldd count complex elements.
+ *   * The f64 entry requires coeff_im == 0 of every record: else CYB_ERR_INVALID, nothing is launched.
+ *   * Windows of one call must not overlap; the caller vouches for that.  Every destination element has exactly one owner: no
+ *     atomics, no second pass, results are bit-identical from run to run.
+ *   * c == 1 copies bits exactly (-0.0, NaN payloads); any other c is one product per component pair, never an FMA with a
+ *     zero addend.
+ *   * Zero extents and n_recs == 0 are valid.  cp is not read where nq == 1, ldd not where h == 1.
+ *   * Everything is validated on the host before anything is uploaded or launched: level counts, negative extents and
+ *     extents beyond 2^30 (h, nq, wn and every level), the products of the levels against h and nq * wn (of a record with a
+ *     source), cp < wn with nq > 1, ldd < (nq - 1) * cp + wn with h > 1, NULL dst of a non-empty window.  A refused call
+ *     returns CYB_ERR_INVALID with a message and leaves the context as it found it.
+ * One wave owns a work item of a record, its lanes on 64 consecutive elements of the window's C order (along a run, or
+ * across several narrow runs and rows), 16-byte stores where every pair of the window is aligned (csrc/tree_place.hip). */
+#define CYB_TREE_PLACE_MAX_LEVELS 6
+typedef struct {
+    double* dst;
+    const double* src; /* NULL: zeros */
+    int64_t h, nq, wn, cp, ldd;
+    int32_t n_row_levels, n_col_levels;
+    int64_t rext[CYB_TREE_PLACE_MAX_LEVELS], rs[CYB_TREE_PLACE_MAX_LEVELS];
+    int64_t cext[CYB_TREE_PLACE_MAX_LEVELS], cs[CYB_TREE_PLACE_MAX_LEVELS];
+    double coeff_re, coeff_im;
+    int32_t src_real, reserved;
+} cyb_tree_place_rec;
+int cyb_tree_place_f64(cyb_ctx_t ctx, const cyb_tree_place_rec* recs, int64_t n_recs);
+int cyb_tree_place_c128(cyb_ctx_t ctx, const cyb_tree_place_rec* recs, int64_t n_recs);
+
 /* ---- grouped matrix exponential of small blocks ---------------------------------------------------------------------
  * E = exp(alpha * A) for every listed square matrix in ONE launch, one workgroup per matrix, the whole computation in LDS
  * (csrc/expm_small.hip).  Replaces NumpyBlockBackend::matrix_exp = scipy.linalg.expm (src/block_backend/numpy.cpp:1227-1234),
