@@ -1135,6 +1135,35 @@ __device__ __forceinline__ bool spin_until(const unsigned int* word, unsigned in
     return true;
 }
 
+// Both words of a hand-off at once: the two loads are in flight together, ONE round trip when both counters are already
+// there (the serial form pays two dependent ones).  Same bound and error word; false when either word fails.
+template <int SLEEP = 1>
+__device__ __forceinline__ bool spin_until2(const unsigned int* word0, const unsigned int* word1, unsigned int target, unsigned int* err)
+{
+    const unsigned long long t0 = wall_clock64(); // 100 MHz
+    unsigned int it = 0;
+    for (;;) {
+        const unsigned int v0 = __hip_atomic_load(word0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned int v1 = __hip_atomic_load(word1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if ((v0 >= target) & (v1 >= target)) return true;
+        __builtin_amdgcn_s_sleep(SLEEP);
+        if ((++it & 63u) == 0u) {
+            if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return false;
+            if (wall_clock64() - t0 > 100000000ull) { // one second
+                __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                return false;
+            }
+        }
+    }
+}
+// RORD: the round's issue order of this file (false: the order it had before, kept for A/B -- CYB_JACOBI_ROUND_ORDER=0)
+template <bool RORD>
+__device__ __forceinline__ bool spin_pair(const unsigned int* word0, const unsigned int* word1, unsigned int target, unsigned int* err)
+{
+    if constexpr (RORD) return spin_until2(word0, word1, target, err);
+    else return spin_until(word0, target, err) && spin_until(word1, target, err);
+}
+
 // J rows of the pair (P, Q), column chunks [j_begin, j_begin + nJ) of 64:  X <- Qm^T X  (Qm in LDS as [k][m], stride QS)
 __device__ __forceinline__ void sweep_update_j(const __amdgpu_buffer_rsrc_t rsJ, const double* Qm, int P, int Q, int nvp, int j_begin,
                                                int nJ, int wave, int lane)
@@ -1180,7 +1209,7 @@ __device__ __forceinline__ void sweep_update_j(const __amdgpu_buffer_rsrc_t rsJ,
     }
 }
 
-template <bool CPLX>
+template <bool CPLX, bool RORD>
 __global__ void __launch_bounds__(NT, 1)
 jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned long long* __restrict__ offmax_bits, SScratch sc)
 {
@@ -1261,9 +1290,7 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
         __syncthreads(); // (also: nobody still reads the LDS of the previous round)
         if (ground > 0) {
             if (tid == 0) {
-                bool ok = spin_until(ready + (size_t)P * G + part, (unsigned int)ground, sc.err);
-                ok = ok && spin_until(ready + (size_t)Q * G + part, (unsigned int)ground, sc.err);
-                flags[1] = ok ? 1 : 0;
+                flags[1] = spin_pair<RORD>(ready + (size_t)P * G + part, ready + (size_t)Q * G + part, (unsigned int)ground, sc.err) ? 1 : 0;
             }
             __syncthreads();
             if (!flags[1]) return;
@@ -1285,6 +1312,17 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
         };
         // ---- 1. partial Gram over the own W share
         double xpre[SW_PRE][JP / 4];
+        // The update's operands: nothing reads them before the pivot solve has ended.  Loads return in order and a wave stalls
+        // once the queue is full, so WHERE they are issued decides what waits behind them (see step 2).
+        auto issue_xpre = [&]() {
+#pragma unroll
+            for (int c = 0; c < SW_PRE; ++c) {
+                if (c < pre_limit) { // (J chunks of a matrix whose J updates may be deferred are loaded after the wait for them)
+#pragma unroll
+                    for (int kk = 0; kk < JP / 4; ++kk) xpre[c][kk] = chunk_load(c, 4 * kk + ukq);
+                }
+            }
+        };
         {
             const int ld = mt.lenp;
             d4 acc00 = d4{0.0, 0.0, 0.0, 0.0}, acc01 = acc00, acc11 = acc00;
@@ -1305,28 +1343,53 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
                     a1[u] = qb.d;
                 }
             };
-            if (c_begin + wave < c_end) load(x0, x1, c_begin + wave);
-#pragma unroll
-            for (int c = 0; c < SW_PRE; ++c) {
-                if (c < pre_limit) { // (J chunks of a matrix whose J updates may be deferred are loaded after the wait for them)
-#pragma unroll
-                    for (int kk = 0; kk < JP / 4; ++kk) xpre[c][kk] = chunk_load(c, 4 * kk + ukq);
-                }
-            }
-            for (int c0 = c_begin + wave; c0 < c_end; c0 += 4 * UN) {
-                const bool more = c0 + 4 * UN < c_end;
-                if (more) load(n0, n1, c0 + 4 * UN);
+            auto gram = [&](const d2 (&a0)[UN], const d2 (&a1)[UN], int c0) {
 #pragma unroll
                 for (int u = 0; u < UN; ++u) {
                     if (c0 + 4 * u < c_end) {
-                        acc00 = __builtin_amdgcn_mfma_f64_16x16x4f64(x0[u].x, x0[u].x, acc00, 0, 0, 0);
-                        acc01 = __builtin_amdgcn_mfma_f64_16x16x4f64(x0[u].x, x1[u].x, acc01, 0, 0, 0);
-                        acc11 = __builtin_amdgcn_mfma_f64_16x16x4f64(x1[u].x, x1[u].x, acc11, 0, 0, 0);
-                        acc00 = __builtin_amdgcn_mfma_f64_16x16x4f64(x0[u].y, x0[u].y, acc00, 0, 0, 0);
-                        acc01 = __builtin_amdgcn_mfma_f64_16x16x4f64(x0[u].y, x1[u].y, acc01, 0, 0, 0);
-                        acc11 = __builtin_amdgcn_mfma_f64_16x16x4f64(x1[u].y, x1[u].y, acc11, 0, 0, 0);
+                        acc00 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[u].x, a0[u].x, acc00, 0, 0, 0);
+                        acc01 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[u].x, a1[u].x, acc01, 0, 0, 0);
+                        acc11 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1[u].x, a1[u].x, acc11, 0, 0, 0);
+                        acc00 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[u].y, a0[u].y, acc00, 0, 0, 0);
+                        acc01 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[u].y, a1[u].y, acc01, 0, 0, 0);
+                        acc11 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1[u].y, a1[u].y, acc11, 0, 0, 0);
                     }
                 }
+            };
+            if constexpr (RORD) {
+                // Nothing but the Gram's own loads is queued here (loads return in order: an update operand between the
+                // groups would sit ahead of the partial Gram the partners wait for).  The two buffers swap roles instead of
+                // being copied, and the test for a next group is hoisted around the MFMA block, so that every path is
+                // straight-line code and MFMA group u waits with a counted vmcnt for its own two loads only.
+                int c0 = c_begin + wave;
+                if (c0 < c_end) {
+                    load(x0, x1, c0);
+                    for (;;) {
+                        if (c0 + 4 * UN < c_end) {
+                            load(n0, n1, c0 + 4 * UN);
+                            gram(x0, x1, c0);
+                        } else {
+                            gram(x0, x1, c0);
+                            break;
+                        }
+                        c0 += 4 * UN;
+                        if (c0 + 4 * UN < c_end) {
+                            load(x0, x1, c0 + 4 * UN);
+                            gram(n0, n1, c0);
+                        } else {
+                            gram(n0, n1, c0);
+                            break;
+                        }
+                        c0 += 4 * UN;
+                    }
+                }
+            } else {
+            if (c_begin + wave < c_end) load(x0, x1, c_begin + wave);
+            issue_xpre();
+            for (int c0 = c_begin + wave; c0 < c_end; c0 += 4 * UN) {
+                const bool more = c0 + 4 * UN < c_end;
+                if (more) load(n0, n1, c0 + 4 * UN);
+                gram(x0, x1, c0);
                 if (more) {
 #pragma unroll
                     for (int u = 0; u < UN; ++u) {
@@ -1334,6 +1397,7 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
                         x1[u] = n1[u];
                     }
                 }
+            }
             }
             double* wpart = Xc + wave * (JP * GS);
 #pragma unroll
@@ -1347,6 +1411,11 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
         }
         __syncthreads();
         SWEEP_STAMP(2);
+        // The Gram loop leaves loads nobody consumes (the clamped tail of its last group).  They have landed by now, but the
+        // compiler's wait counting cannot know (it does not see the drains written as inline assembly), and drains the queue
+        // -- the prefetch below included -- at the first reuse of one of their registers, after the exchange or inside the
+        // pivot solve.  Hence a wait it can see: the builtin.
+        if constexpr (RORD) __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0)
         {
             const int gi = tid >> 3, gj = 4 * (tid & 7);
             d2 lo = d2{0.0, 0.0}, hi = d2{0.0, 0.0};
@@ -1358,10 +1427,10 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
                 hi.x += src[2];
                 hi.y += src[3];
             }
+            // ---- 2. exchange of the partials among the G parts (double buffered by round parity)
+            const __amdgpu_buffer_rsrc_t rs_all = __builtin_amdgcn_make_buffer_rsrc(
+                sc.gpart + ((size_t)pi * 2 + (size_t)(ground & 1)) * RGMAX * (JP * JP), 0, (int)(pbytes * G), 0x00020000);
             if (G > 1) {
-                // ---- 2. exchange of the partials among the G parts (double buffered by round parity)
-                const __amdgpu_buffer_rsrc_t rs_all = __builtin_amdgcn_make_buffer_rsrc(
-                    sc.gpart + ((size_t)pi * 2 + (size_t)(ground & 1)) * RGMAX * (JP * JP), 0, (int)(pbytes * G), 0x00020000);
                 Q16 a, b;
                 a.d = lo;
                 b.d = hi;
@@ -1371,12 +1440,19 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();
                 if (tid == 0) __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            // The update's operands go out HERE: behind the ticket, so that nothing the partners wait for queues behind them,
+            // and in front of the poll, so that their issue (48 loads per lane fill the queue: the wave stalls) falls into
+            // the wait for the partners' tickets.  Issued behind the loads of the partners' partials instead, the sum of the
+            // partials waited for that issue (exchange 5.9 -> 8.5 us).  They land during the poll; the barriers of the pivot
+            // solve carry no vmcnt wait.  ONE site for every G (without an exchange it follows the Gram loop): two sites
+            // meet in register copies, i.e. in a wait for the loads just issued.
+            if constexpr (RORD) issue_xpre();
+            if (G > 1) {
                 if (pendP >= 0) {
                     // ---- the J half of the previous round's update, while the partners' partial Grams are on their way
                     if (tid == 0) {
-                        bool ok = spin_until(readyJ + (size_t)pendP * G + part, (unsigned int)pend_ground, sc.err);
-                        ok = ok && spin_until(readyJ + (size_t)pendQ * G + part, (unsigned int)pend_ground, sc.err);
-                        flags[1] = ok ? 1 : 0;
+                        flags[1] = spin_pair<RORD>(readyJ + (size_t)pendP * G + part, readyJ + (size_t)pendQ * G + part, (unsigned int)pend_ground, sc.err) ? 1 : 0;
                     }
                     __syncthreads();
                     if (!flags[1]) return;
@@ -1559,9 +1635,7 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
             SWEEP_STAMP(5);
             if (ct > nW) { // J is updated in this round: its rows must have been through every earlier round's update
                 if (tid == 0) {
-                    bool ok = spin_until(readyJ + (size_t)P * G + part, (unsigned int)ground, sc.err);
-                    ok = ok && spin_until(readyJ + (size_t)Q * G + part, (unsigned int)ground, sc.err);
-                    flags[1] = ok ? 1 : 0;
+                    flags[1] = spin_pair<RORD>(readyJ + (size_t)P * G + part, readyJ + (size_t)Q * G + part, (unsigned int)ground, sc.err) ? 1 : 0;
                 }
                 __syncthreads();
                 if (!flags[1]) return;
@@ -1615,6 +1689,32 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
                     double xb[JP / 4], xn[JP / 4];
 #pragma unroll
                     for (int kk = 0; kk < JP / 4; ++kk) xb[kk] = chunk_load(SW_PRE, 4 * kk + ukq);
+                    if constexpr (RORD) {
+                        // as in the Gram loop: the buffers swap roles and the test for a next chunk is hoisted, so that the
+                        // MFMAs of a chunk wait with a counted vmcnt and the next chunk's loads stay in flight behind them
+                        auto fetch = [&](double (&x)[JP / 4], int c) {
+#pragma unroll
+                            for (int kk = 0; kk < JP / 4; ++kk) x[kk] = chunk_load(c, 4 * kk + ukq);
+                        };
+                        for (int c = SW_PRE;;) {
+                            if (c + 1 < ct) {
+                                fetch(xn, c + 1);
+                                apply(c, xb);
+                            } else {
+                                apply(c, xb);
+                                break;
+                            }
+                            ++c;
+                            if (c + 1 < ct) {
+                                fetch(xb, c + 1);
+                                apply(c, xn);
+                            } else {
+                                apply(c, xn);
+                                break;
+                            }
+                            ++c;
+                        }
+                    } else
                     for (int c = SW_PRE; c < ct; ++c) {
                         if (c + 1 < ct) {
 #pragma unroll
@@ -1637,8 +1737,11 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
         __syncthreads();
         if (tid == 0) {
             if (skip && nJ > 0) { // (J untouched, but it may only be passed on once the earlier rounds' updates are in)
-                (void)spin_until(readyJ + (size_t)P * G + part, (unsigned int)ground, sc.err);
-                (void)spin_until(readyJ + (size_t)Q * G + part, (unsigned int)ground, sc.err);
+                if constexpr (RORD) (void)spin_until2(readyJ + (size_t)P * G + part, readyJ + (size_t)Q * G + part, (unsigned int)ground, sc.err);
+                else {
+                    (void)spin_until(readyJ + (size_t)P * G + part, (unsigned int)ground, sc.err);
+                    (void)spin_until(readyJ + (size_t)Q * G + part, (unsigned int)ground, sc.err);
+                }
             }
             __hip_atomic_store(ready + (size_t)P * G + part, (unsigned int)(ground + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(ready + (size_t)Q * G + part, (unsigned int)(ground + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1961,11 +2064,16 @@ int jacobi_orthogonalise(cyb_ctx_t ctx, const std::vector<JMat>& h_mats, int max
                 }
                 void* d_rp2 = cached_img;
                 void* d_map = static_cast<char*>(cached_img) + cached_map_off;
+                // CYB_JACOBI_ROUND_ORDER=0: the issue order a round had before (same arithmetic, same protocol: bit-identical results)
+                static const bool round_order = !(getenv("CYB_JACOBI_ROUND_ORDER") && atoi(getenv("CYB_JACOBI_ROUND_ORDER")) == 0);
+                typedef void (*sweep_fn_t)(const RPair*, int, unsigned long long*, SScratch);
+                static const sweep_fn_t sweep_fn[2] = {round_order ? jacobi_sweep_kernel<false, true> : jacobi_sweep_kernel<false, false>,
+                                                       round_order ? jacobi_sweep_kernel<true, true> : jacobi_sweep_kernel<true, false>};
                 static bool attr2_set = false;
                 if (!attr2_set) {
-                    if (hipFuncSetAttribute(reinterpret_cast<const void*>(jacobi_sweep_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                    if (hipFuncSetAttribute(reinterpret_cast<const void*>(sweep_fn[0]), hipFuncAttributeMaxDynamicSharedMemorySize,
                                             (int)SWEEP_LDS_BYTES) != hipSuccess ||
-                        hipFuncSetAttribute(reinterpret_cast<const void*>(jacobi_sweep_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                        hipFuncSetAttribute(reinterpret_cast<const void*>(sweep_fn[1]), hipFuncAttributeMaxDynamicSharedMemorySize,
                                             (int)SWEEP_LDS_BYTES) != hipSuccess) {
                         set_error("jacobi: cannot reserve %zu bytes of LDS for the sweep kernel", SWEEP_LDS_BYTES);
                         status = CYB_ERR_HIP;
@@ -1999,12 +2107,8 @@ int jacobi_orthogonalise(cyb_ctx_t ctx, const std::vector<JMat>& h_mats, int max
                 ss.arrive = reinterpret_cast<unsigned int*>(d_off + w_off);
                 ss.nsw = reinterpret_cast<int*>(ss.arrive + n);
                 one_launch_done = one_launch;
-                if (cplx)
-                    hipLaunchKernelGGL(jacobi_sweep_kernel<true>, dim3((unsigned)n_wg), dim3(NT), SWEEP_LDS_BYTES, st,
-                                       static_cast<const RPair*>(d_rp2), max_inner, d_off, ss);
-                else
-                    hipLaunchKernelGGL(jacobi_sweep_kernel<false>, dim3((unsigned)n_wg), dim3(NT), SWEEP_LDS_BYTES, st,
-                                       static_cast<const RPair*>(d_rp2), max_inner, d_off, ss);
+                hipLaunchKernelGGL(sweep_fn[cplx ? 1 : 0], dim3((unsigned)n_wg), dim3(NT), SWEEP_LDS_BYTES, st,
+                                   static_cast<const RPair*>(d_rp2), max_inner, d_off, ss);
                 if (ss.stamps && wgmap.size() <= 2048) {
                     std::vector<unsigned long long> hs(8 * wgmap.size());
                     if (hipMemcpyAsync(hs.data(), rs.stamps, sizeof(unsigned long long) * hs.size(), hipMemcpyDeviceToHost, st) == hipSuccess &&
