@@ -1602,11 +1602,7 @@ class HipBlockBackend:
             return
         dsts = [dst for dst, _ in outputs]
         srcs = [tm[0] for _, terms in outputs for tm in terms]
-        self._numeric_only(dsts + srcs, 'tree_trace_many')
-        kinds = {d.is_complex for d in dsts}
-        if len(kinds) > 1:
-            raise ValueError('tree_trace_many: the destination views of one call share one dtype')
-        cplx = kinds.pop()
+        cplx = self._tree_entry('tree_trace_many', dsts, srcs)
         nd_max, np_max = _lib.CYB_MAX_NDIM, _lib.CYB_TRACE_MAX_PAIRS
         zeros_nd, zeros_np = (0,) * nd_max, (0,) * np_max
         o_first, o_n, o_shape, o_str = [], [], [], []
@@ -1657,6 +1653,18 @@ class HipBlockBackend:
         _lib.check(fn(self.ctx.handle, oarr.ctypes.data_as(C.POINTER(_lib.TraceWeightedOut)), len(outputs),
                       tarr.ctypes.data_as(C.POINTER(_lib.TraceWeightedTerm)), n_t))
 
+    def _tree_entry(self, what, dsts, srcs, ndim_error=None):
+        """What the ``tree_*_many`` methods ask of their views before they look at one: no boolean view; `ndim_error`, the
+        complaint about views with the wrong number of axes where there are some; destination views of one dtype.  Returns
+        whether the call takes the complex128 entry."""
+        self._numeric_only(dsts + srcs, what)
+        if ndim_error:
+            raise ValueError(f'{what}: {ndim_error}')
+        kinds = {d.is_complex for d in dsts}
+        if len(kinds) > 1:
+            raise ValueError(f'{what}: the destination views of one call share one dtype')
+        return kinds.pop()
+
     def tree_outer_many(self, outputs):
         """Weighted Kronecker products into strided tiles, ONE descriptor upload and ONE launch for all result blocks of a
         fusion-tree outer (``FusionTreeBackend::outer``, fusion_tree_backend.cpp:2609-2667: outer, permute_axes, combine_legs
@@ -1673,13 +1681,8 @@ class HipBlockBackend:
         dsts = [dst for dst, _ in outputs]
         a_srcs = [tm[0] for _, terms in outputs for tm in terms]
         b_srcs = [tm[1] for _, terms in outputs for tm in terms]
-        self._numeric_only(dsts + a_srcs + b_srcs, 'tree_outer_many')
-        if any(x.ndim != 2 for x in dsts + a_srcs + b_srcs):
-            raise ValueError('tree_outer_many: destinations and sources are 2-D views')
-        kinds = {d.is_complex for d in dsts}
-        if len(kinds) > 1:
-            raise ValueError('tree_outer_many: the destination views of one call share one dtype')
-        cplx = kinds.pop()
+        cplx = self._tree_entry('tree_outer_many', dsts, a_srcs + b_srcs,
+                                any(x.ndim != 2 for x in dsts + a_srcs + b_srcs) and 'destinations and sources are 2-D views')
         o_ext, o_ldd, o_first, o_n, t_re, t_im = [], [], [], [], [], []
         for dst, terms in outputs:
             H, W = dst.shape
@@ -1738,13 +1741,8 @@ class HipBlockBackend:
         dsts = [o[0] for o in outputs]
         a_srcs = [tm[0] for o in outputs for tm in o[4]]
         b_srcs = [tm[1] for o in outputs for tm in o[4]]
-        self._numeric_only(dsts + a_srcs + b_srcs, 'tree_compose_many')
-        if any(x.ndim != 2 for x in dsts + a_srcs + b_srcs):
-            raise ValueError('tree_compose_many: destinations and sources are 2-D views')
-        kinds = {d.is_complex for d in dsts}
-        if len(kinds) > 1:
-            raise ValueError('tree_compose_many: the destination views of one call share one dtype')
-        cplx = kinds.pop()
+        cplx = self._tree_entry('tree_compose_many', dsts, a_srcs + b_srcs,
+                                any(x.ndim != 2 for x in dsts + a_srcs + b_srcs) and 'destinations and sources are 2-D views')
         o_ext, o_sd, o_axis, o_first, o_n = [], [], [], [], []
         t_re, t_im, t_K, t_sa, t_bn, t_bk = [], [], [], [], [], []
         for dst, side, m0, m2, terms in outputs:
@@ -1814,13 +1812,8 @@ class HipBlockBackend:
         if not records:
             return
         dsts = [r[0] for r in records]
-        self._numeric_only(dsts + [r[1] for r in records if r[1] is not None], what)
-        if any(d.ndim != 3 for d in dsts):
-            raise ValueError(f'{what}: destinations are 3-D views (rows, runs, columns of a run)')
-        kinds = {d.is_complex for d in dsts}
-        if len(kinds) > 1:
-            raise ValueError(f'{what}: the destination views of one call share one dtype')
-        cplx = kinds.pop()
+        cplx = self._tree_entry(what, dsts, [r[1] for r in records if r[1] is not None],
+                                any(d.ndim != 3 for d in dsts) and 'destinations are 3-D views (rows, runs, columns of a run)')
         nl = _lib.CYB_TREE_PLACE_MAX_LEVELS
         pad = (0,) * nl
         arr = np.zeros(len(records), dtype=_lib.TREE_PLACE_DTYPE)
@@ -1891,8 +1884,7 @@ class HipBlockBackend:
         if not regions:
             return
         blocks = [tm[0] for r in regions for tm in r[4]]
-        self._numeric_only([dst_view] + blocks, what)
-        L, cplx = dst_view.ndim, dst_view.is_complex
+        L, cplx = dst_view.ndim, self._tree_entry(what, [dst_view], blocks)
         if L > _lib.CYB_TREE_DENSE_MAX_LEGS:
             raise ValueError(f'{what}: a destination view with more than {_lib.CYB_TREE_DENSE_MAX_LEGS} axes')
         if any(b.ndim != 2 for b in blocks):
@@ -1950,13 +1942,7 @@ class HipBlockBackend:
             return
         dsts = [o[0] for o in outputs]
         srcs = [tm[0] for o in outputs for tm in o[5]]
-        self._numeric_only(dsts + srcs, what)
-        if any(d.ndim != 2 for d in dsts):
-            raise ValueError(f'{what}: destinations are 2-D views')
-        kinds = {d.is_complex for d in dsts}
-        if len(kinds) > 1:
-            raise ValueError(f'{what}: the destination views of one call share one dtype')
-        cplx = kinds.pop()
+        cplx = self._tree_entry(what, dsts, srcs, any(d.ndim != 2 for d in dsts) and 'destinations are 2-D views')
         table, s_offs, s_cplx = self._tree_pair_table([tm[2] for o in outputs for tm in o[5]])
         if not cplx and (s_cplx or any(a.is_complex for a in srcs)):
             raise ValueError(f'{what}: a complex source or tree tensor needs complex destination views')

@@ -27,80 +27,34 @@
 //     per k for kNB results, the B addresses are wave-uniform, and the lane stores its kNB results sd[axis] apart (along p
 //     the stores of the wave stay contiguous).  With p == axis (the domain layout with m2 = 1, a codomain tile of one
 //     column) n stays in the lanes, which keeps those stores contiguous.  The order of the sums of an element is the same.
-//   * host: every record is cut into work items of kMinChunk..kMaxChunk flat units; ONE WAVE owns an item (four items per
-//     workgroup, no LDS, no barrier), so that one launch balances thousands of 1 x 1 tiles -- a wave each -- beside a tile of
-//     tens of MB.  An item carries the digits and the destination offset of its first unit.
-//   * device: a lane keeps a cursor (four digits, destination offset), decodes its lane offset once per item (below 64:
-//     32-bit divisions) and then advances by the wave's step of 64 units with precomputed digits and a precomputed offset
-//     correction per wrap of a level: additions and compares only, no division per element.  The source offsets are four
-//     multiply-adds per term from the digits.
+//   * every record is cut into one-wave work items and walked by a cursor (four digits, destination offset) as
+//     wave_items.h describes.  The source offsets are four multiply-adds per term from the digits.
 //   * item, record and term are wave-uniform: their fields travel through scalar loads; the k loop is innermost.
-#include "common.h"
-
-#include <algorithm>
+#include "wave_items.h"
 
 namespace {
 
-#define GLOBAL_AS __attribute__((address_space(1)))
-
-constexpr int NT = 256, WAVE = 64, ITEMS_PER_GROUP = NT / WAVE;
-constexpr int64_t kMinChunk = 1024, kMaxChunk = 16384, kTargetItems = 8192; // flat units per work item (multiples of WAVE)
+using namespace cyb_items;
 constexpr int64_t kMaxExtent = (int64_t)1 << 30;
 constexpr int kNB = 4; // values of n a lane holds in registers at a time
-typedef double d2 __attribute__((ext_vector_type(2)));
 typedef cyb_compose_weighted_out Out;
 typedef cyb_compose_weighted_term Term;
 
-// what a lane holds per step: one double, two adjacent doubles, or one complex number
-enum { kF64 = 0, kF64x2 = 1, kC128 = 2 };
-
-// one output as the kernel reads it
+// one output as the kernel reads it; one stream: the destination (doubles; kC128: complex elements)
 struct Rec {
     double* dst;
     int64_t first_term, n_terms;
-    int32_t ext[4];  // (kF64x2: ext[pair] counts pairs)
-    int32_t step[4]; // digits of the step of WAVE units
-    int64_t sd[4];   // destination stride of every level (doubles; kC128: complex elements)
-    int64_t wd[4];   // correction of the destination offset when level l wraps: sd[l - 1] - ext[l] * sd[l]
-    int64_t step_d;  // increment of the destination offset per step, before corrections
+    Levels<4, 1> lv;                    // (kF64x2: ext[pair] counts pairs)
     int32_t mode, axis, pair;           // pair: the level that counts pairs (kF64x2), else -1
     int32_t n_reg;                      // n in registers: its extent N (ext[axis] is 1 then); 0: n runs in the lanes
-    int64_t sn;                         // destination stride of n (as sd)
+    int64_t sn;                         // destination stride of n (as the stream)
 };
 
-struct Item {
-    int32_t rec;
-    int32_t reserved;
-    int64_t count;  // flat units of this item
-    int64_t od;     // destination offset of its first unit (doubles; kC128: complex elements)
-    int32_t idx[4]; // digits of its first unit
-};
-
-struct Cursor {
-    int32_t idx[4];
-    int64_t od;
-};
-
-// c += (digits dg, whose destination offset is dd); every digit below its extent, so a level wraps at most once
-__device__ inline void advance(Cursor& c, const Rec& r, const int32_t (&dg)[4], int64_t dd)
-{
-    c.od += dd;
-    int32_t carry = 0;
-#pragma unroll
-    for (int l = 3; l >= 0; --l) {
-        const int32_t i = c.idx[l] + dg[l] + carry;
-        const bool w = i >= r.ext[l];
-        c.idx[l] = w ? i - r.ext[l] : i;
-        c.od += w ? r.wd[l] : 0;
-        carry = w ? 1 : 0;
-    }
-}
-
-template <int MODE> struct Acc { typedef d2 type; };
-template <> struct Acc<kF64> { typedef double type; };
+typedef cyb_items::Item<4, 1> Item;
+typedef cyb_items::Cursor<4, 1> Cursor;
 
 // acc += c * sum_k A[k] * B[k] of one term at the digits of `c`
-template <int MODE> __device__ inline void add_term(typename Acc<MODE>::type& acc, const Term& tm, const Rec& r, const Cursor& c)
+template <int MODE> __device__ inline void add_term(typename Val<MODE>::type& acc, const Term& tm, const Rec& r, const Cursor& c)
 {
     int64_t oa = 0, ob = 0;
 #pragma unroll
@@ -131,8 +85,7 @@ template <int MODE> __device__ inline void add_term(typename Acc<MODE>::type& ac
         d2 s = d2{0.0, 0.0};
         for (int64_t k = 0; k < tm.K; ++k) {
             const int64_t ia = oa + k * ka, ib = ob + k * kb;
-            const d2 x = tm.a_real ? d2{a[ia], 0.0} : *(const GLOBAL_AS d2*)(a + 2 * ia);
-            const d2 y = tm.b_real ? d2{b[ib], 0.0} : *(const GLOBAL_AS d2*)(b + 2 * ib);
+            const d2 x = load_c(tm.a, ia, tm.a_real), y = load_c(tm.b, ib, tm.b_real);
             s.x += x.x * y.x - x.y * y.y;
             s.y += x.x * y.y + x.y * y.x;
         }
@@ -143,7 +96,7 @@ template <int MODE> __device__ inline void add_term(typename Acc<MODE>::type& ac
 
 // acc[j] += c * sum_k A[k] * B_{n0 + j}[k], j < nn <= kNB, of one term at the digits of `c` (whose digit of `axis` is 0)
 template <int MODE>
-__device__ inline void add_term_block(typename Acc<MODE>::type (&acc)[kNB], const Term& tm, const Rec& r, const Cursor& c, int32_t n0, int32_t nn)
+__device__ inline void add_term_block(typename Val<MODE>::type (&acc)[kNB], const Term& tm, const Rec& r, const Cursor& c, int32_t n0, int32_t nn)
 {
     int64_t oa = 0;
 #pragma unroll
@@ -186,12 +139,12 @@ __device__ inline void add_term_block(typename Acc<MODE>::type (&acc)[kNB], cons
         d2 s[kNB] = {};
         for (int64_t k = 0; k < tm.K; ++k) {
             const int64_t ia = oa + k * ka;
-            const d2 x = tm.a_real ? d2{a[ia], 0.0} : *(const GLOBAL_AS d2*)(a + 2 * ia);
+            const d2 x = load_c(tm.a, ia, tm.a_real);
 #pragma unroll
             for (int j = 0; j < kNB; ++j)
                 if (j < nn) {
                     const int64_t ib = ob + j * tm.b_ns + k * kb;
-                    const d2 y = tm.b_real ? d2{b[ib], 0.0} : *(const GLOBAL_AS d2*)(b + 2 * ib);
+                    const d2 y = load_c(tm.b, ib, tm.b_real);
                     s[j].x += x.x * y.x - x.y * y.y;
                     s[j].y += x.x * y.y + x.y * y.x;
                 }
@@ -206,25 +159,10 @@ __device__ inline void add_term_block(typename Acc<MODE>::type (&acc)[kNB], cons
 
 template <int MODE, bool NREG> __device__ inline void run_item(const Rec& r, const Item& it, const Term* __restrict__ terms, int lane)
 {
-    typedef typename Acc<MODE>::type T;
+    typedef typename Val<MODE>::type T;
     Cursor c;
-#pragma unroll
-    for (int l = 0; l < 4; ++l) c.idx[l] = it.idx[l];
-    c.od = it.od;
-    {
-        // lane offset into the item -> digits (below 64: 32-bit divisions, extents above it never divide)
-        uint32_t d = (uint32_t)lane;
-        int32_t dg[4];
-#pragma unroll
-        for (int l = 3; l >= 0; --l) {
-            const uint32_t e32 = r.ext[l] > WAVE ? (uint32_t)WAVE + 1 : (uint32_t)r.ext[l];
-            const uint32_t q = d / e32;
-            dg[l] = (int32_t)(d - q * e32);
-            d = q;
-        }
-        advance(c, r, dg, dg[0] * r.sd[0] + dg[1] * r.sd[1] + dg[2] * r.sd[2] + dg[3] * r.sd[3]);
-    }
-    GLOBAL_AS double* dst = (GLOBAL_AS double*)r.dst;
+    start(c, r.lv, it.at, lane, 0);
+    double* dst = r.dst;
     for (int64_t u = lane; u < it.count; u += WAVE) {
         if constexpr (NREG) {
             for (int32_t n0 = 0; n0 < r.n_reg; n0 += kNB) {
@@ -233,28 +171,14 @@ template <int MODE, bool NREG> __device__ inline void run_item(const Rec& r, con
                 for (int64_t t = r.first_term; t < r.first_term + r.n_terms; ++t) add_term_block<MODE>(acc, terms[t], r, c, n0, nn);
 #pragma unroll
                 for (int j = 0; j < kNB; ++j)
-                    if (j < nn) {
-                        const int64_t od = c.od + (int64_t)(n0 + j) * r.sn;
-                        if constexpr (MODE == kF64)
-                            dst[od] = acc[j];
-                        else if constexpr (MODE == kF64x2)
-                            *(GLOBAL_AS d2*)(dst + od) = acc[j];
-                        else
-                            *(GLOBAL_AS d2*)(dst + 2 * od) = acc[j];
-                    }
+                    if (j < nn) store_<MODE>(dst, c.off[0] + (int64_t)(n0 + j) * r.sn, acc[j]);
             }
         } else {
-            T acc;
-            if constexpr (MODE == kF64) acc = 0.0; else acc = d2{0.0, 0.0};
+            T acc = zero_<MODE>();
             for (int64_t t = r.first_term; t < r.first_term + r.n_terms; ++t) add_term<MODE>(acc, terms[t], r, c);
-            if constexpr (MODE == kF64)
-                dst[c.od] = acc;
-            else if constexpr (MODE == kF64x2)
-                *(GLOBAL_AS d2*)(dst + c.od) = acc;
-            else
-                *(GLOBAL_AS d2*)(dst + 2 * c.od) = acc;
+            store_<MODE>(dst, c.off[0], acc);
         }
-        advance(c, r, r.step, r.step_d);
+        advance(c, r.lv, r.lv.step, r.lv.step_o, 0);
     }
 }
 
@@ -262,12 +186,10 @@ template <bool CPLX>
 __global__ void __launch_bounds__(NT) compose_weighted_kernel(const Rec* __restrict__ recs, const Term* __restrict__ terms,
                                                               const Item* __restrict__ items, int n_items)
 {
-    // one wave per item: the index is wave-uniform, and so is everything read through it
-    const int i = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * ITEMS_PER_GROUP + threadIdx.x / WAVE));
-    if (i >= n_items) return;
+    int i, lane;
+    if (!my_item(i, lane, n_items)) return;
     const Item& it = items[i];
     const Rec& r = recs[it.rec];
-    const int lane = threadIdx.x & (WAVE - 1);
     if (r.n_reg) {
         if constexpr (CPLX)
             run_item<kC128, true>(r, it, terms, lane);
@@ -285,8 +207,6 @@ __global__ void __launch_bounds__(NT) compose_weighted_kernel(const Rec* __restr
     }
 }
 
-inline bool even_(int64_t v) { return (v & 1) == 0; }
-
 template <bool CPLX>
 int compose_weighted(cyb_ctx_t ctx, const Out* outs, int64_t n_outs, const Term* terms, int64_t n_terms, const char* who)
 {
@@ -300,13 +220,11 @@ int compose_weighted(cyb_ctx_t ctx, const Out* outs, int64_t n_outs, const Term*
     }
     std::vector<Rec> recs;
     std::vector<int64_t> totals;
-    int64_t grand = 0;
     for (int64_t i = 0; i < n_outs; ++i) {
         const Out& o = outs[i];
         CYB_REQUIRE(o.ext[0] >= 0 && o.ext[1] >= 0 && o.ext[2] >= 0 && o.ext[3] >= 0, "%s: output %lld: negative extent", who, (long long)i);
         CYB_REQUIRE(o.axis == 1 || o.axis == 2, "%s: output %lld: axis %d is neither 1 nor 2", who, (long long)i, (int)o.axis);
-        CYB_REQUIRE(o.first_term >= 0 && o.n_terms >= 0 && o.first_term <= n_terms && o.n_terms <= n_terms - o.first_term,
-                    "%s: output %lld: bad term range [%lld, +%lld)", who, (long long)i, (long long)o.first_term, (long long)o.n_terms);
+        CYB_REQUIRE_TERM_RANGE(who, i, o, n_terms);
         int64_t total = 1;
         bool fits = true;
         for (int l = 0; l < 4; ++l) {
@@ -339,53 +257,17 @@ int compose_weighted(cyb_ctx_t ctx, const Out* outs, int64_t n_outs, const Term*
         r.n_reg = p != o.axis ? (int32_t)o.ext[o.axis] : 0;
         r.sn = o.sd[o.axis];
         for (int l = 0; l < 4; ++l) {
-            r.ext[l] = (int32_t)(l == r.pair ? o.ext[l] / 2 : (r.n_reg && l == o.axis ? 1 : o.ext[l]));
-            r.sd[l] = l == r.pair ? 2 : o.sd[l];
+            r.lv.ext[l] = (int32_t)(l == r.pair ? o.ext[l] / 2 : (r.n_reg && l == o.axis ? 1 : o.ext[l]));
+            r.lv.st[0][l] = l == r.pair ? 2 : o.sd[l];
         }
         if (r.n_reg) total /= o.ext[o.axis];
-        int64_t s = WAVE;
-        for (int l = 3; l >= 0; --l) {
-            r.wd[l] = (l > 0 ? r.sd[l - 1] : 0) - r.ext[l] * r.sd[l];
-            // digits of the step; what is left at the outermost level stays there (a cursor is only read while inside the tile)
-            r.step[l] = (int32_t)(l > 0 ? s % r.ext[l] : std::min<int64_t>(s, r.ext[0]));
-            s = l > 0 ? s / r.ext[l] : 0;
-            r.step_d += r.step[l] * r.sd[l];
-        }
+        set_steps(r.lv, 0);
         recs.push_back(r);
         totals.push_back(x2 ? total / 2 : total);
-        grand += totals.back();
     }
-    if (recs.empty()) return CYB_OK;
-    // about kTargetItems waves for a large launch
-    int64_t chunk = (grand / kTargetItems + WAVE - 1) / WAVE * WAVE;
-    chunk = std::min(std::max(chunk, kMinChunk), kMaxChunk);
     std::vector<Item> items;
-    for (size_t i = 0; i < recs.size(); ++i) {
-        const Rec& r = recs[i];
-        for (int64_t e0 = 0; e0 < totals[i]; e0 += chunk) {
-            Item it;
-            memset(&it, 0, sizeof(it));
-            it.rec = (int32_t)i;
-            it.count = std::min(chunk, totals[i] - e0);
-            int64_t e = e0;
-            for (int l = 3; l >= 0; --l) {
-                it.idx[l] = (int32_t)(e % r.ext[l]);
-                e /= r.ext[l];
-                it.od += it.idx[l] * r.sd[l];
-            }
-            items.push_back(it);
-        }
-    }
-    CYB_REQUIRE(items.size() < ((size_t)1 << 31), "%s: too many work items", who);
-    void *d_recs = nullptr, *d_terms = nullptr, *d_items = nullptr;
-    CYB_TRY(cyb::upload_packed(ctx, {{recs.data(), sizeof(Rec) * recs.size(), &d_recs},
-                                     {ht.empty() ? (const void*)recs.data() : (const void*)ht.data(), ht.empty() ? 8 : sizeof(Term) * ht.size(), &d_terms},
-                                     {items.data(), sizeof(Item) * items.size(), &d_items}}));
-    const unsigned grid = (unsigned)((items.size() + ITEMS_PER_GROUP - 1) / ITEMS_PER_GROUP);
-    hipLaunchKernelGGL(compose_weighted_kernel<CPLX>, dim3(grid), dim3(NT), 0, ctx->stream, static_cast<const Rec*>(d_recs),
-                       static_cast<const Term*>(d_terms), static_cast<const Item*>(d_items), (int)items.size());
-    CYB_HIP(hipGetLastError());
-    return CYB_OK;
+    cut_items(items, recs, totals);
+    return launch_items(ctx, compose_weighted_kernel<CPLX>, recs, ht, items, who);
 }
 
 } // namespace

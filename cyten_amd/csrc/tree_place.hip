@@ -16,182 +16,106 @@
 //   * host: the window is the flat index space u = (r * nq + q) * wn + w, which is the C order of the destination levels
 //     (r, q, w) AND of the source levels (r_0 .., x_0 ..).  Source levels of extent 1 are dropped and adjacent levels that
 //     continue each other are merged (a contiguous tile of a block: one row level, one column level).  Every record is cut
-//     into work items of kMinChunk..kMaxChunk flat units; ONE WAVE owns an item (four items per workgroup, no LDS, no
-//     barrier, no scratch), its lanes on 64 consecutive units: along a column run where the run is wide, across several
-//     runs and rows at once where wn is small -- a stacked leg of multiplicity 1 under a large nq leaves no lane idle.
+//     into the one-wave work items of wave_items.h, the lanes of a wave on 64 consecutive units: along a column run where
+//     the run is wide, across several runs and rows at once where wn is small -- a stacked leg of multiplicity 1 under a
+//     large nq leaves no lane idle.
 //   * a lane stores 16 bytes per step: one complex, or a pair of doubles (w, w + 1) where wn is even, cp is even (or nq = 1),
 //     ldd is even (or h = 1), dst is 16-byte aligned and the innermost source level has an even extent -- a pair then never
 //     straddles two runs or two values of a source level, and every pair of the window is aligned.  Else one double per
 //     lane (a window whose runs start 8-byte aligned only is stored 8 bytes wide throughout; the stores of a wave are
 //     consecutive either way).  The pair of the source is ONE 16-byte load where its innermost level has stride 1 and every
 //     pair is aligned, else two loads.
-//   * device: a lane keeps two cursors (destination: three digits; source: up to twelve) with their offsets.  It decodes its
-//     lane offset (below 64: 32-bit divisions) once per item and then advances by the wave's step of 64 units with the
-//     precomputed digits of the step and a precomputed offset correction per wrap of a level: additions and compares only.
+//   * device: a lane keeps two cursors of wave_items.h (destination: three digits; source: up to twelve) over the same flat
+//     units, and an item carries the start of both.
 //     Four steps are taken at a time, their loads issued before the first store.
 //     The source levels are right-aligned; the unused ones are skipped by wave-uniform branches.
 //   * item and record are wave-uniform: their fields travel through scalar loads.
-#include "common.h"
-
-#include <algorithm>
+#include "wave_items.h"
 
 namespace {
 
-#define GLOBAL_AS __attribute__((address_space(1)))
-
-constexpr int NT = 256, WAVE = 64, ITEMS_PER_GROUP = NT / WAVE;
-constexpr int ND = 3, NS = 2 * CYB_TREE_PLACE_MAX_LEVELS;                  // destination levels (r, q, w); source levels at most
-constexpr int64_t kMinChunk = 1024, kMaxChunk = 16384, kTargetItems = 8192; // flat units per work item (multiples of WAVE)
+using namespace cyb_items;
+constexpr int ND = 3, NS = 2 * CYB_TREE_PLACE_MAX_LEVELS; // destination levels (r, q, w); source levels at most
 constexpr int64_t kMaxExtent = (int64_t)1 << 30;
 constexpr int kUnroll = 4; // steps of a lane whose loads are in flight together
-typedef double d2 __attribute__((ext_vector_type(2)));
 typedef cyb_tree_place_rec In;
 
-// what a lane holds per step: one double, two adjacent doubles, or one complex number
-enum { kF64 = 0, kF64x2 = 1, kC128 = 2 };
-
 // one window as the kernel reads it; offsets and strides in doubles (kC128: complex elements of the destination, elements of
-// the source's own type).  Source levels s_first .. NS - 1, the innermost last.
+// the source's own type).  Source levels s.first .. NS - 1, the innermost last.
 struct Rec {
     double* dst;
     const double* src; // NULL: zeros
     double cre, cim;
-    int64_t step_d, step_s; // increment of the offsets per step of WAVE units, before corrections
-    int64_t dsd[ND], dwd[ND]; // stride of a level; correction when it wraps: sd[l - 1] - ext[l] * sd[l]
-    int64_t ssd[NS], swd[NS];
+    Levels<ND, 1> d; // (kF64x2: the last extent counts pairs)
+    Levels<NS, 1> s;
     int64_t pair_cs; // kF64x2: distance of the two source elements of a pair
-    int32_t dext[ND], dstep[ND]; // extents (kF64x2: the last one counts pairs); digits of the step
-    int32_t sext[NS], sstep[NS];
-    int32_t s_first;
-    int32_t mode, src_real, unit, vec_load, reserved;
+    int32_t mode, src_real, unit, vec_load;
 };
 
 struct Item {
     int32_t rec;
     int32_t reserved;
-    int64_t count;  // flat units of this item
-    int64_t od, os; // offsets of its first unit
-    int32_t didx[ND];
-    int32_t sidx[NS];
+    int64_t count; // flat units of this item
+    Start<ND, 1> d; // its first unit
+    Start<NS, 1> s;
 };
 
-// idx += (digits dg, whose offset is dd) over the levels first .. L - 1; every digit below its extent, so a level wraps at
-// most once
-template <int L>
-__device__ inline void advance(int32_t (&idx)[L], int64_t& off, const int32_t (&ext)[L], const int64_t (&wd)[L], const int32_t (&dg)[L], int64_t dd,
-                               int first)
-{
-    off += dd;
-    int32_t carry = 0;
-#pragma unroll
-    for (int l = L - 1; l >= 0; --l) {
-        if (l >= first) { // wave-uniform
-            const int32_t i = idx[l] + dg[l] + carry;
-            const bool w = i >= ext[l];
-            idx[l] = w ? i - ext[l] : i;
-            off += w ? wd[l] : 0;
-            carry = w ? 1 : 0;
-        }
-    }
-}
-
-// lane offset into the item -> digits (below 64: 32-bit divisions, extents above it never divide) and their offset
-template <int L>
-__device__ inline int64_t decode(int32_t (&dg)[L], uint32_t d, const int32_t (&ext)[L], const int64_t (&sd)[L], int first)
-{
-    int64_t dd = 0;
-#pragma unroll
-    for (int l = L - 1; l >= 0; --l) {
-        dg[l] = 0;
-        if (l < first) continue;
-        const uint32_t e32 = ext[l] > WAVE ? (uint32_t)WAVE + 1 : (uint32_t)ext[l];
-        const uint32_t q = d / e32;
-        dg[l] = (int32_t)(d - q * e32);
-        d = q;
-        dd += dg[l] * sd[l];
-    }
-    return dd;
-}
-
-template <int MODE> struct Val { typedef d2 type; };
-template <> struct Val<kF64> { typedef double type; };
-
 // the value of one unit: c * source, the source's bits under c == 1 (else one product per component pair, no addend), or zeros
-template <int MODE> __device__ inline typename Val<MODE>::type load_one(const Rec& r, const GLOBAL_AS double* src, int64_t os, bool zero)
+template <int MODE> __device__ inline typename Val<MODE>::type load_one(const Rec& r, const double* src, int64_t os, bool zero)
 {
     if constexpr (MODE == kF64) {
         if (zero) return 0.0;
-        const double v = src[os];
+        const double v = load_f64(src, os);
         return r.unit ? v : r.cre * v;
     } else if constexpr (MODE == kF64x2) {
         if (zero) return d2{0.0, 0.0};
-        const d2 v = r.vec_load ? *(const GLOBAL_AS d2*)(src + os) : d2{src[os], src[os + r.pair_cs]};
+        const d2 v = r.vec_load ? load_x2(src, os) : d2{load_f64(src, os), load_f64(src, os + r.pair_cs)};
         return r.unit ? v : d2{r.cre * v.x, r.cre * v.y};
     } else {
         if (zero) return d2{0.0, 0.0};
         if (r.src_real) {
-            const double x = src[os];
+            const double x = load_f64(src, os);
             return r.unit ? d2{x, 0.0} : d2{r.cre * x, r.cim * x};
         }
-        const d2 x = *(const GLOBAL_AS d2*)(src + 2 * os);
+        const d2 x = load_c(src, os, false);
         return r.unit ? x : d2{r.cre * x.x - r.cim * x.y, r.cre * x.y + r.cim * x.x};
     }
 }
 
 template <int MODE> __device__ inline void run_item(const Rec& r, const Item& it, int lane)
 {
-    typedef typename Val<MODE>::type T;
-    int32_t di[ND], si[NS];
-#pragma unroll
-    for (int l = 0; l < ND; ++l) di[l] = it.didx[l];
-#pragma unroll
-    for (int l = 0; l < NS; ++l) si[l] = it.sidx[l];
-    int64_t od = it.od, os = it.os;
     const bool zero = r.src == nullptr; // wave-uniform, as every field of the record
-    const int s_first = zero ? NS : r.s_first;
-    {
-        int32_t dg[ND], sg[NS];
-        const int64_t dd = decode<ND>(dg, (uint32_t)lane, r.dext, r.dsd, 0);
-        advance<ND>(di, od, r.dext, r.dwd, dg, dd, 0);
-        const int64_t ds = decode<NS>(sg, (uint32_t)lane, r.sext, r.ssd, s_first);
-        advance<NS>(si, os, r.sext, r.swd, sg, ds, s_first);
-    }
-    GLOBAL_AS double* dst = (GLOBAL_AS double*)r.dst;
-    const GLOBAL_AS double* src = (const GLOBAL_AS double*)r.src;
+    const int s_first = zero ? NS : r.s.first;
+    Cursor<ND, 1> cd;
+    Cursor<NS, 1> cs;
+    start(cd, r.d, it.d, lane, 0);
+    start(cs, r.s, it.s, lane, s_first);
+    double* dst = r.dst;
+    const double* src = r.src;
     // kUnroll steps at a time: their loads are issued before the first store, so that a lane has several requests in flight
     // (destination and source may alias as far as the compiler knows; it would not move a load above a store)
     for (int64_t k = lane; k < it.count; k += kUnroll * WAVE) {
-        T v[kUnroll];
+        typename Val<MODE>::type v[kUnroll];
         int64_t at[kUnroll];
 #pragma unroll
         for (int u = 0; u < kUnroll; ++u) {
-            at[u] = od;
-            if (k + u * WAVE < it.count) v[u] = load_one<MODE>(r, src, os, zero);
-            advance<ND>(di, od, r.dext, r.dwd, r.dstep, r.step_d, 0);
-            advance<NS>(si, os, r.sext, r.swd, r.sstep, r.step_s, s_first);
+            at[u] = cd.off[0];
+            if (k + u * WAVE < it.count) v[u] = load_one<MODE>(r, src, cs.off[0], zero);
+            advance(cd, r.d, r.d.step, r.d.step_o, 0);
+            advance(cs, r.s, r.s.step, r.s.step_o, s_first);
         }
 #pragma unroll
-        for (int u = 0; u < kUnroll; ++u) {
-            if (k + u * WAVE < it.count) {
-                if constexpr (MODE == kF64)
-                    dst[at[u]] = v[u];
-                else if constexpr (MODE == kF64x2)
-                    *(GLOBAL_AS d2*)(dst + at[u]) = v[u];
-                else
-                    *(GLOBAL_AS d2*)(dst + 2 * at[u]) = v[u];
-            }
-        }
+        for (int u = 0; u < kUnroll; ++u)
+            if (k + u * WAVE < it.count) store_<MODE>(dst, at[u], v[u]);
     }
 }
 
 template <bool CPLX> __global__ void __launch_bounds__(NT) tree_place_kernel(const Rec* __restrict__ recs, const Item* __restrict__ items, int n_items)
 {
-    // one wave per item: the index is wave-uniform, and so is everything read through it
-    const int i = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * ITEMS_PER_GROUP + threadIdx.x / WAVE));
-    if (i >= n_items) return;
+    int i, lane;
+    if (!my_item(i, lane, n_items)) return;
     const Item& it = items[i];
     const Rec& r = recs[it.rec];
-    const int lane = threadIdx.x & (WAVE - 1);
     if constexpr (CPLX) {
         run_item<kC128>(r, it, lane);
     } else {
@@ -201,8 +125,6 @@ template <bool CPLX> __global__ void __launch_bounds__(NT) tree_place_kernel(con
             run_item<kF64>(r, it, lane);
     }
 }
-
-inline bool even_(int64_t v) { return (v & 1) == 0; }
 
 // the product of `n` extents if it equals `want`; extents are within [0, kMaxExtent]
 inline bool product_is(const int64_t* ext, int n, int64_t want)
@@ -217,25 +139,10 @@ inline bool product_is(const int64_t* ext, int n, int64_t want)
     return p == want;
 }
 
-// digits of the step of WAVE units over the levels first .. L - 1 and what it adds to the offset; what is left at the
-// outermost level stays there (a cursor is only read while inside the window)
-template <int L> void set_steps(const int32_t (&ext)[L], const int64_t (&sd)[L], int64_t (&wd)[L], int32_t (&step)[L], int64_t& step_off, int first)
-{
-    int64_t s = WAVE;
-    step_off = 0;
-    for (int l = L - 1; l >= first; --l) {
-        wd[l] = (l > first ? sd[l - 1] : 0) - ext[l] * sd[l];
-        step[l] = (int32_t)(l > first ? s % ext[l] : std::min<int64_t>(s, ext[l]));
-        s = l > first ? s / ext[l] : 0;
-        step_off += step[l] * sd[l];
-    }
-}
-
 // validates the list and turns it into the records and work items of the launch (both empty: nothing to do)
 template <bool CPLX> int plan_place(std::vector<Rec>& recs, std::vector<Item>& items, const In* in, int64_t n_recs, const char* who)
 {
     std::vector<int64_t> totals;
-    int64_t grand = 0;
     for (int64_t i = 0; i < n_recs; ++i) {
         const In& o = in[i];
         const long long ii = (long long)i;
@@ -292,48 +199,26 @@ template <bool CPLX> int plan_place(std::vector<Rec>& recs, std::vector<Item>& i
         r.unit = r.cre == 1.0 && r.cim == 0.0;
         r.src_real = CPLX && o.src_real != 0;
         r.mode = CPLX ? kC128 : (x2 ? kF64x2 : kF64);
-        r.dext[0] = (int32_t)o.h, r.dext[1] = (int32_t)o.nq, r.dext[2] = (int32_t)(o.wn / V);
-        r.dsd[0] = ldd, r.dsd[1] = cp, r.dsd[2] = V;
-        set_steps<ND>(r.dext, r.dsd, r.dwd, r.dstep, r.step_d, 0);
-        r.s_first = NS - n;
-        for (int l = 0; l < NS; ++l) r.sext[l] = 1;
-        for (int l = 0; l < n; ++l) r.sext[r.s_first + l] = (int32_t)le[l], r.ssd[r.s_first + l] = ls[l];
+        r.d.ext[0] = (int32_t)o.h, r.d.ext[1] = (int32_t)o.nq, r.d.ext[2] = (int32_t)(o.wn / V);
+        r.d.st[0][0] = ldd, r.d.st[0][1] = cp, r.d.st[0][2] = V;
+        set_steps(r.d, 0);
+        const int s_first = NS - n;
+        for (int l = 0; l < n; ++l) r.s.ext[s_first + l] = (int32_t)le[l], r.s.st[0][s_first + l] = ls[l];
         if (x2 && o.src) {
             r.pair_cs = ls[n - 1];
-            r.sext[NS - 1] = (int32_t)(le[n - 1] / 2), r.ssd[NS - 1] = 2 * ls[n - 1];
+            r.s.ext[NS - 1] = (int32_t)(le[n - 1] / 2), r.s.st[0][NS - 1] = 2 * ls[n - 1];
             r.vec_load = ls[n - 1] == 1 && ((uintptr_t)o.src & 15) == 0;
             for (int l = 0; l + 1 < n; ++l) r.vec_load = r.vec_load && even_(ls[l]);
         }
-        set_steps<NS>(r.sext, r.ssd, r.swd, r.sstep, r.step_s, r.s_first);
+        set_steps(r.s, s_first);
         recs.push_back(r);
         totals.push_back(o.h * o.nq * (o.wn / V));
-        grand += totals.back();
     }
-    // about kTargetItems waves for a large launch
-    int64_t chunk = (grand / kTargetItems + WAVE - 1) / WAVE * WAVE;
-    chunk = std::min(std::max(chunk, kMinChunk), kMaxChunk);
-    for (size_t i = 0; i < recs.size(); ++i) {
-        const Rec& r = recs[i];
-        for (int64_t e0 = 0; e0 < totals[i]; e0 += chunk) {
-            Item it;
-            memset(&it, 0, sizeof(it));
-            it.rec = (int32_t)i;
-            it.count = std::min(chunk, totals[i] - e0);
-            int64_t e = e0;
-            for (int l = ND - 1; l >= 0; --l) {
-                it.didx[l] = (int32_t)(e % r.dext[l]);
-                e /= r.dext[l];
-                it.od += it.didx[l] * r.dsd[l];
-            }
-            e = e0;
-            for (int l = NS - 1; l >= r.s_first; --l) {
-                it.sidx[l] = (int32_t)(e % r.sext[l]);
-                e /= r.sext[l];
-                it.os += it.sidx[l] * r.ssd[l];
-            }
-            items.push_back(it);
-        }
-    }
+    // both cursors of an item start at the same flat unit
+    const int64_t chunk = chunk_for(totals);
+    for (size_t i = 0; i < recs.size(); ++i)
+        for (int64_t e0 = 0; e0 < totals[i]; e0 += chunk)
+            items.push_back(Item{(int32_t)i, 0, std::min(chunk, totals[i] - e0), start_at(recs[i].d, e0), start_at(recs[i].s, e0)});
     CYB_REQUIRE(items.size() < ((size_t)1 << 31), "%s: too many work items", who);
     return CYB_OK;
 }
