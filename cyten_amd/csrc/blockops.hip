@@ -7,42 +7,17 @@
 // linear_combination :1358-1365, eye_matrix :1197-1207, zeros :1322-1335) -- one launch per block
 // LIST instead of one numpy call per block.  All are bandwidth-class work: 16-B accesses where
 // the layout allows, grid-stride loops, deterministic two-stage reductions (no float atomics).
+// Work items, their cutter, the launch tail and the fixed order of the reductions: flat_items.h.
 #include "common.h"
 #include "copy_kernels.h"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace {
 
-using namespace cyb_copy; // GLOBAL_AS, NT, chunk_for, Item, the copy descriptors and device bodies
-
-template <typename D>
-static int make_items(const D* descs, int64_t n, std::vector<Item>& items, int64_t (*count_of)(const D&))
-{
-    int64_t total = 0;
-    for (int64_t i = 0; i < n; ++i) total += count_of(descs[i]);
-    const int64_t chunk = chunk_for(total);
-    for (int64_t i = 0; i < n; ++i) {
-        const int64_t tot = count_of(descs[i]);
-        for (int64_t s = 0; s < tot; s += chunk) items.push_back(Item{(int32_t)i, 0, s, std::min(chunk, tot - s)});
-    }
-    return CYB_OK;
-}
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-// max that keeps a NaN of either side (fmax would return the other operand): np.max(np.abs(x)) is NaN when x holds one
-__device__ __forceinline__ double nan_max(double a, double b) { return (a > b || a != a) ? a : b; }
-__device__ __forceinline__ double wave_max(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = nan_max(v, __shfl_xor(v, o));
-    return v;
-}
+using namespace cyb_copy; // the copy descriptors and device bodies
+using namespace cyb_flat; // Item, NT, the chunk rules, cut, launch, the fixed-order reduction
 
 // ---------------------------------------------------------------------------------------------
 // strided copy (device bodies: copy_kernels.h)
@@ -88,18 +63,17 @@ struct CExpandDev {
 
 __global__ void __launch_bounds__(NT) complex_expand_kernel(const CExpandDev* __restrict__ descs, const Item* __restrict__ items)
 {
-    typedef double d2v __attribute__((ext_vector_type(2)));
     const Item it = items[blockIdx.x];
     const CExpandDev d = descs[it.desc];
-    const GLOBAL_AS d2v* src = (const GLOBAL_AS d2v*)d.src;
+    const GLOBAL_AS d2* src = (const GLOBAL_AS d2*)d.src;
     gp dst = (gp)d.dst;
     for (int64_t e = it.start + threadIdx.x; e < it.start + it.count; e += NT) {
         const int64_t k = e / d.N, n = e - k * d.N;
-        const d2v b = src[k * d.rs + n * d.cs];
-        GLOBAL_AS d2v* r0 = (GLOBAL_AS d2v*)(dst + (2 * k) * (2 * d.N) + 2 * n);
-        GLOBAL_AS d2v* r1 = (GLOBAL_AS d2v*)(dst + (2 * k + 1) * (2 * d.N) + 2 * n);
-        *r0 = d2v{b.x, b.y};
-        *r1 = d2v{-b.y, b.x};
+        const d2 b = src[k * d.rs + n * d.cs];
+        GLOBAL_AS d2* r0 = (GLOBAL_AS d2*)(dst + (2 * k) * (2 * d.N) + 2 * n);
+        GLOBAL_AS d2* r1 = (GLOBAL_AS d2*)(dst + (2 * k + 1) * (2 * d.N) + 2 * n);
+        *r0 = d2{b.x, b.y};
+        *r1 = d2{-b.y, b.x};
     }
 }
 
@@ -112,110 +86,76 @@ struct VecDev {
     int64_t n;
 };
 
-// mode 0: sum x*y (y null: x*x) ; mode 1: max |x|, NaN if any element is NaN
-__device__ __forceinline__ void reduce_stage1_body(const VecDev& d, const Item& it, double* __restrict__ partial, int mode)
+// partial[item] of Op = Sum: sum x*y (y null: x*x) ; Op = NanMax: max |x|, NaN if any element is NaN
+template <class Op> __device__ __forceinline__ void reduce_stage1_body(const VecDev& d, const Item& it, double* __restrict__ partial)
 {
-    __shared__ double red[NT / 64];
+    __shared__ double red[1][WAVES];
     gcp x = (gcp)d.x;
     gcp y = (gcp)d.y;
     double acc = 0.0;
     const int64_t e1 = it.start + it.count;
     // 16-byte accesses when the operands allow (chunk starts are even): half the memory instructions per byte
-    typedef double d2v __attribute__((ext_vector_type(2)));
     const bool al = ((((uintptr_t)(x + it.start)) | (d.y ? (uintptr_t)(y + it.start) : 0)) & 15) == 0;
     const int64_t nv = al ? it.count / 2 : 0;
-    const GLOBAL_AS d2v* xv = (const GLOBAL_AS d2v*)(x + it.start);
-    const GLOBAL_AS d2v* yv = (const GLOBAL_AS d2v*)(y + it.start);
-    if (mode == 0) {
+    const GLOBAL_AS d2* xv = (const GLOBAL_AS d2*)(x + it.start);
+    const GLOBAL_AS d2* yv = (const GLOBAL_AS d2*)(y + it.start);
+    if constexpr (std::is_same<Op, Sum>::value) {
         double acc2 = 0.0;
         if (d.y) {
             for (int64_t i = threadIdx.x; i < nv; i += NT) {
-                const d2v a = xv[i], b = yv[i];
+                const d2 a = xv[i], b = yv[i];
                 acc += a.x * b.x;
                 acc2 += a.y * b.y;
             }
             for (int64_t e = it.start + 2 * nv + threadIdx.x; e < e1; e += NT) acc += x[e] * y[e];
         } else {
             for (int64_t i = threadIdx.x; i < nv; i += NT) {
-                const d2v a = xv[i];
+                const d2 a = xv[i];
                 acc += a.x * a.x;
                 acc2 += a.y * a.y;
             }
             for (int64_t e = it.start + 2 * nv + threadIdx.x; e < e1; e += NT) acc += x[e] * x[e];
         }
-        acc = wave_sum(acc + acc2);
+        acc += acc2;
     } else {
         for (int64_t i = threadIdx.x; i < nv; i += NT) {
-            const d2v a = xv[i];
-            acc = nan_max(acc, nan_max(fabs(a.x), fabs(a.y)));
+            const d2 a = xv[i];
+            acc = Op::op(acc, Op::op(fabs(a.x), fabs(a.y)));
         }
-        for (int64_t e = it.start + 2 * nv + threadIdx.x; e < e1; e += NT) acc = nan_max(acc, fabs(x[e]));
-        acc = wave_max(acc);
+        for (int64_t e = it.start + 2 * nv + threadIdx.x; e < e1; e += NT) acc = Op::op(acc, fabs(x[e]));
     }
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double r = red[0];
-        for (int q = 1; q < NT / 64; ++q) r = (mode == 0) ? r + red[q] : nan_max(r, red[q]);
-        partial[blockIdx.x] = r;
-    }
+    double r[1] = {acc};
+    block_reduce<1, Op>(r, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = r[0];
 }
-__global__ void __launch_bounds__(NT) reduce_stage1_kernel(const VecDev* __restrict__ descs, const Item* __restrict__ items,
-                                                           double* __restrict__ partial, int mode)
+template <class Op>
+__global__ void __launch_bounds__(NT) reduce_stage1_kernel(const VecDev* __restrict__ descs, const Item* __restrict__ items, double* __restrict__ partial)
 {
     const Item it = items[blockIdx.x];
     const VecDev d = descs[it.desc];
-    reduce_stage1_body(d, it, partial, mode);
+    reduce_stage1_body<Op>(d, it, partial);
 }
 // ONE vector: descriptor and chunking travel as kernel arguments -- no descriptor upload (a host call and a copy kernel per
 // launch: most BLAS-1 calls of a Krylov iteration on flat pools are of this kind)
-__global__ void __launch_bounds__(NT) reduce_stage1_one_kernel(VecDev d, int64_t chunk, double* __restrict__ partial, int mode)
+template <class Op> __global__ void __launch_bounds__(NT) reduce_stage1_one_kernel(VecDev d, int64_t chunk, double* __restrict__ partial)
 {
-    const int64_t start = (int64_t)blockIdx.x * chunk;
-    const Item it{0, 0, start, min(chunk, d.n - start)};
-    reduce_stage1_body(d, it, partial, mode);
-}
-
-// result[g] = reduce over partial[seg[g] .. seg[g+1])  (one workgroup per group, fixed order)
-__device__ __forceinline__ void reduce_stage2_body(const double* __restrict__ partial, int64_t s0, int64_t s1, double* __restrict__ result, int mode)
-{
-    __shared__ double red[NT / 64];
-    double acc = 0.0;
-    for (int64_t e = s0 + threadIdx.x; e < s1; e += NT) acc = (mode == 0) ? acc + partial[e] : nan_max(acc, partial[e]);
-    acc = (mode == 0) ? wave_sum(acc) : wave_max(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double r = red[0];
-        for (int q = 1; q < NT / 64; ++q) r = (mode == 0) ? r + red[q] : nan_max(r, red[q]);
-        result[blockIdx.x] = r;
-    }
-}
-__global__ void __launch_bounds__(NT) reduce_stage2_kernel(const double* __restrict__ partial, const int64_t* __restrict__ seg,
-                                                           double* __restrict__ result, int mode)
-{
-    reduce_stage2_body(partial, seg[blockIdx.x], seg[blockIdx.x + 1], result, mode);
-}
-__global__ void __launch_bounds__(NT) reduce_stage2_one_kernel(const double* __restrict__ partial, int64_t n_items, double* __restrict__ result, int mode)
-{
-    reduce_stage2_body(partial, 0, n_items, result, mode);
+    reduce_stage1_body<Op>(d, nth_item(chunk, d.n), partial);
 }
 
 // out = a*x + b*y on complex vectors (a, b complex scalars; y may be null)
 __global__ void __launch_bounds__(NT) axpby_c128_kernel(const VecDev* __restrict__ descs, const Item* __restrict__ items,
                                                         double ar, double ai, double br, double bi)
 {
-    typedef double d2v __attribute__((ext_vector_type(2)));
     const Item it = items[blockIdx.x];
     const VecDev d = descs[it.desc];
-    const GLOBAL_AS d2v* x = (const GLOBAL_AS d2v*)d.x;
-    const GLOBAL_AS d2v* y = (const GLOBAL_AS d2v*)d.y;
-    GLOBAL_AS d2v* out = (GLOBAL_AS d2v*)d.out;
+    const GLOBAL_AS d2* x = (const GLOBAL_AS d2*)d.x;
+    const GLOBAL_AS d2* y = (const GLOBAL_AS d2*)d.y;
+    GLOBAL_AS d2* out = (GLOBAL_AS d2*)d.out;
     for (int64_t e = it.start + threadIdx.x; e < it.start + it.count; e += NT) {
-        const d2v xv = x[e];
-        d2v r = d2v{ar * xv.x - ai * xv.y, ar * xv.y + ai * xv.x};
+        const d2 xv = x[e];
+        d2 r = d2{ar * xv.x - ai * xv.y, ar * xv.y + ai * xv.x};
         if (d.y) {
-            const d2v yv = y[e];
+            const d2 yv = y[e];
             r.x += br * yv.x - bi * yv.y;
             r.y += br * yv.y + bi * yv.x;
         }
@@ -226,7 +166,7 @@ __global__ void __launch_bounds__(NT) axpby_c128_kernel(const VecDev* __restrict
 // complex elementwise: op 0 |z| (real out), 1 sqrt, 2 exp, 3 log, 4 angle (real out), 5 z*w, 6 z/w (Smith).
 // Non-finite arguments, signed zeros and arguments near the ends of the double range follow numpy (C99 Annex G):
 // tests/special_value_cases.py holds the grid.
-typedef double cd2 __attribute__((ext_vector_type(2)));
+typedef d2 cd2;
 #define CYB_DBL_MAX 1.7976931348623157e308
 
 // a product rounded on its own: the empty asm keeps -ffp-contract=fast from fusing it into the add that follows
@@ -392,15 +332,14 @@ __device__ __forceinline__ cd2 cdiv_c128(cd2 z, cd2 w)
 
 __global__ void __launch_bounds__(NT) celementwise_kernel(const VecDev* __restrict__ descs, const Item* __restrict__ items, int op)
 {
-    typedef cd2 d2v;
     const Item it = items[blockIdx.x];
     const VecDev d = descs[it.desc];
-    const GLOBAL_AS d2v* x = (const GLOBAL_AS d2v*)d.x;
-    const GLOBAL_AS d2v* y = (const GLOBAL_AS d2v*)d.y;
-    GLOBAL_AS d2v* outc = (GLOBAL_AS d2v*)d.out;
+    const GLOBAL_AS d2* x = (const GLOBAL_AS d2*)d.x;
+    const GLOBAL_AS d2* y = (const GLOBAL_AS d2*)d.y;
+    GLOBAL_AS d2* outc = (GLOBAL_AS d2*)d.out;
     gp outr = (gp)d.out;
     for (int64_t e = it.start + threadIdx.x; e < it.start + it.count; e += NT) {
-        const d2v z = x[e];
+        const d2 z = x[e];
         if (op == 0) {
             outr[e] = hypot(z.x, z.y);
             continue;
@@ -409,7 +348,7 @@ __global__ void __launch_bounds__(NT) celementwise_kernel(const VecDev* __restri
             outr[e] = atan2(z.y, z.x);
             continue;
         }
-        d2v r;
+        d2 r;
         switch (op) {
         case 1: r = csqrt_c128(z); break;
         case 2: r = cexp_c128(z); break;
@@ -417,8 +356,8 @@ __global__ void __launch_bounds__(NT) celementwise_kernel(const VecDev* __restri
         case 5: {
             // numpy's vectorised loop (fmaddsub): the products with z.y are rounded, those with z.x fused into the sum --
             // which part overflows to Inf and which to NaN depends on it, so the contraction is spelled out
-            const d2v w = y[e];
-            r = d2v{fma(z.x, w.x, -mul_rn(z.y, w.y)), fma(z.x, w.y, mul_rn(z.y, w.x))};
+            const d2 w = y[e];
+            r = d2{fma(z.x, w.x, -mul_rn(z.y, w.y)), fma(z.x, w.y, mul_rn(z.y, w.x))};
             break;
         }
         default: r = cdiv_c128(z, y[e]); break;
@@ -468,22 +407,21 @@ __device__ __forceinline__ void elementwise_body(const VecDev& d, const Item& it
     gp out = (gp)d.out;
     const int64_t e1 = it.start + it.count;
     if (kind == 0) { // a*x + b*y (the Krylov axpy / scale): 16-byte accesses when the three operands allow
-        typedef double d2v __attribute__((ext_vector_type(2)));
         const bool al = ((((uintptr_t)(x + it.start)) | ((uintptr_t)(out + it.start)) | (d.y ? (uintptr_t)(y + it.start) : 0)) & 15) == 0;
         const int64_t nv = al ? it.count / 2 : 0;
-        const GLOBAL_AS d2v* xv2 = (const GLOBAL_AS d2v*)(x + it.start);
-        const GLOBAL_AS d2v* yv2 = (const GLOBAL_AS d2v*)(y + it.start);
-        GLOBAL_AS d2v* ov2 = (GLOBAL_AS d2v*)(out + it.start);
+        const GLOBAL_AS d2* xv2 = (const GLOBAL_AS d2*)(x + it.start);
+        const GLOBAL_AS d2* yv2 = (const GLOBAL_AS d2*)(y + it.start);
+        GLOBAL_AS d2* ov2 = (GLOBAL_AS d2*)(out + it.start);
         if (d.y) {
             for (int64_t i = threadIdx.x; i < nv; i += NT) {
-                const d2v xa = xv2[i], ya = yv2[i];
-                ov2[i] = d2v{a * xa.x + b * ya.x, a * xa.y + b * ya.y};
+                const d2 xa = xv2[i], ya = yv2[i];
+                ov2[i] = d2{a * xa.x + b * ya.x, a * xa.y + b * ya.y};
             }
             for (int64_t e = it.start + 2 * nv + threadIdx.x; e < e1; e += NT) out[e] = a * x[e] + b * y[e];
         } else {
             for (int64_t i = threadIdx.x; i < nv; i += NT) {
-                const d2v xa = xv2[i];
-                ov2[i] = d2v{a * xa.x, a * xa.y};
+                const d2 xa = xv2[i];
+                ov2[i] = d2{a * xa.x, a * xa.y};
             }
             for (int64_t e = it.start + 2 * nv + threadIdx.x; e < e1; e += NT) out[e] = a * x[e];
         }
@@ -529,9 +467,7 @@ __global__ void __launch_bounds__(NT) elementwise_kernel(const VecDev* __restric
 }
 __global__ void __launch_bounds__(NT) elementwise_one_kernel(VecDev d, int64_t chunk, int kind, int op, double a, double b)
 {   // (ONE vector: see reduce_stage1_one_kernel)
-    const int64_t start = (int64_t)blockIdx.x * chunk;
-    const Item it{0, 0, start, min(chunk, d.n - start)};
-    elementwise_body(d, it, kind, op, a, b);
+    elementwise_body(d, nth_item(chunk, d.n), kind, op, a, b);
 }
 
 struct ScaleDev {
@@ -550,19 +486,18 @@ __global__ void __launch_bounds__(NT) scale_axis_kernel(const ScaleDev* __restri
     const int64_t e1 = it.start + it.count;
     // pairs of elements per thread (16-byte accesses) when both buffers are 16-byte aligned; the factor index of
     // the second element of a pair is derived from the first one's without a second division
-    typedef double d2v __attribute__((ext_vector_type(2)));
     const bool al = ((((uintptr_t)(x + it.start)) | ((uintptr_t)(out + it.start))) & 15) == 0;
     const int64_t nv = al ? it.count / 2 : 0;
-    const GLOBAL_AS d2v* xv = (const GLOBAL_AS d2v*)(x + it.start);
-    GLOBAL_AS d2v* ov = (GLOBAL_AS d2v*)(out + it.start);
+    const GLOBAL_AS d2* xv = (const GLOBAL_AS d2*)(x + it.start);
+    GLOBAL_AS d2* ov = (GLOBAL_AS d2*)(out + it.start);
     for (int64_t i = threadIdx.x; i < nv; i += NT) {
         const int64_t e = it.start + 2 * i;
         const int64_t t = e / d.inner, in = e - t * d.inner;
         const int64_t j0 = t % d.axis;
         int64_t j1 = j0;
         if (in + 1 == d.inner) j1 = (j0 + 1 == d.axis) ? 0 : j0 + 1;
-        const d2v v = xv[i];
-        ov[i] = d2v{v.x * f[j0], v.y * f[j1]};
+        const d2 v = xv[i];
+        ov[i] = d2{v.x * f[j0], v.y * f[j1]};
     }
     for (int64_t e = it.start + 2 * nv + threadIdx.x; e < e1; e += NT) {
         const int64_t j = (e / d.inner) % d.axis;
@@ -616,13 +551,12 @@ __global__ void __launch_bounds__(NT) mask_kernel(const MaskDev* __restrict__ de
     }
     if ((d.inner & 1) == 0 && ((((uintptr_t)x) | ((uintptr_t)out)) & 15) == 0) {
         // even inner extent: a pair of neighbours never straddles a kept slice, 16-byte accesses on both sides
-        typedef double d2v __attribute__((ext_vector_type(2)));
         for (int64_t e = it.start + 2 * threadIdx.x; e < e1; e += 2 * NT) {
             const int64_t t = e / d.inner, in = e - t * d.inner;
             const int64_t j = t % d.n_keep, o = t / d.n_keep;
             const int64_t big = (o * d.axis + idx[j]) * d.inner + in;
-            if (scatter) *(GLOBAL_AS d2v*)(out + big) = *(const GLOBAL_AS d2v*)(x + e);
-            else *(GLOBAL_AS d2v*)(out + e) = *(const GLOBAL_AS d2v*)(x + big);
+            if (scatter) *(GLOBAL_AS d2*)(out + big) = *(const GLOBAL_AS d2*)(x + e);
+            else *(GLOBAL_AS d2*)(out + e) = *(const GLOBAL_AS d2*)(x + big);
         }
         return;
     }
@@ -746,7 +680,6 @@ __global__ void __launch_bounds__(NT) count_nonzero_kernel(const uint8_t* __rest
 __global__ void __launch_bounds__(NT) allclose_count_kernel(const double* __restrict__ x_, const double* __restrict__ y_, int64_t n, int cplx,
                                                             double rtol, double atol, unsigned long long* __restrict__ result)
 {
-    typedef double d2v __attribute__((ext_vector_type(2)));
     gcp x = (gcp)x_;
     gcp y = (gcp)y_;
     const double big = 1.7976931348623157e308;
@@ -754,7 +687,7 @@ __global__ void __launch_bounds__(NT) allclose_count_kernel(const double* __rest
     for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n; e += (int64_t)gridDim.x * NT) {
         bool ok;
         if (cplx) {
-            const d2v a = ((const GLOBAL_AS d2v*)x)[e], b = ((const GLOBAL_AS d2v*)y)[e];
+            const d2 a = ((const GLOBAL_AS d2*)x)[e], b = ((const GLOBAL_AS d2*)y)[e];
             const bool fin = fabs(a.x) <= big && fabs(a.y) <= big && fabs(b.x) <= big && fabs(b.y) <= big;
             ok = (a.x == b.x && a.y == b.y) || (fin && hypot(a.x - b.x, a.y - b.y) <= atol + rtol * hypot(b.x, b.y));
         } else {
@@ -877,7 +810,6 @@ struct LinTermC {
 __global__ void __launch_bounds__(NT) lincomb_strided_c128_kernel(const LinDev* __restrict__ descs, const LinTermC* __restrict__ terms,
                                                                   const Item* __restrict__ items)
 {
-    typedef double d2 __attribute__((ext_vector_type(2)));
     const Item it = items[blockIdx.x];
     const LinDev d = descs[it.desc];
     GLOBAL_AS d2* dst = (GLOBAL_AS d2*)d.dst;
@@ -911,31 +843,26 @@ __global__ void __launch_bounds__(NT) lincomb_strided_c128_kernel(const LinDev* 
     }
 }
 
-static int64_t vec_count(const cyb_vec_desc& d) { return d.n; }
-static int64_t scale_count(const cyb_scale_axis_desc& d) { return d.outer * d.axis * d.inner; }
-static int64_t mask_count(const cyb_mask_desc& d) { return d.outer * d.n_keep * d.inner; }
-
-static int upload_vecs(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t n, bool need_y, bool need_out,
-                       std::vector<Item>& items, void** d_descs, void** d_items, bool defer = false, std::vector<VecDev>* keep = nullptr)
+// validates a vector list and cuts it: hv[i] the device form of descs[i], items over all of them
+static int vec_items(const char* who, const cyb_vec_desc* descs, int64_t n, bool need_y, bool need_out, std::vector<VecDev>& hv,
+                     std::vector<Item>& items)
 {
-    std::vector<VecDev> hv((size_t)n);
+    hv.resize((size_t)n);
+    std::vector<int64_t> totals((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
         CYB_REQUIRE(descs[i].n >= 0, "vector desc %lld: negative length", (long long)i);
         CYB_REQUIRE(descs[i].n == 0 || descs[i].x, "vector desc %lld: x is NULL", (long long)i);
         CYB_REQUIRE(!need_y || descs[i].n == 0 || descs[i].y, "vector desc %lld: y is NULL", (long long)i);
         CYB_REQUIRE(!need_out || descs[i].n == 0 || descs[i].out, "vector desc %lld: out is NULL", (long long)i);
         hv[(size_t)i] = VecDev{descs[i].x, descs[i].y, descs[i].out, descs[i].n};
+        totals[(size_t)i] = descs[i].n;
     }
-    make_items<cyb_vec_desc>(descs, n, items, vec_count);
-    if (defer) { // (the caller packs further arrays into the same upload)
-        keep->swap(hv);
-        return CYB_OK;
-    }
-    return cyb::upload_packed(ctx, {{hv.data(), sizeof(VecDev) * hv.size(), d_descs}, {items.data(), sizeof(Item) * items.size(), d_items}});
+    CYB_CUT(who, items, totals, chunk_real(sum_of(totals)));
+    return CYB_OK;
 }
 
 // shared body of the three reductions. per_entry: one result per list entry, else one total
-static int reduce_common(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t n, double* result_dev, int mode, bool per_entry)
+template <class Op> static int reduce_common(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t n, double* result_dev, bool per_entry)
 {
     CYB_REQUIRE(ctx && result_dev, "reduction: NULL argument");
     CYB_REQUIRE(n >= 0 && (n == 0 || descs), "reduction: bad descriptor list");
@@ -944,18 +871,15 @@ static int reduce_common(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t n, do
     if (n == 1 && descs[0].n > 0) { // ONE vector: no descriptor upload
         CYB_REQUIRE(descs[0].x, "vector desc 0: x is NULL");
         const VecDev d{descs[0].x, descs[0].y, nullptr, descs[0].n};
-        const int64_t chunk = chunk_for(d.n), n_items = cdiv64(d.n, chunk);
-        void* ws1 = nullptr;
-        CYB_TRY(ctx->workspace(sizeof(double) * (size_t)n_items, &ws1));
-        hipLaunchKernelGGL(reduce_stage1_one_kernel, dim3((unsigned)n_items), dim3(NT), 0, ctx->stream, d, chunk, static_cast<double*>(ws1), mode);
-        hipLaunchKernelGGL(reduce_stage2_one_kernel, dim3(1), dim3(NT), 0, ctx->stream, static_cast<const double*>(ws1), n_items, result_dev, mode);
-        CYB_HIP(hipGetLastError());
-        return CYB_OK;
+        const int64_t chunk = chunk_real(d.n), n_items = cdiv64(d.n, chunk);
+        return two_stage<1, Op>(ctx, (size_t)n_items, nullptr, 1, result_dev, [&](double* partial) {
+            hipLaunchKernelGGL(reduce_stage1_one_kernel<Op>, dim3((unsigned)n_items), dim3(NT), 0, ctx->stream, d, chunk, partial);
+            return CYB_OK;
+        });
     }
-    std::vector<Item> items;
-    void *d_descs = nullptr, *d_items = nullptr;
     std::vector<VecDev> hv;
-    CYB_TRY(upload_vecs(ctx, descs, n, false, false, items, &d_descs, &d_items, true, &hv));
+    std::vector<Item> items;
+    CYB_TRY(vec_items("reduction", descs, n, false, false, hv, items));
     // segment table for stage 2
     std::vector<int64_t> seg((size_t)n_groups + 1, 0);
     if (per_entry) {
@@ -968,19 +892,14 @@ static int reduce_common(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t n, do
     } else {
         seg[1] = (int64_t)items.size();
     }
-    void* d_seg = nullptr;
-    CYB_TRY(cyb::upload_packed(ctx, {{hv.data(), sizeof(VecDev) * hv.size(), &d_descs},
-                                {items.data(), sizeof(Item) * items.size(), &d_items},
-                                {seg.data(), sizeof(int64_t) * seg.size(), &d_seg}}));
-    void* ws = nullptr;
-    CYB_TRY(ctx->workspace(sizeof(double) * std::max<size_t>(items.size(), 1), &ws));
-    if (!items.empty())
-        hipLaunchKernelGGL(reduce_stage1_kernel, dim3((unsigned)items.size()), dim3(NT), 0, ctx->stream,
-                           static_cast<const VecDev*>(d_descs), static_cast<const Item*>(d_items), static_cast<double*>(ws), mode);
-    hipLaunchKernelGGL(reduce_stage2_kernel, dim3((unsigned)n_groups), dim3(NT), 0, ctx->stream, static_cast<const double*>(ws),
-                       static_cast<const int64_t*>(d_seg), result_dev, mode);
-    CYB_HIP(hipGetLastError());
-    return CYB_OK;
+    // (the segment table travels with the descriptors; an all-empty list still writes its zero results)
+    return with_arrays(ctx, "reduction", items.size(), arrays(hv, items, seg),
+                       [&](dim3 grid, const VecDev* d_descs, const Item* d_items, const int64_t* d_seg) {
+                           return two_stage<1, Op>(ctx, items.size(), d_seg, n_groups, result_dev, [&](double* partial) {
+                               hipLaunchKernelGGL(reduce_stage1_kernel<Op>, grid, dim3(NT), 0, ctx->stream, d_descs, d_items, partial);
+                               return CYB_OK;
+                           });
+                       });
 }
 
 static int elementwise_common(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t n, int kind, int op, double a, double b,
@@ -992,19 +911,15 @@ static int elementwise_common(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t 
     if (n == 1 && descs[0].n > 0) { // ONE vector: no descriptor upload
         CYB_REQUIRE(descs[0].x && descs[0].out && (!need_y || descs[0].y), "vector desc 0: NULL operand");
         const VecDev d{descs[0].x, descs[0].y, descs[0].out, descs[0].n};
-        const int64_t chunk = chunk_for(d.n);
+        const int64_t chunk = chunk_real(d.n);
         hipLaunchKernelGGL(elementwise_one_kernel, dim3((unsigned)cdiv64(d.n, chunk)), dim3(NT), 0, ctx->stream, d, chunk, kind, op, a, b);
         CYB_HIP(hipGetLastError());
         return CYB_OK;
     }
+    std::vector<VecDev> hv;
     std::vector<Item> items;
-    void *d_descs = nullptr, *d_items = nullptr;
-    CYB_TRY(upload_vecs(ctx, descs, n, need_y, true, items, &d_descs, &d_items));
-    if (items.empty()) return CYB_OK;
-    hipLaunchKernelGGL(elementwise_kernel, dim3((unsigned)items.size()), dim3(NT), 0, ctx->stream,
-                       static_cast<const VecDev*>(d_descs), static_cast<const Item*>(d_items), kind, op, a, b);
-    CYB_HIP(hipGetLastError());
-    return CYB_OK;
+    CYB_TRY(vec_items("elementwise", descs, n, need_y, true, hv, items));
+    return launch(ctx, "elementwise", elementwise_kernel, arrays(hv, items), kind, op, a, b);
 }
 
 } // namespace
@@ -1018,12 +933,11 @@ int cyb_copy_strided_batched(cyb_ctx_t ctx, const cyb_copy_desc* descs, int64_t 
     CYB_REQUIRE(elem_size == 1 || elem_size == 4 || elem_size == 8 || elem_size == 16,
                 "cyb_copy_strided_batched: unsupported elem_size %d", elem_size);
     if (n == 0) return CYB_OK;
+    const char* who = "cyb_copy_strided_batched";
     std::vector<CopyDev> hd((size_t)n);
-    std::vector<Item> items;
-    std::vector<CopyT> ht;    // descriptors that take the tiled transposing path
-    std::vector<Item> titems; // their work items (ranges of tiles)
-    std::vector<int64_t> pending; // descriptors that take the strided path
-    int64_t pending_total = 0;
+    std::vector<CopyT> ht;                         // descriptors that take the tiled transposing path
+    std::vector<int64_t> totals((size_t)n, 0), tiles; // elements of a descriptor on the strided path, tiles of one on the tiled path
+    const int64_t tsz = elem_size == 8 ? 64 : 32;  // (conj needs elem_size 16)
     for (int64_t i = 0; i < n; ++i) {
         const cyb_copy_desc& d = descs[i];
         CYB_REQUIRE(d.ndim >= 0 && d.ndim <= CYB_MAX_NDIM, "copy desc %lld: ndim %d out of range", (long long)i, d.ndim);
@@ -1034,71 +948,46 @@ int cyb_copy_strided_batched(cyb_ctx_t ctx, const cyb_copy_desc* descs, int64_t 
         c.conj = d.conj;
         // drop singleton axes and merge axes that are contiguous in BOTH operands
         CYB_REQUIRE(normalize_copy(d.shape, d.dst_strides, d.src_strides, d.ndim, c), "copy desc %lld: negative extent", (long long)i);
-        const int64_t tot = c.total;
-        CYB_REQUIRE(tot == 0 || (d.dst && d.src), "copy desc %lld: NULL pointer", (long long)i);
+        CYB_REQUIRE(c.total == 0 || (d.dst && d.src), "copy desc %lld: NULL pointer", (long long)i);
         static const bool no_tiled = getenv("CYB_COPY_NOTILED") != nullptr;
-        const int64_t tsz = (elem_size == 8 && !d.conj) ? 64 : 32;
         CopyT t;
         int64_t ntile = 0;
         if (!no_tiled && classify_transpose(c, tsz, t, ntile)) {
             t.dst = d.dst;
             t.src = d.src;
             t.conj = d.conj;
-            const int64_t kTilesPerItem = tiles_per_item(tsz);
-            for (int64_t s0 = 0; s0 < ntile; s0 += kTilesPerItem)
-                titems.push_back(Item{(int32_t)ht.size(), 0, s0, std::min(kTilesPerItem, ntile - s0)});
             ht.push_back(t);
+            tiles.push_back(ntile);
             continue;
         }
-        pending.push_back(i);
-        pending_total += tot;
+        totals[(size_t)i] = c.total;
     }
-    const int64_t chunk = chunk_for(pending_total);
-    for (int64_t i : pending) {
-        const int64_t tot = hd[(size_t)i].total;
-        for (int64_t s = 0; s < tot; s += chunk) items.push_back(Item{(int32_t)i, 0, s, std::min(chunk, tot - s)});
-    }
-    if (!titems.empty()) {
-        void *d_t = nullptr, *d_ti = nullptr;
-        CYB_TRY(cyb::upload_packed(ctx, {{ht.data(), sizeof(CopyT) * ht.size(), &d_t}, {titems.data(), sizeof(Item) * titems.size(), &d_ti}}));
-        const dim3 tgrid((unsigned)titems.size()), tblock(NT);
-        const CopyT* dt = static_cast<const CopyT*>(d_t);
-        const Item* dti = static_cast<const Item*>(d_ti);
-        switch (elem_size) {
-        case 1: hipLaunchKernelGGL(copy_transpose_kernel<uint8_t>, tgrid, tblock, 0, ctx->stream, dt, dti); break;
-        case 4: hipLaunchKernelGGL(copy_transpose_kernel<uint32_t>, tgrid, tblock, 0, ctx->stream, dt, dti); break;
-        case 8: hipLaunchKernelGGL(copy_transpose64_kernel, tgrid, tblock, 0, ctx->stream, dt, dti); break;
-        default: hipLaunchKernelGGL(copy_transpose_kernel<u128>, tgrid, tblock, 0, ctx->stream, dt, dti); break;
-        }
-        CYB_HIP(hipGetLastError());
-    }
-    if (items.empty()) return CYB_OK;
-    void *d_descs = nullptr, *d_items = nullptr;
-    CYB_TRY(cyb::upload_packed(ctx, {{hd.data(), sizeof(CopyDev) * hd.size(), &d_descs}, {items.data(), sizeof(Item) * items.size(), &d_items}}));
-    const dim3 grid((unsigned)items.size()), block(NT);
-    const CopyDev* dd = static_cast<const CopyDev*>(d_descs);
-    const Item* di = static_cast<const Item*>(d_items);
-    switch (elem_size) {
-    case 1: hipLaunchKernelGGL(copy_strided_kernel<uint8_t>, grid, block, 0, ctx->stream, dd, di); break;
-    case 4: hipLaunchKernelGGL(copy_strided_kernel<uint32_t>, grid, block, 0, ctx->stream, dd, di); break;
-    case 8: hipLaunchKernelGGL(copy_strided_kernel<uint64_t>, grid, block, 0, ctx->stream, dd, di); break;
-    default: hipLaunchKernelGGL(copy_strided_kernel<u128>, grid, block, 0, ctx->stream, dd, di); break;
-    }
-    CYB_HIP(hipGetLastError());
-    return CYB_OK;
+    std::vector<Item> items, titems;
+    CYB_CUT(who, titems, tiles, tiles_per_item(tsz));
+    CYB_CUT(who, items, totals, chunk_real(sum_of(totals)));
+    void (*const tkernel)(const CopyT*, const Item*) = elem_size == 1   ? copy_transpose_kernel<uint8_t>
+                                                       : elem_size == 4 ? copy_transpose_kernel<uint32_t>
+                                                       : elem_size == 8 ? copy_transpose64_kernel
+                                                                        : copy_transpose_kernel<u128>;
+    void (*const kernel)(const CopyDev*, const Item*) = elem_size == 1   ? copy_strided_kernel<uint8_t>
+                                                        : elem_size == 4 ? copy_strided_kernel<uint32_t>
+                                                        : elem_size == 8 ? copy_strided_kernel<uint64_t>
+                                                                         : copy_strided_kernel<u128>;
+    CYB_TRY(launch(ctx, who, tkernel, arrays(ht, titems)));
+    return launch(ctx, who, kernel, arrays(hd, items));
 }
 
 int cyb_dot_batched_f64(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t n, double* result_dev)
 {
-    return reduce_common(ctx, descs, n, result_dev, 0, false);
+    return reduce_common<Sum>(ctx, descs, n, result_dev, false);
 }
 int cyb_dot_each_f64(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t n, double* result_dev)
 {
-    return reduce_common(ctx, descs, n, result_dev, 0, true);
+    return reduce_common<Sum>(ctx, descs, n, result_dev, true);
 }
 int cyb_maxabs_batched_f64(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t n, double* result_dev)
 {
-    return reduce_common(ctx, descs, n, result_dev, 1, false);
+    return reduce_common<NanMax>(ctx, descs, n, result_dev, false);
 }
 int cyb_axpby_batched_f64(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t n, double a, double b)
 {
@@ -1204,7 +1093,7 @@ static int lincomb_common(cyb_ctx_t ctx, const cyb_lincomb_desc* descs, int64_t 
     if (n == 0) return CYB_OK;
     std::vector<LinDev> hd((size_t)n);
     std::vector<TermDev> ht((size_t)n_terms);
-    int64_t total = 0;
+    std::vector<int64_t> totals((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
         const cyb_lincomb_desc& d = descs[i];
         CYB_REQUIRE(d.ndim >= 0 && d.ndim <= CYB_MAX_NDIM, "lincomb desc %lld: ndim %d out of range", (long long)i, d.ndim);
@@ -1227,23 +1116,12 @@ static int lincomb_common(cyb_ctx_t ctx, const cyb_lincomb_desc* descs, int64_t 
         CYB_REQUIRE(tot == 0 || d.dst, "lincomb desc %lld: dst is NULL", (long long)i);
         for (int32_t t = d.term_begin; t < d.term_end; ++t)
             CYB_REQUIRE(tot == 0 || terms[t].src, "lincomb term %d: src is NULL", t);
-        total += tot;
+        totals[(size_t)i] = tot;
     }
     for (int64_t t = 0; t < n_terms; ++t) fill(ht[(size_t)t], terms[t]);
     std::vector<Item> items;
-    const int64_t chunk = chunk_for(total);
-    for (int64_t i = 0; i < n; ++i)
-        for (int64_t s0 = 0; s0 < hd[(size_t)i].total; s0 += chunk)
-            items.push_back(Item{(int32_t)i, 0, s0, std::min(chunk, hd[(size_t)i].total - s0)});
-    if (items.empty()) return CYB_OK;
-    void *d_descs = nullptr, *d_terms = nullptr, *d_items = nullptr;
-    CYB_TRY(cyb::upload_packed(ctx, {{hd.data(), sizeof(LinDev) * hd.size(), &d_descs},
-                                {ht.empty() ? (const void*)hd.data() : (const void*)ht.data(), ht.empty() ? 8 : sizeof(TermDev) * ht.size(), &d_terms},
-                                {items.data(), sizeof(Item) * items.size(), &d_items}}));
-    hipLaunchKernelGGL(kernel, dim3((unsigned)items.size()), dim3(NT), 0, ctx->stream,
-                       static_cast<const LinDev*>(d_descs), static_cast<const TermDev*>(d_terms), static_cast<const Item*>(d_items));
-    CYB_HIP(hipGetLastError());
-    return CYB_OK;
+    CYB_CUT("cyb_lincomb_strided_batched", items, totals, chunk_real(sum_of(totals)));
+    return launch(ctx, "cyb_lincomb_strided_batched", kernel, arrays(hd, ht, items));
 }
 
 } // extern "C++"
@@ -1283,21 +1161,17 @@ int cyb_scale_axis_batched_f64(cyb_ctx_t ctx, const cyb_scale_axis_desc* descs, 
     CYB_REQUIRE(n >= 0 && (n == 0 || descs), "cyb_scale_axis_batched_f64: bad descriptor list");
     if (n == 0) return CYB_OK;
     std::vector<ScaleDev> hd((size_t)n);
+    std::vector<int64_t> totals((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
         const auto& d = descs[i];
         CYB_REQUIRE(d.outer >= 0 && d.axis >= 0 && d.inner >= 0, "scale_axis desc %lld: negative extent", (long long)i);
         CYB_REQUIRE(d.outer * d.axis * d.inner == 0 || (d.x && d.f && d.out), "scale_axis desc %lld: NULL pointer", (long long)i);
         hd[(size_t)i] = ScaleDev{d.x, d.f, d.out, d.outer, d.axis, d.inner};
+        totals[(size_t)i] = d.outer * d.axis * d.inner;
     }
     std::vector<Item> items;
-    make_items<cyb_scale_axis_desc>(descs, n, items, scale_count);
-    if (items.empty()) return CYB_OK;
-    void *d_descs = nullptr, *d_items = nullptr;
-    CYB_TRY(cyb::upload_packed(ctx, {{hd.data(), sizeof(ScaleDev) * hd.size(), &d_descs}, {items.data(), sizeof(Item) * items.size(), &d_items}}));
-    hipLaunchKernelGGL(scale_axis_kernel, dim3((unsigned)items.size()), dim3(NT), 0, ctx->stream,
-                       static_cast<const ScaleDev*>(d_descs), static_cast<const Item*>(d_items));
-    CYB_HIP(hipGetLastError());
-    return CYB_OK;
+    CYB_CUT("cyb_scale_axis_batched_f64", items, totals, chunk_real(sum_of(totals)));
+    return launch(ctx, "cyb_scale_axis_batched_f64", scale_axis_kernel, arrays(hd, items));
 }
 
 static int mask_common(cyb_ctx_t ctx, const cyb_mask_desc* descs, int64_t n, int scatter)
@@ -1306,24 +1180,20 @@ static int mask_common(cyb_ctx_t ctx, const cyb_mask_desc* descs, int64_t n, int
     CYB_REQUIRE(n >= 0 && (n == 0 || descs), "mask op: bad descriptor list");
     if (n == 0) return CYB_OK;
     std::vector<MaskDev> hd((size_t)n);
+    std::vector<int64_t> totals((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
         const auto& d = descs[i];
         CYB_REQUIRE(d.outer >= 0 && d.axis >= 0 && d.inner >= 0 && d.n_keep >= 0 && d.n_keep <= d.axis,
                     "mask desc %lld: bad extents", (long long)i);
         CYB_REQUIRE(d.outer * d.n_keep * d.inner == 0 || (d.x && d.out && d.idx), "mask desc %lld: NULL pointer", (long long)i);
         hd[(size_t)i] = MaskDev{d.x, d.out, d.idx, d.outer, d.axis, d.inner, d.n_keep};
+        totals[(size_t)i] = d.outer * d.n_keep * d.inner;
         if (scatter && d.outer * d.axis * d.inner > 0)
             CYB_HIP(hipMemsetAsync(d.out, 0, sizeof(double) * (size_t)(d.outer * d.axis * d.inner), ctx->stream));
     }
     std::vector<Item> items;
-    make_items<cyb_mask_desc>(descs, n, items, mask_count);
-    if (items.empty()) return CYB_OK;
-    void *d_descs = nullptr, *d_items = nullptr;
-    CYB_TRY(cyb::upload_packed(ctx, {{hd.data(), sizeof(MaskDev) * hd.size(), &d_descs}, {items.data(), sizeof(Item) * items.size(), &d_items}}));
-    hipLaunchKernelGGL(mask_kernel, dim3((unsigned)items.size()), dim3(NT), 0, ctx->stream,
-                       static_cast<const MaskDev*>(d_descs), static_cast<const Item*>(d_items), scatter);
-    CYB_HIP(hipGetLastError());
-    return CYB_OK;
+    CYB_CUT("mask op", items, totals, chunk_real(sum_of(totals)));
+    return launch(ctx, "mask op", mask_kernel, arrays(hd, items), scatter);
 }
 
 int cyb_mask_gather_batched_f64(cyb_ctx_t ctx, const cyb_mask_desc* descs, int64_t n) { return mask_common(ctx, descs, n, 0); }
@@ -1365,22 +1235,17 @@ int cyb_complex_expand_batched_f64(cyb_ctx_t ctx, const cyb_cexpand_desc* descs,
     CYB_REQUIRE(n >= 0 && (n == 0 || descs), "cyb_complex_expand_batched_f64: bad descriptor list");
     if (n == 0) return CYB_OK;
     std::vector<CExpandDev> hd((size_t)n);
-    std::vector<Item> items;
+    std::vector<int64_t> totals((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
         const cyb_cexpand_desc& d = descs[i];
         CYB_REQUIRE(d.K >= 0 && d.N >= 0, "complex expand desc %lld: negative extent", (long long)i);
-        const int64_t tot = d.K * d.N;
-        CYB_REQUIRE(tot == 0 || (d.src && d.dst), "complex expand desc %lld: NULL pointer", (long long)i);
+        totals[(size_t)i] = d.K * d.N;
+        CYB_REQUIRE(totals[(size_t)i] == 0 || (d.src && d.dst), "complex expand desc %lld: NULL pointer", (long long)i);
         hd[(size_t)i] = CExpandDev{d.src, d.rs, d.cs, d.K, d.N, d.dst};
-        for (int64_t s0 = 0; s0 < tot; s0 += CHUNK) items.push_back(Item{(int32_t)i, 0, s0, std::min(CHUNK, tot - s0)});
     }
-    if (items.empty()) return CYB_OK;
-    void *d_descs = nullptr, *d_items = nullptr;
-    CYB_TRY(cyb::upload_packed(ctx, {{hd.data(), sizeof(CExpandDev) * hd.size(), &d_descs}, {items.data(), sizeof(Item) * items.size(), &d_items}}));
-    hipLaunchKernelGGL(complex_expand_kernel, dim3((unsigned)items.size()), dim3(NT), 0, ctx->stream,
-                       static_cast<const CExpandDev*>(d_descs), static_cast<const Item*>(d_items));
-    CYB_HIP(hipGetLastError());
-    return CYB_OK;
+    std::vector<Item> items;
+    CYB_CUT("cyb_complex_expand_batched_f64", items, totals, kMaxChunk);
+    return launch(ctx, "cyb_complex_expand_batched_f64", complex_expand_kernel, arrays(hd, items));
 }
 
 int cyb_elementwise_batched_c128(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t n, int32_t op)
@@ -1388,14 +1253,10 @@ int cyb_elementwise_batched_c128(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64
     CYB_REQUIRE(ctx, "cyb_elementwise_batched_c128: ctx is NULL");
     CYB_REQUIRE(n >= 0 && (n == 0 || descs), "cyb_elementwise_batched_c128: bad descriptor list");
     CYB_REQUIRE(op >= 0 && op <= 6, "cyb_elementwise_batched_c128: unknown op %d", op);
+    std::vector<VecDev> hv;
     std::vector<Item> items;
-    void *d_descs = nullptr, *d_items = nullptr;
-    CYB_TRY(upload_vecs(ctx, descs, n, op >= 5, true, items, &d_descs, &d_items));
-    if (items.empty()) return CYB_OK;
-    hipLaunchKernelGGL(celementwise_kernel, dim3((unsigned)items.size()), dim3(NT), 0, ctx->stream,
-                       static_cast<const VecDev*>(d_descs), static_cast<const Item*>(d_items), op);
-    CYB_HIP(hipGetLastError());
-    return CYB_OK;
+    CYB_TRY(vec_items("cyb_elementwise_batched_c128", descs, n, op >= 5, true, hv, items));
+    return launch(ctx, "cyb_elementwise_batched_c128", celementwise_kernel, arrays(hv, items), op);
 }
 
 int cyb_axpby_batched_c128(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t n, double a_re, double a_im, double b_re,
@@ -1403,14 +1264,10 @@ int cyb_axpby_batched_c128(cyb_ctx_t ctx, const cyb_vec_desc* descs, int64_t n, 
 {
     CYB_REQUIRE(ctx, "cyb_axpby_batched_c128: ctx is NULL");
     CYB_REQUIRE(n >= 0 && (n == 0 || descs), "cyb_axpby_batched_c128: bad descriptor list");
+    std::vector<VecDev> hv;
     std::vector<Item> items;
-    void *d_descs = nullptr, *d_items = nullptr;
-    CYB_TRY(upload_vecs(ctx, descs, n, false, true, items, &d_descs, &d_items));
-    if (items.empty()) return CYB_OK;
-    hipLaunchKernelGGL(axpby_c128_kernel, dim3((unsigned)items.size()), dim3(NT), 0, ctx->stream,
-                       static_cast<const VecDev*>(d_descs), static_cast<const Item*>(d_items), a_re, a_im, b_re, b_im);
-    CYB_HIP(hipGetLastError());
-    return CYB_OK;
+    CYB_TRY(vec_items("cyb_axpby_batched_c128", descs, n, false, true, hv, items));
+    return launch(ctx, "cyb_axpby_batched_c128", axpby_c128_kernel, arrays(hv, items), a_re, a_im, b_re, b_im);
 }
 
 } // extern "C"

@@ -11,6 +11,14 @@
 
 #include "../../include/cyten_amd.h"
 
+#ifdef __HIPCC__
+// device code: global-memory pointers (loads and stores through them are global_*, not flat_*) and the 16-byte pair
+#define GLOBAL_AS __attribute__((address_space(1)))
+typedef double d2 __attribute__((ext_vector_type(2)));
+typedef GLOBAL_AS double* gp;
+typedef const GLOBAL_AS double* gcp;
+#endif
+
 namespace cyb {
 
 void set_error(const char* fmt, ...);

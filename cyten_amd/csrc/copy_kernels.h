@@ -1,33 +1,14 @@
 // Strided N-d copies: the device bodies and the host-side classification shared by the batched copy of blockops.hip
 // (descriptors with addresses, built per call) and the placement plans of place_plan.hip (records with block numbers,
-// built once; the addresses come from two tables at enqueue time).
+// built once; the addresses come from two tables at enqueue time).  The work item of a body is the flat Item of
+// flat_items.h: a range of elements (strided body) or of tiles (transposing bodies).
 #pragma once
-#include "common.h"
-
-#include <algorithm>
+#include "flat_items.h"
 
 namespace cyb_copy {
 
-#define GLOBAL_AS __attribute__((address_space(1)))
-typedef GLOBAL_AS double* gp;
-typedef const GLOBAL_AS double* gcp;
-
-constexpr int NT = 256;
-constexpr int64_t CHUNK = 1 << 16; // largest number of elements per workgroup work item
-// Work-item size for a list of `total` elements: 64 K elements once the list fills the chip eight workgroups per CU
-// deep, smaller (down to 8 K, always a multiple of 1024) for the 10-100 MB lists of one tensor operation, which
-// would otherwise run as a few hundred workgroups on 256 CUs.
-inline int64_t chunk_for(int64_t total)
-{
-    int64_t c = ((total / 2048) + 1023) & ~(int64_t)1023;
-    return std::min(CHUNK, std::max<int64_t>(8192, c));
-}
-
-struct Item {
-    int32_t desc;
-    int32_t pad;
-    int64_t start, count;
-};
+using cyb_flat::Item;
+using cyb_flat::NT;
 
 // ---------------------------------------------------------------------------------------------
 // strided copy
@@ -194,7 +175,6 @@ __device__ __forceinline__ void copy_transpose_body(const CopyT& d, const GLOBAL
 constexpr int T64_TS = 64, T64_LS = T64_TS + 2; // `tile` of the body below: double[T64_TS * T64_LS], 16-byte aligned
 __device__ __forceinline__ void copy_transpose64_body(const CopyT& d, gcp src, gp dst, const Item& it, double* tile)
 {
-    typedef double d2v __attribute__((ext_vector_type(2)));
     constexpr int TS = T64_TS, LS = T64_LS; // tile[s * LS + d]
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     for (int64_t t = it.start; t < it.start + it.count; ++t) {
@@ -218,7 +198,7 @@ __device__ __forceinline__ void copy_transpose64_body(const CopyT& d, gcp src, g
                 gcp p = src + so + (dI / d.nD2) * d.ssD + (dI % d.nD2) * d.ssD2 + sI;
                 double v0, v1 = 0.0;
                 if (sI + 1 < d.nS && (((uintptr_t)p) & 15) == 0) {
-                    const d2v v = *(const GLOBAL_AS d2v*)p;
+                    const d2 v = *(const GLOBAL_AS d2*)p;
                     v0 = v.x;
                     v1 = v.y;
                 } else {
@@ -235,9 +215,9 @@ __device__ __forceinline__ void copy_transpose64_body(const CopyT& d, gcp src, g
             const int64_t sI = s0 + ty + 8 * q, dI = d0 + 2 * tx;
             if (sI < d.nS && dI < d.nD) {
                 gp p = dst + dof + (sI / d.nS2) * d.dsS + (sI % d.nS2) * d.dsS2 + dI;
-                const d2v v = *reinterpret_cast<const d2v*>(&tile[(ty + 8 * q) * LS + 2 * tx]);
+                const d2 v = *reinterpret_cast<const d2*>(&tile[(ty + 8 * q) * LS + 2 * tx]);
                 if (dI + 1 < d.nD && (((uintptr_t)p) & 15) == 0) {
-                    *(GLOBAL_AS d2v*)p = v;
+                    *(GLOBAL_AS d2*)p = v;
                 } else {
                     p[0] = v.x;
                     if (dI + 1 < d.nD) p[1] = v.y;

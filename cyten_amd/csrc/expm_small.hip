@@ -15,7 +15,7 @@
 //
 // cyb_norm1_batched_*: max_j sum_i |a_ij| of every listed matrix in one launch -- the norm table of the blocks that are too
 // large for the kernel above, which the host reads once to choose their s.
-#include "common.h"
+#include "flat_items.h"
 
 #include <algorithm>
 
@@ -23,7 +23,6 @@ namespace {
 
 constexpr int NT = 256;
 constexpr int GRID = 16; // threads per side of the thread grid
-typedef double d2 __attribute__((ext_vector_type(2)));
 
 template <class T> struct Num;
 template <> struct Num<double> {
@@ -288,13 +287,7 @@ template <bool CPLX> int norm1_batched(cyb_ctx_t ctx, const cyb_expm_desc* descs
     }
     CYB_REQUIRE(n <= INT32_MAX, "%s: too many matrices", who);
     CYB_HIP(hipMemsetAsync(result_dev, 0, sizeof(double) * (size_t)n, ctx->stream));
-    if (items.empty()) return CYB_OK;
-    void *d_descs = nullptr, *d_items = nullptr;
-    CYB_TRY(cyb::upload_packed(ctx, {{descs, sizeof(cyb_expm_desc) * (size_t)n, &d_descs}, {items.data(), sizeof(NormItem) * items.size(), &d_items}}));
-    hipLaunchKernelGGL(norm1_kernel<CPLX>, dim3((unsigned)items.size()), dim3(NT), 0, ctx->stream, static_cast<const cyb_expm_desc*>(d_descs),
-                       static_cast<const NormItem*>(d_items), reinterpret_cast<unsigned long long*>(result_dev));
-    CYB_HIP(hipGetLastError());
-    return CYB_OK;
+    return cyb_flat::launch(ctx, who, norm1_kernel<CPLX>, cyb_flat::arrays(cyb_flat::arr(descs, n), items), reinterpret_cast<unsigned long long*>(result_dev));
 }
 
 } // namespace

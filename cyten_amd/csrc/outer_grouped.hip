@@ -18,18 +18,15 @@
 //     step and precomputed offset corrections per wrap of a level: additions and compares only, no division in the loop.
 //   * float64: a lane owns the 16-byte aligned pairs of its item (two cursors, one per element of the pair); the one element
 //     before the first aligned pair and the one after the last are stored once per item by a single lane.
-#include "common.h"
+#include "flat_items.h"
 
 #include <algorithm>
 
 namespace {
 
-#define GLOBAL_AS __attribute__((address_space(1)))
-
 constexpr int NT = 256;
 constexpr int ML = CYB_MAX_NDIM;
 constexpr int64_t kMinChunk = 2048, kMaxChunk = 65536; // flat elements per work item (multiples of 2 * NT)
-typedef double d2 __attribute__((ext_vector_type(2)));
 
 // one record as the kernel reads it: levels right-aligned (level ML - 1 is the innermost of dst), unused outer levels have
 // extent 1 and zeros elsewhere
@@ -252,18 +249,7 @@ template <class T> int outer_grouped(cyb_ctx_t ctx, const cyb_outer_rec* recs, i
             items.push_back(it);
         }
     }
-    CYB_REQUIRE(items.size() < ((size_t)1 << 31), "%s: too many work items", who);
-    void *d_recs = nullptr, *d_items = nullptr;
-    CYB_TRY(cyb::upload_packed(ctx, {{dev.data(), sizeof(Rec) * dev.size(), &d_recs}, {items.data(), sizeof(Item) * items.size(), &d_items}}));
-    const dim3 grid((unsigned)items.size()), block(NT);
-    if (max_levels <= 3)
-        hipLaunchKernelGGL((outer_grouped_kernel<T, 3>), grid, block, 0, ctx->stream, static_cast<const Rec*>(d_recs),
-                           static_cast<const Item*>(d_items));
-    else
-        hipLaunchKernelGGL((outer_grouped_kernel<T, ML>), grid, block, 0, ctx->stream, static_cast<const Rec*>(d_recs),
-                           static_cast<const Item*>(d_items));
-    CYB_HIP(hipGetLastError());
-    return CYB_OK;
+    return cyb_flat::launch(ctx, who, max_levels <= 3 ? outer_grouped_kernel<T, 3> : outer_grouped_kernel<T, ML>, cyb_flat::arrays(dev, items));
 }
 
 } // namespace

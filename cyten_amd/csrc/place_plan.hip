@@ -10,6 +10,7 @@
 namespace {
 
 using namespace cyb_copy;
+using namespace cyb_flat; // Item, NT, chunk_real, cut
 
 // device records: the normalised copy (its own address fields unused) + where the two blocks are found
 struct PlaceRow {
@@ -82,8 +83,7 @@ int build_direction(cyb_place_plan_s* pl, int reverse)
     std::vector<PlaceRow> rows;
     std::vector<PlaceTile> tiles;
     std::vector<Item> items, titems;
-    std::vector<int64_t> row_total;
-    int64_t pending_total = 0;
+    std::vector<int64_t> totals, tile_totals; // elements of a row, tiles of a tiled record
     const int64_t tsz = pl->elem_size == 8 ? 64 : 32;
     for (const cyb_place_rec& r : pl->recs) {
         const int64_t* rs = reverse ? r.dst_strides : r.src_strides; // strides on the side that is read
@@ -99,19 +99,15 @@ int build_direction(cyb_place_plan_s* pl, int reverse)
         int64_t ntile = 0;
         if (classify_transpose(row.d, tsz, t.d, ntile)) {
             t.rblock = row.rblock, t.wblock = row.wblock, t.roff = row.roff, t.woff = row.woff;
-            const int64_t per = tiles_per_item(tsz);
-            for (int64_t s0 = 0; s0 < ntile; s0 += per) titems.push_back(Item{(int32_t)tiles.size(), 0, s0, std::min(per, ntile - s0)});
             tiles.push_back(t);
+            tile_totals.push_back(ntile);
             continue;
         }
         rows.push_back(row);
-        pending_total += row.d.total;
+        totals.push_back(row.d.total);
     }
-    const int64_t chunk = chunk_for(pending_total);
-    for (size_t i = 0; i < rows.size(); ++i) {
-        const int64_t tot = rows[i].d.total;
-        for (int64_t s = 0; s < tot; s += chunk) items.push_back(Item{(int32_t)i, 0, s, std::min(chunk, tot - s)});
-    }
+    CYB_REQUIRE(cut(titems, tile_totals, tiles_per_item(tsz)) && cut(items, totals, chunk_real(sum_of(totals))),
+                "cyb_place_plan: too many work items");
     // one allocation, each part 256-byte aligned
     const size_t parts[4] = {sizeof(PlaceRow) * rows.size(), sizeof(Item) * items.size(), sizeof(PlaceTile) * tiles.size(),
                              sizeof(Item) * titems.size()};

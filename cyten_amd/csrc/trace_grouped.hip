@@ -14,17 +14,14 @@
 //   * wave  (64 lanes per element): the lanes stride over the traced multi-index; shuffle tree of fixed shape.
 //   * group (256 lanes per element): few elements with very many addends (trace_full); the four wave sums are added by
 //     lane 0 in wave order through LDS.
-#include "common.h"
+#include "flat_items.h"
 
 #include <algorithm>
 
 namespace {
 
-#define GLOBAL_AS __attribute__((address_space(1)))
-
 constexpr int NT = 256;
 constexpr int kPairs = CYB_TRACE_MAX_PAIRS;
-typedef double d2 __attribute__((ext_vector_type(2)));
 
 struct Item {
     int32_t out;   // output record
@@ -197,15 +194,7 @@ int trace_grouped(cyb_ctx_t ctx, const cyb_trace_out* outs, int64_t n_outs, cons
         const int64_t step = p.lanes == 1 ? chunk : NT / p.lanes; // wave: 4 elements (one per wave), group: 1 element per workgroup
         for (int64_t s = 0; s < p.total; s += step) items.push_back(Item{(int32_t)i, p.lanes, s, std::min(step, p.total - s)});
     }
-    if (items.empty()) return CYB_OK;
-    void *d_outs = nullptr, *d_terms = nullptr, *d_items = nullptr;
-    CYB_TRY(cyb::upload_packed(ctx, {{outs, sizeof(cyb_trace_out) * (size_t)n_outs, &d_outs},
-                                     {ht.empty() ? (const void*)outs : (const void*)ht.data(), ht.empty() ? 8 : sizeof(cyb_trace_term) * ht.size(), &d_terms},
-                                     {items.data(), sizeof(Item) * items.size(), &d_items}}));
-    hipLaunchKernelGGL(trace_grouped_kernel<T>, dim3((unsigned)items.size()), dim3(NT), 0, ctx->stream, static_cast<const cyb_trace_out*>(d_outs),
-                       static_cast<const cyb_trace_term*>(d_terms), static_cast<const Item*>(d_items));
-    CYB_HIP(hipGetLastError());
-    return CYB_OK;
+    return cyb_flat::launch(ctx, who, trace_grouped_kernel<T>, cyb_flat::arrays(cyb_flat::arr(outs, n_outs), ht, items));
 }
 
 } // namespace

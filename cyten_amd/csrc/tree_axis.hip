@@ -13,7 +13,7 @@
 //   scatter : dst[(o * A' + idx[a]) * inner + i, x] = src[(o * A + a) * inner + i, x]        (enlarge_leg; the entry
 //             point zero-fills the regions the caller lists before the launch)
 //
-// Memory-bound work, organised like blockops.hip: records are cut into work items of chunk_for(total) elements, one
+// Memory-bound work, organised like blockops.hip: records are cut into work items of chunk_real(total) elements (flat_items.h), one
 // workgroup each.  Lanes run along whichever matrix index has unit stride in the destination.  Where that index has unit
 // stride in the source too and the contiguous run is at least 16 elements long a wave owns a run: the run's offsets (and
 // its factor, if it has one) are decoded once; the four waves share a run of 2048 elements or more.  Float64 runs whose
@@ -26,16 +26,13 @@
 // bit-identical from run to run): FusionTreeBackend::inner (:1238-1259), ::norm (:1280-1296) and, with the diagonal as a
 // one-column view against a constant one, ::trace_full (:1261-1278) -- one launch chain instead of a reduction and a host
 // wait per coupled sector.
-#include "common.h"
-#include "copy_kernels.h"
+#include "flat_items.h"
 
 #include <algorithm>
 
 namespace {
 
-using namespace cyb_copy; // GLOBAL_AS, gp, gcp, NT, chunk_for, Item
-
-typedef double d2 __attribute__((ext_vector_type(2)));
+using namespace cyb_flat; // Item, NT, chunk_real, cut, launch, the fixed-order reduction
 
 enum { LAY_ELEM_X = 0, LAY_ELEM_T, LAY_RUN_X, LAY_RUN_T_SCALE, LAY_RUN_T_INNER };
 
@@ -240,7 +237,6 @@ template <class T> int tree_axis(cyb_ctx_t ctx, const cyb_tree_axis_rec* recs, i
     }
     std::vector<Rec> dev;
     std::vector<int64_t> totals;
-    int64_t grand = 0;
     const int64_t lim = (int64_t)1 << 31;
     for (int64_t i = 0; i < n; ++i) {
         const cyb_tree_axis_rec& in = recs[i];
@@ -289,23 +285,13 @@ template <class T> int tree_axis(cyb_ctx_t ctx, const cyb_tree_axis_rec* recs, i
         }
         dev.push_back(r);
         totals.push_back(total);
-        grand += total;
     }
     // everything is validated: from here on work is enqueued
     for (int64_t i = 0; i < n_fills; ++i)
         if (fills[i].bytes > 0) CYB_HIP(hipMemsetAsync(fills[i].ptr, 0, (size_t)fills[i].bytes, ctx->stream));
-    if (dev.empty()) return CYB_OK;
-    const int64_t chunk = chunk_for(grand);
     std::vector<Item> items;
-    for (size_t i = 0; i < dev.size(); ++i)
-        for (int64_t s = 0; s < totals[i]; s += chunk) items.push_back(Item{(int32_t)i, 0, s, std::min(chunk, totals[i] - s)});
-    CYB_REQUIRE(items.size() < ((size_t)1 << 31), "%s: too many work items", who);
-    void *d_recs = nullptr, *d_items = nullptr;
-    CYB_TRY(cyb::upload_packed(ctx, {{dev.data(), sizeof(Rec) * dev.size(), &d_recs}, {items.data(), sizeof(Item) * items.size(), &d_items}}));
-    hipLaunchKernelGGL(tree_axis_kernel<T>, dim3((unsigned)items.size()), dim3(NT), 0, ctx->stream, static_cast<const Rec*>(d_recs),
-                       static_cast<const Item*>(d_items));
-    CYB_HIP(hipGetLastError());
-    return CYB_OK;
+    CYB_CUT(who, items, totals, chunk_real(sum_of(totals)));
+    return launch(ctx, who, tree_axis_kernel<T>, arrays(dev, items));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -318,39 +304,13 @@ struct WDot {
     int32_t flat, pad; // both operands contiguous: element e of the flat range is at offset e
 };
 
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// the workgroup's sum of `acc` (C numbers per thread) in a fixed order; valid in thread 0
-template <int C> __device__ inline void block_sum(double (&acc)[C])
-{
-    __shared__ double red[C][NT / 64];
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        acc[c] = wave_sum(acc[c]);
-        if ((threadIdx.x & 63) == 0) red[c][threadIdx.x >> 6] = acc[c];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            double s = red[c][0];
-            for (int q = 1; q < NT / 64; ++q) s += red[c][q];
-            acc[c] = s;
-        }
-    }
-}
-
 // partial[C * item + c] = w * sum over the item's elements; complex: (re, im) of conj?(x) y
 template <bool CPLX>
 __global__ void __launch_bounds__(NT) wdot_stage1_kernel(const WDot* __restrict__ descs, const Item* __restrict__ items,
                                                          double* __restrict__ partial, int conj_x)
 {
     constexpr int C = CPLX ? 2 : 1;
+    __shared__ double red[C][WAVES];
     const Item it = items[blockIdx.x];
     const WDot d = descs[it.desc];
     double acc[C];
@@ -375,26 +335,10 @@ __global__ void __launch_bounds__(NT) wdot_stage1_kernel(const WDot* __restrict_
             acc[0] += a * (d.y ? ((gcp)d.y)[yo] : a);
         }
     }
-    block_sum<C>(acc);
+    block_reduce<C>(acc, red);
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int c = 0; c < C; ++c) partial[C * (int64_t)blockIdx.x + c] = d.w * acc[c];
-    }
-}
-
-template <int C> __global__ void __launch_bounds__(NT) wdot_stage2_kernel(const double* __restrict__ partial, int64_t n_items, double* __restrict__ result)
-{
-    double acc[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) acc[c] = 0.0;
-    for (int64_t e = threadIdx.x; e < n_items; e += NT) {
-#pragma unroll
-        for (int c = 0; c < C; ++c) acc[c] += partial[C * e + c];
-    }
-    block_sum<C>(acc);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int c = 0; c < C; ++c) result[c] = acc[c];
     }
 }
 
@@ -405,7 +349,6 @@ template <bool CPLX> int dot_weighted(cyb_ctx_t ctx, const cyb_wdot_desc* descs,
     CYB_REQUIRE(n >= 0 && (n == 0 || descs), "%s: bad descriptor list", who);
     std::vector<WDot> hd;
     std::vector<int64_t> totals;
-    int64_t grand = 0;
     for (int64_t i = 0; i < n; ++i) {
         const cyb_wdot_desc& d = descs[i];
         CYB_REQUIRE(d.rows >= 0 && d.cols >= 0, "%s: desc %lld: negative extent", who, (long long)i);
@@ -420,26 +363,20 @@ template <bool CPLX> int dot_weighted(cyb_ctx_t ctx, const cyb_wdot_desc* descs,
         w.flat = contiguous(d.x_rs, d.x_cs) && (!d.y || contiguous(d.y_rs, d.y_cs));
         hd.push_back(w);
         totals.push_back(total);
-        grand += total;
     }
     if (hd.empty()) {
         CYB_HIP(hipMemsetAsync(result_dev, 0, sizeof(double) * C, ctx->stream));
         return CYB_OK;
     }
-    const int64_t chunk = chunk_for(grand);
     std::vector<Item> items;
-    for (size_t i = 0; i < hd.size(); ++i)
-        for (int64_t s = 0; s < totals[i]; s += chunk) items.push_back(Item{(int32_t)i, 0, s, std::min(chunk, totals[i] - s)});
-    CYB_REQUIRE(items.size() < ((size_t)1 << 31), "%s: too many work items", who);
-    void *d_descs = nullptr, *d_items = nullptr, *ws = nullptr;
-    CYB_TRY(cyb::upload_packed(ctx, {{hd.data(), sizeof(WDot) * hd.size(), &d_descs}, {items.data(), sizeof(Item) * items.size(), &d_items}}));
-    CYB_TRY(ctx->workspace(sizeof(double) * C * items.size(), &ws));
-    hipLaunchKernelGGL(wdot_stage1_kernel<CPLX>, dim3((unsigned)items.size()), dim3(NT), 0, ctx->stream, static_cast<const WDot*>(d_descs),
-                       static_cast<const Item*>(d_items), static_cast<double*>(ws), conj_x);
-    hipLaunchKernelGGL(wdot_stage2_kernel<C>, dim3(1), dim3(NT), 0, ctx->stream, static_cast<const double*>(ws), (int64_t)items.size(),
-                       result_dev);
-    CYB_HIP(hipGetLastError());
-    return CYB_OK;
+    CYB_CUT(who, items, totals, chunk_real(sum_of(totals)));
+    // (the upload comes before the workspace, as in the reductions of blockops.hip)
+    return with_arrays(ctx, who, items.size(), arrays(hd, items), [&](dim3 grid, const WDot* d_descs, const Item* d_items) {
+        return two_stage<C, Sum>(ctx, items.size(), nullptr, 1, result_dev, [&](double* partial) {
+            hipLaunchKernelGGL(wdot_stage1_kernel<CPLX>, grid, dim3(NT), 0, ctx->stream, d_descs, d_items, partial, conj_x);
+            return CYB_OK;
+        });
+    });
 }
 
 } // namespace

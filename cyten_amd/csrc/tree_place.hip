@@ -230,14 +230,7 @@ template <bool CPLX> int tree_place(cyb_ctx_t ctx, const In* in, int64_t n_recs,
     std::vector<Rec> recs;
     std::vector<Item> items;
     CYB_TRY(plan_place<CPLX>(recs, items, in, n_recs, who));
-    if (items.empty()) return CYB_OK;
-    void *d_recs = nullptr, *d_items = nullptr;
-    CYB_TRY(cyb::upload_packed(ctx, {{recs.data(), sizeof(Rec) * recs.size(), &d_recs}, {items.data(), sizeof(Item) * items.size(), &d_items}}));
-    const unsigned grid = (unsigned)((items.size() + ITEMS_PER_GROUP - 1) / ITEMS_PER_GROUP);
-    hipLaunchKernelGGL(tree_place_kernel<CPLX>, dim3(grid), dim3(NT), 0, ctx->stream, static_cast<const Rec*>(d_recs), static_cast<const Item*>(d_items),
-                       (int)items.size());
-    CYB_HIP(hipGetLastError());
-    return CYB_OK;
+    return cyb_flat::launch<ITEMS_PER_GROUP>(ctx, who, tree_place_kernel<CPLX>, cyb_flat::arrays(recs, items), (int)items.size());
 }
 
 } // namespace

@@ -21,17 +21,14 @@
 //     shape per term, lane 0 multiplies by the coefficient and adds.
 //   * group (256 lanes per element): few elements with very many addends (a bond-pair trace, the full trace); the four
 //     wave sums of a term are added by lane 0 in wave order through LDS.
-#include "common.h"
+#include "flat_items.h"
 
 #include <algorithm>
 
 namespace {
 
-#define GLOBAL_AS __attribute__((address_space(1)))
-
 constexpr int NT = 256;
 constexpr int kPairs = CYB_TRACE_MAX_PAIRS;
-typedef double d2 __attribute__((ext_vector_type(2)));
 typedef cyb_trace_weighted_out Out;
 typedef cyb_trace_weighted_term Term;
 
@@ -306,15 +303,7 @@ int trace_weighted(cyb_ctx_t ctx, const Out* outs, int64_t n_outs, const Term* t
         for (int64_t s = 0; s < p.total; s += step)
             items.push_back(Item{(int32_t)i, (int16_t)p.lanes, (int16_t)p.mode, s, std::min(step, p.total - s)});
     }
-    if (items.empty()) return CYB_OK;
-    void *d_outs = nullptr, *d_terms = nullptr, *d_items = nullptr;
-    CYB_TRY(cyb::upload_packed(ctx, {{ho.data(), sizeof(Out) * ho.size(), &d_outs},
-                                     {ht.empty() ? (const void*)ho.data() : (const void*)ht.data(), ht.empty() ? 8 : sizeof(Term) * ht.size(), &d_terms},
-                                     {items.data(), sizeof(Item) * items.size(), &d_items}}));
-    hipLaunchKernelGGL(trace_weighted_kernel<CPLX>, dim3((unsigned)items.size()), dim3(NT), 0, ctx->stream, static_cast<const Out*>(d_outs),
-                       static_cast<const Term*>(d_terms), static_cast<const Item*>(d_items));
-    CYB_HIP(hipGetLastError());
-    return CYB_OK;
+    return cyb_flat::launch(ctx, who, trace_weighted_kernel<CPLX>, cyb_flat::arrays(ho, ht, items));
 }
 
 } // namespace

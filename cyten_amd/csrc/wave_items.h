@@ -16,7 +16,7 @@
 // (tests/wave_items_walk.cpp).
 #pragma once
 #ifdef __HIPCC__
-#include "common.h"
+#include "flat_items.h"
 #define WI_HD __host__ __device__
 #else
 #define WI_HD
@@ -168,9 +168,6 @@ template <int L, int S> WI_HD inline void start(Cursor<L, S>& c, const Levels<L,
 #ifdef __HIPCC__
 // ---- device: the kernel prologue, loads and stores ---------------------------------------------------------------------
 
-#define GLOBAL_AS __attribute__((address_space(1)))
-typedef double d2 __attribute__((ext_vector_type(2)));
-
 // one wave per item: the index is wave-uniform, and so is everything read through it.  false: no item for this wave
 __device__ inline bool my_item(int& i, int& lane, int n_items)
 {
@@ -217,22 +214,12 @@ __device__ inline d2 load_c(const double* p_, int64_t o, bool real)
     CYB_REQUIRE((o).first_term >= 0 && (o).n_terms >= 0 && (o).first_term <= (n_terms) && (o).n_terms <= (n_terms) - (o).first_term,       \
                 "%s: output %lld: bad term range [%lld, +%lld)", who, (long long)(i), (long long)(o).first_term, (long long)(o).n_terms)
 
+// the launch tail of flat_items.h with four items per workgroup; the kernel learns the number of items
 template <class RecT, class TermT, class ItemT, class... Extra>
 int launch_items(cyb_ctx_t ctx, void (*kernel)(const RecT*, const TermT*, const ItemT*, int, Extra...), const std::vector<RecT>& recs,
                  const std::vector<TermT>& terms, const std::vector<ItemT>& items, const char* who, Extra... extra)
 {
-    if (items.empty()) return CYB_OK;
-    CYB_REQUIRE(items.size() < ((size_t)1 << 31), "%s: too many work items", who);
-    void *d_recs = nullptr, *d_terms = nullptr, *d_items = nullptr;
-    // (an empty term list travels as 8 bytes nobody reads)
-    CYB_TRY(cyb::upload_packed(ctx, {{recs.data(), sizeof(RecT) * recs.size(), &d_recs},
-                                     {terms.empty() ? (const void*)recs.data() : (const void*)terms.data(), terms.empty() ? 8 : sizeof(TermT) * terms.size(), &d_terms},
-                                     {items.data(), sizeof(ItemT) * items.size(), &d_items}}));
-    const unsigned grid = (unsigned)((items.size() + ITEMS_PER_GROUP - 1) / ITEMS_PER_GROUP);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(NT), 0, ctx->stream, static_cast<const RecT*>(d_recs), static_cast<const TermT*>(d_terms),
-                       static_cast<const ItemT*>(d_items), (int)items.size(), extra...);
-    CYB_HIP(hipGetLastError());
-    return CYB_OK;
+    return cyb_flat::launch<ITEMS_PER_GROUP>(ctx, who, kernel, cyb_flat::arrays(recs, terms, items), (int)items.size(), extra...);
 }
 #endif // __HIPCC__
 

@@ -360,7 +360,7 @@ def dot_c128_case(rng, ns=(3001, 257, 4100)):
 
     def launch(lib, h, p):
         return lib.cyb_dot_batched_c128(h, _vec_descs(p, [(f'x{i}', f'y{i}', None, n) for i, n in enumerate(ns)]), len(ns), _vp(p['r']))
-    chunk = min(1 << 15, max(4096, ((sum(ns) // 2048) + 511) & ~511))      # chunk_for of krylov_vec.hip
+    chunk = min(1 << 15, max(4096, ((sum(ns) // 2048) + 511) & ~511))      # chunk_complex of flat_items.h
     items = sum(-(-n // chunk) for n in ns)
     return Call('cyb_dot_batched_c128', ins, {'r': _sentinel(2)}, launch, {'r': np.array([z.real, z.imag])}, {'r': 1e-13 * scale},
                 uploads=1 if len(ns) > 1 else 0, ws_bytes=(0, 16 * max(items, 1)))
