@@ -2,8 +2,8 @@
 //
 //   A = Q R,  Q = H_0 H_1 ... H_{k-1},  H_j = I - tau_j v_j v_j^T  (LAPACK dgeqrf conventions),
 //   panels of NBK columns: unblocked Householder inside the panel (one workgroup per matrix),
-//   compact-WY block reflector  I - V T V^T  applied to the trailing matrix / to Q's columns with
-//   three grouped GEMM launches per panel step for the WHOLE batch.
+//   compact-WY block reflector  I - V T V^T  applied to the trailing matrix / to Q's columns in
+//   32-column strips, one launch per panel step for the WHOLE batch (two when the strips' rows are split).
 #pragma once
 #include "common.h"
 
@@ -18,8 +18,8 @@ struct BqrMat {
     double* V;       // col-major m x k (same ld): explicit unit-lower-trapezoidal reflectors
     double* T;       // ceil(k/NBK) blocks of NBK x NBK (row-major, upper triangular)
     double* tau;     // k
-    double* scratch; // (1 + kWSplit) * scr_half doubles: W2, then the row-chunk partials of W1; the wide application of Q
-                     // (bqr_apply_q) keeps the row-chunk partials of a whole group's W1 here instead: scr_total doubles
+    double* scratch; // scr_total doubles: the wide application of Q (bqr_apply_q) keeps the row-chunk partials of a whole
+                     // group's W1 here; the strips need none of it (still sized for at least (1 + kWSplit) * scr_half)
     int64_t scr_half; // NBK * max(n, kc_max)
     int64_t scr_total = 0; // doubles behind `scratch` (set by bqr_carve)
     int32_t v_zeroed = 0; // the caller has zero-filled V (a memset of its workspace): the panel kernels skip the rows above a panel

@@ -2,6 +2,7 @@
 // scipy.linalg.qr (reference src/block_backend/numpy.cpp:1236-1245) for large blocks and is the
 // preconditioner / null-space provider of the Jacobi SVD (svd_jacobi.hip).
 #include "blocked_qr.h"
+#include "qr_strip_chunks.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -161,7 +162,6 @@ __global__ void __launch_bounds__(PNT) qr_panel_kernel(const PanelDesc* __restri
 #endif
 constexpr int RP_NT = 512;
 constexpr int RP_RPT = 3;
-constexpr int RP_RPT_FUSED = 2;
 constexpr int RP_NW = RP_NT / 64;
 
 __device__ __forceinline__ double dshfl_xor(double v, int m) { return __shfl_xor(v, m); }
@@ -423,8 +423,7 @@ __device__ __forceinline__ void panel_steps(double (&P)[RPT][NBK], PanelShared& 
     (panel_step<Is, RPT, NT>(P, sh, d, tid), ...);
 }
 
-// RPT rows per thread: 3 for the stand-alone kernel (panels of up to 1536 rows), 2 inside the strip kernel (up to 1024
-// rows: 64 registers less, so that the panel body fits behind the strip phases without spilling)
+// RPT rows per thread, NT threads: 3 x 512 for panels of up to 1536 rows, 3 x 64 / 128 / 256 for the short ones
 template <int RPT, int NT = RP_NT>
 __device__ __forceinline__ void panel_reg_body(const PanelDesc& d, PanelShared& sh, const int tid)
 {
@@ -758,8 +757,8 @@ __global__ void __launch_bounds__(256) qr_panel_wave4_kernel(const PanelDesc* __
 // Block-reflector application to one 32-column strip, ONE launch per panel step for the whole batch:
 //     C_s <- (I - V P V^T) C_s,   P = T (apply Q) or T^T (apply Q^T, the trailing update of the factorisation).
 // A strip is private to its workgroup, so the three products of the compact-WY update chain inside the
-// kernel instead of across launches (the grouped-GEMM formulation needs two launches per panel step,
-// ~34 us each at the chi=4096 sizes, almost all of it launch + tail latency of narrow problems):
+// kernel instead of across launches (the grouped-GEMM formulation this replaced needed two launches per panel
+// step, ~34 us each at the chi=4096 sizes, almost all of it launch + tail latency of narrow problems):
 //   1. W1 = V^T C_s   (32 x 32, K = rows): f64 MFMA 16x16x4, K split over the eight waves, both operands are
 //      read as row PAIRS of a column (the two k-steps of a pair use the same pairing on both sides);
 //   2. W2 = P W1      (32 x 32 x 32) from LDS, one 16 x 16 tile per wave;
@@ -772,15 +771,12 @@ struct StripDesc {
     const double* T; // NBK x NBK row-major, zero outside the leading pw x pw block
     int64_t ldc, ldv;
     int32_t mr, nc, pw, transT;
-    int64_t next_off; // factorisation only: this strip holds the columns of the NEXT panel; byte offset of its PanelDesc from the strip descriptors (0: none)
     // early stop (see panel_stop_check): a strip of panel step `step` returns at once if the matrix was stopped at or before
     // that step; a factorisation strip leaves the squared norm of the rows it wrote BELOW the panel's pw rows in *part_out
     const double* ctl = nullptr;
     double* part_out = nullptr;
     int32_t step = 0, pad2 = 0;
 };
-constexpr int ST_NT_CHECK = 512;
-static_assert(ST_NT_CHECK == RP_NT, "the fused look-ahead runs the panel body with the strip kernel's workgroup");
 constexpr int ST_NT = 512; // two waves per SIMD: the loads of one hide behind the MFMAs of the other
 constexpr int ST_NW = ST_NT / 64;
 constexpr int ST_LS = NBK + 1;
@@ -788,49 +784,15 @@ constexpr int ST_UN = 4;
 
 // NORM: the strips also leave the squared norm of what they wrote (early stop; a separate instantiation -- the accumulator
 // costs the kernel 20 B of scratch, which the plain strips must not pay)
-// LA (role-split look-ahead, factorisation only): the launch carries n_strips strip workgroups and, behind them, one PANEL
-// workgroup per entry of pnext.  The strip whose columns are the next panel (next_off = index + 1 of that entry) raises
-// la_flags[index] to la_tag once its stores are out (agent-scope release); the panel workgroup waits for it (acquire) and
-// factors panel p + 1 while the other strips of step p are still running: a panel step costs max(strips, strip 0 + panel)
-// instead of their sum, with no cross-stream dependency.  The panel workgroups come LAST in the grid, so every strip they
-// wait for has been dispatched before them; a wait that runs out of time (1 s) sets la_flags[n_flags - 1] (read back by the host).
-template <bool FUSE_PANEL, bool NORM = false, bool LA = false>
-__global__ void __launch_bounds__(ST_NT) reflector_strip_kernel(const StripDesc* __restrict__ descs, int n_strips, const PanelDesc* __restrict__ pnext,
-                                                                unsigned int* la_flags, unsigned int la_tag, int la_err)
+template <bool NORM>
+__global__ void __launch_bounds__(ST_NT) reflector_strip_kernel(const StripDesc* __restrict__ descs)
 {
-    if constexpr (LA) {
-        if ((int)blockIdx.x >= n_strips) {
-            __shared__ PanelShared psh;
-            const int idx = (int)blockIdx.x - n_strips;
-            const PanelDesc pd = pnext[idx];
-            if (threadIdx.x == 0) {
-                const long long t0 = wall_clock64();
-                while (__hip_atomic_load(la_flags + idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != la_tag) {
-                    __builtin_amdgcn_s_sleep(8);
-                    if (wall_clock64() - t0 > 100000000ll) { // 1 s at 100 MHz
-                        __hip_atomic_store(la_flags + la_err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        break;
-                    }
-                }
-            }
-            __syncthreads();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            if (panel_stop_check<RP_NT>(pd, &psh.wsum[0][0], (int)threadIdx.x)) return;
-            panel_reg_body<RP_RPT>(pd, psh, (int)threadIdx.x);
-            return;
-        }
-    }
     __shared__ double part[ST_NW][NBK][ST_LS];
     __shared__ double W1s[NBK][ST_LS], W2s[NBK][ST_LS], Ps[NBK][ST_LS];
     const StripDesc d = descs[blockIdx.x];
     if (d.ctl) { // (workgroup-uniform)
         const double stopped = *(gcp)d.ctl;
-        if (stopped != 0.0 && (double)d.step >= stopped - 1.0) {
-            if constexpr (LA)
-                if (d.next_off && threadIdx.x == 0) // (its panel workgroup leaves on the same test)
-                    __hip_atomic_store(la_flags + (d.next_off - 1), la_tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            return;
-        }
+        if (stopped != 0.0 && (double)d.step >= stopped - 1.0) return;
     }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int x = lane & 15, kq = lane >> 4;
@@ -1006,29 +968,6 @@ __global__ void __launch_bounds__(ST_NT) reflector_strip_kernel(const StripDesc*
                 for (int w = 0; w < ST_NW; ++w) t += W1s[0][w];
                 *(gp)d.part_out = t;
             }
-        }
-    }
-    // ---- look-ahead inside the launch: the updated strip IS the next panel -- its 32-column latency chain runs while the
-    //      other workgroups of this launch are still updating their strips (a stream-level look-ahead pays ~20 us per
-    //      cross-stream dependency, this one nothing)
-    // (a separate instantiation: with the panel body inlined the kernel needs scratch and 22 KB more LDS, which costs the
-    //  plain strips of large matrices ~15 us per launch -- 41 -> 57 us at chi=4096 -- so they keep the lean kernel)
-    if constexpr (LA) {
-        if (d.next_off) { // workgroup-uniform
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads(); // every wave's stores have left for L2
-            if (tid == 0) {
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-                __hip_atomic_store(la_flags + (d.next_off - 1), la_tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-    }
-    if constexpr (FUSE_PANEL) {
-        __shared__ PanelShared psh;
-        if (d.next_off) { // workgroup-uniform
-            __syncthreads(); // (the strip's stores are visible to the whole workgroup: same CU, write-through L1)
-            const PanelDesc pd = *reinterpret_cast<const PanelDesc*>(reinterpret_cast<const char*>(descs) + d.next_off);
-            panel_reg_body<RP_RPT_FUSED>(pd, psh, tid);
         }
     }
 }
@@ -1448,97 +1387,111 @@ static inline int w_split(int64_t mr)
     return mr >= 2600 ? 4 : mr >= 1800 ? 3 : mr >= 700 ? 2 : 1;
 }
 
-// The block-reflector application runs as ONE strip kernel per panel step (reflector_strip_kernel) unless
-// CYB_QR_GEMM_UPDATE is set (the two-launch grouped-GEMM formulation, kept for comparison).
-static inline bool use_strips()
-{
-    static const bool off = getenv("CYB_QR_GEMM_UPDATE") != nullptr;
-    return !off;
-}
 static void add_strips(std::vector<StripDesc>& out, double* C, int64_t ldc, int64_t ncols, const double* V, int64_t ldv,
-                       const double* T, int64_t mr, int pw, int transT, int64_t next_tag = -1)
+                       const double* T, int64_t mr, int pw, int transT)
 {
-    // next_tag >= 0: index of the PanelDesc (in the caller's list) that strip 0 factors after its update; resolved to a
-    // device pointer once the image offsets are known
     for (int64_t c0 = 0; c0 < ncols; c0 += NBK)
-        out.push_back(StripDesc{C + (size_t)c0 * ldc, V, T, ldc, ldv, (int32_t)mr, (int32_t)std::min<int64_t>(NBK, ncols - c0), pw, transT,
-                                c0 == 0 && next_tag >= 0 ? next_tag + 1 : 0});
-}
-static void sort_strips(std::vector<StripDesc>& v)
-{
-    // longest strips first: the launch is one wave of workgroups, the tail is the longest strip
-    std::stable_sort(v.begin(), v.end(), [](const StripDesc& a, const StripDesc& b) { return a.mr > b.mr; });
+        out.push_back(StripDesc{C + (size_t)c0 * ldc, V, T, ldc, ldv, (int32_t)mr, (int32_t)std::min<int64_t>(NBK, ncols - c0), pw, transT});
 }
 
-// ---- row-split strips (strip_w1_kernel + strip_apply_kernel)
-// The chunk size is chosen PER PANEL STEP so that the chunk workgroups of the step fit the chip once (one workgroup per CU:
-// the kernels use the whole register file): a single large matrix has ~45 strips per step and is cut into chunks of 384
-// rows, a list whose strips fill the chip anyway is not cut at all (two launches of two rounds each measured SLOWER than the
-// one-launch strip kernel there: chi=4096 list 26.3 -> 28.9 ms with a fixed 384, single 1442^2 block 20.9 -> 17.4 ms).
-constexpr int kChunkRowsMin = 192;
-static const int kChunkRowsChoices[] = {192, 256, 384, 512, 768, 1024, 1536};
+// ---- row-split strips (strip_w1_kernel + strip_apply_kernel): the chunk arithmetic is in qr_strip_chunks.h
 static int strip_split_mode()
 {
     // CYB_QR_CHUNK_ROWS: unset / -1 = adaptive, 0 = never split, n = fixed chunk rows (multiple of 16)
     static const int v = getenv("CYB_QR_CHUNK_ROWS") ? atoi(getenv("CYB_QR_CHUNK_ROWS")) : -1;
     return v < 0 ? -1 : v / 16 * 16;
 }
-int bqr_strip_slots(int64_t rows)
+int bqr_strip_slots(int64_t rows) { return strip_slot_bound(rows, strip_split_mode()); }
+// chunk rows of a panel step whose strips are (rows, count) pairs; 0: whole strips (the one-launch strip kernel)
+static int step_chunk_rows(const std::vector<std::pair<int, int>>& strips, int n_cu)
 {
-    if (strip_split_mode() == 0) return 1;
-    const int ch = strip_split_mode() > 0 ? std::min(strip_split_mode(), kChunkRowsMin) : kChunkRowsMin; // (the bound for every choice)
-    return (int)std::max<int64_t>(1, (rows + ch - 1) / ch);
-}
-// rows per chunk of a strip of mr rows cut into chunks of at most ch rows: even shares, multiples of 16 rows (ch == 0: one chunk)
-static int strip_chunk_share(int mr, int ch)
-{
-    if (ch <= 0 || mr <= ch) return std::max(mr, 1);
-    const int ns = (mr + ch - 1) / ch;
-    return ((mr + ns - 1) / ns + 15) / 16 * 16;
-}
-static int strip_chunks(int mr, int ch)
-{
-    const int share = strip_chunk_share(mr, ch);
-    return std::max(1, (mr + share - 1) / share);
-}
-// chunk rows of a panel step whose strips are (rows, count) pairs; 0: no split (the one-launch strip kernel)
-static int choose_chunk_rows(const std::vector<std::pair<int, int>>& strips, int n_cu)
-{
-    const int mode = strip_split_mode();
-    if (mode == 0) return 0;
-    if (mode > 0) return mode;
-    int64_t n_strips = 0;
-    for (const auto& s : strips) n_strips += s.second;
-    if (n_strips == 0 || n_strips * 4 > (int64_t)n_cu * 3) return 0; // the strips fill three quarters of the chip: leave them whole
     static const int ch_min = getenv("CYB_QR_CHUNK_MIN") ? atoi(getenv("CYB_QR_CHUNK_MIN")) : kChunkRowsMin;
-    for (int ch : kChunkRowsChoices) {
-        if (ch < ch_min) continue;
-        int64_t tot = 0;
-        bool any = false;
-        for (const auto& s : strips) {
-            const int c = strip_chunks(s.first, ch);
-            tot += (int64_t)c * s.second;
-            any = any || c > 1;
-        }
-        if (tot <= n_cu) return any ? ch : 0;
-    }
-    return 0;
+    return choose_chunk_rows(strips, n_cu, strip_split_mode(), ch_min);
 }
-// the chunk descriptors of a strip list; wbase: the partial-W1 workspace (NBK * NBK doubles per chunk)
-static void make_chunks(const std::vector<StripDesc>& sd, double* wbase, int ch, std::vector<ChunkDesc>& out)
+// the partial-W1 workspace of the row-split strips (slot 4): n_slots x NBK * NBK doubles, or null when the strips are never split
+static int split_workspace(cyb_ctx_t ctx, size_t n_slots, double** out)
 {
-    out.clear();
-    size_t slot_base = 0;
-    for (const StripDesc& d : sd) {
-        const int share = strip_chunk_share(d.mr, ch), nch = strip_chunks(d.mr, ch);
-        for (int sl = 0; sl < nch; ++sl) {
-            const int r0 = sl * share;
-            out.push_back(ChunkDesc{d.C + r0, d.V + r0, d.T, wbase + slot_base * (size_t)(NBK * NBK), d.ldc, d.ldv, std::min(share, d.mr - r0), d.nc, d.pw,
-                                    d.transT, sl, nch, r0, d.step, d.ctl, d.part_out ? d.part_out + sl : nullptr});
-        }
-        slot_base += (size_t)nch;
-    }
+    *out = nullptr;
+    if (strip_split_mode() == 0) return CYB_OK;
+    void* w = nullptr;
+    CYB_TRY(ctx->workspace(sizeof(double) * NBK * NBK * std::max<size_t>(n_slots, 1), &w, 4));
+    *out = static_cast<double*>(w);
+    return CYB_OK;
 }
+
+// one more 256-byte aligned piece of a host image that goes up in one upload; returns its offset
+static size_t put(std::vector<char>& image, const void* src, size_t bytes)
+{
+    const size_t off = al256(image.size());
+    image.resize(off + bytes);
+    memcpy(image.data() + off, src, bytes);
+    return off;
+}
+
+// Panel steps are staged, uploaded and launched in CHUNKS of 2, 6, 18, ... steps: the host builds the next chunk while the
+// device runs the previous ones.  With one image for the whole factorisation the device sat idle for the 0.30-0.36 ms it
+// takes to lay out 46 steps of a 15-matrix list (kernel trace of the chi=4096 step: the gap in front of the first panel
+// kernel of either QR).  for (StepChunks c(n); c.more(); c.next()) covers steps [c.begin, c.end) of n.
+struct StepChunks {
+    int n, begin = 0, len = 2, end;
+    explicit StepChunks(int n_steps) : n(n_steps), end(std::min(n_steps, 2)) {}
+    bool more() const { return begin < n; }
+    void next()
+    {
+        begin += len;
+        len *= 3;
+        end = std::min(n, begin + len);
+    }
+};
+
+// The block-reflector update of ONE panel step for the whole batch, staged into the step's host image and launched from
+// its device copy: the row-split pair strip_w1_kernel + strip_apply_kernel when the step's strips are cut into chunks,
+// else the one-launch reflector_strip_kernel.
+struct StripStep {
+    size_t off_sd = 0, off_cd = 0;
+    unsigned n_sd = 0, n_cd = 0;
+    bool norm = false; // some strip leaves its squared norm for the early-stop test (the instantiations with the accumulator)
+    // ch: the step's chunk rows (step_chunk_rows, 0: whole strips; the caller's, because bqr_factor lays out part_out by them), wsplit: the partial-W1 workspace
+    void stage(std::vector<StripDesc>& sd, int ch, double* wsplit, std::vector<char>& image)
+    {
+        if (sd.empty()) return;
+        // longest strips first: the launch is one wave of workgroups, the tail is the longest strip
+        std::stable_sort(sd.begin(), sd.end(), [](const StripDesc& a, const StripDesc& b) { return a.mr > b.mr; });
+        n_sd = (unsigned)sd.size();
+        off_sd = put(image, sd.data(), sizeof(StripDesc) * sd.size());
+        if (ch <= 0) return;
+        std::vector<ChunkDesc> cd;
+        size_t slot_base = 0;
+        for (const StripDesc& d : sd) {
+            const int nch = strip_chunks(d.mr, ch);
+            for (int sl = 0; sl < nch; ++sl) {
+                const StripChunk c = strip_chunk(d.mr, ch, sl);
+                cd.push_back(ChunkDesc{d.C + c.row0, d.V + c.row0, d.T, wsplit + slot_base * (size_t)(NBK * NBK), d.ldc, d.ldv, c.rows, d.nc, d.pw,
+                                       d.transT, sl, nch, c.row0, d.step, d.ctl, d.part_out ? d.part_out + sl : nullptr});
+            }
+            slot_base += (size_t)nch;
+        }
+        n_cd = (unsigned)cd.size();
+        off_cd = put(image, cd.data(), sizeof(ChunkDesc) * cd.size());
+    }
+    int launch(cyb_ctx_t ctx, const void* d_image) const
+    {
+        if (!n_sd) return CYB_OK;
+        const char* base = static_cast<const char*>(d_image);
+        const ChunkDesc* cdp = reinterpret_cast<const ChunkDesc*>(base + off_cd);
+        const StripDesc* sdp = reinterpret_cast<const StripDesc*>(base + off_sd);
+        if (n_cd) {
+            hipLaunchKernelGGL(strip_w1_kernel, dim3(n_cd), dim3(ST_NT), 0, ctx->stream, cdp);
+            if (norm) hipLaunchKernelGGL(strip_apply_kernel<true>, dim3(n_cd), dim3(ST_NT), 0, ctx->stream, cdp);
+            else hipLaunchKernelGGL(strip_apply_kernel<false>, dim3(n_cd), dim3(ST_NT), 0, ctx->stream, cdp);
+        } else if (norm)
+            hipLaunchKernelGGL(reflector_strip_kernel<true>, dim3(n_sd), dim3(ST_NT), 0, ctx->stream, sdp);
+        else
+            hipLaunchKernelGGL(reflector_strip_kernel<false>, dim3(n_sd), dim3(ST_NT), 0, ctx->stream, sdp);
+        CYB_HIP(hipGetLastError());
+        return CYB_OK;
+    }
+};
 
 // ---- wide application of Q (bqr_apply_q): switches, read once per process
 //   CYB_QR_APPLY_WIDE   unset: the shape rule below; 0: strips for every target; 1: wide for every target with more than one panel
@@ -1605,87 +1558,42 @@ size_t bqr_carve(BqrMat& q, char* base, int64_t kc)
     return off;
 }
 
+// the early-stop fields of a panel descriptor (PanelDesc or PanelDescM, see panel_stop_check)
+template <typename Desc>
+static void set_panel_stop(Desc& d, const BqrMat& q, int n_parts, int step)
+{
+    d.ctl = q.ctl;
+    d.parts = q.parts;
+    d.rel2 = q.stop_rel2;
+    d.n_parts = n_parts;
+    d.step = step;
+}
+
 int bqr_factor(cyb_ctx_t ctx, const std::vector<BqrMat>& mats)
 {
     auto pflags = [](const BqrMat& q) { return (q.v_zeroed ? PANEL_V_ZEROED : 0) | (q.reflect_always ? PANEL_REFLECT_ALWAYS : 0); };
     int max_pan = 0;
     for (const auto& q : mats) max_pan = std::max(max_pan, (q.k + NBK - 1) / NBK);
-    // LOOK-AHEAD.  A panel step is [panel kernel: one workgroup per matrix, a latency chain of 32 column steps] ->
-    // [trailing update: two grouped-GEMM launches over the whole chip].  The next panel only needs ITS 32 columns
-    // updated, so the update is cut in two: the next panel's columns (two small launches, main stream) and the rest
-    // (two launches on a side stream that leaves a few CUs free, context aux()).  The rest of step p then runs
-    // BESIDE the panel kernel of step p + 1 instead of in front of it:
-    //   main:  panel(p) . record P[p] . wait R[p-1] . next-columns(p) . panel(p+1) ...          (critical path)
-    //   side:  wait P[p] . rest(p) . record R[p]
-    // (columns >= j1 + 32 are written by rest(p) only, columns [j1, j1 + 32) by next-columns(p) and panel(p + 1) only;
-    //  their scratch regions are disjoint).
-    // MEASURED AND LEFT OFF (opt-in: CYB_QR_LOOKAHEAD=1): correct, but every panel step pays two cross-stream event
-    // waits, and a dependency between two HIP streams costs more than the ~60 us of update it takes off the chain --
-    // chi=4096 SVD list 50.2 -> 62.7 ms, one 1442 x 1442 block 37.0 -> 47.1 ms (profiles/README.md, round 2).
-    static const bool want_la = getenv("CYB_QR_LOOKAHEAD") != nullptr;
-    hipStream_t side = nullptr;
-    const bool strips = use_strips();
-    const bool lookahead = !strips && want_la && max_pan >= 6 && ctx->aux(&side) == CYB_OK;
-    // Stage 1: the descriptors of EVERY panel step (they depend on shapes and pointers only) go into one host
-    // image; stage 2: one upload; stage 3: the launches, panel step by panel step.
+    // A panel step is [panel kernels: one workgroup per matrix (a few for a panel of more than 1536 rows), a latency chain
+    // of 32 column steps] -> [trailing update: the 32-column strips of every matrix in one launch, or in two when their rows
+    // are split (StripStep)].  Stage 1: the descriptors of a chunk of panel steps (they depend on shapes and pointers only)
+    // go into one host image; stage 2: one upload; stage 3: the launches, panel step by panel step.
     struct Step {
-        size_t off_pd = 0, off_pdr = 0;
-        unsigned n_pd = 0, n_pdr = 0;
-        GemmStaged s1, s3;     // whole trailing matrix (unsplit) or its next-panel columns (look-ahead)
-        GemmStaged r1, r3;     // look-ahead: the rest of the trailing matrix
-        bool has_rest = false;
-        size_t off_sd = 0;     // strip formulation: the descriptors of this step's strips
-        unsigned n_sd = 0;
-        bool fused = false;    // some strip of this step factors the next panel (kernel instantiation with the panel body)
-        bool norm = false;     // some strip of this step leaves its squared norm for the early-stop test (kernel instantiation with the accumulator)
-        unsigned n_la = 0;     // role-split look-ahead: panel workgroups behind the strips (their descriptors at off_pn)
-        size_t off_pn = 0;
-        size_t off_cd = 0;     // row-split strips: chunk descriptors (strip_w1_kernel + strip_apply_kernel instead of the strip kernel)
-        unsigned n_cd = 0;
-        int wave = 0;          // every register-resident panel of this step is short enough for the one- / two- / four-wave kernel (1, 2, 4)
-        size_t off_pdm = 0;    // panels of more than 1536 rows: several workgroups per matrix (qr_panel_multi_kernel)
-        unsigned n_pdm = 0;
+        size_t off_pd = 0, off_pdr = 0, off_pdm = 0; // global-memory panels, register-resident panels, multi-workgroup panels
+        unsigned n_pd = 0, n_pdr = 0, n_pdm = 0;
+        int wave = 0; // every register-resident panel of this step is short enough for the one- / two- / four-wave kernel (1, 2, 4)
+        StripStep strips;
     };
     std::vector<Step> steps;
     std::vector<char> image;
-    auto put = [&image](const void* src, size_t bytes) {
-        const size_t off = (image.size() + 255) / 256 * 256;
-        image.resize(off + bytes);
-        memcpy(image.data() + off, src, bytes);
-        return off;
-    };
-    // In-launch look-ahead (strip formulation): the workgroup that updates strip 0 of step p factors panel p + 1 right
-    // after it (reflector_strip_kernel<true>) -- that panel's launch disappears and its latency chain runs beside the
-    // other strips.  BUILT, CORRECT, AND LEFT OFF (opt-in: CYB_QR_FUSE=1; tests/test_gpu_decomp.py runs it): it buys nothing.
-    // The kernel instantiation with the panel body needs scratch and 22 KB more LDS and is ~15 us slower per launch on
-    // the strips of large matrices (41 -> 57 us at chi=4096: 37.6 -> 39.9 ms per step when it served every launch), so it
-    // may only serve steps whose active matrices all have at most CYB_QR_FUSE_ROWS rows (default 768, two panel rows per
-    // thread) -- and there, A/B on one box with the lean kernel back in place for everything else, the toy DMRG at
-    // chi=256 runs 0.300 / 0.291 s per sweep with it and 0.303 / 0.287 without: a panel step of a 140-row matrix is the
-    // 105 us latency chain of the panel either way, the ~8 us strip and one launch gap beside it do not show.
-    static const bool no_fuse = getenv("CYB_QR_FUSE") == nullptr;
-    static const int fuse_rows = getenv("CYB_QR_FUSE_ROWS") ? atoi(getenv("CYB_QR_FUSE_ROWS")) : 768;
-    std::vector<char> fused(mats.size(), 0); // panel p of this matrix was factored inside step p - 1's strip launch
-    // Role-split look-ahead (reflector_strip_kernel<.., LA>): panels of more than la_min_rows rows (the eight-wave register
-    // kernel) are factored by an extra workgroup of the PREVIOUS step's strip launch.
-    // BUILT, CORRECT (tests/test_gpu_decomp.py + test_gpu_fullsize.py green with it on), AND LEFT OFF (opt-in: CYB_QR_LA=1).
-    // Round-3 A/B on one box, two alternations: one 1442 x 1442 block 24.66 / 24.75 ms with it, 24.68 / 24.96 without;
-    // full-rank 1442 55.7-56.0 vs 55.6; chi=4096 15-block list 34.7 / 34.8 ms WITH vs 31.0 / 30.9 without; full-rank 3-block
-    // list 65.6 / 65.9 vs 61.7 / 61.9.  Why it cannot win: every strip of a step takes the same ~38 us (each workgroup
-    // streams the whole 1442 x 32 reflector panel), so the strip the panel waits for finishes WITH the others, not before
-    // them -- the chain per step stays strip + panel (~40 + 117 us) and only the launch gap goes; and the instantiation with
-    // the panel role (115 KB LDS, 12-28 B scratch) slows the strip role of multi-matrix launches by more than that.
-    static const bool la_on = getenv("CYB_QR_LA") && atoi(getenv("CYB_QR_LA")) != 0;
-    static const int la_min_rows = getenv("CYB_QR_LA_MIN") ? atoi(getenv("CYB_QR_LA_MIN")) : 4 * RP_WAVE_ROWS;
-    unsigned int* la_flags = nullptr;
-    const int la_err = (int)mats.size();
-    bool la_used = false;
     // exchange buffers of the multi-workgroup panel kernel (matrices with more than 1536 rows), one region per matrix:
     // [tickets of all matrices | error word | per matrix: NBK x n_wg x 64 doubles]
     static const bool no_multi = getenv("CYB_QR_NOMULTI") != nullptr;
+    static const bool no_reg = getenv("CYB_QR_PANEL_GLOBAL") != nullptr;
+    static const bool no_wave = getenv("CYB_QR_NOWAVE") != nullptr;
     std::vector<size_t> x_off(mats.size(), 0);
     size_t x_bytes = 0, n_multi_wg = 0;
-    const size_t t_bytes = (sizeof(unsigned int) * NBK * mats.size() + 255) / 256 * 256;
+    const size_t t_bytes = al256(sizeof(unsigned int) * NBK * mats.size());
     for (size_t qi = 0; qi < mats.size(); ++qi) {
         const int wmax = (mats[qi].m + RPM_ROWS - 1) / RPM_ROWS;
         if (mats[qi].m > RPM_ROWS && std::min(mats[qi].m, mats[qi].n) > 0) {
@@ -1696,144 +1604,67 @@ int bqr_factor(cyb_ctx_t ctx, const std::vector<BqrMat>& mats)
     }
     const bool multi = !no_multi && x_bytes > 0 && n_multi_wg <= (size_t)ctx->n_cu; // (all workgroups of a launch must be resident)
     char* xbase = nullptr;
-    bool la_any = false; // some panel is tall enough for the role-split look-ahead: its flags live behind the exchange region
-    if (la_on && use_strips())
-        for (const auto& q : mats) la_any = la_any || (q.k > NBK && q.m - NBK > la_min_rows);
-    if (multi || la_any) {
-        const size_t x_total = multi ? (t_bytes + 256 + x_bytes + 255) / 256 * 256 : 0;
+    if (multi) {
         void* xw = nullptr;
-        CYB_TRY(ctx->workspace(x_total + 256 + sizeof(unsigned int) * (mats.size() + 1), &xw, 3));
+        CYB_TRY(ctx->workspace(al256(t_bytes + 256 + x_bytes), &xw, 3));
         xbase = static_cast<char*>(xw);
-        if (multi) CYB_HIP(hipMemsetAsync(xbase + t_bytes, 0, 256, ctx->stream)); // the error word
-        if (la_any) {
-            la_flags = reinterpret_cast<unsigned int*>(xbase + x_total);
-            CYB_HIP(hipMemsetAsync(la_flags, 0, sizeof(unsigned int) * (mats.size() + 1), ctx->stream));
-        }
+        CYB_HIP(hipMemsetAsync(xbase + t_bytes, 0, 256, ctx->stream)); // the error word
     }
-    // The descriptors are built, uploaded and launched in CHUNKS of panel steps (2, 6, 18, ... steps): the host builds the
-    // next chunk while the device runs the previous ones.  With one image for the whole factorisation the device sat idle for
-    // the 0.30-0.36 ms it takes to lay out 46 steps of a 15-matrix list (kernel trace of the chi=4096 step: the gap in front
-    // of the first panel kernel of either QR).
-    const bool multi_ok = multi; // (panels of more than 1536 rows stop too when they run on the multi-workgroup kernel)
     static const bool no_stop = getenv("CYB_QR_NOSTOP") != nullptr;
-    static const bool no_reg_g = getenv("CYB_QR_PANEL_GLOBAL") != nullptr;
-    auto stoppable = [&](const BqrMat& q) {
-        return !no_stop && strips && !no_reg_g && q.ctl && q.parts && q.stop_rel2 > 0.0 && (q.m <= RP_NT * RP_RPT || multi_ok);
+    auto stoppable = [&](const BqrMat& q) { // (panels of more than 1536 rows stop too when they run on the multi-workgroup kernel)
+        return !no_stop && !no_reg && q.ctl && q.parts && q.stop_rel2 > 0.0 && (q.m <= RPM_ROWS || multi);
     };
-    // row-split strips (two launches per step, see strip_w1_kernel): not together with the opt-in look-ahead forms
-    const bool split = strips && strip_split_mode() != 0 && no_fuse && !la_on;
+    size_t n_slots = 0;
+    for (const auto& q : mats) n_slots += (size_t)((q.n + NBK - 1) / NBK) * (size_t)bqr_strip_slots(q.m);
     double* wsplit = nullptr;
-    if (split) {
-        size_t n_ch = 0;
-        for (const auto& q : mats) n_ch += (size_t)((q.n + NBK - 1) / NBK) * (size_t)bqr_strip_slots(q.m);
-        void* w = nullptr;
-        CYB_TRY(ctx->workspace(sizeof(double) * NBK * NBK * std::max<size_t>(n_ch, 1), &w, 4));
-        wsplit = static_cast<double*>(w);
-    }
+    CYB_TRY(split_workspace(ctx, n_slots, &wsplit));
     std::vector<int> n_parts_prev(mats.size(), 0); // strips the previous step's update wrote for this matrix
     static const int stop_every = std::max(1, getenv("CYB_QR_STOP_EVERY") ? atoi(getenv("CYB_QR_STOP_EVERY")) : 2);
-    bool all_done = false;
-    int last_rest = -1;
-    const int side_cu = ctx->n_cu - (ctx->n_cu + 15) / 16; // persistent grid of the side stream: the CUs its mask leaves it
-    int chunk = lookahead ? max_pan : 2;
-    for (int c0 = 0; c0 < max_pan && !all_done; c0 += chunk, chunk *= 3) {
-    const int c1 = std::min(max_pan, c0 + chunk);
-    steps.clear();
-    image.clear();
-    for (int p = c0; p < c1; ++p) {
-        std::vector<PanelDesc> pd, pd_reg, pd_next;
-        std::vector<PanelDescM> pdm;
-        std::vector<StripDesc> sd;
-        GemmBatch g1, g3, h1, h3;
-        int n_active = 0;
-        int max_m = 0; // the fused kernel instantiation serves the whole launch: only when every active matrix is small
-        for (const auto& q : mats)
-            if (p * NBK < q.k) max_m = std::max(max_m, q.m);
-        const bool step_fuse = !no_fuse && max_m <= fuse_rows;
-        const bool step_la = la_on && strips && !step_fuse && la_flags != nullptr;
-        bool step_has_la = false;
-        bool step_norm = false;
-        int step_ch = 0; // chunk rows of this step's strips (0: whole strips)
-        if (split && !step_fuse) {
-            std::vector<std::pair<int, int>> cnt;
+    for (StepChunks c(max_pan); c.more(); c.next()) {
+        steps.clear();
+        image.clear();
+        for (int p = c.begin; p < c.end; ++p) {
+            std::vector<PanelDesc> pd, pd_reg;
+            std::vector<PanelDescM> pdm;
+            std::vector<StripDesc> sd;
+            std::vector<std::pair<int, int>> cnt; // (rows, strips) of every matrix with a trailing block
             for (const auto& q : mats) {
                 const int j0 = p * NBK;
                 if (j0 >= q.k) continue;
                 const int64_t nt = q.n - (j0 + std::min(NBK, q.k - j0));
                 if (nt > 0) cnt.push_back({q.m - j0, (int)((nt + NBK - 1) / NBK)});
             }
-            step_ch = choose_chunk_rows(cnt, ctx->n_cu);
-        }
-        for (size_t qi = 0; qi < mats.size(); ++qi) {
-            const auto& q = mats[qi];
-            const int j0 = p * NBK;
-            if (j0 >= q.k) continue;
-            ++n_active;
-            const int pw = std::min(NBK, q.k - j0);
-            static const bool no_reg = getenv("CYB_QR_PANEL_GLOBAL") != nullptr;
-            if (fused[qi]) fused[qi] = 0;
-            else if (!no_reg && q.m - j0 <= RP_NT * RP_RPT) {
-                pd_reg.push_back(PanelDesc{q.Ac, q.V, q.T + (size_t)p * NBK * NBK, q.tau, q.ld, q.m, j0, pw, pflags(q)});
-                if (stoppable(q)) {
-                    PanelDesc& d = pd_reg.back();
-                    d.ctl = q.ctl;
-                    d.parts = q.parts;
-                    d.rel2 = q.stop_rel2;
-                    d.n_parts = n_parts_prev[qi];
-                    d.step = p;
-                }
-            } else if (multi && !no_reg) {
-                const int n_wg = (q.m - j0 + RPM_ROWS - 1) / RPM_ROWS;
-                for (int w = 0; w < n_wg; ++w)
-                {
-                    pdm.push_back(PanelDescM{q.Ac, q.V, q.T + (size_t)p * NBK * NBK, q.tau, reinterpret_cast<double*>(xbase + x_off[qi]),
-                                             reinterpret_cast<unsigned int*>(xbase) + qi * NBK, reinterpret_cast<unsigned int*>(xbase + t_bytes),
-                                             q.ld, q.m, j0, pw, pflags(q), w, n_wg, 0, 0});
-                    if (stoppable(q)) {
-                        PanelDescM& d = pdm.back();
-                        d.ctl = q.ctl;
-                        d.parts = q.parts;
-                        d.rel2 = q.stop_rel2;
-                        d.n_parts = n_parts_prev[qi];
-                        d.step = p;
+            const int step_ch = step_chunk_rows(cnt, ctx->n_cu);
+            Step st;
+            for (size_t qi = 0; qi < mats.size(); ++qi) {
+                const auto& q = mats[qi];
+                const int j0 = p * NBK;
+                if (j0 >= q.k) continue;
+                const int pw = std::min(NBK, q.k - j0);
+                double* Tp = q.T + (size_t)p * NBK * NBK;
+                const bool stop = stoppable(q);
+                // ---- the panel: register-resident, spread over several workgroups, or (fallback) in global memory
+                if (!no_reg && q.m - j0 <= RPM_ROWS) {
+                    pd_reg.push_back(PanelDesc{q.Ac, q.V, Tp, q.tau, q.ld, q.m, j0, pw, pflags(q)});
+                    if (stop) set_panel_stop(pd_reg.back(), q, n_parts_prev[qi], p);
+                } else if (multi && !no_reg) {
+                    const int n_wg = (q.m - j0 + RPM_ROWS - 1) / RPM_ROWS;
+                    for (int w = 0; w < n_wg; ++w) {
+                        pdm.push_back(PanelDescM{q.Ac, q.V, Tp, q.tau, reinterpret_cast<double*>(xbase + x_off[qi]),
+                                                 reinterpret_cast<unsigned int*>(xbase) + qi * NBK, reinterpret_cast<unsigned int*>(xbase + t_bytes),
+                                                 q.ld, q.m, j0, pw, pflags(q), w, n_wg, 0, 0});
+                        if (stop) set_panel_stop(pdm.back(), q, n_parts_prev[qi], p);
                     }
-                }
-            } else
-                pd.push_back(PanelDesc{q.Ac, q.V, q.T + (size_t)p * NBK * NBK, q.tau, q.ld, q.m, j0, pw, pflags(q) & PANEL_REFLECT_ALWAYS});
-            const int j1 = j0 + pw;
-            const int64_t nt = q.n - j1, mr = q.m - j0;
-            const int parts_lag = n_parts_prev[qi];
-            n_parts_prev[qi] = 0;
-            if (nt <= 0) continue;
-            double* W1 = q.scratch + q.scr_half; // up to kWSplit partials of scr_half doubles
-            const double* Vp = q.V + (size_t)j0 * q.ld + j0;        // (i,a) at a*ld + i
-            const double* Tp = q.T + (size_t)p * NBK * NBK;
-            if (strips) {
-                int64_t tag = -1;
-                if (step_fuse && !no_reg && !stoppable(q) && j1 < q.k && q.m - j1 <= RP_NT * RP_RPT_FUSED) {
-                    tag = (int64_t)pd_next.size();
-                    pd_next.push_back(PanelDesc{q.Ac, q.V, q.T + (size_t)(p + 1) * NBK * NBK, q.tau, q.ld, q.m, j1, std::min(NBK, q.k - j1), pflags(q)});
-                    fused[qi] = 1;
-                } else if (step_la && !no_reg && j1 < q.k && q.m - j1 <= RP_NT * RP_RPT && q.m - j1 > la_min_rows) {
-                    tag = (int64_t)pd_next.size();
-                    pd_next.push_back(PanelDesc{q.Ac, q.V, q.T + (size_t)(p + 1) * NBK * NBK, q.tau, q.ld, q.m, j1, std::min(NBK, q.k - j1), pflags(q)});
-                    if (stoppable(q)) {
-                        // the panel runs BESIDE this step's strips: it may only read the norms the previous step left, and only
-                        // if this step does not overwrite them (the stop then comes one panel later than without look-ahead)
-                        const bool measure = p % stop_every == stop_every - 1;
-                        PanelDesc& d = pd_next.back();
-                        d.ctl = q.ctl;
-                        d.parts = q.parts;
-                        d.rel2 = q.stop_rel2;
-                        d.n_parts = measure ? 0 : parts_lag;
-                        d.step = p + 1;
-                    }
-                    fused[qi] = 1;
-                    step_has_la = true;
-                }
+                } else
+                    pd.push_back(PanelDesc{q.Ac, q.V, Tp, q.tau, q.ld, q.m, j0, pw, pflags(q) & PANEL_REFLECT_ALWAYS});
+                // ---- the strips of the trailing block A[j0:, j1:]
+                const int j1 = j0 + pw;
+                const int64_t nt = q.n - j1, mr = q.m - j0;
+                n_parts_prev[qi] = 0;
+                if (nt <= 0) continue;
                 const size_t s_begin = sd.size();
-                add_strips(sd, q.Ac + (size_t)j1 * q.ld + j0, q.ld, nt, Vp, q.ld, Tp, mr, pw, 1, tag);
-                if (stoppable(q)) {
+                add_strips(sd, q.Ac + (size_t)j1 * q.ld + j0, q.ld, nt, q.V + (size_t)j0 * q.ld + j0, q.ld, Tp, mr, pw, 1);
+                if (stop) {
                     const bool measure = p % stop_every == stop_every - 1; // (the trailing norm is measured every stop_every-th step)
                     const int nch = strip_chunks((int)mr, step_ch); // (every strip of a matrix has the same rows: the same chunks)
                     for (size_t si = s_begin; si < sd.size(); ++si) {
@@ -1843,160 +1674,48 @@ int bqr_factor(cyb_ctx_t ctx, const std::vector<BqrMat>& mats)
                     }
                     if (measure) {
                         n_parts_prev[qi] = (int)(sd.size() - s_begin) * nch;
-                        step_norm = true;
+                        st.strips.norm = true;
                     }
                 }
-                continue;
             }
-            // W2_s (pw x nt) = T^T (Vp[rows of chunk s]^T At[rows of chunk s]): the T factor is applied in the
-            // epilogue of the product (left factor of the grouped GEMM), the row-chunk partials are summed
-            // as K-segments of the rank-pw update:  At^T (nt x mr, ld) -= sum_s W2_s^T Vp^T
-            const int ns = w_split(mr);
-            const int64_t chunk = ((mr + ns - 1) / ns + 15) / 16 * 16;
-            // column ranges of the trailing matrix: [0, nn) = the next panel (or everything), [nn, nt) = the rest
-            const int64_t nn = lookahead ? std::min<int64_t>(NBK, nt) : nt;
-            auto add = [&](GemmBatch& a1, GemmBatch& a3, int64_t c0, int64_t nc, size_t scr_off) {
-                if (nc <= 0) return;
-                double* At = q.Ac + (size_t)(j1 + c0) * q.ld + j0;  // (i,c) at c*ld + i
-                const int32_t seg0 = (int32_t)a3.segs.size();
-                for (int sidx = 0; sidx < ns; ++sidx) {
-                    const int64_t r0 = chunk * sidx, rows = std::min(chunk, mr - r0);
-                    if (rows <= 0) break;
-                    double* W2s = W1 + (size_t)sidx * q.scr_half + scr_off;
-                    a1.add_post(W2s, pw, nc, nc, Vp + r0, q.ld, 1, At + r0, 1, q.ld, rows, 1.0, 0.0, Tp, 1, NBK);
-                    a3.segs.push_back(cyb_gemm_seg{W2s, Vp, pw, 1, nc, q.ld, 1});
-                }
-                a3.probs.push_back(cyb_gemm_prob{At, nc, mr, q.ld, seg0, (int32_t)a3.segs.size(), -1.0, 1.0});
-            };
-            add(g1, g3, 0, nn, 0);
-            add(h1, h3, nn, nt - nn, (size_t)NBK * NBK); // (scratch: NBK*NBK doubles for the next-panel part, the rest behind it)
+            st.n_pd = (unsigned)pd.size();
+            st.n_pdr = (unsigned)pd_reg.size();
+            st.n_pdm = (unsigned)pdm.size();
+            if (st.n_pd) st.off_pd = put(image, pd.data(), sizeof(PanelDesc) * pd.size());
+            if (st.n_pdr) st.off_pdr = put(image, pd_reg.data(), sizeof(PanelDesc) * pd_reg.size());
+            if (st.n_pdm) st.off_pdm = put(image, pdm.data(), sizeof(PanelDescM) * pdm.size());
+            int max_rows = 0;
+            for (const auto& d : pd_reg) max_rows = std::max(max_rows, d.m - d.j0);
+            st.wave = (no_wave || st.n_pdr == 0) ? 0 : max_rows <= RP_WAVE_ROWS ? 1 : max_rows <= 2 * RP_WAVE_ROWS ? 2 : max_rows <= 4 * RP_WAVE_ROWS ? 4 : 0;
+            st.strips.stage(sd, step_ch, wsplit, image);
+            steps.push_back(st);
         }
-        if (n_active == 0) {
-            all_done = true;
-            break;
-        }
-        Step st;
-        st.n_pd = (unsigned)pd.size();
-        st.n_pdr = (unsigned)pd_reg.size();
-        if (st.n_pd) st.off_pd = put(pd.data(), sizeof(PanelDesc) * pd.size());
-        if (st.n_pdr) st.off_pdr = put(pd_reg.data(), sizeof(PanelDesc) * pd_reg.size());
-        st.n_pdm = (unsigned)pdm.size();
-        if (st.n_pdm) st.off_pdm = put(pdm.data(), sizeof(PanelDescM) * pdm.size());
-        static const bool no_wave = getenv("CYB_QR_NOWAVE") != nullptr;
-        int max_rows = 0;
-        for (const auto& d : pd_reg) max_rows = std::max(max_rows, d.m - d.j0);
-        st.wave = (no_wave || st.n_pdr == 0) ? 0 : max_rows <= RP_WAVE_ROWS ? 1 : max_rows <= 2 * RP_WAVE_ROWS ? 2 : max_rows <= 4 * RP_WAVE_ROWS ? 4 : 0;
-        if (!sd.empty()) {
-            sort_strips(sd);
-            st.n_sd = (unsigned)sd.size();
-            st.fused = !pd_next.empty() && !step_has_la;
-            st.norm = step_norm;
-            const size_t off_pn = pd_next.empty() ? 0 : put(pd_next.data(), sizeof(PanelDesc) * pd_next.size());
-            const size_t off_sd = (image.size() + 255) / 256 * 256; // (where put() will place the strips)
-            if (step_has_la) { // (next_off stays the index + 1 of the panel entry = of its flag)
-                st.n_la = (unsigned)pd_next.size();
-                st.off_pn = off_pn;
-                la_used = true;
-            } else
-                for (auto& d : sd)
-                    if (d.next_off) d.next_off = (int64_t)(off_pn + (size_t)(d.next_off - 1) * sizeof(PanelDesc)) - (int64_t)off_sd;
-            st.off_sd = put(sd.data(), sizeof(StripDesc) * sd.size());
-            if (step_ch > 0 && !st.fused && !st.n_la) {
-                std::vector<ChunkDesc> cd;
-                make_chunks(sd, wsplit, step_ch, cd);
-                st.n_cd = (unsigned)cd.size();
-                st.off_cd = put(cd.data(), sizeof(ChunkDesc) * cd.size());
+        void* d_image = nullptr;
+        CYB_TRY(ctx->upload(image.data(), image.size(), &d_image));
+        char* dbase = static_cast<char*>(d_image);
+        for (const Step& st : steps) {
+            if (st.n_pd)
+                hipLaunchKernelGGL(qr_panel_kernel, dim3(st.n_pd), dim3(PNT), 0, ctx->stream,
+                                   reinterpret_cast<const PanelDesc*>(dbase + st.off_pd));
+            if (st.n_pdm) {
+                CYB_HIP(hipMemsetAsync(xbase, 0, t_bytes, ctx->stream)); // the tickets of every matrix
+                hipLaunchKernelGGL(qr_panel_multi_kernel, dim3(st.n_pdm), dim3(RP_NT), 0, ctx->stream,
+                                   reinterpret_cast<const PanelDescM*>(dbase + st.off_pdm));
             }
-        }
-        if (!g1.empty()) {
-            CYB_TRY(g1.stage(ctx, image, st.s1));
-            CYB_TRY(g3.stage(ctx, image, st.s3));
-        }
-        if (!h1.empty()) {
-            CYB_TRY(h1.stage(ctx, image, st.r1));
-            CYB_TRY(h3.stage(ctx, image, st.r3));
-            st.has_rest = true;
-        }
-        steps.push_back(st);
-    }
-    if (steps.empty()) break;
-    void* d_image = nullptr;
-    CYB_TRY(ctx->upload(image.data(), image.size(), &d_image));
-    char* dbase = static_cast<char*>(d_image);
-    if (lookahead) CYB_TRY(ctx->events(2 * steps.size()));
-    for (size_t p = 0; p < steps.size(); ++p) {
-        const Step& st = steps[p];
-        if (st.n_pd)
-            hipLaunchKernelGGL(qr_panel_kernel, dim3(st.n_pd), dim3(PNT), 0, ctx->stream,
-                               reinterpret_cast<const PanelDesc*>(dbase + st.off_pd));
-        if (st.n_pdm) {
-            CYB_HIP(hipMemsetAsync(xbase, 0, t_bytes, ctx->stream)); // the tickets of every matrix
-            hipLaunchKernelGGL(qr_panel_multi_kernel, dim3(st.n_pdm), dim3(RP_NT), 0, ctx->stream,
-                               reinterpret_cast<const PanelDescM*>(dbase + st.off_pdm));
-        }
-        if (st.n_pdr && st.wave == 1)
-            hipLaunchKernelGGL(qr_panel_wave_kernel, dim3(st.n_pdr), dim3(64), 0, ctx->stream,
-                               reinterpret_cast<const PanelDesc*>(dbase + st.off_pdr));
-        else if (st.n_pdr && st.wave == 2)
-            hipLaunchKernelGGL(qr_panel_wave2_kernel, dim3(st.n_pdr), dim3(128), 0, ctx->stream,
-                               reinterpret_cast<const PanelDesc*>(dbase + st.off_pdr));
-        else if (st.n_pdr && st.wave == 4)
-            hipLaunchKernelGGL(qr_panel_wave4_kernel, dim3(st.n_pdr), dim3(256), 0, ctx->stream,
-                               reinterpret_cast<const PanelDesc*>(dbase + st.off_pdr));
-        else if (st.n_pdr)
-            hipLaunchKernelGGL(qr_panel_reg_kernel, dim3(st.n_pdr), dim3(RP_NT), 0, ctx->stream,
-                               reinterpret_cast<const PanelDesc*>(dbase + st.off_pdr));
-        CYB_HIP(hipGetLastError());
-        if (lookahead && st.has_rest) {
-            hipEvent_t evP = ctx->ev_pool[2 * p], evR = ctx->ev_pool[2 * p + 1];
-            CYB_HIP(hipEventRecord(evP, ctx->stream));
-            CYB_HIP(hipStreamWaitEvent(side, evP, 0));
-            CYB_TRY(gemm_launch_staged(ctx, st.r1, d_image, side, side_cu));
-            CYB_TRY(gemm_launch_staged(ctx, st.r3, d_image, side, side_cu));
-            CYB_HIP(hipEventRecord(evR, side));
-            if (last_rest >= 0) CYB_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_pool[2 * (size_t)last_rest + 1], 0));
-            last_rest = (int)p;
-        } else if (lookahead && last_rest >= 0) {
-            CYB_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_pool[2 * (size_t)last_rest + 1], 0));
-            last_rest = -1;
-        }
-        if (st.n_sd) {
-            const StripDesc* sdp = reinterpret_cast<const StripDesc*>(dbase + st.off_sd);
-            const PanelDesc* pnp = reinterpret_cast<const PanelDesc*>(dbase + st.off_pn);
-            const unsigned la_tag = (unsigned)(c0 + (int)p + 1); // (unique per panel step of this call; the flags start at zero)
-            const PanelDesc* no_pn = nullptr;
-            unsigned int* no_fl = nullptr;
-            if (st.n_cd) {
-                const ChunkDesc* cdp = reinterpret_cast<const ChunkDesc*>(dbase + st.off_cd);
-                hipLaunchKernelGGL(strip_w1_kernel, dim3(st.n_cd), dim3(ST_NT), 0, ctx->stream, cdp);
-                if (st.norm) hipLaunchKernelGGL(strip_apply_kernel<true>, dim3(st.n_cd), dim3(ST_NT), 0, ctx->stream, cdp);
-                else hipLaunchKernelGGL(strip_apply_kernel<false>, dim3(st.n_cd), dim3(ST_NT), 0, ctx->stream, cdp);
-            } else if (st.n_la && st.norm)
-                hipLaunchKernelGGL((reflector_strip_kernel<false, true, true>), dim3(st.n_sd + st.n_la), dim3(ST_NT), 0, ctx->stream, sdp,
-                                   (int)st.n_sd, pnp, la_flags, la_tag, la_err);
-            else if (st.n_la)
-                hipLaunchKernelGGL((reflector_strip_kernel<false, false, true>), dim3(st.n_sd + st.n_la), dim3(ST_NT), 0, ctx->stream, sdp,
-                                   (int)st.n_sd, pnp, la_flags, la_tag, la_err);
-            else if (st.fused)
-                hipLaunchKernelGGL(reflector_strip_kernel<true>, dim3(st.n_sd), dim3(ST_NT), 0, ctx->stream, sdp, (int)st.n_sd, no_pn, no_fl, 0u, 0);
-            else if (st.norm)
-                hipLaunchKernelGGL((reflector_strip_kernel<false, true>), dim3(st.n_sd), dim3(ST_NT), 0, ctx->stream, sdp, (int)st.n_sd, no_pn, no_fl, 0u, 0);
-            else
-                hipLaunchKernelGGL(reflector_strip_kernel<false>, dim3(st.n_sd), dim3(ST_NT), 0, ctx->stream, sdp, (int)st.n_sd, no_pn, no_fl, 0u, 0);
+            if (st.n_pdr && st.wave == 1)
+                hipLaunchKernelGGL(qr_panel_wave_kernel, dim3(st.n_pdr), dim3(64), 0, ctx->stream,
+                                   reinterpret_cast<const PanelDesc*>(dbase + st.off_pdr));
+            else if (st.n_pdr && st.wave == 2)
+                hipLaunchKernelGGL(qr_panel_wave2_kernel, dim3(st.n_pdr), dim3(128), 0, ctx->stream,
+                                   reinterpret_cast<const PanelDesc*>(dbase + st.off_pdr));
+            else if (st.n_pdr && st.wave == 4)
+                hipLaunchKernelGGL(qr_panel_wave4_kernel, dim3(st.n_pdr), dim3(256), 0, ctx->stream,
+                                   reinterpret_cast<const PanelDesc*>(dbase + st.off_pdr));
+            else if (st.n_pdr)
+                hipLaunchKernelGGL(qr_panel_reg_kernel, dim3(st.n_pdr), dim3(RP_NT), 0, ctx->stream,
+                                   reinterpret_cast<const PanelDesc*>(dbase + st.off_pdr));
             CYB_HIP(hipGetLastError());
-        }
-        CYB_TRY(gemm_launch_staged(ctx, st.s1, d_image));
-        CYB_TRY(gemm_launch_staged(ctx, st.s3, d_image));
-    }
-    } // chunks of panel steps
-    if (last_rest >= 0) CYB_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_pool[2 * (size_t)last_rest + 1], 0)); // join
-    if (la_used) { // (a wait that ran out of time means wrong factors, not a hang)
-        unsigned int h_err = 0;
-        CYB_HIP(hipMemcpyAsync(&h_err, la_flags + la_err, sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
-        CYB_HIP(hipStreamSynchronize(ctx->stream));
-        if (h_err) {
-            set_error("blocked QR: a look-ahead panel workgroup waited more than a second for its strip");
-            return CYB_ERR_HIP;
+            CYB_TRY(st.strips.launch(ctx, d_image));
         }
     }
     if (multi) { // (the rare path pays one read-back: a poll that ran out of time means wrong factors, not a hang)
@@ -2016,114 +1735,44 @@ static int apply_q_strips(cyb_ctx_t ctx, const std::vector<BqrMat>& mats, const 
 {
     int max_pan = 0;
     for (const auto& t : targets) max_pan = std::max(max_pan, (mats[(size_t)t.mat].k + NBK - 1) / NBK);
-    const bool strips = use_strips();
-    struct Step {
-        GemmStaged s1, s3;
-        size_t off_sd = 0;
-        unsigned n_sd = 0;
-        size_t off_cd = 0; // row-split strips (see bqr_factor)
-        unsigned n_cd = 0;
-    };
-    const bool split = strips && strip_split_mode() != 0;
+    size_t n_slots = 0;
+    for (const auto& t : targets) n_slots += (size_t)((t.kc + NBK - 1) / NBK) * (size_t)bqr_strip_slots(mats[(size_t)t.mat].m);
     double* wsplit = nullptr;
-    if (split) {
-        size_t n_ch = 0;
-        for (const auto& t : targets) n_ch += (size_t)((t.kc + NBK - 1) / NBK) * (size_t)bqr_strip_slots(mats[(size_t)t.mat].m);
-        void* w = nullptr;
-        CYB_TRY(ctx->workspace(sizeof(double) * NBK * NBK * std::max<size_t>(n_ch, 1), &w, 4));
-        wsplit = static_cast<double*>(w);
-    }
-    std::vector<Step> steps; // panel steps staged in chunks (2, 6, 18, ... steps), one descriptor upload per chunk: the host
-    std::vector<char> image; // lays out the next chunk while the device runs the previous ones (see bqr_factor)
-    int chunk = 2;
-    for (int c0 = max_pan - 1; c0 >= 0; c0 -= chunk, chunk *= 3) {
-    const int c1 = std::max(-1, c0 - chunk); // steps c0, c0 - 1, ..., c1 + 1
-    steps.clear();
-    image.clear();
-    for (int p = c0; p > c1; --p) {
-        GemmBatch g1, g3;
-        std::vector<StripDesc> sd;
-        for (const auto& t : targets) {
-            const BqrMat& q = mats[(size_t)t.mat];
-            const int j0 = p * NBK;
-            if (j0 >= q.k || t.kc <= 0) continue;
-            const int pw = std::min(NBK, q.k - j0);
-            const int64_t mr = q.m - j0;
-            double* W1 = q.scratch + q.scr_half;
-            CYB_REQUIRE((int64_t)NBK * t.kc <= q.scr_half, "bqr_apply_q: target wider than the carved scratch");
-            const double* Vp = q.V + (size_t)j0 * q.ld + j0;
-            double* Ct = t.C + j0; // rows j0.. of every column
-            const double* Tp = q.T + (size_t)p * NBK * NBK;
-            if (strips) {
+    CYB_TRY(split_workspace(ctx, n_slots, &wsplit));
+    std::vector<StripStep> steps;
+    std::vector<char> image;
+    for (StepChunks c(max_pan); c.more(); c.next()) {
+        steps.clear();
+        image.clear();
+        for (int i = c.begin; i < c.end; ++i) {
+            const int p = max_pan - 1 - i;
+            std::vector<StripDesc> sd;
+            for (const auto& t : targets) {
+                const BqrMat& q = mats[(size_t)t.mat];
+                const int j0 = p * NBK;
+                if (j0 >= q.k || t.kc <= 0) continue;
+                CYB_REQUIRE((int64_t)NBK * t.kc <= q.scr_half, "bqr_apply_q: target wider than the carved scratch");
                 const size_t s_begin = sd.size();
-                add_strips(sd, Ct, t.ldc, t.kc, Vp, q.ld, Tp, mr, pw, 0);
+                // rows j0.. of every column of the target
+                add_strips(sd, t.C + j0, t.ldc, t.kc, q.V + (size_t)j0 * q.ld + j0, q.ld, q.T + (size_t)p * NBK * NBK, q.m - j0, std::min(NBK, q.k - j0), 0);
                 if (q.ctl && q.stop_rel2 > 0.0) // (panels the factorisation skipped are the identity: their strips return at once)
                     for (size_t si = s_begin; si < sd.size(); ++si) {
                         sd[si].ctl = q.ctl;
                         sd[si].step = p;
                     }
-                continue;
             }
-            // W2_s = T (Vp[chunk s]^T C[chunk s]) (T in the epilogue);  C^T -= sum_s W2_s^T Vp^T
-            const int ns = w_split(mr);
-            const int64_t chunk = ((mr + ns - 1) / ns + 15) / 16 * 16;
-            const int32_t seg0 = (int32_t)g3.segs.size();
-            for (int sidx = 0; sidx < ns; ++sidx) {
-                const int64_t r0 = chunk * sidx, rows = std::min(chunk, mr - r0);
-                if (rows <= 0) break;
-                double* W2s = W1 + (size_t)sidx * q.scr_half;
-                g1.add_post(W2s, pw, t.kc, t.kc, Vp + r0, q.ld, 1, Ct + r0, 1, t.ldc, rows, 1.0, 0.0, Tp, NBK, 1);
-                g3.segs.push_back(cyb_gemm_seg{W2s, Vp, pw, 1, t.kc, q.ld, 1});
-            }
-            g3.probs.push_back(cyb_gemm_prob{Ct, t.kc, mr, t.ldc, seg0, (int32_t)g3.segs.size(), -1.0, 1.0});
-        }
-        if (g1.empty() && sd.empty()) continue;
-        Step st;
-        if (!g1.empty()) {
-            CYB_TRY(g1.stage(ctx, image, st.s1));
-            CYB_TRY(g3.stage(ctx, image, st.s3));
-        }
-        if (!sd.empty()) {
-            sort_strips(sd);
-            st.n_sd = (unsigned)sd.size();
-            const size_t off = (image.size() + 255) / 256 * 256;
-            image.resize(off + sizeof(StripDesc) * sd.size());
-            memcpy(image.data() + off, sd.data(), sizeof(StripDesc) * sd.size());
-            st.off_sd = off;
+            if (sd.empty()) continue;
             std::vector<std::pair<int, int>> cnt;
             for (const auto& d : sd) cnt.push_back({d.mr, 1});
-            const int step_ch = split ? choose_chunk_rows(cnt, ctx->n_cu) : 0;
-            if (step_ch > 0) {
-                std::vector<ChunkDesc> cd;
-                make_chunks(sd, wsplit, step_ch, cd);
-                st.n_cd = (unsigned)cd.size();
-                const size_t offc = (image.size() + 255) / 256 * 256;
-                image.resize(offc + sizeof(ChunkDesc) * cd.size());
-                memcpy(image.data() + offc, cd.data(), sizeof(ChunkDesc) * cd.size());
-                st.off_cd = offc;
-            }
+            StripStep st;
+            st.stage(sd, step_chunk_rows(cnt, ctx->n_cu), wsplit, image);
+            steps.push_back(st);
         }
-        steps.push_back(st);
+        if (steps.empty()) continue;
+        void* d_image = nullptr;
+        CYB_TRY(ctx->upload(image.data(), image.size(), &d_image));
+        for (const auto& st : steps) CYB_TRY(st.launch(ctx, d_image));
     }
-    if (steps.empty()) continue;
-    void* d_image = nullptr;
-    CYB_TRY(ctx->upload(image.data(), image.size(), &d_image));
-    for (const auto& st : steps) {
-        if (st.n_cd) {
-            const ChunkDesc* cdp = reinterpret_cast<const ChunkDesc*>(static_cast<char*>(d_image) + st.off_cd);
-            hipLaunchKernelGGL(strip_w1_kernel, dim3(st.n_cd), dim3(ST_NT), 0, ctx->stream, cdp);
-            hipLaunchKernelGGL(strip_apply_kernel<false>, dim3(st.n_cd), dim3(ST_NT), 0, ctx->stream, cdp);
-            CYB_HIP(hipGetLastError());
-        } else if (st.n_sd) {
-            hipLaunchKernelGGL(reflector_strip_kernel<false>, dim3(st.n_sd), dim3(ST_NT), 0, ctx->stream,
-                               reinterpret_cast<const StripDesc*>(static_cast<char*>(d_image) + st.off_sd), (int)st.n_sd,
-                               static_cast<const PanelDesc*>(nullptr), static_cast<unsigned int*>(nullptr), 0u, 0);
-            CYB_HIP(hipGetLastError());
-        }
-        CYB_TRY(gemm_launch_staged(ctx, st.s1, d_image));
-        CYB_TRY(gemm_launch_staged(ctx, st.s3, d_image));
-    }
-    } // chunks of panel steps
     return CYB_OK;
 }
 
