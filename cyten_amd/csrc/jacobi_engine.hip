@@ -1089,6 +1089,11 @@ struct SScratch {
     // the update fills what was idle time.  readyJ[block][part]: rounds whose J update (or skip) is complete, as `ready` for W.
     unsigned int* readyJ;
     int defer_j;
+    // Granule form of the Gram exchange (template parameter GRAN): [part of the launch][round parity] regions of SW_GRAN_U64
+    // tagged words each, zeroed with the counters before every launch.  A matrix's regions start at unit
+    // (RPair.pad[1] - gran_np), its pair `slot` at 2 * slot * G behind that: [parity][part].
+    unsigned long long* gran;
+    int gran_np;
     // Cross-only pivot solves (real engine, one inner sweep): the 31 rotation sets of a pivot solve are 16 sets of pairs (row of
     // block P, row of block Q) and 15 sets of pairs inside a block.  A sweep needs every pair of rows ONCE; the pairs inside a
     // block are met again in every round the block takes part in.  With cross_every = k > 0 only the rounds with round % k == 0
@@ -1099,6 +1104,10 @@ constexpr int SW_MAX_ENT = 64; // entries per workgroup the one-launch form keep
 
 constexpr int SW_UN = 8;                                        // 8-column Gram chunks in flight per wave and buffer
 constexpr int SW_PRE = 6;                                       // update chunks held in registers across the eigensolve
+// One partial Gram as granules: every double is two 8-byte words {tag, low half} {tag, high half} (tag in the upper 32 bits),
+// each written by ONE aligned 8-byte store and read by one 8-byte load.
+constexpr int SW_GRAN_U64 = 2 * JP * JP;
+constexpr unsigned int SW_GRAN_BYTES = 8u * SW_GRAN_U64;
 // [Gs | region shared by the wave slices of the partial Gram (Xc) and the eigensolver's G2 / Va / Vb | Qm of this round and of the
 //  previous one (the deferred J update still reads it while the next Gram runs) | reduction scratch]
 constexpr int SWEEP_XREG = (4 * JP * GS > JP * GS + 2 * JP * VS) ? 4 * JP * GS : JP * GS + 2 * JP * VS;
@@ -1209,7 +1218,9 @@ __device__ __forceinline__ void sweep_update_j(const __amdgpu_buffer_rsrc_t rsJ,
     }
 }
 
-template <bool CPLX, bool RORD>
+// GRAN: the partial Grams travel as tagged granules (step 2; false: stores, drain, ticket and poll as before, kept for
+// A/B -- CYB_JACOBI_EXCHANGE=0)
+template <bool CPLX, bool RORD, bool GRAN>
 __global__ void __launch_bounds__(NT, 1)
 jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned long long* __restrict__ offmax_bits, SScratch sc)
 {
@@ -1228,7 +1239,7 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
     int* perm = ibase;
     int* zrow = ibase + JP;
     int* zout = ibase + 2 * JP;
-    int* flags = ibase + 3 * JP; // [0] any null  [1] wait ok  [2] every entry of this workgroup has converged
+    int* flags = ibase + 3 * JP; // [0] any null  [1] wait ok  [2] every entry of this workgroup has converged  [3] a granule sweep gave up
     int* edone = flags + 4;      // [SW_MAX_ENT] one-launch form: entry has converged
 
     const int tid = threadIdx.x;
@@ -1296,6 +1307,9 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
             if (!flags[1]) return;
         }
         SWEEP_STAMP(1);
+        if constexpr (GRAN) {
+            if (tid == 0) flags[3] = 0; // (read behind the barrier that ends step 2; two barriers lie between)
+        }
         // byte offset of element (row k of the pair, own chunk c, column un of this wave's 16) and its descriptor
         auto chunk_off = [&](int c, int k, bool& in_w) -> unsigned int {
             in_w = c < nW;
@@ -1430,7 +1444,33 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
             // ---- 2. exchange of the partials among the G parts (double buffered by round parity)
             const __amdgpu_buffer_rsrc_t rs_all = __builtin_amdgcn_make_buffer_rsrc(
                 sc.gpart + ((size_t)pi * 2 + (size_t)(ground & 1)) * RGMAX * (JP * JP), 0, (int)(pbytes * G), 0x00020000);
-            if (G > 1) {
+            // Granule form: the data is the flag.  Every 32-bit half of a partial travels in an 8-byte word {tag, half}, written
+            // by ONE aligned 8-byte agent-scope store (write-through), tag = ground + 1: counted within the launch, never 0
+            // (the regions are zeroed before every launch), different in every round this pair runs in the launch.  No drain,
+            // no barrier, no ticket: a consumer re-reads the words until every tag is this round's and then holds the data.
+            // The regions are double buffered by round parity like the slabs of the ticket form, by the same argument: a
+            // part stores round g + 2 only after its own sweep of round g + 1 has seen every partner's words of g + 1, and a
+            // partner stores those only after its sweep of round g has ended -- nobody still reads what g + 2 overwrites, and
+            // a reader of round g can meet the tags g - 1 (or 0) and g + 1 only.
+            const unsigned int gtag = (unsigned int)(ground + 1);
+            GLOBAL_AS unsigned long long* gran_pair =
+                (GLOBAL_AS unsigned long long*)sc.gran +
+                ((size_t)(mt.pad[1] - sc.gran_np) + (size_t)(2 * mt.slot + (ground & 1)) * (size_t)G) * SW_GRAN_U64;
+            if constexpr (GRAN) {
+                if (G > 1) {
+                    // word j of lane l of wave w sits at [w][j][l]: the 64 lanes of a store fill 512 contiguous bytes
+                    // (thread-major, 64 partial lines per store: exchange 8.3 us)
+                    GLOBAL_AS unsigned long long* mine = gran_pair + (size_t)part * SW_GRAN_U64 + (size_t)(wave * 512 + lane);
+                    const double v[4] = {lo.x, lo.y, hi.x, hi.y};
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        __hip_atomic_store(mine + 128 * k, ((unsigned long long)gtag << 32) | (unsigned int)__double2loint(v[k]), __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT);
+                        __hip_atomic_store(mine + 128 * k + 64, ((unsigned long long)gtag << 32) | (unsigned int)__double2hiint(v[k]), __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                }
+            } else if (G > 1) {
                 Q16 a, b;
                 a.d = lo;
                 b.d = hi;
@@ -1441,9 +1481,9 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
                 __syncthreads();
                 if (tid == 0) __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
-            // The update's operands go out HERE: behind the ticket, so that nothing the partners wait for queues behind them,
-            // and in front of the poll, so that their issue (48 loads per lane fill the queue: the wave stalls) falls into
-            // the wait for the partners' tickets.  Issued behind the loads of the partners' partials instead, the sum of the
+            // The update's operands go out HERE: behind the ticket (granule form: behind the granule stores), so that nothing the
+            // partners wait for queues behind them, and in front of the poll (the first granule sweep), so that their issue (48
+            // loads per lane fill the queue: the wave stalls) falls into the wait for the partners' tickets (words).  Issued behind the loads of the partners' partials instead, the sum of the
             // partials waited for that issue (exchange 5.9 -> 8.5 us).  They land during the poll; the barriers of the pivot
             // solve carry no vmcnt wait.  ONE site for every G (without an exchange it follows the Gram loop): two sites
             // meet in register copies, i.e. in a wait for the loads just issued.
@@ -1465,11 +1505,74 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
                     }
                     pendP = -1;
                 }
+                const d2 own_lo = lo, own_hi = hi;
+                lo = d2{0.0, 0.0};
+                hi = d2{0.0, 0.0};
+                if constexpr (GRAN) {
+                    // Every thread sweeps the eight words of its own four elements in the partners' parts (its own partial comes
+                    // from its registers, at its place in the order of the sum), four parts in flight as in the ticket form, with 8-byte
+                    // write-through-aware loads to registers at the offsets it stores to (512 contiguous bytes per wave and
+                    // load), and repeats a group of parts until the wave has seen this round's tag on every word.  Bounded
+                    // like spin_until: one second, the same error word; a wave that gives up raises flags[3] and the workgroup
+                    // leaves behind the barrier that ends this step.
+                    const __amdgpu_buffer_rsrc_t rs_gran = __builtin_amdgcn_make_buffer_rsrc((unsigned long long*)gran_pair, 0, (int)(SW_GRAN_BYTES * G), 0x00020000);
+                    const unsigned long long t0 = wall_clock64(); // 100 MHz
+                    unsigned int it = 0, passes = 0;
+                    bool good = true;
+                    for (int g0 = 0; g0 < G && good; g0 += 4) {
+                        u32x2 w[4][8];
+                        for (;;) {
+                            asm volatile("" ::: "memory"); // (every pass loads anew)
+                            unsigned int bad = 0u; // (branch-free: nonzero when some tag is not this round's)
+#pragma unroll
+                            for (int g = 0; g < 4; ++g) {
+                                if (g0 + g < G && g0 + g != part) {
+#pragma unroll
+                                    for (int j = 0; j < 8; ++j)
+                                        // (addresses that do not depend on the part: it goes into the scalar offset -- an address
+                                        //  register written between two loads costs a wait for the loads in flight)
+                                        w[g][j] = __builtin_amdgcn_raw_buffer_load_b64(rs_gran, (unsigned int)(wave * 4096 + lane * 8) + 512u * j, (g0 + g) * (int)SW_GRAN_BYTES, 16);
+                                }
+                            }
+#pragma unroll
+                            for (int g = 0; g < 4; ++g) {
+                                if (g0 + g < G && g0 + g != part) {
+#pragma unroll
+                                    for (int j = 0; j < 8; ++j) bad |= w[g][j][1] ^ gtag;
+                                }
+                            }
+                            ++passes;
+                            if (__all(bad == 0u)) break;
+                            __builtin_amdgcn_s_sleep(1);
+                            if ((++it & 63u) == 0u) {
+                                if (__hip_atomic_load(sc.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) good = false;
+                                else if (wall_clock64() - t0 > 100000000ull) { // one second
+                                    __hip_atomic_store(sc.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                    good = false;
+                                }
+                                if (!good) break;
+                            }
+                        }
+                        if (!good) break;
+#pragma unroll
+                        for (int g = 0; g < 4; ++g) {
+                            if (g0 + g == part) { // (the own partial never left its registers; it takes its place in the order)
+                                lo += own_lo;
+                                hi += own_hi;
+                            } else if (g0 + g < G) {
+                                lo.x += __hiloint2double((int)w[g][1][0], (int)w[g][0][0]);
+                                lo.y += __hiloint2double((int)w[g][3][0], (int)w[g][2][0]);
+                                hi.x += __hiloint2double((int)w[g][5][0], (int)w[g][4][0]);
+                                hi.y += __hiloint2double((int)w[g][7][0], (int)w[g][6][0]);
+                            }
+                        }
+                    }
+                    if (!good && lane == 0) flags[3] = 1;
+                    if (sc.stamps && tid == 0 && round == sc.stamp_round) sc.stamps[(size_t)blockIdx.x * 8 + 7] = passes; // (diagnostic: passes of wave 0)
+                } else {
                 if (tid == 0) flags[1] = spin_until(ticket, (unsigned int)G * (unsigned int)(ground + 1), sc.err) ? 1 : 0;
                 __syncthreads();
                 if (!flags[1]) return;
-                lo = d2{0.0, 0.0};
-                hi = d2{0.0, 0.0};
                 for (int g0 = 0; g0 < G; g0 += 4) { // four parts' loads in flight at a time; the same order in every part
                     Q16 pa[4], pb[4];
 #pragma unroll
@@ -1487,6 +1590,7 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
                         }
                     }
                 }
+                } // (ticket form)
             }
             double* dst = Gs + gi * GS + gj;
             dst[0] = lo.x;
@@ -1495,6 +1599,9 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
             dst[3] = hi.y;
         }
         __syncthreads();
+        if constexpr (GRAN) {
+            if (G > 1 && flags[3]) return;
+        }
         SWEEP_STAMP(3);
         // ---- 3a. deflation
         if (tid == 0) flags[0] = 0;
@@ -1877,17 +1984,27 @@ int jacobi_orthogonalise(cyb_ctx_t ctx, const std::vector<JMat>& h_mats, int max
         size_t n_ready = 0; // persistent sweep: one counter per (matrix, block, part), at most RGMAX parts
         for (int m : order) n_ready += (size_t)h_mats[(size_t)m].nb * RGMAX;
         const size_t b_ready = (sizeof(unsigned int) * (2 * n_ready + np) + 15) / 16 * 16; // ready counters (W and J) + one ticket per pair
+        // CYB_JACOBI_EXCHANGE=0: the partial Grams of the sweep kernel travel by stores, drain, ticket and poll as before (same
+        // sums in the same order: bit-identical results); default: as tagged granules
+        static const bool gran_exchange = !(getenv("CYB_JACOBI_EXCHANGE") && atoi(getenv("CYB_JACOBI_EXCHANGE")) == 0);
+        // granule regions of the sweep kernel: room for a part on every resident workgroup (a launch zeroes and uses those of
+        // the parts it assigns; a list with more parts than that shares workgroups and runs every pair in one part: no exchange)
+        const size_t sweep_slots = (size_t)SWEEP_WG_PER_CU * (size_t)ctx->n_cu; // resident workgroups the sweep kernel may use
+        const size_t b_gran = gran_exchange ? 2 * (size_t)SW_GRAN_BYTES * sweep_slots : 0;
         void* wsp = nullptr;
-        status = ctx->workspace(b_off + 16 + b_cnt + b_ready + 2 * b_gpart + 2 * (b_q + b_z + b_f) + b_c + 1024, &wsp, 2);
+        status = ctx->workspace(b_off + 16 + b_cnt + b_ready + b_gran + 2 * b_gpart + 2 * (b_q + b_z + b_f) + b_c + 1024, &wsp, 2);
         if (status != CYB_OK) break;
         char* bp = static_cast<char*>(wsp);
         RScratch rs;
-        // one zeroed block: [off-norm words | error word | tickets of the round kernel | tickets + ready counters of the sweep kernel]
+        // one zeroed block: [off-norm words | error word | tickets of the round kernel | tickets + ready counters of the sweep kernel |
+        // granule regions of the sweep kernel's parts]
         unsigned long long* d_off = reinterpret_cast<unsigned long long*>(bp);
         rs.err = reinterpret_cast<unsigned int*>(bp + b_off);
         rs.cnt = reinterpret_cast<unsigned int*>(bp + b_off + 16);
         unsigned int* d_ready = reinterpret_cast<unsigned int*>(bp + b_off + 16 + b_cnt);
-        bp += b_off + 16 + b_cnt + b_ready;
+        const size_t b_zero = b_off + 16 + b_cnt + b_ready; // (+ the granule regions in use: known once the parts are assigned)
+        unsigned long long* d_gran = reinterpret_cast<unsigned long long*>(bp + b_zero);
+        bp += b_zero + b_gran;
         rs.gpart = reinterpret_cast<double*>(bp);
         bp += 2 * b_gpart;
         rs.np = (int)np;
@@ -1907,10 +2024,8 @@ int jacobi_orthogonalise(cyb_ctx_t ctx, const std::vector<JMat>& h_mats, int max
             bp += b_f;
         }
         sc.cnt = reinterpret_cast<unsigned int*>(bp);
-        if (hipMemsetAsync(wsp, 0, b_off + 16 + b_cnt + b_ready, st) != hipSuccess) {
-            status = CYB_ERR_HIP;
-            break;
-        }
+        // ONE fill per sweep, issued by whichever path runs it (the sweep kernel adds the granule regions of its parts)
+        auto zero_block = [&](size_t gran_bytes) { return hipMemsetAsync(wsp, 0, b_zero + gran_bytes, st) == hipSuccess; };
         std::vector<RPair> rp(np);
         for (size_t k = 0; k < np; ++k) {
             const JMat& jm = h_mats[(size_t)wl[k].mat];
@@ -1956,7 +2071,6 @@ int jacobi_orthogonalise(cyb_ctx_t ctx, const std::vector<JMat>& h_mats, int max
         bool big_ok = true;
         for (int m : order)
             big_ok = big_ok && (size_t)h_mats[(size_t)m].nvp * (size_t)std::max(h_mats[(size_t)m].lenp, h_mats[(size_t)m].nvp) * 8 < ((size_t)1 << 31);
-        const size_t sweep_slots = (size_t)SWEEP_WG_PER_CU * (size_t)ctx->n_cu; // resident workgroups the sweep kernel may use
         // (lists with more pairs than resident workgroups: short matrices share workgroups -- CYB_JACOBI_NOSHARE sends them
         //  to the launch-per-round paths as before)
         static const bool no_share = getenv("CYB_JACOBI_NOSHARE") != nullptr;
@@ -2067,8 +2181,13 @@ int jacobi_orthogonalise(cyb_ctx_t ctx, const std::vector<JMat>& h_mats, int max
                 // CYB_JACOBI_ROUND_ORDER=0: the issue order a round had before (same arithmetic, same protocol: bit-identical results)
                 static const bool round_order = !(getenv("CYB_JACOBI_ROUND_ORDER") && atoi(getenv("CYB_JACOBI_ROUND_ORDER")) == 0);
                 typedef void (*sweep_fn_t)(const RPair*, int, unsigned long long*, SScratch);
-                static const sweep_fn_t sweep_fn[2] = {round_order ? jacobi_sweep_kernel<false, true> : jacobi_sweep_kernel<false, false>,
-                                                       round_order ? jacobi_sweep_kernel<true, true> : jacobi_sweep_kernel<true, false>};
+                static const sweep_fn_t sweep_fns[2][2][2] = { // [CPLX][RORD][GRAN]
+                    {{jacobi_sweep_kernel<false, false, false>, jacobi_sweep_kernel<false, false, true>},
+                     {jacobi_sweep_kernel<false, true, false>, jacobi_sweep_kernel<false, true, true>}},
+                    {{jacobi_sweep_kernel<true, false, false>, jacobi_sweep_kernel<true, false, true>},
+                     {jacobi_sweep_kernel<true, true, false>, jacobi_sweep_kernel<true, true, true>}}};
+                static const sweep_fn_t sweep_fn[2] = {sweep_fns[0][round_order ? 1 : 0][gran_exchange ? 1 : 0],
+                                                       sweep_fns[1][round_order ? 1 : 0][gran_exchange ? 1 : 0]};
                 static bool attr2_set = false;
                 if (!attr2_set) {
                     if (hipFuncSetAttribute(reinterpret_cast<const void*>(sweep_fn[0]), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -2107,6 +2226,21 @@ int jacobi_orthogonalise(cyb_ctx_t ctx, const std::vector<JMat>& h_mats, int max
                 ss.arrive = reinterpret_cast<unsigned int*>(d_off + w_off);
                 ss.nsw = reinterpret_cast<int*>(ss.arrive + n);
                 one_launch_done = one_launch;
+                // granule regions: two (round parity) per part, laid out by the flag bases (nb is even: nb * G_m units per matrix)
+                bool any_parts = false;
+                for (int m : order) any_parts = any_parts || Gm[(size_t)m] > 1;
+                const size_t gran_bytes = (gran_exchange && any_parts) ? (size_t)(fb - (int)np) * SW_GRAN_BYTES : 0;
+                ss.gran = d_gran;
+                ss.gran_np = (int)np;
+                if (gran_bytes > b_gran) {
+                    set_error("jacobi: %zu bytes of granule regions exceed the %zu reserved", gran_bytes, b_gran);
+                    status = CYB_ERR_INVALID;
+                    break;
+                }
+                if (!zero_block(gran_bytes)) {
+                    status = CYB_ERR_HIP;
+                    break;
+                }
                 hipLaunchKernelGGL(sweep_fn[cplx ? 1 : 0], dim3((unsigned)n_wg), dim3(NT), SWEEP_LDS_BYTES, st,
                                    static_cast<const RPair*>(d_rp2), max_inner, d_off, ss);
                 if (ss.stamps && wgmap.size() <= 2048) {
@@ -2114,19 +2248,21 @@ int jacobi_orthogonalise(cyb_ctx_t ctx, const std::vector<JMat>& h_mats, int max
                     if (hipMemcpyAsync(hs.data(), rs.stamps, sizeof(unsigned long long) * hs.size(), hipMemcpyDeviceToHost, st) == hipSuccess &&
                         hipStreamSynchronize(st) == hipSuccess) {
                         // phase times of round `stamp_round` for the workgroups of the matrix with the most blocks
-                        double acc[6] = {0, 0, 0, 0, 0, 0};
+                        double acc[6] = {0, 0, 0, 0, 0, 0}, passes = 0;
                         int cntw = 0;
                         const int mbig = order.front();
+                        const bool swept = gran_exchange && Gm[(size_t)mbig] > 1; // (slot 7: granule passes of wave 0)
                         for (size_t b = 0; b < wgmap.size(); ++b) {
                             if (wl[(size_t)wgmap[b].x].mat != mbig) continue;
                             for (int k = 0; k < 6; ++k) acc[k] += (double)(hs[8 * b + k + 1] - hs[8 * b + k]) * 0.01;
+                            if (swept) passes += (double)hs[8 * b + 7];
                             ++cntw;
                         }
                         if (cntw)
                             fprintf(stderr, "[jacobi sweep stamps] sweep %d round %d, largest matrix (G=%d, %d workgroups of %zu): wait %.2f load+gram %.2f "
-                                            "exch %.2f defl+eig %.2f sort %.2f upd+publish %.2f us\n",
+                                            "exch %.2f defl+eig %.2f sort %.2f upd+publish %.2f us, granule passes %.1f\n",
                                     sweep, ss.stamp_round, Gm[(size_t)mbig], cntw, wgmap.size(), acc[0] / cntw, acc[1] / cntw,
-                                    acc[2] / cntw, acc[3] / cntw, acc[4] / cntw, acc[5] / cntw);
+                                    acc[2] / cntw, acc[3] / cntw, acc[4] / cntw, acc[5] / cntw, passes / cntw);
                     }
                 }
                 did_sweep = true;
@@ -2138,6 +2274,10 @@ int jacobi_orthogonalise(cyb_ctx_t ctx, const std::vector<JMat>& h_mats, int max
             break;
         }
         if (!did_sweep) {
+        if (!zero_block(0)) {
+            status = CYB_ERR_HIP;
+            break;
+        }
         cached_img = nullptr; // (the uploads below recycle the ring)
         {
             void* d_mats_v = nullptr;
