@@ -196,6 +196,19 @@ class TreePlaceRec(C.Structure):
                 ('coeff_re', C.c_double), ('coeff_im', C.c_double), ('src_real', C.c_int32), ('reserved', C.c_int32)]
 
 
+class TreeStripOut(C.Structure):
+    _fields_ = [('dst', C.c_void_p), ('h', C.c_int64), ('nq', C.c_int64), ('wn', C.c_int64), ('cp', C.c_int64), ('ldd', C.c_int64),
+                ('n_row_levels', C.c_int32), ('n_col_levels', C.c_int32),
+                ('rext', C.c_int64 * CYB_TREE_PLACE_MAX_LEVELS), ('rs', C.c_int64 * CYB_TREE_PLACE_MAX_LEVELS),
+                ('cext', C.c_int64 * CYB_TREE_PLACE_MAX_LEVELS), ('cs', C.c_int64 * CYB_TREE_PLACE_MAX_LEVELS),
+                ('first_term', C.c_int64), ('n_terms', C.c_int64)]
+
+
+class TreeStripTerm(C.Structure):
+    _fields_ = [('src', C.c_void_p), ('coeff_re', C.c_double), ('coeff_im', C.c_double), ('src_real', C.c_int32), ('reserved', C.c_int32),
+                ('base', C.c_int64)]
+
+
 class ExpmDesc(C.Structure):
     _fields_ = [('A', C.c_void_p), ('lda', C.c_int64), ('n', C.c_int64), ('a_is_real', C.c_int32), ('reserved', C.c_int32),
                 ('E', C.c_void_p), ('lde', C.c_int64)]
@@ -259,6 +272,8 @@ TREE_TO_DENSE_TERM_DTYPE = _np.dtype(TreeToDenseTerm)
 TREE_FROM_DENSE_OUT_DTYPE = _np.dtype(TreeFromDenseOut)
 TREE_FROM_DENSE_TERM_DTYPE = _np.dtype(TreeFromDenseTerm)
 TREE_PLACE_DTYPE = _np.dtype(TreePlaceRec)
+TREE_STRIP_OUT_DTYPE = _np.dtype(TreeStripOut)
+TREE_STRIP_TERM_DTYPE = _np.dtype(TreeStripTerm)
 EXPM_DTYPE = _np.dtype(ExpmDesc)
 OUTER_DTYPE = _np.dtype(OuterRec)
 SEG_DTYPE = _np.dtype(SegRec)
@@ -357,6 +372,8 @@ PROTOTYPES = {
     'cyb_tree_from_dense_c128': [_ctx, _P(TreeFromDenseOut), C.c_int64, _P(TreeFromDenseTerm), C.c_int64, C.c_void_p],
     'cyb_tree_place_f64': [_ctx, _P(TreePlaceRec), C.c_int64],
     'cyb_tree_place_c128': [_ctx, _P(TreePlaceRec), C.c_int64],
+    'cyb_tree_strip_f64': [_ctx, _P(TreeStripOut), C.c_int64, _P(TreeStripTerm), C.c_int64],
+    'cyb_tree_strip_c128': [_ctx, _P(TreeStripOut), C.c_int64, _P(TreeStripTerm), C.c_int64],
     'cyb_expm_small_batched_f64': [_ctx, _P(ExpmDesc), C.c_int64, C.c_double],
     'cyb_expm_small_batched_c128': [_ctx, _P(ExpmDesc), C.c_int64, C.c_double, C.c_double],
     'cyb_norm1_batched_f64': [_ctx, _P(ExpmDesc), C.c_int64, _vp],

@@ -1839,6 +1839,88 @@ class HipBlockBackend:
         self.ctx.sync_stream()
         _lib.check(fn(self.ctx.handle, arr.ctypes.data_as(C.POINTER(_lib.TreePlaceRec)), len(records)))
 
+    def tree_strip_many(self, outs):
+        """Weighted sums of permuted strips, ONE descriptor upload and ONE launch for all strips of one side of a factorized
+        fusion-tree move (``FactorizedTreeMapping::transform_splitting_trees`` / ``::transform_fusion_trees``,
+        fusion_tree_mapping.cpp:627-725: get_item, mul and operator+ per (new tree, old tree), permute_combined_idx and
+        set_item per new tree, into a zero-filled block).  `outs`: a list of ``(dst, side, start, stop, dims, axes, terms)``;
+        ``dst`` is a 2-D block with unit column stride, written in place in the strip ``start:stop`` of its rows (``side == 0``,
+        all columns) or of its columns (``side == 1``, all rows); the strips of one call must not overlap.  ``terms``: a list of
+        ``(src, src_start, coeff)``, 2-D blocks read in place through their strides -- the strip of as many rows / columns from
+        `src_start` on, all of one block shape and stride pair per output:
+        ``dst[strip] = permute_combined_idx(sum_terms coeff * src[strip of the term], side, dims, axes)``
+        (the strip index split into `dims`, at most ``CYB_TREE_PLACE_MAX_LEVELS`` of them, transposed by `axes` and combined again;
+        the permutation is strides, never a pass), zeros without a term, the terms added in the order given.  The destinations
+        decide the entry: all float64 (real sources, real coefficients) or all complex128 (a float64 source is then read as it
+        stands, no promotion pass).  One term with ``coeff == 1`` copies bits; every element has one owner, bit-identical from
+        run to run (csrc/tree_strip.hip)."""
+        what = 'tree_strip_many'
+        outs = [(dst, side, start, stop, tuple(dims), tuple(axes), list(terms)) for dst, side, start, stop, dims, axes, terms in outs]
+        if not outs:
+            return
+        dsts = [o[0] for o in outs]
+        srcs = [tm[0] for o in outs for tm in o[6]]
+        cplx = self._tree_entry(what, dsts, srcs, any(x.ndim != 2 for x in dsts + srcs) and 'destinations and sources are 2-D blocks')
+        nl = _lib.CYB_TREE_PLACE_MAX_LEVELS
+        pad = (0,) * nl
+        es = 16 if cplx else 8
+        rows, splits = [], {}         # one record per row, as the int64 words of cyb_tree_strip_out
+        t_re, t_im, t_base = [], [], []
+        for dst, side, start, stop, dims, axes, terms in outs:
+            if side not in (0, 1):
+                raise ValueError(f'{what}: side is 0 (rows) or 1 (columns), not {side}')
+            if dst.strides[1] != 1 and dst.shape[1] > 1:
+                raise ValueError(f'{what}: a destination block needs the column stride 1')
+            if not 0 <= start <= stop <= dst.shape[side]:
+                raise ValueError(f'{what}: the strip {start}:{stop} leaves axis {side} of its block of shape {tuple(dst.shape)}')
+            n, other = stop - start, dst.shape[1 - side]
+            split = splits.get((dims, axes))
+            if split is None:                # (the strips of one side share the permutation and, per class of trees, the dimensions)
+                if len(dims) > nl:
+                    raise ValueError(f'{what}: a strip of {len(dims)} levels, at most {nl}')
+                if sorted(axes) != list(range(len(dims))) or min(dims, default=1) < 0:
+                    raise ValueError(f'{what}: the dimensions {dims} under the axes {axes} for a strip of {n}')
+                old = _c_strides(dims)
+                split = splits[(dims, axes)] = (math.prod(dims), (tuple(dims[a] for a in axes) + pad)[:nl], tuple(old[a] for a in axes))
+            if split[0] != n:
+                raise ValueError(f'{what}: the dimensions {dims} under the axes {axes} for a strip of {n}')
+            ext, lev, strides = split[1], (), None
+            for src, src_start, coeff in terms:
+                coeff = complex(coeff)
+                if not cplx and (src.is_complex or coeff.imag != 0):
+                    raise ValueError(f'{what}: a complex source or coefficient needs complex destination blocks')
+                if src.shape[1 - side] != other or not 0 <= src_start <= src_start + n <= src.shape[side]:
+                    raise ValueError(f'{what}: the strip {src_start}:{src_start + n} of axis {side} of a source of shape {tuple(src.shape)} '
+                                     f'for a destination of shape {tuple(dst.shape)}')
+                if strides is None:
+                    strides = src.strides
+                    lev = tuple(u * strides[side] for u in split[2])
+                elif src.strides != strides:
+                    raise ValueError(f'{what}: the sources of one strip differ in their strides, {strides} and {src.strides}')
+                t_re.append(coeff.real)
+                t_im.append(coeff.imag)
+                t_base.append(src_start * strides[side])
+            across = strides[1 - side] if terms else 0
+            ldd = dst.strides[0]
+            one, step = (other,) + pad[1:], (across,) + pad[1:]
+            lev = (lev + pad)[:nl]
+            if side == 0:     # (the two int32 level counts share a word: rows low, columns high)
+                rows.append((dst.ptr + start * ldd * es, n, 1, other, other, ldd, len(dims) | 1 << 32) + ext + lev + one + step
+                            + (len(t_re) - len(terms), len(terms)))
+            else:
+                rows.append((dst.ptr + start * es, other, 1, n, n, ldd, 1 | len(dims) << 32) + one + step + ext + lev
+                            + (len(t_re) - len(terms), len(terms)))
+        oarr = np.array(rows, dtype=np.int64).view(_lib.TREE_STRIP_OUT_DTYPE).reshape(len(outs))
+        n_t = len(srcs)
+        tarr = np.zeros(max(n_t, 1), dtype=_lib.TREE_STRIP_TERM_DTYPE)
+        if n_t:
+            tarr['src'], tarr['coeff_re'], tarr['coeff_im'], tarr['base'] = [a.ptr for a in srcs], t_re, t_im, t_base
+            tarr['src_real'] = [0 if a.is_complex or not cplx else 1 for a in srcs]
+        fn = self.lib.cyb_tree_strip_c128 if cplx else self.lib.cyb_tree_strip_f64
+        self.ctx.sync_stream()
+        _lib.check(fn(self.ctx.handle, oarr.ctypes.data_as(C.POINTER(_lib.TreeStripOut)), len(outs),
+                      tarr.ctypes.data_as(C.POINTER(_lib.TreeStripTerm)), n_t))
+
     def _tree_pair_table(self, tensors):
         """the tree-pair tensors of one call (host arrays, each once) as ONE device table: (table block or None, offset of
         every tensor by id, whether the table is complex)"""

@@ -126,19 +126,6 @@ template <bool CPLX> __global__ void __launch_bounds__(NT) tree_place_kernel(con
     }
 }
 
-// the product of `n` extents if it equals `want`; extents are within [0, kMaxExtent]
-inline bool product_is(const int64_t* ext, int n, int64_t want)
-{
-    for (int l = 0; l < n; ++l)
-        if (ext[l] == 0) return want == 0;
-    int64_t p = 1;
-    for (int l = 0; l < n; ++l) {
-        p *= ext[l];
-        if (p > ((int64_t)1 << 61)) return false; // (want = h or nq * wn is at most 2^60)
-    }
-    return p == want;
-}
-
 // validates the list and turns it into the records and work items of the launch (both empty: nothing to do)
 template <bool CPLX> int plan_place(std::vector<Rec>& recs, std::vector<Item>& items, const In* in, int64_t n_recs, const char* who)
 {
@@ -171,22 +158,11 @@ template <bool CPLX> int plan_place(std::vector<Rec>& recs, std::vector<Item>& i
         int64_t le[NS], ls[NS];
         int n = 0;
         if (o.src) {
-            for (int l = 0; l < o.n_row_levels + o.n_col_levels; ++l) {
-                const int64_t e = l < o.n_row_levels ? o.rext[l] : o.cext[l - o.n_row_levels];
-                const int64_t s = l < o.n_row_levels ? o.rs[l] : o.cs[l - o.n_row_levels];
-                if (e == 1) continue;
-                le[n] = e, ls[n] = s, ++n;
+            for (int l = 0; l < o.n_row_levels + o.n_col_levels; ++l, ++n) {
+                le[n] = l < o.n_row_levels ? o.rext[l] : o.cext[l - o.n_row_levels];
+                ls[n] = l < o.n_row_levels ? o.rs[l] : o.cs[l - o.n_row_levels];
             }
-            int64_t me[NS], ms[NS]; // merged, the innermost first
-            int m = 0;
-            for (int l = n - 1; l >= 0; --l) {
-                if (m > 0 && (__int128)ls[l] == (__int128)me[m - 1] * ms[m - 1] && le[l] * me[m - 1] <= kMaxExtent)
-                    me[m - 1] *= le[l];
-                else
-                    me[m] = le[l], ms[m] = ls[l], ++m;
-            }
-            n = m;
-            for (int l = 0; l < n; ++l) le[l] = me[n - 1 - l], ls[l] = ms[n - 1 - l];
+            n = merge_levels(le, ls, n, kMaxExtent);
         }
         // pairs of doubles: (w, w + 1) share q and every source digit but the innermost, and every pair is 16-byte aligned
         bool x2 = !CPLX && even_(o.wn) && even_(cp) && even_(ldd) && ((uintptr_t)o.dst & 15) == 0;

@@ -1,5 +1,5 @@
 // One wave per work item over a mixed-radix index space: the machinery shared by the fusion-tree kernels that write strided
-// tiles in ONE launch (tree_outer.hip, tree_compose.hip, tree_dense.hip, tree_place.hip).
+// tiles in ONE launch (tree_outer.hip, tree_compose.hip, tree_dense.hip, tree_place.hip, tree_strip.hip).
 //
 // A *record* is an index space of up to L levels in C order (the last level fastest) with S offset streams -- destination,
 // sources -- that each have a stride per level.  The levels in use are first .. L - 1; the ones before them have extent 1
@@ -83,6 +83,36 @@ template <int L, int S> void set_steps(Levels<L, S>& t, int first)
         s = l > first ? s / t.ext[l] : 0;
         for (int a = 0; a < S; ++a) t.step_o[a] += t.step[l] * t.st[a][l];
     }
+}
+
+// the product of `n` extents if it equals `want`; extents are within [0, 2^30], want is at most 2^60
+inline bool product_is(const int64_t* ext, int n, int64_t want)
+{
+    for (int l = 0; l < n; ++l)
+        if (ext[l] == 0) return want == 0;
+    int64_t p = 1;
+    for (int l = 0; l < n; ++l) {
+        p *= ext[l];
+        if (p > ((int64_t)1 << 61)) return false;
+    }
+    return p == want;
+}
+
+// The levels (ext[l], st[l]), l < n in C order, of a strided view that is walked in C order, in place: a level of extent 1 is
+// dropped and a level that continues its inner neighbour is merged into it while the extent stays within max_extent (a
+// contiguous tile of a block: one row level, one column level).  Returns the number of levels left.
+inline int merge_levels(int64_t* ext, int64_t* st, int n, int64_t max_extent)
+{
+    int m = 0; // levels kept so far, the innermost first
+    for (int l = n - 1; l >= 0; --l) {
+        if (ext[l] == 1) continue;
+        if (m > 0 && (__int128)st[l] == (__int128)ext[n - m] * st[n - m] && ext[l] * ext[n - m] <= max_extent)
+            ext[n - m] *= ext[l];
+        else
+            ++m, ext[n - m] = ext[l], st[n - m] = st[l];
+    }
+    for (int l = 0; l < m; ++l) ext[l] = ext[n - m + l], st[l] = st[n - m + l];
+    return m;
 }
 
 // flat units per work item: about kTargetItems waves for a large launch

@@ -23,6 +23,11 @@ module mirrors is everything BETWEEN that layer and the block backend:
   symmetry layer as data; the loops over coupled sectors and tree pairs are the reference's, but instead of ``zeros`` +
   (``get_item``, ``mul``, ``operator+``) per term + ``permute_combined_matrix`` + ``set_item`` per tree pair they fill ONE
   descriptor list for ``HipBlockBackend.transform_blocks`` (one zero fill + one launch per tensor, complex coefficients).
+* :func:`transform_tensor_factorized`  <- ``FactorizedTreeMapping::transform_tensor`` (fusion_tree_mapping.cpp:728-792) with
+  ``transform_splitting_trees`` (:627-674) and ``transform_fusion_trees`` (:676-725), the other route of ``apply_instructions``
+  (braids and twists inside each side): one sparse map over the splitting trees of the codomain, one over the fusion trees of
+  the domain.  One strip record per new tree and one term per old tree that feeds it; the arithmetic is ONE
+  ``tree_strip_many`` launch per side that is no identity, into blocks that are not zero-filled.
 * :func:`inner` / :func:`trace_full` / :func:`norm`  <- ``::inner`` (:1238-1259), ``::trace_full`` (:1261-1278), ``::norm``
   (:1280-1296): ONE quantum-dimension weighted reduction (``inner_weighted_many`` / ``trace_weighted_many``) instead of a
   reduction and a host wait per coupled sector.  :func:`mul`, :func:`linear_combination`, :func:`dagger`,
@@ -70,13 +75,14 @@ module mirrors is everything BETWEEN that layer and the block backend:
 from __future__ import annotations
 
 import itertools
+import math
 from dataclasses import dataclass, field
 from typing import NamedTuple
 
 import numpy as np
 
 __all__ = ['TreeBlock', 'TreeSpace', 'FusionTreeData', 'compose', 'svd', 'qr', 'lq', 'eigh', 'truncate_singular_values',
-           'transform_tensor', 'discard_zero_blocks', 'norm', 'inner', 'trace_full', 'mul', 'linear_combination', 'dagger',
+           'transform_tensor', 'transform_tensor_factorized', 'discard_zero_blocks', 'norm', 'inner', 'trace_full', 'mul', 'linear_combination', 'dagger',
            'almost_equal', 'TreeAxisRecord', 'TreeMask', 'leg_keys', 'scale_axis', 'mask_contract', 'truncated_svd', 'TreeTensor',
            'same_space', 'TreeTrace', 'partial_trace', 'TreeOuter', 'outer', 'TreeInsert', 'partial_compose',
            'TreeDense', 'to_dense_block', 'from_dense_block', 'from_grid', 'from_tree_pairs', 'eye']
@@ -422,6 +428,120 @@ def transform_tensor(bb, data: FusionTreeData, codomain: TreeSpace, domain: Tree
     if not shapes:
         return FusionTreeData(np.zeros((0, 2), np.int64), [])
     return FusionTreeData(np.array(new_rows, dtype=np.int64), bb.transform_blocks(data.blocks, shapes, updates))
+
+
+MAX_STRIP_LEGS = 6      # flat legs of one side of a factorized move (the levels of a strip, CYB_TREE_PLACE_MAX_LEVELS)
+
+
+def _strip_records(live, blocks, side: int, old_space: TreeSpace, new_space: TreeSpace, axes, table, name: str):
+    """the loops of ``transform_splitting_trees`` (side 0, fusion_tree_mapping.cpp:627-674) / ``transform_fusion_trees`` (side 1,
+    :676-725) over the sectors `live` = [(i, j)] whose current blocks are `blocks`: per sector the strip records of its new
+    trees, ``(start, stop, mults_old_order, [(old start, coefficient)])`` with the terms in ascending order of the old tree's
+    start, or None where no new tree of the sector has a term (the block is dropped, :773 / :780)"""
+    what = 'codomain' if side == 0 else 'domain'
+    if sorted(axes) != list(range(len(axes))) or len(axes) != new_space.num_legs:
+        raise ValueError(f'{name}: the {what} axes {list(axes)} are no permutation of the {new_space.num_legs} legs of the new {what}')
+    if len(axes) > MAX_STRIP_LEGS:
+        raise ValueError(f'{name}: {len(axes)} {what} legs, at most {MAX_STRIP_LEGS} on a side')
+    inv = [0] * len(axes)
+    for pos, a in enumerate(axes):
+        inv[a] = pos
+    by_new: dict = {}        # new tree -> [(old tree, coefficient)]
+    for old_tree, targets in table.items():
+        for new_tree, coeff in targets.items():
+            by_new.setdefault(new_tree, []).append((old_tree, coeff))
+    old_sectors, new_sectors = old_space.sectors.tolist(), new_space.sectors.tolist()
+    out = []
+    for (i, j), blk in zip(live, blocks):
+        s = (i, j)[side]
+        sector = new_sectors[s]
+        strips, fed = [], False
+        for x2 in new_space.tree_blocks[s]:
+            if len(x2.multiplicities) != len(axes):
+                raise ValueError(f'{name}: the new {what} tree {x2.tree!r} has {len(x2.multiplicities)} multiplicities for {len(axes)} legs')
+            mults_old = tuple(x2.multiplicities[k] for k in inv)
+            terms = []
+            for X, coeff in by_new.get(x2.tree, ()):
+                if not old_space.has_tree(X):
+                    raise ValueError(f'{name}: the old {what} holds no tree {X!r}')
+                io, xb = old_space.tree_block_slice(X)
+                if old_sectors[io] != sector:
+                    raise ValueError(f'{name}: the old {what} tree {X!r} and the new tree {x2.tree!r} lie in different coupled sectors')
+                if tuple(xb.multiplicities) != mults_old:
+                    raise ValueError(f'{name}: the old {what} tree {X!r} has the multiplicities {tuple(xb.multiplicities)}, the new tree '
+                                     f'{x2.tree!r} in the old leg order {mults_old}')
+                if xb.stop > blk.shape[side]:
+                    raise ValueError(f'{name}: the strip {xb.start}:{xb.stop} of the old {what} tree {X!r} does not fit its block of shape '
+                                     f'{tuple(blk.shape)}')
+                terms.append((xb.start, coeff))
+            if x2.stop - x2.start != math.prod(mults_old) or x2.stop > new_space.block_size(s):
+                raise ValueError(f'{name}: the strip {x2.start}:{x2.stop} of the new {what} tree {x2.tree!r} does not fit its multiplicities '
+                                 f'{tuple(x2.multiplicities)} or its block of {new_space.block_size(s)}')
+            terms.sort(key=lambda tm: tm[0])
+            fed = fed or bool(terms)
+            strips.append((x2.start, x2.stop, mults_old, terms))
+        out.append(strips if fed else None)
+    return out
+
+
+def transform_tensor_factorized(bb, data: FusionTreeData, codomain: TreeSpace, domain: TreeSpace, new_codomain: TreeSpace,
+                                new_domain: TreeSpace, codomain_idcs, domain_idcs, splitting=None, fusion=None) -> FusionTreeData:
+    """``FactorizedTreeMapping::transform_tensor`` (fusion_tree_mapping.cpp:728-792), the route of
+    ``FusionTreeBackend::apply_instructions`` for moves that stay inside each side (braids and twists, no bends).  `splitting` /
+    `fusion`: the data of the two halves of the symmetry layer's FactorizedTreeMapping, ``{old tree: {new tree: coefficient}}``
+    over the splitting trees of the codomain / the fusion trees of the domain (``SparseMappingFusionTree::data``); None stands
+    for the ``IdentityMappingFusionTree``.  `codomain_idcs`: a permutation of ``range(J)``, `domain_idcs`: one of ``range(J, N)``
+    (numbered as for :func:`transform_tensor`).
+
+    Loops as in the reference -- common coupled sectors of the new spaces, the old block through the coupled sector in the old
+    domain (:762), per new tree of a side the old trees that feed it -- but what they emit is one strip record per new tree
+    (its rows and all columns, or its columns and all rows) with one term per old tree, added in ascending order of the old
+    tree's start; the arithmetic is ONE ``tree_strip_many`` launch per side that is no identity, into blocks from
+    ``empty_many``: every element is written once, a new tree without a term as zeros, nothing is zero-filled.  A sector none
+    of whose new trees has a term is dropped (:773, :780); with both sides None the result holds the old block objects.  The
+    result is complex if the data or a coefficient is (:747-750); float64 data is then read as it stands."""
+    name = 'transform_tensor_factorized'
+    J, K = codomain.num_legs, domain.num_legs
+    N = J + K
+    codomain_idcs, domain_idcs = [int(i) for i in codomain_idcs], [int(i) for i in domain_idcs]
+    if sorted(codomain_idcs) != list(range(J)) or sorted(domain_idcs) != list(range(J, N)):
+        raise ValueError(f'{name}: codomain_idcs {codomain_idcs} / domain_idcs {domain_idcs} are no permutations of the {J} codomain / the '
+                         f'{K} domain legs: a move that mixes the sides takes transform_tensor')
+    axes2 = [(N - 1) - i for i in domain_idcs]                                        # (:741-745)
+    old_dom = {tuple(sec): jd for jd, sec in enumerate(domain.sectors.tolist())}
+    block_of_dom = {int(j): n for n, j in enumerate(data.block_inds[:, 1])}
+    live, blocks = [], []
+    for i, j in common_sectors(new_codomain, new_domain):
+        n = block_of_dom.get(old_dom.get(tuple(new_codomain.sectors[i].tolist())))
+        if n is not None:                                                             # (no old block: no result block, :763)
+            live.append((i, j))
+            blocks.append(data.blocks[n])
+    cplx = any(_is_complex(b) for b in data.blocks) or any(
+        complex(c).imag != 0 for table in (splitting, fusion) if table is not None for targets in table.values() for c in targets.values())
+    dtype = np.complex128 if cplx else np.float64
+    # both sides are planned and checked before anything is enqueued (the codomain pass keeps the columns of a block)
+    passes = [(side, new_space, axes, _strip_records(live, blocks, side, old_space, new_space, axes, table, name))
+              for side, old_space, new_space, axes, table in ((0, codomain, new_codomain, codomain_idcs, splitting),
+                                                              (1, domain, new_domain, axes2, fusion)) if table is not None]
+    keep = [k for k in range(len(live)) if all(plan[k] is not None for _, _, _, plan in passes)]          # (:773, :780)
+    for k in keep:
+        (i, j), sh = live[k], tuple(blocks[k].shape)
+        want = (new_codomain.block_size(i) if splitting is not None else sh[0], new_domain.block_size(j) if fusion is not None else sh[1])
+        if want != (new_codomain.block_size(i), new_domain.block_size(j)):
+            raise ValueError(f'{name}: the old block of the coupled sector {new_codomain.sectors[i].tolist()} has the shape {sh}, the new '
+                             f'spaces ask for {(new_codomain.block_size(i), new_domain.block_size(j))}: a strip does not fit its block')
+    live, blocks = [live[k] for k in keep], [blocks[k] for k in keep]
+    for side, new_space, axes, plan in passes:
+        if not live:
+            break
+        shapes = [((new_space.block_size(i), b.shape[1]) if side == 0 else (b.shape[0], new_space.block_size(j))) for (i, j), b in zip(live, blocks)]
+        outs = bb.empty_many(shapes, dtype=dtype)
+        bb.tree_strip_many([(out, side, start, stop, mults_old, axes, [(src, s0, c) for s0, c in terms])
+                            for out, src, k in zip(outs, blocks, keep) for start, stop, mults_old, terms in plan[k]])
+        blocks = outs
+    if not live:
+        return FusionTreeData(np.zeros((0, 2), np.int64), [])
+    return FusionTreeData(np.array(live, dtype=np.int64), list(blocks))
 
 
 def discard_zero_blocks(bb, data: FusionTreeData, eps: float) -> FusionTreeData:

@@ -147,13 +147,16 @@ class TreeChainOperator:
     * ``('compose_left', A)``: ``X <- A X``, `A` a :class:`fusion_tree.TreeTensor` whose domain is X's codomain;
     * ``('compose_right', B)``: ``X <- X B``, `B` a TreeTensor whose codomain is X's domain;
     * ``('transform', new_codomain, new_domain, codomain_idcs, domain_idcs, mapping)``: one ``ft.transform_tensor``;
+    * ``('transform_factorized', new_codomain, new_domain, codomain_idcs, domain_idcs, splitting, fusion)``: one
+      ``ft.transform_tensor_factorized`` -- braids and twists inside each side, either map may be None (the identity);
     * ``('partial_compose', B, b_codomain, b_domain, new_codomain, new_domain, insert)``: one ``ft.partial_compose`` of X with
       the blocks `B` (a :class:`fusion_tree.FusionTreeData`) on (`b_codomain`, `b_domain`), `insert` a
       :class:`fusion_tree.TreeInsert` -- a site operator or a gate applied to some legs of one side of X.
 
     ``matvec`` tracks the spaces through the chain; the constructor checks that every step fits the spaces the one before
     leaves.  ``is_complex``: any operand block, mapping coefficient or insert amplitude is complex.  This is host composition of the existing
-    launches (one grouped GEMM per compose, one ``transform_blocks`` per transform); recording and replaying the launch
+    launches (one grouped GEMM per compose, one ``transform_blocks`` per transform, at most two ``tree_strip_many`` per
+    factorized transform); recording and replaying the launch
     sequence (:mod:`cyten_amd.replay`) is out of scope here."""
 
     def __init__(self, bb, steps, codomain, domain):
@@ -181,6 +184,13 @@ class TreeChainOperator:
                 cod, dom = st[1], st[2]
                 cplx = cplx or any(isinstance(c, (complex, np.complexfloating)) and complex(c).imag != 0.0
                                    for targets in st[5].values() for c in targets.values())
+            elif kind == 'transform_factorized':
+                if len(st) != 7:
+                    raise ValueError(f'step {n}: (\'transform_factorized\', new_codomain, new_domain, codomain_idcs, domain_idcs, splitting, '
+                                     'fusion) expected')
+                cod, dom = st[1], st[2]
+                cplx = cplx or any(isinstance(c, (complex, np.complexfloating)) and complex(c).imag != 0.0
+                                   for table in st[5:7] if table is not None for targets in table.values() for c in targets.values())
             elif kind == 'partial_compose':
                 if len(st) != 7 or not isinstance(st[1], ft.FusionTreeData) or not isinstance(st[6], ft.TreeInsert):
                     raise ValueError(f'step {n}: (\'partial_compose\', FusionTreeData, b_codomain, b_domain, new_codomain, new_domain, '
@@ -204,6 +214,10 @@ class TreeChainOperator:
             elif st[0] == 'partial_compose':
                 _, B, b_cod, b_dom, new_cod, new_dom, insert = st
                 data = ft.partial_compose(bb, data, cod, dom, B, b_cod, b_dom, new_cod, new_dom, insert)
+                cod, dom = new_cod, new_dom
+            elif st[0] == 'transform_factorized':
+                _, new_cod, new_dom, codomain_idcs, domain_idcs, splitting, fusion = st
+                data = ft.transform_tensor_factorized(bb, data, cod, dom, new_cod, new_dom, codomain_idcs, domain_idcs, splitting, fusion)
                 cod, dom = new_cod, new_dom
             else:
                 _, new_cod, new_dom, codomain_idcs, domain_idcs, mapping = st

@@ -805,6 +805,53 @@ typedef struct {
 int cyb_tree_place_f64(cyb_ctx_t ctx, const cyb_tree_place_rec* recs, int64_t n_recs);
 int cyb_tree_place_c128(cyb_ctx_t ctx, const cyb_tree_place_rec* recs, int64_t n_recs);
 
+/* ---- grouped, weighted sums of strided windows ----------------------------------------------------------------------
+ * Every strip of every result block of one side of a factorized fusion-tree move in ONE launch:
+ * FactorizedTreeMapping::transform_splitting_trees / ::transform_fusion_trees (src/backends/fusion_tree_mapping.cpp:627-674,
+ * :676-725) make get_item, mul and operator+ per (new tree, old tree), then permute_combined_idx and set_item per new tree,
+ * into a zero-filled block.  An output record is one window of a result block, the window of cyb_tree_place_rec (h rows, nq
+ * runs of wn columns, one run every cp columns, leading dimension ldd; dst addresses its first element), with ONE table of
+ * source levels that all of its terms share; a term record is one source: a pointer, a coefficient and a base offset:
+ *   dst[r * ldd + q * cp + w] = sum_t c_t * src_t[base_t + sum_l r_l * rs[l] + sum_l x_l * cs[l]]      r < h, q < nq, w < wn
+ * r is counted in C order over the n_row_levels levels rext[] (their product is h), x = q * wn + w in C order over the
+ * n_col_levels levels cext[] (their product is nq * wn); c_t = coeff_re + i coeff_im; t runs over first_term ..
+ * first_term + n_terms - 1 of the term list.
+ *   * An output with no terms is written as zeros (its levels and strides are not read): nothing needs a memset.
+ *   * Every destination element has exactly one owner, which adds its terms in ascending order in registers: no atomics, no
+ *     zero fill, no second pass; results are bit-identical from run to run.  The first term is assigned: an output with one
+ *     term and c == 1 receives the bits of its source (-0.0, NaN payloads); any other c is one product per component pair.
+ *   * Source strides and base count elements of the source's own type and may be zero or negative.  Sources are read in
+ *     place, transposed views included, and may overlap each other.  The caller vouches for every address they reach.
+ *   * src_real != 0 (c128 entry only; the f64 entry ignores it): the source is float64 data read as it stands, strides and
+ *     base in doubles -- real data under a complex coefficient needs no promotion pass.  The c128 entry reads and writes
+ *     interleaved (re, im) storage otherwise; cp and ldd count complex elements.
+ *   * The f64 entry requires coeff_im == 0 of every term: else CYB_ERR_INVALID, nothing is launched.
+ *   * Windows of one call must not overlap each other or a source; the caller vouches for that.
+ *   * Zero extents and empty lists are valid.  cp is not read where nq == 1, ldd not where h == 1.
+ *   * Everything is validated on the host before anything is uploaded or launched: level counts, term ranges, negative
+ *     extents and extents beyond 2^30, the products of the levels against h and nq * wn (of an output with terms), cp < wn
+ *     with nq > 1, ldd < (nq - 1) * cp + wn with h > 1, NULL dst of a non-empty window, NULL src of one of its terms.  A
+ *     refused call returns CYB_ERR_INVALID with a message and leaves the context as it found it.
+ * One wave owns a work item of a record; 16-byte stores where every pair of the window is aligned, one 16-byte load per pair
+ * where the innermost source level has the stride 1 and every term is aligned, gathered loads where a permutation moves the
+ * innermost level (csrc/tree_strip.hip). */
+typedef struct {
+    double* dst;
+    int64_t h, nq, wn, cp, ldd;
+    int32_t n_row_levels, n_col_levels;
+    int64_t rext[CYB_TREE_PLACE_MAX_LEVELS], rs[CYB_TREE_PLACE_MAX_LEVELS];
+    int64_t cext[CYB_TREE_PLACE_MAX_LEVELS], cs[CYB_TREE_PLACE_MAX_LEVELS];
+    int64_t first_term, n_terms;
+} cyb_tree_strip_out;
+typedef struct {
+    const double* src;
+    double coeff_re, coeff_im;
+    int32_t src_real, reserved;
+    int64_t base; /* offset of the term's first element from src */
+} cyb_tree_strip_term;
+int cyb_tree_strip_f64(cyb_ctx_t ctx, const cyb_tree_strip_out* outs, int64_t n_outs, const cyb_tree_strip_term* terms, int64_t n_terms);
+int cyb_tree_strip_c128(cyb_ctx_t ctx, const cyb_tree_strip_out* outs, int64_t n_outs, const cyb_tree_strip_term* terms, int64_t n_terms);
+
 /* ---- grouped matrix exponential of small blocks ---------------------------------------------------------------------
  * E = exp(alpha * A) for every listed square matrix in ONE launch, one workgroup per matrix, the whole computation in LDS
  * (csrc/expm_small.hip).  Replaces NumpyBlockBackend::matrix_exp = scipy.linalg.expm (src/block_backend/numpy.cpp:1227-1234),
