@@ -22,7 +22,7 @@ struct JMat {
     int32_t nv;     // true vector count
     int32_t len;    // true vector length
     int32_t rec_j;  // J == nullptr because the caller rebuilds the rotations afterwards (svd_jacobi.hip, rotation recovery): the
-                    // matrix keeps the parts per pair it would have with J (see the chain estimate of jacobi_orthogonalise)
+                    // matrix keeps the parts per pair it would have with J (see the chain estimate of plan_parts, jacobi_plan.h)
     double tol;     // convergence threshold on |g_ij| / sqrt(g_ii g_jj)
     double thr2;    // rows with 0 < |w|^2 <= thr2 are numerically null and get zeroed (deflation); 0: off
 };
@@ -34,7 +34,8 @@ struct JWork {
 
 // Host driver: runs sweeps over all matrices until converged (or max_sweeps).  `h_mats` are the
 // host copies of the descriptors (device copy made inside).  sweeps_out[i] = sweeps used, or
-// -1 if matrix i did not converge.  Synchronises the stream once per sweep (reads a few bytes).
+// -1 if matrix i did not converge.  Synchronises the stream once per sweep (reads a few bytes), or once
+// per call where one launch runs every sweep (lists of small matrices).  The plan of a sweep is jacobi_plan.h.
 int jacobi_orthogonalise(cyb_ctx_t ctx, const std::vector<JMat>& h_mats, int max_sweeps,
                          std::vector<int32_t>& sweeps_out, bool cplx = false);
 

@@ -3,28 +3,31 @@
 // Replaces the per-block LAPACK calls of the reference (scipy.linalg.svd -> dgesdd,
 // src/block_backend/numpy.cpp:1247-1297; np.linalg.eigh -> dsyevd, numpy.cpp:658-680) with a
 // Hestenes one-sided Jacobi in *block* form so that the O(len * nv^2) work per sweep runs on the
-// f64 MFMA pipe:
-//   for every round of the round-robin schedule over blocks of JB=16 vectors, a block pair (P,Q) of one
-//   matrix goes through TWO launches:
-//     A. jacobi_gram_kernel (G workgroups per pair)
-//          Gram   G = X X^T       X = [W_P; W_Q] (32 x len), MFMA 16x16x4 f64 straight from global memory,
-//                                 K = len split over the G parts, last arriver sums the partials
-//          eigh   G ~ Qm L Qm^T   ONE sweep of two-sided Jacobi on the 32x32 Gram matrix in LDS (16 disjoint
-//                                 rotations per inner round, one barrier each), deflation of numerically null
-//                                 rows, in-pair descending sort, Qm published
-//          (+ workgroups that apply the PREVIOUS round's Qm to J, which nothing reads before the end)
-//     B. jacobi_update_kernel     X <- Qm^T X on W (64-column chunks, MFMA, operands straight from global)
-//   Rounds are separate launches (the next round needs this round's rows); the per-sweep
-//   convergence measure max |g_ij|/sqrt(g_ii g_jj) is accumulated with an atomic max and read by
-//   the host once per sweep.
+// f64 MFMA pipe.  The rows of a matrix are cut into blocks of JB=16 vectors; a sweep takes every pair of blocks
+// (P,Q) once, in the nb - 1 rounds of a round-robin schedule.  A pair visit is
+//     Gram   G = X X^T       X = [W_P; W_Q] (32 x len), MFMA 16x16x4 f64 straight from global memory
+//     eigh   G ~ Qm L Qm^T   two-sided Jacobi on the 32x32 Gram matrix in LDS, deflation of numerically null
+//                            rows, in-pair descending sort
+//     update X <- Qm^T X     on W, and on J where the rotations are accumulated (64-column chunks, MFMA)
+// and the per-sweep convergence measure max |g_ij|/sqrt(g_ii g_jj) is accumulated with an atomic max.
+//
+// THE ENGINE is the persistent sweep, jacobi_sweep_kernel: ONE launch per sweep (or for all sweeps of a list of small
+// matrices), every (pair slot, column part) workgroup resident for the whole launch, rounds handed on through counters
+// in memory.  Its plan -- parts per pair, shared workgroups, layout of the counters, convergence rule -- is
+// jacobi_plan.h.  The host reads the off-norms once per sweep.
+//
+// THE FALLBACK is the split route, jacobi_gram_kernel + jacobi_update_kernel: two launches per round, no residency
+// constraint, operands addressed with 64-bit pointers.  It serves lists that hold a matrix of 2^31 bytes or more (the
+// sweep kernel addresses W and J through 32-bit buffer offsets) and CYB_JACOBI_NOSWEEP, the test hook that keeps it
+// exercised; embedded complex rows have no fallback and are refused there.
 #include "jacobi_engine.h"
+#include "jacobi_plan.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 
 namespace cyb {
-constexpr double kPredictQuad = 16.0; // the last sweep is predicted only behind a step with off <= kPredictQuad * prev^2 (jacobi_orthogonalise)
 namespace {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
@@ -121,6 +124,9 @@ __device__ __forceinline__ void jacobi_rot(double a, double d, double b, double&
 
 __device__ __forceinline__ int xrow(int i, int P, int Q) { return (i < JB) ? P * JB + i : Q * JB + (i - JB); }
 
+// ================================================================================================
+// Split route (the fallback): TWO launches per round of the round-robin schedule.
+//
 // Per-round scratch shared by the two kernels of a round (one entry per block pair of the round).
 struct JScratch {
     double* gpart;        // [pair][part][JP*JP]  partial Gram matrices
@@ -496,37 +502,53 @@ jacobi_update_kernel(const JMat* __restrict__ mats, const JWork* __restrict__ wo
     update_role(mats, work, round, blockIdx.x / U, blockIdx.x % U, U, sc, buf, do_w != 0, do_j != 0, smem, zflag);
 }
 
-
 // ================================================================================================
-// Fused round: ONE launch per round of the round-robin schedule (the default path).
+// Persistent sweep: ONE launch per sweep (all rounds of the round-robin schedule of every matrix).
 //
-// grid = pairs x G.  The G workgroups of a block pair own disjoint COLUMN shares of the pair's 32 rows
-// (whole 64-column chunks of W, and of J) for the whole launch:
-//   0. ONE 64-byte descriptor read (pair + matrix), then every global load of the launch is issued up front: the own W
-//      share in Gram layout and -- for shares of up to six chunks -- the own W / J share in update layout, which waits
-//      in registers behind the eigensolve
+// Workgroup (pair slot s of matrix m, column part g) stays on its CU for the whole sweep and walks the rounds
+// r = 0 .. nb_m - 2 itself.  What used to be a kernel boundary between two rounds is a DATAFLOW hand-off: the rows of
+// block P (column share g) updated in round r by the workgroup that held P then are picked up in round r + 1 by the
+// workgroup whose slot the schedule moves P to -- same part g, so every (block, part) piece has exactly one owner per
+// round and ownership travels with a monotonic counter  ready[block][part] = rounds completed  (Guideline 16: the piece
+// is stored write-through (sc1), every storing wave drains, barrier, ONE lane publishes the counter; the next owner polls
+// it with ONE lane, barrier, then reads the piece with sc1 loads).  Consequences:
+//   * no launch ramp / drain / descriptor fetch per round (8-10 us of a 44 us round with a launch of its own);
+//   * matrices are DECOUPLED: a small block never waits for a large one and vice versa -- the lockstep of a
+//     launch per round makes every round as slow as its slowest pair and keeps the small blocks' pairs (most of the
+//     pairs of a theta list) in the large blocks' rounds;
+//   * parts per pair are chosen per matrix (long chains get the CUs): G_m in RPair.pad[0].
+//
+// A round of a workgroup.  The G workgroups of a block pair own disjoint COLUMN shares of the pair's 32 rows (whole
+// 64-column chunks of W, and of J) for the whole launch:
+//   0. wait for the two row blocks (above); every global load of the round is issued as early as its place in the load
+//      queue allows: the own W share in Gram layout and -- for shares of up to SW_PRE chunks -- the own W / J share in
+//      update layout, which waits in registers behind the eigensolve
 //   1. partial Gram over the own W share (MFMA, operands straight from memory)
-//   2. G > 1: every part publishes its 32x32 partial (16-byte write-through stores, drained, one arrival ticket per
-//      workgroup) and ALL G parts wait for the G tickets (one lane polls, bounded), then every part reads the G
-//      partials (16-byte sc1 loads, all in flight at once) and sums them in the same fixed order -- bit-identical
-//      Gram matrices in all of them
+//   2. G > 1: the parts EXCHANGE their 32x32 partials and every part sums the G partials in the same fixed order --
+//      bit-identical Gram matrices in all of them.  Two forms (template parameter GRAN).  Ticket form: every part publishes
+//      its partial with 16-byte write-through stores, every storing wave drains, ONE lane adds an arrival ticket for the
+//      workgroup and polls it (bounded) until all G have arrived, workgroup barrier, then every part reads the G partials
+//      with 16-byte sc1 loads, all in flight at once.  Granule form: the data is the flag (see step 2 in the kernel).
+//      In both the partials are DOUBLE BUFFERED by round parity, and the ticket is monotonic (target G (r + 1)): a part
+//      can be at most one exchange ahead of its partners -- it cannot store round r + 2 before its own wait of round r + 1
+//      has seen every partner's partial of r + 1, which a partner publishes only after it has read those of round r -- so
+//      nobody still reads the buffer a store overwrites, and nothing is reset between rounds.
 //   3. deflation test, convergence measure, two-sided Jacobi eigensolve of the 32x32 Gram, REDUNDANTLY in every part
 //      (the chip is idle otherwise; no second exchange, no publish of Qm)
-//   4. X <- Qm^T X on the own column share of W and J, in place
-// No workgroup reads or writes a column another workgroup of the launch touches, so rows need no hand-off inside
-// the launch; the only inter-workgroup data are the 8 KB partials (cdna_hip_programming.md Guideline 16: sc1
-// stores, every storing wave drained, one agent-scope ticket per workgroup, one polling lane, workgroup barrier,
-// sc1 loads).  The wait needs the G parts of a pair to be co-resident: the host keeps grid <= number of CUs and the
-// kernel asks for more than half a CU's LDS, so every workgroup has a CU of its own.  Every spin is bounded (wall
-// clock); a timeout raises a flag the host turns into an error.
+//   4. X <- Qm^T X on the own column share of W and J, in place, then the hand-off of the two row blocks
+// No workgroup reads or writes a column another workgroup of the launch touches, so within a round rows need no hand-off;
+// the only data that cross between the parts of a pair are the 8 KB partials.
 //
-// Eigensolver, second version: the Gram matrix and the accumulated rotations live in LDS in POSITION space --
-// thread (pr, pc) always owns the 2x2 block at block position (pr, pc), the matrix is physically permuted by the
-// writes of every step (Brent-Luk ring: position 0 fixed, the other 31 advance one place), so a step is ONE LDS
-// round trip (own block + the two diagonal blocks that define the thread's row and column rotation, both derived
-// redundantly by every thread, branch-free so that the two dependent chains interleave), the 2x2 updates, eight
-// scattered stores and one barrier: no schedule table, no lane exchange.  After 31 steps every index is back at its
-// position.
+// Eigensolver: the Gram matrix and the accumulated rotations live in LDS in POSITION space -- thread (pr, pc) always owns
+// the 2x2 block at block position (pr, pc), the matrix is physically permuted by the writes of every step (Brent-Luk ring:
+// position 0 fixed, the other 31 advance one place, ring_next), so a step is ONE LDS round trip (own block + the diagonal
+// block that defines the thread's column rotation, derived branch-free by every thread; the row rotation comes from the lane
+// that derived it as its column rotation), the 2x2 updates, eight scattered stores and one barrier: no schedule table.
+// After 31 steps every index is back at its position.
+//
+// Every wait is bounded by the wall clock AND leaves as soon as any workgroup has raised the error word, so a lost partner
+// turns into an error code within a second, never into a hang.  All workgroups must be resident: the host launches at most
+// one per CU and the kernel's LDS request (more than half a CU's) admits no second one.
 struct RPair {            // everything a workgroup needs to know about its pair: one 64-byte read
     double* W;
     double* J;            // may be null
@@ -537,14 +559,6 @@ struct RPair {            // everything a workgroup needs to know about its pair
 };
 static_assert(sizeof(RPair) == 64, "RPair is read as one 64-byte descriptor");
 
-struct RScratch {
-    double* gpart;       // [pair][G][JP*JP]  partial Gram matrices
-    unsigned int* cnt;   // [round][pair]     arrival tickets (zeroed once per sweep)
-    unsigned int* err;   // [1]               set when a bounded wait ran out
-    int np;              // pairs per round row of cnt
-    unsigned long long* stamps; // diagnostic runs only (CYB_JACOBI_STAMPS): [workgroup][8] wall-clock stamps, else null
-};
-
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 union Q16 {               // one 16-byte memory word = two doubles
     u32x4 u;
@@ -552,11 +566,7 @@ union Q16 {               // one 16-byte memory word = two doubles
 };
 
 constexpr int VS = JP + 2;                                      // row stride of V in LDS (position space)
-constexpr int ROUND_LDS_DOUBLES = 2 * JP * GS + 2 * JP * VS + JP * QS + 4 * JP * GS + 8;
-constexpr size_t ROUND_LDS_BYTES = 88 * 1024;                  // > half of the CU's 160 KB: one workgroup per CU
-static_assert(ROUND_LDS_DOUBLES * 8 + 1024 <= ROUND_LDS_BYTES, "LDS carve-up of the fused round kernel");
-constexpr int RGMAX = 8;                                        // most parts per pair
-constexpr int RPRE = 6;                                         // update chunks held in registers across the eigensolve
+static_assert(sizeof(RPair) == kPlanPairBytes && sizeof(int2) == kPlanMapBytes && sizeof(PlanRange) == sizeof(int2), "descriptor image of jacobi_plan.h");
 
 __device__ __forceinline__ int ring_next(int p)  // destination position of position p after one step
 {
@@ -603,366 +613,7 @@ __device__ __forceinline__ void jacobi_rot_bf(double a, double d, double b, doub
     s = ok ? (pos ? sabs : -sabs) : 0.0;
 }
 
-__global__ void __launch_bounds__(NT, 1)
-jacobi_round_kernel(const RPair* __restrict__ pairs, int round, int G, int max_inner,
-                    unsigned long long* __restrict__ offmax_bits, RScratch sc)
-{
-    extern __shared__ __attribute__((aligned(16))) double rsm[];
-    double* Gs = rsm;                    // Gram, buffer a
-    double* G2 = Gs + JP * GS;           // Gram, buffer b
-    double* Va = G2 + JP * GS;           // accumulated rotations, buffer a
-    double* Vb = Va + JP * VS;
-    double* Qs = Vb + JP * VS;           // Qm^T operand of the update: [k][m], output-row order
-    double* Xc = Qs + JP * QS;           // wave slices of the partial Gram (4 x JP x GS)
-    double* red = Xc + 4 * JP * GS;
-    int* ibase = reinterpret_cast<int*>(red + 8);
-    int* perm = ibase;                   // output row -> eigenvector column (descending eigenvalue)
-    int* zrow = ibase + JP;              // 1: this row of the pair is numerically null (deflated)
-    int* zout = ibase + 2 * JP;          // zrow in output-row order
-    int* flags = ibase + 3 * JP;         // [0] any null  [1] wait ok
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int pi = blockIdx.x / G, part = blockIdx.x % G;
-    // (diagnostic stamps go to a buffer nothing else reads; no output depends on them)
-#define ROUND_STAMP(k)                                                                              \
-    do {                                                                                            \
-        if (sc.stamps && tid == 0) sc.stamps[(size_t)blockIdx.x * 8 + (k)] = wall_clock64();        \
-    } while (0)
-    ROUND_STAMP(0);
-    const RPair mt = pairs[pi];
-    if (round >= mt.nb - 1) return; // this matrix has fewer rounds per sweep
-    int P, Q;
-    circle_pair(mt.nb, round, mt.slot, P, Q);
-    if (P > Q) {
-        const int t = P;
-        P = Q;
-        Q = t;
-    }
-    // column shares in whole 64-column chunks
-    const int cw = mt.lenp / 64, cj = mt.J ? mt.nvp / 64 : 0;
-    const int w_begin = (int)((int64_t)part * cw / G), w_end = (int)((int64_t)(part + 1) * cw / G);
-    const int j_begin = (int)((int64_t)part * cj / G), j_end = (int)((int64_t)(part + 1) * cj / G);
-    const int nW = w_end - w_begin, nJ = j_end - j_begin;
-    const int ct = nW + nJ;
-    const int un = lane & 15, ukq = lane >> 4;
-    auto chunk_ptr = [&](int c, int k) -> gp { // update layout: element (row k of the pair, column un of wave's 16) of own chunk c
-        const bool in_w = c < nW;
-        gp base = (gp)(in_w ? mt.W : mt.J);
-        const int ld = in_w ? mt.lenp : mt.nvp;
-        const int cc = in_w ? w_begin + c : j_begin + (c - nW);
-        return base + (int64_t)xrow(k, P, Q) * ld + cc * 64 + wave * 16 + un;
-    };
-
-    // ---- 1. partial Gram over the own W share (see jacobi_gram_kernel for the operand mapping)
-    double xpre[RPRE][JP / 4];
-    {
-        gp W = (gp)mt.W;
-        const int ld = mt.lenp;
-        d4 acc00 = d4{0.0, 0.0, 0.0, 0.0}, acc01 = acc00, acc11 = acc00;
-        const int r = lane & 15, g2 = 2 * (lane >> 4);
-        gcp2 s0 = (gcp2)(W + (int64_t)xrow(r, P, Q) * ld + g2);
-        gcp2 s1 = (gcp2)(W + (int64_t)xrow(r + 16, P, Q) * ld + g2);
-        const int c_begin = 8 * w_begin, c_end = 8 * w_end; // in 8-column chunks
-        constexpr int UN = 8;
-        d2 x0[UN], x1[UN], n0[UN], n1[UN];
-        auto load = [&](d2 (&a0)[UN], d2 (&a1)[UN], int c0) {
-#pragma unroll
-            for (int u = 0; u < UN; ++u) {
-                const int c = min(c0 + 4 * u, c_end - 1);
-                a0[u] = s0[c * 4];
-                a1[u] = s1[c * 4];
-            }
-        };
-        if (c_begin + wave < c_end) load(x0, x1, c_begin + wave);
-        // the operands of step 4 (own share in update layout) are requested now and wait behind the eigensolve
-#pragma unroll
-        for (int c = 0; c < RPRE; ++c) {
-            if (c < ct) {
-#pragma unroll
-                for (int kk = 0; kk < JP / 4; ++kk) xpre[c][kk] = *chunk_ptr(c, 4 * kk + ukq);
-            }
-        }
-        for (int c0 = c_begin + wave; c0 < c_end; c0 += 4 * UN) {
-            const bool more = c0 + 4 * UN < c_end;
-            if (more) load(n0, n1, c0 + 4 * UN);
-#pragma unroll
-            for (int u = 0; u < UN; ++u) {
-                if (c0 + 4 * u < c_end) {
-                    acc00 = __builtin_amdgcn_mfma_f64_16x16x4f64(x0[u].x, x0[u].x, acc00, 0, 0, 0);
-                    acc01 = __builtin_amdgcn_mfma_f64_16x16x4f64(x0[u].x, x1[u].x, acc01, 0, 0, 0);
-                    acc11 = __builtin_amdgcn_mfma_f64_16x16x4f64(x1[u].x, x1[u].x, acc11, 0, 0, 0);
-                    acc00 = __builtin_amdgcn_mfma_f64_16x16x4f64(x0[u].y, x0[u].y, acc00, 0, 0, 0);
-                    acc01 = __builtin_amdgcn_mfma_f64_16x16x4f64(x0[u].y, x1[u].y, acc01, 0, 0, 0);
-                    acc11 = __builtin_amdgcn_mfma_f64_16x16x4f64(x1[u].y, x1[u].y, acc11, 0, 0, 0);
-                }
-            }
-            if (more) {
-#pragma unroll
-                for (int u = 0; u < UN; ++u) {
-                    x0[u] = n0[u];
-                    x1[u] = n1[u];
-                }
-            }
-        }
-        double* wpart = Xc + wave * (JP * GS);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int rr = (lane >> 4) + 4 * q, cc = lane & 15;
-            wpart[rr * GS + cc] = acc00[q];
-            wpart[rr * GS + 16 + cc] = acc01[q];
-            wpart[(16 + cc) * GS + rr] = acc01[q]; // mirror of tile (0,1)
-            wpart[(16 + rr) * GS + 16 + cc] = acc11[q];
-        }
-    }
-    __syncthreads();
-    ROUND_STAMP(1);
-    {
-        // every thread owns four consecutive entries of the 32 x 32 matrix (row e4 / 8, columns 4 (e4 % 8) ...)
-        const int gi = tid >> 3, gj = 4 * (tid & 7);
-        d2 lo = d2{0.0, 0.0}, hi = d2{0.0, 0.0};
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const double* src = Xc + w * (JP * GS) + gi * GS + gj;
-            lo.x += src[0];
-            lo.y += src[1];
-            hi.x += src[2];
-            hi.y += src[3];
-        }
-        if (G > 1) {
-            // ---- 2. exchange of the partials among the G parts of this pair
-            const unsigned int pbytes = JP * JP * 8;
-            __amdgpu_buffer_rsrc_t rs_all = __builtin_amdgcn_make_buffer_rsrc(sc.gpart + (size_t)pi * G * (JP * JP), 0, pbytes * G, 0x00020000);
-            Q16 a, b;
-            a.d = lo;
-            b.d = hi;
-            const unsigned int off = (unsigned int)part * pbytes + (unsigned int)tid * 32u;
-            __builtin_amdgcn_raw_buffer_store_b128(a.u, rs_all, off, 0, 16);        // aux 16 = sc1: write-through
-            __builtin_amdgcn_raw_buffer_store_b128(b.u, rs_all, off + 16u, 0, 16);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // every storing wave drains ...
-            __syncthreads();                                  // ... before ONE lane takes the ticket for the workgroup
-            if (tid == 0) {
-                unsigned int* ticket = sc.cnt + (size_t)round * sc.np + pi;
-                __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                int ok = 1;
-                const unsigned long long t0 = wall_clock64(); // 100 MHz
-                while (__hip_atomic_load(ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned int)G) {
-                    __builtin_amdgcn_s_sleep(1);
-                    if (wall_clock64() - t0 > 100000000ull) { // one second: a partner is not resident / died
-                        ok = 0;
-                        __hip_atomic_store(sc.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        break;
-                    }
-                }
-                flags[1] = ok;
-            }
-            __syncthreads(); // the polling wave joins the barrier after its poll matched; the others load after it
-            if (!flags[1]) return;
-            Q16 pa[RGMAX], pb[RGMAX];
-#pragma unroll
-            for (int g = 0; g < RGMAX; ++g) { // every load in flight before the first use
-                if (g < G) {
-                    pa[g].u = __builtin_amdgcn_raw_buffer_load_b128(rs_all, (unsigned int)g * pbytes + (unsigned int)tid * 32u, 0, 16);
-                    pb[g].u = __builtin_amdgcn_raw_buffer_load_b128(rs_all, (unsigned int)g * pbytes + (unsigned int)tid * 32u + 16u, 0, 16);
-                }
-            }
-            lo = d2{0.0, 0.0};
-            hi = d2{0.0, 0.0};
-#pragma unroll
-            for (int g = 0; g < RGMAX; ++g) { // the same order in every part: bit-identical sums
-                if (g < G) {
-                    lo += pa[g].d;
-                    hi += pb[g].d;
-                }
-            }
-        }
-        double* dst = Gs + gi * GS + gj;
-        dst[0] = lo.x;
-        dst[1] = lo.y;
-        dst[2] = hi.x;
-        dst[3] = hi.y;
-    }
-    __syncthreads();
-    ROUND_STAMP(2);
-    // ---- 3a. deflation: rows whose squared norm fell below the numerical-rank threshold are zeroed
-    if (tid == 0) flags[0] = 0;
-    __syncthreads();
-    if (tid < JP) {
-        const double g = Gs[tid * GS + tid];
-        const int z = (g > 0.0 && g <= mt.thr2) ? 1 : 0;
-        zrow[tid] = z;
-        perm[tid] = tid;
-        if (z) flags[0] = 1;
-    }
-    __syncthreads();
-    const bool any_null = flags[0] != 0;
-    if (any_null) {
-        for (int e = tid; e < JP * JP; e += NT) {
-            const int i = e / JP, j = e % JP;
-            if (zrow[i] || zrow[j]) Gs[i * GS + j] = 0.0;
-        }
-        __syncthreads();
-    }
-    // ---- 3b. convergence measure; nothing to do if this pair is already orthogonal
-    const double off = gram_offmax(Gs, red, tid);
-    if (part == 0 && tid == 0) atomicMax(offmax_bits + mt.mat, (unsigned long long)__double_as_longlong(off));
-    if (off <= mt.tol && !any_null) return; // (the same decision in every part: identical Gram matrices)
-
-    ROUND_STAMP(3);
-    // ---- 3c. two-sided Jacobi eigensolve in position space
-    for (int e = tid; e < JP * VS; e += NT) Va[e] = ((e / VS) == (e % VS)) ? 1.0 : 0.0;
-    __syncthreads();
-    double* Ga = Gs;
-    double* Gb = G2;
-    double* Vc = Va;
-    double* Vn = Vb;
-    {
-        const int pr = tid >> 4, pc = tid & 15;
-        const int r0 = 2 * pr, c0 = 2 * pc;
-        const int dr0 = ring_next(r0), dr1 = ring_next(r0 + 1), dc0 = ring_next(c0), dc1 = ring_next(c0 + 1);
-        for (int sweep = 0; sweep < (off <= mt.tol ? 0 : max_inner); ++sweep) {
-            for (int r = 0; r < JP - 1; ++r) {
-                const d2 g0 = *reinterpret_cast<const d2*>(Ga + r0 * GS + c0);
-                const d2 g1 = *reinterpret_cast<const d2*>(Ga + (r0 + 1) * GS + c0);
-                const d2 ac = *reinterpret_cast<const d2*>(Ga + c0 * GS + c0);
-                const double dc = Ga[(c0 + 1) * GS + c0 + 1];
-                const d2 v0 = *reinterpret_cast<const d2*>(Vc + r0 * VS + c0);
-                const d2 v1 = *reinterpret_cast<const d2*>(Vc + (r0 + 1) * VS + c0);
-                // ONE rotation chain per thread (its column pair); the row pair's rotation comes from lane pc == pr of the
-                // same 16-lane row (the step is bound by the f64 instruction count: 1196 -> 935 cycles, eig_step_probe.hip)
-                double c1, s1, c2, s2;
-                jacobi_rot_bf(ac.x, dc, ac.y, c2, s2);
-                const int rsrc = (lane & 48) | pr;
-                c1 = __shfl(c2, rsrc);
-                s1 = __shfl(s2, rsrc);
-                // G <- R1^T G R2 on the own 2x2 block
-                const double hik = c1 * g0.x - s1 * g1.x, hil = c1 * g0.y - s1 * g1.y;
-                const double hjk = s1 * g0.x + c1 * g1.x, hjl = s1 * g0.y + c1 * g1.y;
-                double nik = c2 * hik - s2 * hil, nil = s2 * hik + c2 * hil;
-                double njk = c2 * hjk - s2 * hjl, njl = s2 * hjk + c2 * hjl;
-                if (pr == pc) { // the rotated diagonal block is diagonal by construction
-                    nil = 0.0;
-                    njk = 0.0;
-                }
-                Gb[dr0 * GS + dc0] = nik;
-                Gb[dr0 * GS + dc1] = nil;
-                Gb[dr1 * GS + dc0] = njk;
-                Gb[dr1 * GS + dc1] = njl;
-                // V <- V R2 : rows (r0, r0 + 1) stay, column positions move with the ring
-                Vn[r0 * VS + dc0] = c2 * v0.x - s2 * v0.y;
-                Vn[r0 * VS + dc1] = s2 * v0.x + c2 * v0.y;
-                Vn[(r0 + 1) * VS + dc0] = c2 * v1.x - s2 * v1.y;
-                Vn[(r0 + 1) * VS + dc1] = s2 * v1.x + c2 * v1.y;
-                __syncthreads();
-                double* t = Ga;
-                Ga = Gb;
-                Gb = t;
-                t = Vc;
-                Vc = Vn;
-                Vn = t;
-            }
-            if (sweep + 1 < max_inner) {
-                const double off_in = gram_offmax(Ga, red, tid);
-                if (off_in <= 0.25 * mt.tol) break;
-            }
-        }
-    }
-    __syncthreads();
-    ROUND_STAMP(4);
-    // de Rijk-style ordering inside the pair: larger norms to the lower rows; padding rows stay last (see jacobi_gram_kernel)
-    if (off > mt.tol && tid < JP) {
-        auto key = [&](int i) { return xrow(i, P, Q) < mt.nv ? Ga[i * GS + i] : -1.0e300; };
-        const double g = key(tid);
-        int rk = 0;
-        for (int j = 0; j < JP; ++j) {
-            const double gj = key(j);
-            rk += (gj > g || (gj == g && j < tid)) ? 1 : 0;
-        }
-        perm[rk] = tid;
-    }
-    __syncthreads();
-    // ---- 4. X <- Qm^T X on the own chunks.  A operand of the MFMA: A[m][k] = Qm[k][perm[m]], kept as [k][m]
-    for (int e = tid; e < JP * JP; e += NT) {
-        const int k = e / JP, m = e % JP;
-        Qs[k * QS + m] = Vc[k * VS + perm[m]];
-    }
-    if (tid < JP) zout[tid] = zrow[perm[tid]];
-    __syncthreads();
-    ROUND_STAMP(5);
-    if (ct <= 0) return;
-    const double* ap0 = Qs + (lane >> 4) * QS + (lane & 15);
-    const double* ap1 = ap0 + 16;
-    double a0[JP / 4], a1[JP / 4];
-#pragma unroll
-    for (int kk = 0; kk < JP / 4; ++kk) {
-        a0[kk] = ap0[kk * 4 * QS];
-        a1[kk] = ap1[kk * 4 * QS];
-    }
-    int zr[2][4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) zr[i][q] = zout[i * 16 + (lane >> 4) + 4 * q];
-    auto apply = [&](int c, const double (&xb)[JP / 4]) {
-        d4 acc[2] = {d4{0.0, 0.0, 0.0, 0.0}, d4{0.0, 0.0, 0.0, 0.0}};
-#pragma unroll
-        for (int kk = 0; kk < JP / 4; ++kk) {
-            acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[kk], xb[kk], acc[0], 0, 0, 0);
-            acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1[kk], xb[kk], acc[1], 0, 0, 0);
-        }
-        const bool zero_null = c < nW; // deflated rows are zeroed in W only
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int row = i * 16 + (lane >> 4) + 4 * q;
-                *chunk_ptr(c, row) = (zero_null && zr[i][q]) ? 0.0 : acc[i][q];
-            }
-    };
-#pragma unroll
-    for (int c = 0; c < RPRE; ++c)
-        if (c < ct) apply(c, xpre[c]);
-    if (ct > RPRE) { // long shares (few parts per pair): the rest streams with one chunk of prefetch
-        double xb[JP / 4], xn[JP / 4];
-#pragma unroll
-        for (int kk = 0; kk < JP / 4; ++kk) xb[kk] = *chunk_ptr(RPRE, 4 * kk + ukq);
-        for (int c = RPRE; c < ct; ++c) {
-            if (c + 1 < ct) {
-#pragma unroll
-                for (int kk = 0; kk < JP / 4; ++kk) xn[kk] = *chunk_ptr(c + 1, 4 * kk + ukq);
-            }
-            apply(c, xb);
-#pragma unroll
-            for (int kk = 0; kk < JP / 4; ++kk) xb[kk] = xn[kk];
-        }
-    }
-    __syncthreads();
-    ROUND_STAMP(6);
-#undef ROUND_STAMP
-}
-
-
-// ================================================================================================
-// Persistent sweep: ONE launch per sweep (all rounds of the round-robin schedule of every matrix).
-//
-// Workgroup (pair slot s of matrix m, column part g) stays on its CU for the whole sweep and walks the rounds
-// r = 0 .. nb_m - 2 itself.  What used to be a kernel boundary between two rounds is a DATAFLOW hand-off: the rows of
-// block P (column share g) updated in round r by the workgroup that held P then are picked up in round r + 1 by the
-// workgroup whose slot the schedule moves P to -- same part g, so every (block, part) piece has exactly one owner per
-// round and ownership travels with a monotonic counter  ready[block][part] = rounds completed  (Guideline 16: the piece
-// is stored write-through (sc1), every storing wave drains, barrier, ONE lane publishes the counter; the next owner polls
-// it with ONE lane, barrier, then reads the piece with sc1 loads).  Consequences:
-//   * no launch ramp / drain / descriptor fetch per round (8-10 us of a 44 us fused round);
-//   * matrices are DECOUPLED: a small block never waits for a large one and vice versa -- the lockstep of the
-//     launch-per-round paths made every round as slow as its slowest pair and kept the small blocks' pairs (most of the
-//     pairs of a theta list) in the large blocks' rounds;
-//   * parts per pair are chosen per matrix (long chains get the CUs): G_m in RPair.pad[0].
-// The partial-Gram exchange among the G parts of a pair is the one of jacobi_round_kernel, with the partials double
-// buffered by round parity (a part can be at most one exchange ahead of its partners) and a monotonic ticket
-// (target G (r + 1)).  Every wait is bounded by the wall clock AND leaves as soon as any workgroup has raised the error
-// word, so a lost partner turns into an error code within a second, never into a hang.  All workgroups must be resident:
-// the host launches at most one per CU and the kernel's LDS request admits no second one.
-// ---------------------------------------------------------------------------------------------
 // Structure-preserving pivot solve for the interleaved real embedding of COMPLEX rows: the
 // 32 x 32 Gram matrix of a pair of 16-row blocks -- 8 + 8 complex rows, real row 2a (+1) = real (imaginary) embedding row of
 // complex row a -- is M(G_c) of a 16 x 16 Hermitian G_c.  One wave diagonalises G_c by cyclic complex Jacobi rotations in
@@ -1108,6 +759,7 @@ constexpr int SW_PRE = 6;                                       // update chunks
 // each written by ONE aligned 8-byte store and read by one 8-byte load.
 constexpr int SW_GRAN_U64 = 2 * JP * JP;
 constexpr unsigned int SW_GRAN_BYTES = 8u * SW_GRAN_U64;
+static_assert(SW_GRAN_BYTES == kPlanGranBytes, "granule regions of jacobi_plan.h");
 // [Gs | region shared by the wave slices of the partial Gram (Xc) and the eigensolver's G2 / Va / Vb | Qm of this round and of the
 //  previous one (the deferred J update still reads it while the next Gram runs) | reduction scratch]
 constexpr int SWEEP_XREG = (4 * JP * GS > JP * GS + 2 * JP * VS) ? 4 * JP * GS : JP * GS + 2 * JP * VS;
@@ -1642,7 +1294,7 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
                 if (tid < 64) hermitian_pivot_solve(Gs, G2, Vb, Va, Gs, max_inner, tid, 0.25 * mt.tol * mt.tol, cross);
                 __syncthreads();
             } else {
-            // ---- 3c. eigensolve in position space (see jacobi_round_kernel)
+            // ---- 3c. eigensolve in position space (see the head of this section)
             auto cpos = [](int i) { return i < JB ? 2 * i : 2 * (i - JB) + 1; };     // index -> interleaved position
             pos_is_interleaved = cross;
             if (cross) {
@@ -1864,7 +1516,7 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
     }
     } // entries x rounds
     if (n_sw == 1) break;
-    // ---- end of a sweep, one-launch form: the host's convergence test (jacobi_orthogonalise), on the device.  Every entry
+    // ---- end of a sweep, one-launch form: the host's convergence test (jacobi_sweep_done), on the device.  Every entry
     //      of a matrix sees the same off-norms, hence takes the same decision; an entry waits until all entries of its
     //      matrix have finished the sweep, workgroups whose entries have all converged leave.
     __syncthreads();
@@ -1883,9 +1535,7 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
             const double prev = sw ? __longlong_as_double((long long)__hip_atomic_load(offmax_bits + (size_t)(sw - 1) * sc.n_mats + mt.mat,
                                                                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
                                    : 1e300;
-            const bool stagnated = sw + 1 >= 6 && off <= 64.0 * mt.tol && off >= 0.5 * prev;
-            const bool predicted = off <= 0.1 * sqrt(mt.tol) && prev < 1.0 && off <= prev * sqrt(prev) && off <= kPredictQuad * prev * prev;
-            if (off <= mt.tol || stagnated || predicted) {
+            if (jacobi_sweep_done(off, prev, mt.tol, sw + 1)) { // (the rule counts sweeps from one)
                 edone[ent - went.x] = 1;
                 if (mt.slot == 0 && wm.y == 0) sc.nsw[mt.mat] = sw + 1;
             } else all = 0;
@@ -1899,15 +1549,388 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
 #undef SWEEP_STAMP
 }
 
+// ================================================================================================
+// Host driver.  One sweep over the list is six steps (see jacobi_orthogonalise): work list, plan, scratch, launch,
+// read-back, verdicts.
+
+struct JSwitches {       // CYB_JACOBI_* (DESIGN.md section 7), read once per process
+    bool no_sweep;       // NOSWEEP: every list takes the split route (the test hook of the fallback)
+    bool per_sweep;      // PERSWEEP: a launch per sweep for every list
+    bool one_launch_all; // ONELAUNCH: one launch for all sweeps of every list
+    bool trace;          // TRACE: print every matrix's off-norm after every sweep
+    bool stamps;         // STAMPS: phase times of one round of the sweep kernel
+    bool no_predict;     // NOPREDICT: the last sweep is never predicted
+    bool gran_exchange;  // EXCHANGE=0: the partial Grams of the sweep kernel travel by stores, drain, ticket and poll (same sums
+                         // in the same order: bit-identical results); default: as tagged granules
+    bool round_order;    // ROUND_ORDER=0: the issue order a round had before (same arithmetic, same protocol: bit-identical results)
+    bool no_defer_j;     // NODEFERJ: the sweep kernel updates J at once
+    bool cross_small;    // CROSS_SMALL: cross-only pivot solves for lists of small matrices too
+    int g;               // G: parts per pair (0: chosen by plan_parts / per split round)
+    int inner;           // INNER: inner sweeps per pivot solve (0: chosen per list)
+    int cross;           // CROSS: SScratch::cross_every
+    int cross_min_nb;    // CROSS_MINNB: SScratch::cross_min_nb
+};
+const JSwitches& switches()
+{
+    static const JSwitches s = [] {
+        auto on = [](const char* name) { return getenv(name) != nullptr; };
+        auto num = [](const char* name, int dflt) { return getenv(name) ? atoi(getenv(name)) : dflt; };
+        JSwitches w;
+        w.no_sweep = on("CYB_JACOBI_NOSWEEP");
+        w.per_sweep = on("CYB_JACOBI_PERSWEEP");
+        w.one_launch_all = on("CYB_JACOBI_ONELAUNCH");
+        w.trace = on("CYB_JACOBI_TRACE");
+        w.stamps = on("CYB_JACOBI_STAMPS");
+        w.no_predict = on("CYB_JACOBI_NOPREDICT");
+        w.gran_exchange = num("CYB_JACOBI_EXCHANGE", 1) != 0;
+        w.round_order = num("CYB_JACOBI_ROUND_ORDER", 1) != 0;
+        w.no_defer_j = on("CYB_JACOBI_NODEFERJ");
+        w.cross_small = on("CYB_JACOBI_CROSS_SMALL");
+        w.g = num("CYB_JACOBI_G", 0);
+        w.inner = num("CYB_JACOBI_INNER", 0);
+        w.cross = num("CYB_JACOBI_CROSS", -1);
+        w.cross_min_nb = num("CYB_JACOBI_CROSS_MINNB", 0);
+        return w;
+    }();
+    return s;
+}
+
+struct SweepCall {   // what stays the same over the sweeps of one call
+    int n;           // matrices of the call (active or not: the convergence words are indexed by matrix)
+    int n_sw_dev;    // sweeps the one-launch form may run on the device (1: a launch per sweep)
+    size_t w_off;    // off-norm words: n * n_sw_dev
+    size_t b_off;    // bytes of the convergence words; the error word follows
+    bool cplx;
+};
+
+// ---- step 1: work list
+struct SweepList {
+    std::vector<int> order;    // active matrices, more row blocks first (late rounds of the split route use a prefix of the grid)
+    std::vector<JWork> wl;     // one item per block pair: (matrix, pair slot)
+    std::vector<PlanMat> pm;   // [position in order] what the plan looks at
+    int max_nb = 0;
+    bool any_j = false;
+    bool big_ok = true;        // every W and J lies within the 32-bit buffer offsets of the sweep kernel
+};
+SweepList build_work_list(const std::vector<JMat>& h_mats, const std::vector<int>& active)
+{
+    SweepList l;
+    l.order = active;
+    std::stable_sort(l.order.begin(), l.order.end(), [&](int a, int b) { return h_mats[(size_t)a].nb > h_mats[(size_t)b].nb; });
+    for (int m : l.order) {
+        const JMat& jm = h_mats[(size_t)m];
+        l.max_nb = std::max(l.max_nb, jm.nb);
+        for (int k = 0; k < jm.nb / 2; ++k) l.wl.push_back(JWork{m, k});
+        l.pm.push_back(PlanMat{jm.nb, jm.nvp, jm.lenp, jm.J != nullptr || jm.rec_j != 0});
+        l.any_j = l.any_j || jm.J != nullptr;
+        l.big_ok = l.big_ok && (size_t)jm.nvp * (size_t)std::max(jm.lenp, jm.nvp) * 8 < ((size_t)1 << 31);
+    }
+    return l;
+}
+
+// ---- step 3: scratch of both routes in one grow-only workspace:
+//      [zeroed block (SweepLayout) | granule regions | Gram partials | hand-off of the split route]
+struct SweepScratch {
+    void* base = nullptr;         // the zeroed block starts here: ONE fill per sweep, issued by whichever route runs it
+    size_t zero_bytes;            // ... and is this long (the sweep kernel adds the granule regions of its parts)
+    unsigned long long* d_off;    // convergence words: off-norm bits per matrix (one-launch form: see jacobi_orthogonalise)
+    unsigned int* d_err;          // set when a bounded wait ran out
+    unsigned int* d_ready;        // [one ticket per pair | ready counters of W | ready counters of J]
+    unsigned long long* d_gran;
+    double* gpart;                // (a sweep runs one route or the other)
+    JScratch split;
+    size_t split_cnt_bytes;
+};
+int carve_scratch(cyb_ctx_t ctx, const SweepLayout& L, size_t b_off, SweepScratch& s)
+{
+    const size_t np = L.np;
+    const size_t b_gpart = sizeof(double) * np * RGMAX * JP * JP, b_q = sizeof(double) * np * JP * JP;
+    const size_t b_z = sizeof(int32_t) * np * JP, b_f = (sizeof(int32_t) * np + 15) / 16 * 16, b_c = (sizeof(unsigned int) * np + 15) / 16 * 16;
+    void* wsp = nullptr;
+    const int status = ctx->workspace(L.zero_bytes + L.gran_reserved + 2 * b_gpart + 2 * (b_q + b_z + b_f) + b_c + 1024, &wsp, 2);
+    if (status != CYB_OK) return status;
+    char* bp = static_cast<char*>(wsp);
+    s.base = wsp;
+    s.zero_bytes = L.zero_bytes;
+    s.d_off = reinterpret_cast<unsigned long long*>(bp);
+    s.d_err = reinterpret_cast<unsigned int*>(bp + b_off);
+    s.d_ready = reinterpret_cast<unsigned int*>(bp + b_off + 16);
+    s.d_gran = reinterpret_cast<unsigned long long*>(bp + L.zero_bytes);
+    bp += L.zero_bytes + L.gran_reserved;
+    s.gpart = reinterpret_cast<double*>(bp);
+    bp += 2 * b_gpart;
+    s.split.gpart = s.gpart;
+    for (int h = 0; h < 2; ++h) {
+        s.split.qout[h] = reinterpret_cast<double*>(bp);
+        bp += b_q;
+    }
+    for (int h = 0; h < 2; ++h) {
+        s.split.zout[h] = reinterpret_cast<int32_t*>(bp);
+        bp += b_z;
+    }
+    for (int h = 0; h < 2; ++h) {
+        s.split.flag[h] = reinterpret_cast<int32_t*>(bp);
+        bp += b_f;
+    }
+    s.split.cnt = reinterpret_cast<unsigned int*>(bp);
+    s.split_cnt_bytes = b_c;
+    return CYB_OK;
+}
+
+// ---- step 4, sweep kernel.  Its descriptors ([pair descriptors | entry map | workgroup map], ONE upload) stay on the device
+//      while the active set and its parts are those of the previous sweep and the ring slot is still alive.
+struct ImageCache {
+    std::vector<int> order, G;
+    uint64_t at = 0;
+    void* img = nullptr;
+};
+int descriptor_image(cyb_ctx_t ctx, ImageCache& cache, const std::vector<JMat>& h_mats, const SweepList& list, const SweepPlan& plan)
+{
+    uint64_t& cached_at = cache.at; // n_uploads after the upload that filled the image (tests/test_call_sequences.py: the ring's contract)
+    if (cache.img && list.order == cache.order && plan.G == cache.G && ctx->n_uploads - cached_at < (uint64_t)cyb_ctx_s::kSlots / 2 - 1)
+        return CYB_OK;
+    const SweepLayout& L = plan.layout;
+    std::vector<char> img(L.image_bytes);
+    RPair* rp = reinterpret_cast<RPair*>(img.data());
+    int2* wgmap = reinterpret_cast<int2*>(img.data() + L.map_off);
+    size_t k = 0, e = 0;
+    for (size_t i = 0; i < list.order.size(); ++i) {
+        const JMat& jm = h_mats[(size_t)list.order[i]];
+        for (int slot = 0; slot < jm.nb / 2; ++slot, ++k) {
+            RPair& q = rp[k];
+            q.W = jm.W;
+            q.J = jm.J;
+            q.tol = jm.tol;
+            q.thr2 = jm.thr2;
+            q.nvp = jm.nvp;
+            q.lenp = jm.lenp;
+            q.nb = jm.nb;
+            q.nv = jm.nv;
+            q.mat = list.order[i];
+            q.slot = slot;
+            q.pad[0] = plan.G[i];
+            q.pad[1] = L.flag_base[i];
+            for (int g = 0; g < plan.G[i]; ++g) wgmap[e++] = make_int2((int)k, g);
+        }
+    }
+    if (!plan.share.ranges.empty()) memcpy(img.data() + L.ent_off, plan.share.ranges.data(), sizeof(PlanRange) * plan.share.ranges.size());
+    const int status = ctx->upload(img.data(), img.size(), &cache.img);
+    if (status != CYB_OK) return status;
+    cache.order = list.order;
+    cache.G = plan.G;
+    cached_at = ctx->n_uploads;
+    return CYB_OK;
+}
+
+typedef void (*sweep_fn_t)(const RPair*, int, unsigned long long*, SScratch);
+int sweep_kernel_for(bool cplx, sweep_fn_t& fn)
+{
+    static const sweep_fn_t sweep_fns[2][2][2] = { // [CPLX][RORD][GRAN]
+        {{jacobi_sweep_kernel<false, false, false>, jacobi_sweep_kernel<false, false, true>},
+         {jacobi_sweep_kernel<false, true, false>, jacobi_sweep_kernel<false, true, true>}},
+        {{jacobi_sweep_kernel<true, false, false>, jacobi_sweep_kernel<true, false, true>},
+         {jacobi_sweep_kernel<true, true, false>, jacobi_sweep_kernel<true, true, true>}}};
+    const JSwitches& sw = switches();
+    static const sweep_fn_t sweep_fn[2] = {sweep_fns[0][sw.round_order ? 1 : 0][sw.gran_exchange ? 1 : 0],
+                                           sweep_fns[1][sw.round_order ? 1 : 0][sw.gran_exchange ? 1 : 0]};
+    static bool attr_set = false;
+    if (!attr_set) {
+        for (int c = 0; c < 2; ++c)
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(sweep_fn[c]), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)SWEEP_LDS_BYTES) != hipSuccess) {
+                set_error("jacobi: cannot reserve %zu bytes of LDS for the sweep kernel", SWEEP_LDS_BYTES);
+                return CYB_ERR_HIP;
+            }
+        attr_set = true;
+    }
+    fn = sweep_fn[cplx ? 1 : 0];
+    return CYB_OK;
+}
+
+// CYB_JACOBI_STAMPS: phase times of round `stamp_round` for the workgroups of the matrix with the most blocks (the first
+// of the work list: its entries are the first nb / 2 * G of the launch)
+void print_sweep_stamps(hipStream_t st, const unsigned long long* d_stamps, const SweepList& list, const SweepPlan& plan, int sweep, int stamp_round)
+{
+    const size_t entries = plan.layout.entries;
+    std::vector<unsigned long long> hs(8 * entries);
+    if (hipMemcpyAsync(hs.data(), d_stamps, sizeof(unsigned long long) * hs.size(), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return;
+    double acc[6] = {0, 0, 0, 0, 0, 0}, passes = 0;
+    const int cntw = list.pm[0].nb / 2 * plan.G[0];
+    const bool swept = switches().gran_exchange && plan.G[0] > 1; // (slot 7: granule passes of wave 0)
+    for (size_t b = 0; b < (size_t)cntw; ++b) {
+        for (int k = 0; k < 6; ++k) acc[k] += (double)(hs[8 * b + k + 1] - hs[8 * b + k]) * 0.01;
+        if (swept) passes += (double)hs[8 * b + 7];
+    }
+    if (cntw)
+        fprintf(stderr, "[jacobi sweep stamps] sweep %d round %d, largest matrix (G=%d, %d workgroups of %zu): wait %.2f load+gram %.2f "
+                        "exch %.2f defl+eig %.2f sort %.2f upd+publish %.2f us, granule passes %.1f\n",
+                sweep, stamp_round, plan.G[0], cntw, entries, acc[0] / cntw, acc[1] / cntw, acc[2] / cntw, acc[3] / cntw, acc[4] / cntw,
+                acc[5] / cntw, passes / cntw);
+}
+
+// Every pair of every matrix gets its workgroups for the whole sweep.  one_launch: this launch runs every sweep of the call.
+int launch_sweep(cyb_ctx_t ctx, const std::vector<JMat>& h_mats, const SweepList& list, const SweepPlan& plan, const SweepScratch& s,
+                 ImageCache& cache, const SweepCall& call, int sweep, int max_inner, bool& one_launch)
+{
+    const JSwitches& sw = switches();
+    const SweepLayout& L = plan.layout;
+    hipStream_t st = ctx->stream;
+    int status = descriptor_image(ctx, cache, h_mats, list, plan);
+    if (status != CYB_OK) return status;
+    sweep_fn_t fn = nullptr;
+    status = sweep_kernel_for(call.cplx, fn);
+    if (status != CYB_OK) return status;
+    const std::vector<PlanRange>& ranges = plan.share.ranges;
+    static unsigned long long* d_stamps = nullptr; // diagnostic runs only: 2048 workgroups x 8 stamps
+    if (sw.stamps && !d_stamps && hipMalloc(reinterpret_cast<void**>(&d_stamps), sizeof(unsigned long long) * 8 * 2048) != hipSuccess) d_stamps = nullptr;
+    SScratch ss;
+    ss.gpart = s.gpart;
+    ss.ticket = s.d_ready;                   // [0, np): tickets; behind them the ready counters (flag_base offsets)
+    ss.ready = s.d_ready;
+    ss.readyJ = s.d_ready + L.ready_reserved; // (same offsets, second array)
+    ss.defer_j = sw.no_defer_j ? 0 : 1;
+    // (lists of small matrices run three inner sweeps per pivot solve: cross-only there is opt-in, CYB_JACOBI_CROSS_SMALL=1)
+    ss.cross_every = (max_inner == 1 || sw.cross_small) ? sw.cross : 0;
+    ss.cross_min_nb = sw.cross_min_nb;
+    ss.err = s.d_err;
+    ss.wgmap = reinterpret_cast<const int2*>(static_cast<char*>(cache.img) + L.map_off);
+    ss.wgent = ranges.empty() ? nullptr : reinterpret_cast<const int2*>(static_cast<char*>(cache.img) + L.ent_off);
+    ss.stamps = ranges.empty() ? d_stamps : nullptr;
+    ss.stamp_round = std::min(3, list.max_nb - 2);
+    size_t max_ent = 1;
+    for (const PlanRange& we : ranges) max_ent = std::max(max_ent, (size_t)(we.end - we.begin));
+    one_launch = call.n_sw_dev > 1 && sweep == 1 && max_ent <= (size_t)SW_MAX_ENT;
+    ss.n_sweeps = one_launch ? call.n_sw_dev : 1;
+    ss.n_mats = call.n;
+    ss.arrive = reinterpret_cast<unsigned int*>(s.d_off + call.w_off);
+    ss.nsw = reinterpret_cast<int*>(ss.arrive + call.n);
+    ss.gran = s.d_gran;
+    ss.gran_np = (int)L.np;
+    if (L.gran_used > L.gran_reserved) {
+        set_error("jacobi: %zu bytes of granule regions exceed the %zu reserved", L.gran_used, L.gran_reserved);
+        return CYB_ERR_INVALID;
+    }
+    if (hipMemsetAsync(s.base, 0, s.zero_bytes + L.gran_used, st) != hipSuccess) return CYB_ERR_HIP;
+    const size_t n_wg = ranges.empty() ? L.entries : ranges.size();
+    hipLaunchKernelGGL(fn, dim3((unsigned)n_wg), dim3(NT), SWEEP_LDS_BYTES, st, static_cast<const RPair*>(cache.img), max_inner, s.d_off, ss);
+    if (ss.stamps && L.entries <= 2048) print_sweep_stamps(st, d_stamps, list, plan, sweep, ss.stamp_round);
+    return CYB_OK;
+}
+
+// ---- step 4, fallback: every round of the sweep on the split route, all matrices in lockstep.  The J half of a round's
+//      update is deferred: it rides along with the next round's Gram launch (nothing reads J before the end).
+int launch_rounds_split(cyb_ctx_t ctx, const std::vector<JMat>& h_mats, const SweepList& list, const SweepScratch& s, int max_inner)
+{
+    hipStream_t st = ctx->stream;
+    const JScratch& sc = s.split;
+    const int g_env = switches().g;
+    if (hipMemsetAsync(s.base, 0, s.zero_bytes, st) != hipSuccess) return CYB_ERR_HIP;
+    void *d_mats_v = nullptr, *d_wl = nullptr;
+    int status = ctx->upload(h_mats.data(), sizeof(JMat) * h_mats.size(), &d_mats_v);
+    if (status == CYB_OK) status = ctx->upload(list.wl.data(), sizeof(JWork) * list.wl.size(), &d_wl);
+    if (status != CYB_OK) return status;
+    const JMat* d_mats = static_cast<const JMat*>(d_mats_v);
+    if (hipMemsetAsync(sc.cnt, 0, s.split_cnt_bytes, st) != hipSuccess) return CYB_ERR_HIP;
+    int pend_round = -1;   // round whose J half is still to be applied ...
+    size_t pend_cnt = 0;   // ... for this many pairs
+    for (int r = 0; r < list.max_nb - 1; ++r) {
+        size_t cnt = 0; // grid = prefix of the work list holding matrices with nb - 1 > r
+        for (int m : list.order) {
+            if (h_mats[(size_t)m].nb - 1 > r) cnt += (size_t)h_mats[(size_t)m].nb / 2;
+            else break;
+        }
+        if (cnt == 0) break;
+        // spread every pair over enough workgroups to fill the chip (2 resident per CU for A, more for B)
+        const int slots = 2 * ctx->n_cu;
+        // measured (chi=4096 list): splitting the Gram further than 2 ways costs more in the partial
+        // exchange than it saves (G = 1: 72.2, 2: 71.9, 4: 75.4, 8: 88.7 ms per batched SVD)
+        int G = g_env > 0 ? g_env : ((size_t)2 * cnt <= (size_t)slots ? 2 : 1);
+        G = std::min(G, RGMAX);
+        // the update kernel holds 3 workgroups per CU: one full wave of workgroups, no tail
+        const int U = (int)std::min<size_t>(16, std::max<size_t>(1, (size_t)(3 * ctx->n_cu) / cnt));
+        const int buf = r & 1;
+        const int n_gram = (int)(cnt * G);
+        int UJ = 1;
+        size_t n_jwg = 0;
+        if (pend_round >= 0) { // the J half of the previous round rides along in the idle workgroup slots
+            const long long free_slots = (long long)slots - (long long)n_gram;
+            UJ = (int)std::max<long long>(1, std::min<long long>(8, free_slots / (long long)pend_cnt));
+            n_jwg = pend_cnt * (size_t)UJ;
+        }
+        hipLaunchKernelGGL(jacobi_gram_kernel, dim3((unsigned)(n_gram + n_jwg)), dim3(NT), 0, st, d_mats,
+                           static_cast<const JWork*>(d_wl), r, G, max_inner, s.d_off, sc, buf, n_gram, pend_round, UJ);
+        const bool defer = list.any_j;
+        hipLaunchKernelGGL(jacobi_update_kernel, dim3((unsigned)(cnt * U)), dim3(NT), 0, st, d_mats,
+                           static_cast<const JWork*>(d_wl), r, U, sc, buf, 1, defer ? 0 : 1);
+        pend_round = defer ? r : -1;
+        pend_cnt = cnt;
+    }
+    if (pend_round >= 0) { // the J half of the last round: the work list changes with the sweep
+        const int U = (int)std::min<size_t>(16, std::max<size_t>(1, (size_t)(3 * ctx->n_cu) / pend_cnt));
+        hipLaunchKernelGGL(jacobi_update_kernel, dim3((unsigned)(pend_cnt * U)), dim3(NT), 0, st, d_mats,
+                           static_cast<const JWork*>(d_wl), pend_round, U, sc, pend_round & 1, 0, 1);
+    }
+    return CYB_OK;
+}
+
+// ---- step 5: ONE read-back per sweep: [convergence words | error word]
+int read_back(cyb_ctx_t ctx, const SweepScratch& s, std::vector<unsigned long long>& h_off, size_t b_off)
+{
+    if (ctx->d2h(h_off.data(), s.d_off, b_off + 16) != CYB_OK) {
+        set_error("jacobi: reading the convergence flags failed: %s", hipGetErrorString(hipGetLastError()));
+        return CYB_ERR_HIP;
+    }
+    unsigned int h_err = 0;
+    memcpy(&h_err, reinterpret_cast<const char*>(h_off.data()) + b_off, sizeof(unsigned int));
+    if (h_err) {
+        set_error("jacobi round kernel: a workgroup waited more than a second for the Gram partials of its pair "
+                  "(partner workgroup not resident?)");
+        return CYB_ERR_HIP;
+    }
+    return CYB_OK;
+}
+
+// ---- step 6: which matrices are done after sweep `sweep` (one-based); the others stay in `active`
+void sweep_verdicts(const std::vector<JMat>& h_mats, const std::vector<unsigned long long>& h_off, int sweep, std::vector<int>& active,
+                    std::vector<double>& prev_off, std::vector<int32_t>& sweeps_out)
+{
+    const JSwitches& sw = switches();
+    std::vector<int> still;
+    for (int m : active) {
+        const JMat& jm = h_mats[(size_t)m];
+        double off;
+        memcpy(&off, &h_off[(size_t)m], sizeof(double));
+        if (sw.trace) fprintf(stderr, "[jacobi] sweep %2d mat %3d (nv=%d len=%d) off=%.3e tol=%.3e\n", sweep, m, jm.nv, jm.len, off, jm.tol);
+        if (jacobi_sweep_done(off, prev_off[(size_t)m], jm.tol, sweep, !sw.no_predict)) sweeps_out[(size_t)m] = sweep;
+        else still.push_back(m);
+        prev_off[(size_t)m] = off;
+    }
+    active.swap(still);
+}
+// ... and after a launch that ran every sweep: matrices the device marked converged are done, the rest did not converge
+void one_launch_verdicts(const std::vector<unsigned long long>& h_off, const SweepCall& call, std::vector<int>& active,
+                         std::vector<int32_t>& sweeps_out)
+{
+    const int* h_nsw = reinterpret_cast<const int*>(reinterpret_cast<const unsigned int*>(h_off.data() + call.w_off) + call.n);
+    std::vector<int> still;
+    for (int m : active) {
+        if (h_nsw[m] > 0) sweeps_out[(size_t)m] = h_nsw[m];
+        else still.push_back(m);
+    }
+    active.swap(still);
+}
+
 } // namespace
 
 int jacobi_orthogonalise(cyb_ctx_t ctx, const std::vector<JMat>& h_mats, int max_sweeps,
                          std::vector<int32_t>& sweeps_out, bool cplx)
-{   // cplx: the rows are the interleaved real embedding of complex rows (structure-preserving pivot solve; persistent path only)
+{   // cplx: the rows are the interleaved real embedding of complex rows (structure-preserving pivot solve; sweep kernel only)
     const int n = (int)h_mats.size();
     sweeps_out.assign((size_t)n, 0);
     if (n == 0) return CYB_OK;
-    hipStream_t st = ctx->stream;
+    const JSwitches& sw = switches();
 
     std::vector<int> active;
     for (int i = 0; i < n; ++i) {
@@ -1927,501 +1950,61 @@ int jacobi_orthogonalise(cyb_ctx_t ctx, const std::vector<JMat>& h_mats, int max
     // few workgroups per matrix wait at a sweep's end, and the seven read-backs are a visible part of a 2 ms call; toy DMRG,
     // three runs each: 0.271 / 0.275 / 0.280 against 0.282 / 0.283 / 0.285 s per sweep).  CYB_JACOBI_ONELAUNCH=1: every list,
     // CYB_JACOBI_PERSWEEP=1: none.
-    static const bool one_launch_ok = getenv("CYB_JACOBI_PERSWEEP") == nullptr && getenv("CYB_JACOBI_TRACE") == nullptr &&
-                                      getenv("CYB_JACOBI_STAMPS") == nullptr && getenv("CYB_JACOBI_NOPREDICT") == nullptr;
-    static const bool one_launch_all = getenv("CYB_JACOBI_ONELAUNCH") != nullptr;
+    const bool one_launch_ok = !sw.per_sweep && !sw.trace && !sw.stamps && !sw.no_predict;
     int nb_max_all = 0;
     for (int i = 0; i < n; ++i) nb_max_all = std::max(nb_max_all, h_mats[(size_t)i].nb);
-    const int n_sw_dev = (one_launch_ok && (one_launch_all || nb_max_all <= 16)) ? max_sweeps : 1;
-    const size_t w_off = (size_t)n * (size_t)n_sw_dev; // off-norm words
-    const size_t b_off = (sizeof(unsigned long long) * w_off + 2 * sizeof(unsigned int) * (size_t)n + 15) / 16 * 16;
-    std::vector<unsigned long long> h_off(b_off / 8 + 2);
-    bool one_launch_done = false;
-    // descriptors of the persistent sweep stay on the device while the set of active matrices does not change
-    std::vector<int> cached_order, cached_G;
-    uint64_t cached_at = 0;
-    void* cached_img = nullptr;
-    size_t cached_map_off = 0;
+    SweepCall call;
+    call.n = n;
+    call.n_sw_dev = (one_launch_ok && (sw.one_launch_all || nb_max_all <= 16)) ? max_sweeps : 1;
+    call.w_off = (size_t)n * (size_t)call.n_sw_dev;
+    call.b_off = (sizeof(unsigned long long) * call.w_off + 2 * sizeof(unsigned int) * (size_t)n + 15) / 16 * 16;
+    call.cplx = cplx;
+    std::vector<unsigned long long> h_off(call.b_off / 8 + 2);
+    const size_t sweep_slots = (size_t)SWEEP_WG_PER_CU * (size_t)ctx->n_cu; // resident workgroups the sweep kernel may use
+    ImageCache cache;
     std::vector<double> prev_off((size_t)n, 1e300);
+    bool one_launch_done = false;
     int status = CYB_OK;
     for (int sweep = 1; sweep <= max_sweeps && !active.empty(); ++sweep) {
-        // work list: matrices with more blocks first, so that late rounds use a prefix of the grid
-        std::vector<int> order = active;
-        std::stable_sort(order.begin(), order.end(),
-                         [&](int a, int b) { return h_mats[(size_t)a].nb > h_mats[(size_t)b].nb; });
-        std::vector<JWork> wl;
-        int max_nb = 0;
-        for (int m : order) {
-            const int nb = h_mats[(size_t)m].nb;
-            max_nb = std::max(max_nb, nb);
-            for (int k = 0; k < nb / 2; ++k) wl.push_back(JWork{m, k});
-        }
-        const JMat* d_mats = nullptr; // (uploaded by the launch-per-round paths only)
-        void* d_wl = nullptr;
-        // Two ways to run a round.  FUSED (jacobi_round_kernel): one launch, the parts of a pair exchange their Gram
-        // partials inside it -- the latency path, for rounds with few pairs (the large blocks once the small ones have
-        // converged, a single block, a DMRG-sized list).  SPLIT (jacobi_gram_kernel + jacobi_update_kernel): two launches,
-        // no residency constraint, the update spread over three workgroups per CU -- the throughput path for rounds
-        // with many pairs, where the f64 MFMA rate of the whole chip (not a dependency chain) bounds the update.
-        // Within a sweep the pair count only falls (matrices drop out of the lockstep as r passes their nb - 1), so a
-        // sweep starts split and turns fused.
-        static const bool legacy = getenv("CYB_JACOBI_LEGACY") != nullptr;
-        static const int fused_max = getenv("CYB_JACOBI_FUSED_MAX") ? atoi(getenv("CYB_JACOBI_FUSED_MAX")) : 64;
-        // inner sweeps: few while far from convergence (the outer iteration repeats anyway)
+        // 1. work list
+        const SweepList list = build_work_list(h_mats, active);
         // inner Jacobi sweeps per pair visit: measurements and a numpy model agree that more than two
         // buy no outer sweeps, and one is fastest overall (measured: 81 vs 88 ms on the chi=4096 list)
         // ... except for batches of small matrices (at most 8 row blocks each: the DMRG regime around chi = 256), where a
         // round is all latency and an outer sweep costs a host read-back: three inner sweeps save outer sweeps there
         // (toy DMRG chi=256, eleven sweeps: 6.6-6.7 -> 6.3-6.6 s; the 13-block chi=1024 list, 23 row blocks: 11.6 -> 14.9 ms, so not there)
-        static const int inner_env = getenv("CYB_JACOBI_INNER") ? atoi(getenv("CYB_JACOBI_INNER")) : 0;
-        const int max_inner = inner_env > 0 ? inner_env : (max_nb <= 8 ? 3 : 1);
-        constexpr int kGmax = RGMAX;
-        const size_t np = wl.size();
-        // ---- scratch of both paths in one grow-only workspace: [tickets | error word | Gram partials | split-path hand-off]
-        const size_t b_cnt = (sizeof(unsigned int) * np * (size_t)std::max(max_nb - 1, 1) + 15) / 16 * 16;
-        const size_t b_gpart = sizeof(double) * np * kGmax * JP * JP, b_q = sizeof(double) * np * JP * JP;
-        const size_t b_z = sizeof(int32_t) * np * JP, b_f = (sizeof(int32_t) * np + 15) / 16 * 16, b_c = (sizeof(unsigned int) * np + 15) / 16 * 16;
-        size_t n_ready = 0; // persistent sweep: one counter per (matrix, block, part), at most RGMAX parts
-        for (int m : order) n_ready += (size_t)h_mats[(size_t)m].nb * RGMAX;
-        const size_t b_ready = (sizeof(unsigned int) * (2 * n_ready + np) + 15) / 16 * 16; // ready counters (W and J) + one ticket per pair
-        // CYB_JACOBI_EXCHANGE=0: the partial Grams of the sweep kernel travel by stores, drain, ticket and poll as before (same
-        // sums in the same order: bit-identical results); default: as tagged granules
-        static const bool gran_exchange = !(getenv("CYB_JACOBI_EXCHANGE") && atoi(getenv("CYB_JACOBI_EXCHANGE")) == 0);
-        // granule regions of the sweep kernel: room for a part on every resident workgroup (a launch zeroes and uses those of
-        // the parts it assigns; a list with more parts than that shares workgroups and runs every pair in one part: no exchange)
-        const size_t sweep_slots = (size_t)SWEEP_WG_PER_CU * (size_t)ctx->n_cu; // resident workgroups the sweep kernel may use
-        const size_t b_gran = gran_exchange ? 2 * (size_t)SW_GRAN_BYTES * sweep_slots : 0;
-        void* wsp = nullptr;
-        status = ctx->workspace(b_off + 16 + b_cnt + b_ready + b_gran + 2 * b_gpart + 2 * (b_q + b_z + b_f) + b_c + 1024, &wsp, 2);
+        const int max_inner = sw.inner > 0 ? sw.inner : (list.max_nb <= 8 ? 3 : 1);
+        // 2. plan: parts per pair, shared workgroups, layout (arithmetic only; the scratch is sized from its layout)
+        const SweepPlan plan = plan_sweep(list.pm, sweep_slots, sw.g, call.b_off + 16, sw.gran_exchange);
+        // 3. scratch
+        SweepScratch scratch;
+        status = carve_scratch(ctx, plan.layout, call.b_off, scratch);
         if (status != CYB_OK) break;
-        char* bp = static_cast<char*>(wsp);
-        RScratch rs;
-        // one zeroed block: [off-norm words | error word | tickets of the round kernel | tickets + ready counters of the sweep kernel |
-        // granule regions of the sweep kernel's parts]
-        unsigned long long* d_off = reinterpret_cast<unsigned long long*>(bp);
-        rs.err = reinterpret_cast<unsigned int*>(bp + b_off);
-        rs.cnt = reinterpret_cast<unsigned int*>(bp + b_off + 16);
-        unsigned int* d_ready = reinterpret_cast<unsigned int*>(bp + b_off + 16 + b_cnt);
-        const size_t b_zero = b_off + 16 + b_cnt + b_ready; // (+ the granule regions in use: known once the parts are assigned)
-        unsigned long long* d_gran = reinterpret_cast<unsigned long long*>(bp + b_zero);
-        bp += b_zero + b_gran;
-        rs.gpart = reinterpret_cast<double*>(bp);
-        bp += 2 * b_gpart;
-        rs.np = (int)np;
-        rs.stamps = nullptr;
-        JScratch sc;
-        sc.gpart = rs.gpart; // (a round runs one path or the other)
-        for (int h = 0; h < 2; ++h) {
-            sc.qout[h] = reinterpret_cast<double*>(bp);
-            bp += b_q;
-        }
-        for (int h = 0; h < 2; ++h) {
-            sc.zout[h] = reinterpret_cast<int32_t*>(bp);
-            bp += b_z;
-        }
-        for (int h = 0; h < 2; ++h) {
-            sc.flag[h] = reinterpret_cast<int32_t*>(bp);
-            bp += b_f;
-        }
-        sc.cnt = reinterpret_cast<unsigned int*>(bp);
-        // ONE fill per sweep, issued by whichever path runs it (the sweep kernel adds the granule regions of its parts)
-        auto zero_block = [&](size_t gran_bytes) { return hipMemsetAsync(wsp, 0, b_zero + gran_bytes, st) == hipSuccess; };
-        std::vector<RPair> rp(np);
-        for (size_t k = 0; k < np; ++k) {
-            const JMat& jm = h_mats[(size_t)wl[k].mat];
-            RPair& q = rp[k];
-            q.W = jm.W;
-            q.J = jm.J;
-            q.tol = jm.tol;
-            q.thr2 = jm.thr2;
-            q.nvp = jm.nvp;
-            q.lenp = jm.lenp;
-            q.nb = jm.nb;
-            q.nv = jm.nv;
-            q.mat = wl[k].mat;
-            q.slot = wl[k].slot;
-            q.pad[0] = q.pad[1] = 0;
-        }
-        void* d_rp = nullptr; // (uploaded by the launch-per-round paths only)
-        static const bool want_stamps = getenv("CYB_JACOBI_STAMPS") != nullptr;
-        static unsigned long long* d_stamps = nullptr; // diagnostic runs only: 2048 workgroups x 8 stamps
-        if (want_stamps) {
-            if (!d_stamps && hipMalloc(reinterpret_cast<void**>(&d_stamps), sizeof(unsigned long long) * 8 * 2048) != hipSuccess) d_stamps = nullptr;
-            rs.stamps = d_stamps;
-        }
-        static bool attr_set = false;
-        if (!attr_set) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(jacobi_round_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)ROUND_LDS_BYTES) != hipSuccess) {
-                set_error("jacobi: cannot reserve %zu bytes of LDS for the round kernel", ROUND_LDS_BYTES);
-                status = CYB_ERR_HIP;
-                break;
-            }
-            attr_set = true;
-        }
-        bool any_j = false;
-        for (int m : order) any_j = any_j || h_mats[(size_t)m].J != nullptr;
-        static const bool defer_j = getenv("CYB_JACOBI_NODEFER") == nullptr;
-        static const int g_env = getenv("CYB_JACOBI_G") ? atoi(getenv("CYB_JACOBI_G")) : 0;
-        static const int u_max = getenv("CYB_JACOBI_UMAX") ? atoi(getenv("CYB_JACOBI_UMAX")) : 16;
-        // ---- persistent sweep (jacobi_sweep_kernel): every pair of every matrix gets its workgroups for the whole sweep;
-        //      possible when they all fit on the chip at once (one workgroup per CU)
-        static const bool no_sweep = getenv("CYB_JACOBI_NOSWEEP") != nullptr;
-        bool did_sweep = false;
-        bool big_ok = true;
-        for (int m : order)
-            big_ok = big_ok && (size_t)h_mats[(size_t)m].nvp * (size_t)std::max(h_mats[(size_t)m].lenp, h_mats[(size_t)m].nvp) * 8 < ((size_t)1 << 31);
-        // (lists with more pairs than resident workgroups: short matrices share workgroups -- CYB_JACOBI_NOSHARE sends them
-        //  to the launch-per-round paths as before)
-        static const bool no_share = getenv("CYB_JACOBI_NOSHARE") != nullptr;
-        if (!legacy && !no_sweep && big_ok && (np <= sweep_slots || !no_share)) {
-            // parts per pair, matrix by matrix: start with one, then keep giving a CU per pair to the matrix whose sweep
-            // is the longest chain (rounds x per-round work / parts) while the chip has room
-            std::vector<int> Gm((size_t)n, 1);
-            auto chain = [&](int m) {
-                const JMat& jm = h_mats[(size_t)m];
-                // (rec_j: a matrix whose rotations are rebuilt afterwards streams half the columns, but the estimate keeps counting
-                //  J for it.  Its fixed part is too small -- a round of the largest chi=4096 block is 12 us of wait + pivot solve +
-                //  sort and 6-11 us of exchange whatever G is -- so with the halved width the greedy loop gave that block five parts
-                //  and every other block one: list 26.5 ms against 24.3 ms with the parts of the accumulating run, 3 / 2 / 1)
-                const double per_round = 8.0 + 22.0 * (double)(jm.lenp + ((jm.J || jm.rec_j) ? jm.nvp : 0)) / 2240.0 / (double)Gm[(size_t)m]
-                                         + (Gm[(size_t)m] > 1 ? 4.0 : 0.0); // us: fixed part + MFMA share (+ exchange)
-                return per_round * (double)(jm.nb - 1);
-            };
-            size_t used = np;
-            while (true) {
-                int best = -1;
-                double worst = 0.0;
-                for (int m : order) {
-                    const JMat& jm = h_mats[(size_t)m];
-                    const int cw_ = jm.lenp / 64;
-                    if (Gm[(size_t)m] >= RGMAX || Gm[(size_t)m] >= cw_ || used + (size_t)jm.nb / 2 > sweep_slots) continue;
-                    const double c = chain(m);
-                    if (c > worst) {
-                        worst = c;
-                        best = m;
-                    }
-                }
-                if (best < 0) break;
-                ++Gm[(size_t)best];
-                used += (size_t)h_mats[(size_t)best].nb / 2;
-            }
-            if (g_env > 0)
-                for (int m : order) Gm[(size_t)m] = std::max(1, std::min({g_env, RGMAX, h_mats[(size_t)m].lenp / 64}));
-            size_t total = 0;
-            for (int m : order) total += (size_t)h_mats[(size_t)m].nb / 2 * (size_t)Gm[(size_t)m];
-            if (total <= sweep_slots || (!no_share && total == np)) {
-                std::vector<int> flag_base((size_t)n, 0);
-                int fb = (int)np; // the tickets come first in the zeroed block
-                for (int m : order) {
-                    flag_base[(size_t)m] = fb;
-                    fb += h_mats[(size_t)m].nb * Gm[(size_t)m];
-                }
-                std::vector<int2> wgmap;
-                for (size_t k = 0; k < np; ++k) {
-                    rp[k].pad[0] = Gm[(size_t)wl[k].mat];
-                    rp[k].pad[1] = flag_base[(size_t)wl[k].mat];
-                    for (int g = 0; g < Gm[(size_t)wl[k].mat]; ++g) wgmap.push_back(make_int2((int)k, g));
-                }
-                // More entries than resident workgroups (a list of many large matrices: 23 hermitian blocks up to 1238^2 have
-                // 301 pairs): workgroups take several entries and run them one after the other in every round.  A matrix
-                // whose pairs sit on shared workgroups advances at 1/m of the pace, so the longest chains keep workgroups of
-                // their own and the short matrices share: split the list (sorted by row blocks) where
-                // max(rounds of the longest, m x rounds of the longest shared) is smallest.
-                std::vector<int2> wgent;
-                if (wgmap.size() > sweep_slots) {
-                    std::vector<size_t> ent_before; // entries of the matrices before position i of `order`
-                    size_t acc = 0;
-                    for (int m : order) {
-                        ent_before.push_back(acc);
-                        acc += (size_t)h_mats[(size_t)m].nb / 2;
-                    }
-                    ent_before.push_back(acc);
-                    size_t best_i = 0, best_m = 0;
-                    double best_cost = 1e300;
-                    for (size_t i = 0; i <= order.size(); ++i) {
-                        const size_t D = ent_before[i], S = acc - D;
-                        if (D > sweep_slots || (S > 0 && D >= sweep_slots)) break;
-                        const size_t m = S ? (S + (sweep_slots - D) - 1) / (sweep_slots - D) : 1;
-                        const double own = (double)(h_mats[(size_t)order[0]].nb - 1);
-                        const double shared = i < order.size() ? (double)m * (double)(h_mats[(size_t)order[i]].nb - 1) : 0.0;
-                        const double cost = std::max(own, shared);
-                        if (cost < best_cost) {
-                            best_cost = cost;
-                            best_i = i;
-                            best_m = m;
-                        }
-                    }
-                    const size_t D = ent_before[best_i];
-                    for (size_t e = 0; e < D; ++e) wgent.push_back(make_int2((int)e, (int)e + 1));
-                    for (size_t e = D; e < wgmap.size(); e += best_m)
-                        wgent.push_back(make_int2((int)e, (int)std::min(e + best_m, wgmap.size())));
-                }
-                const size_t n_wg = wgent.empty() ? wgmap.size() : wgent.size();
-                // ONE upload ([pair descriptors | entry map | workgroup -> entries]), and none at all while the active set and
-                // its parts are those of the previous sweep and the ring slot is still alive
-                std::vector<int> g_now;
-                for (int m : order) g_now.push_back(Gm[(size_t)m]);
-                const size_t map_off = (sizeof(RPair) * np + 255) / 256 * 256;
-                const size_t ent_off = (map_off + sizeof(int2) * wgmap.size() + 255) / 256 * 256;
-                if (!(cached_img && order == cached_order && g_now == cached_G && ctx->n_uploads - cached_at < (uint64_t)cyb_ctx_s::kSlots / 2 - 1)) {
-                    std::vector<char> img(ent_off + sizeof(int2) * wgent.size());
-                    memcpy(img.data(), rp.data(), sizeof(RPair) * np);
-                    memcpy(img.data() + map_off, wgmap.data(), sizeof(int2) * wgmap.size());
-                    if (!wgent.empty()) memcpy(img.data() + ent_off, wgent.data(), sizeof(int2) * wgent.size());
-                    status = ctx->upload(img.data(), img.size(), &cached_img);
-                    if (status != CYB_OK) break;
-                    cached_order = order;
-                    cached_G = g_now;
-                    cached_at = ctx->n_uploads;
-                    cached_map_off = map_off;
-                }
-                void* d_rp2 = cached_img;
-                void* d_map = static_cast<char*>(cached_img) + cached_map_off;
-                // CYB_JACOBI_ROUND_ORDER=0: the issue order a round had before (same arithmetic, same protocol: bit-identical results)
-                static const bool round_order = !(getenv("CYB_JACOBI_ROUND_ORDER") && atoi(getenv("CYB_JACOBI_ROUND_ORDER")) == 0);
-                typedef void (*sweep_fn_t)(const RPair*, int, unsigned long long*, SScratch);
-                static const sweep_fn_t sweep_fns[2][2][2] = { // [CPLX][RORD][GRAN]
-                    {{jacobi_sweep_kernel<false, false, false>, jacobi_sweep_kernel<false, false, true>},
-                     {jacobi_sweep_kernel<false, true, false>, jacobi_sweep_kernel<false, true, true>}},
-                    {{jacobi_sweep_kernel<true, false, false>, jacobi_sweep_kernel<true, false, true>},
-                     {jacobi_sweep_kernel<true, true, false>, jacobi_sweep_kernel<true, true, true>}}};
-                static const sweep_fn_t sweep_fn[2] = {sweep_fns[0][round_order ? 1 : 0][gran_exchange ? 1 : 0],
-                                                       sweep_fns[1][round_order ? 1 : 0][gran_exchange ? 1 : 0]};
-                static bool attr2_set = false;
-                if (!attr2_set) {
-                    if (hipFuncSetAttribute(reinterpret_cast<const void*>(sweep_fn[0]), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)SWEEP_LDS_BYTES) != hipSuccess ||
-                        hipFuncSetAttribute(reinterpret_cast<const void*>(sweep_fn[1]), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)SWEEP_LDS_BYTES) != hipSuccess) {
-                        set_error("jacobi: cannot reserve %zu bytes of LDS for the sweep kernel", SWEEP_LDS_BYTES);
-                        status = CYB_ERR_HIP;
-                        break;
-                    }
-                    attr2_set = true;
-                }
-                SScratch ss;
-                ss.gpart = rs.gpart;
-                ss.ticket = d_ready;           // [0, np): tickets; behind them the ready counters (flag_base offsets)
-                ss.ready = d_ready;
-                ss.readyJ = d_ready + n_ready; // (same offsets, second array)
-                static const bool no_defer_j = getenv("CYB_JACOBI_NODEFERJ") != nullptr;
-                ss.defer_j = no_defer_j ? 0 : 1;
-                static const int cross_env = getenv("CYB_JACOBI_CROSS") ? atoi(getenv("CYB_JACOBI_CROSS")) : -1;
-                // (lists of small matrices run three inner sweeps per pivot solve: cross-only there is opt-in, CYB_JACOBI_CROSS_SMALL=1)
-                static const bool cross_small = getenv("CYB_JACOBI_CROSS_SMALL") != nullptr;
-                ss.cross_every = (max_inner == 1 || cross_small) ? cross_env : 0;
-                static const int cross_min_nb = getenv("CYB_JACOBI_CROSS_MINNB") ? atoi(getenv("CYB_JACOBI_CROSS_MINNB")) : 0;
-                ss.cross_min_nb = cross_min_nb;
-                ss.err = rs.err;
-                ss.wgmap = static_cast<const int2*>(d_map);
-                ss.wgent = wgent.empty() ? nullptr : reinterpret_cast<const int2*>(static_cast<char*>(cached_img) + ent_off);
-                ss.stamps = wgent.empty() ? rs.stamps : nullptr;
-                ss.stamp_round = std::min(3, max_nb - 2);
-                size_t max_ent = 1;
-                for (const int2& we : wgent) max_ent = std::max(max_ent, (size_t)(we.y - we.x));
-                const bool one_launch = n_sw_dev > 1 && sweep == 1 && max_ent <= (size_t)SW_MAX_ENT;
-                ss.n_sweeps = one_launch ? n_sw_dev : 1;
-                ss.n_mats = n;
-                ss.arrive = reinterpret_cast<unsigned int*>(d_off + w_off);
-                ss.nsw = reinterpret_cast<int*>(ss.arrive + n);
-                one_launch_done = one_launch;
-                // granule regions: two (round parity) per part, laid out by the flag bases (nb is even: nb * G_m units per matrix)
-                bool any_parts = false;
-                for (int m : order) any_parts = any_parts || Gm[(size_t)m] > 1;
-                const size_t gran_bytes = (gran_exchange && any_parts) ? (size_t)(fb - (int)np) * SW_GRAN_BYTES : 0;
-                ss.gran = d_gran;
-                ss.gran_np = (int)np;
-                if (gran_bytes > b_gran) {
-                    set_error("jacobi: %zu bytes of granule regions exceed the %zu reserved", gran_bytes, b_gran);
-                    status = CYB_ERR_INVALID;
-                    break;
-                }
-                if (!zero_block(gran_bytes)) {
-                    status = CYB_ERR_HIP;
-                    break;
-                }
-                hipLaunchKernelGGL(sweep_fn[cplx ? 1 : 0], dim3((unsigned)n_wg), dim3(NT), SWEEP_LDS_BYTES, st,
-                                   static_cast<const RPair*>(d_rp2), max_inner, d_off, ss);
-                if (ss.stamps && wgmap.size() <= 2048) {
-                    std::vector<unsigned long long> hs(8 * wgmap.size());
-                    if (hipMemcpyAsync(hs.data(), rs.stamps, sizeof(unsigned long long) * hs.size(), hipMemcpyDeviceToHost, st) == hipSuccess &&
-                        hipStreamSynchronize(st) == hipSuccess) {
-                        // phase times of round `stamp_round` for the workgroups of the matrix with the most blocks
-                        double acc[6] = {0, 0, 0, 0, 0, 0}, passes = 0;
-                        int cntw = 0;
-                        const int mbig = order.front();
-                        const bool swept = gran_exchange && Gm[(size_t)mbig] > 1; // (slot 7: granule passes of wave 0)
-                        for (size_t b = 0; b < wgmap.size(); ++b) {
-                            if (wl[(size_t)wgmap[b].x].mat != mbig) continue;
-                            for (int k = 0; k < 6; ++k) acc[k] += (double)(hs[8 * b + k + 1] - hs[8 * b + k]) * 0.01;
-                            if (swept) passes += (double)hs[8 * b + 7];
-                            ++cntw;
-                        }
-                        if (cntw)
-                            fprintf(stderr, "[jacobi sweep stamps] sweep %d round %d, largest matrix (G=%d, %d workgroups of %zu): wait %.2f load+gram %.2f "
-                                            "exch %.2f defl+eig %.2f sort %.2f upd+publish %.2f us, granule passes %.1f\n",
-                                    sweep, ss.stamp_round, Gm[(size_t)mbig], cntw, wgmap.size(), acc[0] / cntw, acc[1] / cntw,
-                                    acc[2] / cntw, acc[3] / cntw, acc[4] / cntw, acc[5] / cntw, passes / cntw);
-                    }
-                }
-                did_sweep = true;
-            }
-        }
-        if (!did_sweep && cplx) {
+        // 4. launch: the sweep kernel, or every round on the split route
+        if (!sw.no_sweep && list.big_ok && plan.layout.fits) {
+            status = launch_sweep(ctx, h_mats, list, plan, scratch, cache, call, sweep, max_inner, one_launch_done);
+        } else if (cplx) {
             set_error("block-Jacobi on embedded complex rows needs the persistent sweep kernel (list too large for one launch)");
             status = CYB_ERR_UNSUPPORTED;
-            break;
+        } else {
+            cache.img = nullptr; // (the uploads of the split route recycle the ring)
+            status = launch_rounds_split(ctx, h_mats, list, scratch, max_inner);
         }
-        if (!did_sweep) {
-        if (!zero_block(0)) {
-            status = CYB_ERR_HIP;
-            break;
-        }
-        cached_img = nullptr; // (the uploads below recycle the ring)
-        {
-            void* d_mats_v = nullptr;
-            status = ctx->upload(h_mats.data(), sizeof(JMat) * (size_t)n, &d_mats_v);
-            if (status == CYB_OK) status = ctx->upload(wl.data(), sizeof(JWork) * wl.size(), &d_wl);
-            if (status == CYB_OK) status = ctx->upload(rp.data(), sizeof(RPair) * np, &d_rp);
-            if (status != CYB_OK) break;
-            d_mats = static_cast<const JMat*>(d_mats_v);
-            if (hipMemsetAsync(sc.cnt, 0, b_c, st) != hipSuccess) {
-                status = CYB_ERR_HIP;
-                break;
-            }
-        }
-        int pend_round = -1;   // split path: round whose J half is still to be applied ...
-        size_t pend_cnt = 0;   // ... for this many pairs
-        auto flush_pending = [&]() {
-            if (pend_round < 0) return;
-            const int U = (int)std::min<size_t>(16, std::max<size_t>(1, (size_t)(3 * ctx->n_cu) / pend_cnt));
-            hipLaunchKernelGGL(jacobi_update_kernel, dim3((unsigned)(pend_cnt * U)), dim3(NT), 0, st, d_mats,
-                               static_cast<const JWork*>(d_wl), pend_round, U, sc, pend_round & 1, 0, 1);
-            pend_round = -1;
-        };
-        for (int r = 0; r < max_nb - 1; ++r) {
-            size_t cnt = 0; // grid = prefix of the work list holding matrices with nb - 1 > r
-            for (int m : order) {
-                if (h_mats[(size_t)m].nb - 1 > r) cnt += (size_t)h_mats[(size_t)m].nb / 2;
-                else break;
-            }
-            if (cnt == 0) break;
-            const bool fused = !legacy && cnt <= (size_t)fused_max && cnt <= (size_t)ctx->n_cu;
-            if (fused) {
-                flush_pending(); // (the J half of the last split round)
-                // The G parts of a pair wait for one another: all of them must be resident, i.e. at most one workgroup
-                // per CU (the kernel's LDS request allows no second one).
-                int G = (int)std::min<size_t>(kGmax, (size_t)ctx->n_cu / cnt);
-                if (g_env > 0 && (size_t)g_env * cnt <= (size_t)ctx->n_cu) G = std::min(g_env, kGmax);
-                G = std::max(G, 1);
-                hipLaunchKernelGGL(jacobi_round_kernel, dim3((unsigned)(cnt * G)), dim3(NT), ROUND_LDS_BYTES, st,
-                                   static_cast<const RPair*>(d_rp), r, G, max_inner, d_off, rs);
-                if (rs.stamps && r == max_nb / 2 && cnt * (size_t)G <= 2048) { // diagnostic: phase times of one round, all workgroups
-                    std::vector<unsigned long long> hs(8 * cnt * G);
-                    if (hipMemcpyAsync(hs.data(), rs.stamps, sizeof(unsigned long long) * hs.size(), hipMemcpyDeviceToHost, st) == hipSuccess &&
-                        hipStreamSynchronize(st) == hipSuccess) {
-                        double acc[6] = {0, 0, 0, 0, 0, 0}, tot = 0, mx = 0;
-                        for (size_t b = 0; b < cnt * G; ++b) {
-                            for (int k = 0; k < 6; ++k) acc[k] += (double)(hs[8 * b + k + 1] - hs[8 * b + k]) * 0.01;
-                            const double t = (double)(hs[8 * b + 6] - hs[8 * b]) * 0.01;
-                            tot += t;
-                            mx = std::max(mx, t);
-                        }
-                        const double nb_ = (double)(cnt * G);
-                        fprintf(stderr, "[jacobi stamps] sweep %d round %d: %zu pairs x G=%d | gram %.2f exch %.2f defl %.2f eig %.2f sort %.2f upd %.2f | wg mean %.2f max %.2f us\n",
-                                sweep, r, cnt, G, acc[0] / nb_, acc[1] / nb_, acc[2] / nb_, acc[3] / nb_, acc[4] / nb_, acc[5] / nb_, tot / nb_, mx);
-                    }
-                }
-                continue;
-            }
-            // ---- split round: spread every pair over enough workgroups to fill the chip (2 resident per CU for A, more for B)
-            const int slots = 2 * ctx->n_cu;
-            // measured (chi=4096 list): splitting the Gram further than 2 ways costs more in the partial
-            // exchange than it saves (G = 1: 72.2, 2: 71.9, 4: 75.4, 8: 88.7 ms per batched SVD)
-            int G = g_env > 0 ? g_env : ((size_t)2 * cnt <= (size_t)slots ? 2 : 1);
-            G = std::min(G, kGmax);
-            // the update kernel holds 3 workgroups per CU: one full wave of workgroups, no tail
-            const int U = (int)std::min<size_t>((size_t)u_max, std::max<size_t>(1, (size_t)(3 * ctx->n_cu) / cnt));
-            const int buf = r & 1;
-            const int n_gram = (int)(cnt * G);
-            int UJ = 1;
-            size_t n_jwg = 0;
-            if (pend_round >= 0) { // the J half of the previous round rides along in the idle workgroup slots
-                const long long free_slots = (long long)slots - (long long)n_gram;
-                UJ = (int)std::max<long long>(1, std::min<long long>(8, free_slots / (long long)pend_cnt));
-                n_jwg = pend_cnt * (size_t)UJ;
-            }
-            hipLaunchKernelGGL(jacobi_gram_kernel, dim3((unsigned)(n_gram + n_jwg)), dim3(NT), 0, st, d_mats,
-                               static_cast<const JWork*>(d_wl), r, G, max_inner, d_off, sc, buf, n_gram, pend_round, UJ);
-            const bool defer = defer_j && any_j;
-            hipLaunchKernelGGL(jacobi_update_kernel, dim3((unsigned)(cnt * U)), dim3(NT), 0, st, d_mats,
-                               static_cast<const JWork*>(d_wl), r, U, sc, buf, 1, defer ? 0 : 1);
-            pend_round = defer ? r : -1;
-            pend_cnt = cnt;
-        }
-        flush_pending(); // the work list changes with the sweep
-        } // launch-per-round paths
+        if (status != CYB_OK) break;
         if (hipGetLastError() != hipSuccess) {
             set_error("jacobi round kernels: launch failed");
             status = CYB_ERR_HIP;
             break;
         }
-        unsigned int h_err = 0;
-        if (ctx->d2h(h_off.data(), d_off, b_off + 16) != CYB_OK) {
-            set_error("jacobi: reading the convergence flags failed: %s", hipGetErrorString(hipGetLastError()));
-            status = CYB_ERR_HIP;
+        // 5. read back
+        status = read_back(ctx, scratch, h_off, call.b_off);
+        if (status != CYB_OK) break;
+        // 6. verdicts
+        if (one_launch_done) {
+            one_launch_verdicts(h_off, call, active, sweeps_out);
             break;
         }
-        memcpy(&h_err, reinterpret_cast<const char*>(h_off.data()) + b_off, sizeof(unsigned int));
-        if (h_err) {
-            set_error("jacobi round kernel: a workgroup waited more than a second for the Gram partials of its pair "
-                      "(partner workgroup not resident?)");
-            status = CYB_ERR_HIP;
-            break;
-        }
-        std::vector<int> still;
-        if (one_launch_done) { // every sweep has run: matrices the device marked converged are done, the rest did not converge
-            const int* h_nsw = reinterpret_cast<const int*>(reinterpret_cast<const unsigned int*>(h_off.data() + w_off) + n);
-            for (int m : active) {
-                if (h_nsw[m] > 0) sweeps_out[(size_t)m] = h_nsw[m];
-                else still.push_back(m);
-            }
-            active.swap(still);
-            break;
-        }
-        static const bool trace = getenv("CYB_JACOBI_TRACE") != nullptr;
-        for (int m : active) {
-            double off;
-            memcpy(&off, &h_off[(size_t)m], sizeof(double));
-            if (trace)
-                fprintf(stderr, "[jacobi] sweep %2d mat %3d (nv=%d len=%d) off=%.3e tol=%.3e\n", sweep, m,
-                        h_mats[(size_t)m].nv, h_mats[(size_t)m].len, off, h_mats[(size_t)m].tol);
-            const double tol = h_mats[(size_t)m].tol;
-            // converged, or stagnated within a small factor of the threshold (rounding floor of the
-            // Gram products for long vectors)
-            const bool stagnated = sweep >= 6 && off <= 64.0 * tol && off >= 0.5 * prev_off[(size_t)m];
-            // `off` was measured pair by pair BEFORE this sweep rotated the pair.  In the quadratic regime the
-            // sweep leaves off^2 behind: once off <= sqrt(tol)/10 the rotations just applied have already
-            // taken the matrix to the rounding floor and another sweep would only re-measure it
-            // (chi=4096 list: 1.8e-4 -> 2.3e-9 -> 3.4e-14 in the last three sweeps, tol 3.4e-14).
-            static const bool no_predict = getenv("CYB_JACOBI_NOPREDICT") != nullptr;
-            // ... but only when the decrease is actually superlinear: with clustered singular values the off-norm
-            // can creep down linearly (1.7e-8 -> 4.4e-9 per sweep was measured) and a sweep is then NOT the last
-            // ... and only when the last decrease WAS quadratic (off <= kPredictQuad * prev^2): a 128-fold zero eigenvalue
-            // (Gram matrix of a rank-132 block, scripts/svd_fuzz.py seed 301) went 5.0e-7 -> 3.2e-10 -> 1.6e-10 -> 1.3e-14 --
-            // superlinear by the test above, but the rotations inside the cluster (equal norms: large angles on couplings of
-            // 1e-10) carry the couplings to the other rows from one cluster row to the next instead of annihilating them, and
-            // the predicted stop left 1.6e-10 of non-orthogonality.  Quadratic steps measured here have off / prev^2 = 0.07 ... 0.2
-            // (chi=4096 list: 1.8e-4 -> 2.3e-9), that one 1280.
-            const double prev = prev_off[(size_t)m];
-            const bool predicted = !no_predict && off <= 0.1 * std::sqrt(tol) && prev < 1.0 && off <= prev * std::sqrt(prev) &&
-                                   off <= kPredictQuad * prev * prev;
-            if (off <= tol || stagnated || predicted) sweeps_out[(size_t)m] = sweep;
-            else still.push_back(m);
-            prev_off[(size_t)m] = off;
-        }
-        active.swap(still);
+        sweep_verdicts(h_mats, h_off, sweep, active, prev_off, sweeps_out);
     }
     if (status != CYB_OK) return status;
     if (!active.empty()) {
@@ -2433,3 +2016,4 @@ int jacobi_orthogonalise(cyb_ctx_t ctx, const std::vector<JMat>& h_mats, int max
 }
 
 } // namespace cyb
+

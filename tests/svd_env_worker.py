@@ -27,6 +27,20 @@ res = bb.matrix_svd_batched([bb.as_block(m) for m in mats])
 for m, (U, S, Vh) in zip(mats, res):
     check_svd_invariants(m, bb.to_numpy(U), bb.to_numpy(S), bb.to_numpy(Vh), 1e-10, sref=np.linalg.svd(m, compute_uv=False))
 
+# Single blocks just above the in-LDS kernels: four block pairs per round.  Under CYB_JACOBI_NOSWEEP these are the few-pair
+# rounds of the split route: with J (SVD of a square block), and without J and without QR (eigh)
+one = rng.standard_normal((70, 70))
+(U, S, Vh), = bb.matrix_svd_batched([bb.as_block(one)])
+check_svd_invariants(one, bb.to_numpy(U), bb.to_numpy(S), bb.to_numpy(Vh), 1e-10, sref=np.linalg.svd(one, compute_uv=False))
+sym = rng.standard_normal((100, 100))
+sym = sym + sym.T
+(W, V), = bb.eigh_batched([bb.as_block(sym)])
+W, V = bb.to_numpy(W), bb.to_numpy(V)
+nrm = np.linalg.norm(sym)
+assert np.abs(np.sort(W) - np.linalg.eigvalsh(sym)).max() <= 1e-10 * nrm
+assert np.abs((V * W) @ V.T - sym).max() <= 1e-10 * nrm
+assert np.abs(V.T @ V - np.eye(100)).max() <= 1e-10
+
 # complex128 blocks on the same pipeline through the interleaved embedding (CYB_SVD_EMBEDDED_COMPLEX): full rank, tall /
 # wide rank deficiency (pair-wise deflation, completion), degenerate and graded spectra, one null direction
 def crandn(shape):

@@ -257,7 +257,7 @@ def test_svd_pipeline_variants(env):
     """Every switchable stage of the SVD pipeline against LAPACK on the same list: the default (QR -> LQ -> persistent
     block-Jacobi sweeps -> completion from Q2), the plain iteration on R (`CYB_SVD_NOLQ`), the FALLBACK from the LQ iteration
     to the plain one (forced with `CYB_SVD_LQ_FORCE_REDO`: in production it is taken when a row of S Z^T is exactly zero or
-    the iteration does not settle), small blocks in an iteration of their own, one launch per Jacobi round, all sweeps in ONE launch
+    the iteration does not settle), small blocks in an iteration of their own, every Jacobi round on the two-launch split route (the engine's fallback), all sweeps in ONE launch
     with the convergence test on the device (the default for lists of small matrices only) / one launch per sweep for every list,
     the first QR without / with a per-step test of its early stop.  The switches are read
     once per process, hence the child process (one GPU process at a time)."""
