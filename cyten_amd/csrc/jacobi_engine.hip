@@ -534,7 +534,9 @@ jacobi_update_kernel(const JMat* __restrict__ mats, const JWork* __restrict__ wo
 //      has seen every partner's partial of r + 1, which a partner publishes only after it has read those of round r -- so
 //      nobody still reads the buffer a store overwrites, and nothing is reset between rounds.
 //   3. deflation test, convergence measure, two-sided Jacobi eigensolve of the 32x32 Gram, REDUNDANTLY in every part
-//      (the chip is idle otherwise; no second exchange, no publish of Qm)
+//      (the chip is idle otherwise; no second exchange, no publish of Qm).  Template parameter RP: test and measure share
+//      ONE interval between two barriers and work from the registers that hold the sums, a cross candidate's Gram is written
+//      in interleaved positions at once, the rows are ranked on all four waves, and step 4 reads Qm from V through perm
 //   4. X <- Qm^T X on the own column share of W and J, in place, then the hand-off of the two row blocks
 // No workgroup reads or writes a column another workgroup of the launch touches, so within a round rows need no hand-off;
 // the only data that cross between the parts of a pair are the 8 KB partials.
@@ -872,10 +874,13 @@ __device__ __forceinline__ void sweep_update_j(const __amdgpu_buffer_rsrc_t rsJ,
 
 // GRAN: the partial Grams travel as tagged granules (step 2; false: stores, drain, ticket and poll as before, kept for
 // A/B -- CYB_JACOBI_EXCHANGE=0)
-template <bool CPLX, bool RORD, bool GRAN>
+// RP: the LDS passes around the pivot solve in their folded form (steps 3a-3c and the head of step 4; false: the passes and
+// barriers as before, kept for A/B -- CYB_JACOBI_ROUND_PASSES=0).  Only the default order and exchange have the folded form.
+template <bool CPLX, bool RORD, bool GRAN, bool RP>
 __global__ void __launch_bounds__(NT, 1)
 jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned long long* __restrict__ offmax_bits, SScratch sc)
 {
+    static_assert(!RP || (RORD && GRAN), "the folded passes exist for the default round order and exchange only");
     extern __shared__ __attribute__((aligned(16))) double rsm[];
     // LDS carve-up for two to three workgroups per CU: the wave slices of the partial Gram (Xc) are dead once the
     // exchange has produced Gs, so they share their space with the eigensolver's second Gram buffer, V and Qs
@@ -962,6 +967,19 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
         if constexpr (GRAN) {
             if (tid == 0) flags[3] = 0; // (read behind the barrier that ends step 2; two barriers lie between)
         }
+        if constexpr (RP) {
+            if (tid == 0) flags[0] = 0; // (raised in step 3a behind the barrier that ends step 2, last read before the round's end)
+        }
+        // Everything that decides a cross-only solve except the null rows is known here (the same in every part)
+        // (cross_every < 0: adaptive -- at least four full rounds per sweep of a matrix, whatever its block count)
+        const int cross_k = sc.cross_every > 0 ? sc.cross_every : max(4, (mt.nb + 2) / 4);
+        const bool cross_terms = sc.cross_every != 0 && mt.nb >= sc.cross_min_nb && (round % cross_k) != 0;
+        auto cpos = [](int i) { return i < JB ? 2 * i : 2 * (i - JB) + 1; };     // index -> interleaved position
+        auto cidx = [](int p) { return (p & 1) ? JB + (p >> 1) : (p >> 1); };    // interleaved position -> index
+        // RP: a cross candidate's Gram is WRITTEN in interleaved positions (there is no natural copy; the rare round with a null
+        // row writes it again from the registers)
+        const bool ilv = RP && !CPLX && cross_terms;
+        double gv[4] = {0.0, 0.0, 0.0, 0.0};                                     // RP: the four sums of this thread (row gi, columns gj ..)
         // byte offset of element (row k of the pair, own chunk c, column un of this wave's 16) and its descriptor
         auto chunk_off = [&](int c, int k, bool& in_w) -> unsigned int {
             in_w = c < nW;
@@ -1244,17 +1262,79 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
                 }
                 } // (ticket form)
             }
+            if constexpr (RP) {
+                gv[0] = lo.x;
+                gv[1] = lo.y;
+                gv[2] = hi.x;
+                gv[3] = hi.y;
+                // (Gs is no part of the region the wave slices share: no wave still reads what these stores overwrite)
+                double* dst = Gs + (ilv ? cpos(gi) * GS + cpos(gj) : gi * GS + gj);
+                const int ds = ilv ? 2 : 1;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) dst[k * ds] = gv[k];
+            } else {
             double* dst = Gs + gi * GS + gj;
             dst[0] = lo.x;
             dst[1] = lo.y;
             dst[2] = hi.x;
             dst[3] = hi.y;
+            }
         }
         __syncthreads();
         if constexpr (GRAN) {
             if (G > 1 && flags[3]) return;
         }
         SWEEP_STAMP(3);
+        // ---- 3a, 3b. deflation and convergence measure
+        double off;
+        bool any_null;
+        if constexpr (RP) {
+            // ONE interval between two barriers: every thread measures its four elements from its registers against the diagonal
+            // in LDS (the terms of gram_offmax, each formed once by the thread that holds the element), lanes < JP test the
+            // rows, and V is filled with the identity in the layout the Gram was written in (V and the second Gram buffer lie in
+            // the region of the wave slices, which the barrier behind the exchange has just released)
+            const int gi = tid >> 3, gj = 4 * (tid & 7);
+            double m = 0.0;
+            if (gi < gj + 3) {
+                const double gii = Gs[(ilv ? cpos(gi) : gi) * (GS + 1)];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int j = gj + k;
+                    if (gi < j) {
+                        const double den = gii * Gs[(ilv ? cpos(j) : j) * (GS + 1)];
+                        if (den > 0.0) m = fmax(m, fabs(gv[k]) * rsqrt(den));
+                    }
+                }
+            }
+            m = wave_max(m);
+            if (lane == 0) red[wave] = m;
+            if (tid < JP) {
+                double g = Gs[(ilv ? cpos(tid) : tid) * (GS + 1)];
+                if constexpr (CPLX) g = fmax(g, Gs[(tid ^ 1) * (GS + 1)]); // (a complex row is null or not as a whole)
+                const int z = (g > 0.0 && g <= mt.thr2) ? 1 : 0;
+                zrow[tid] = z;
+                perm[tid] = tid;
+                if (z) flags[0] = 1;
+            }
+            if constexpr (!CPLX) {
+                for (int e = tid; e < JP * VS; e += NT) {
+                    const int k = e / VS;
+                    Va[e] = ((ilv ? cpos(k) : k) == (e % VS)) ? 1.0 : 0.0;
+                }
+            }
+            __syncthreads();
+            off = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+            any_null = flags[0] != 0;
+            if (any_null) {
+                // rare: the measure is taken on the Gram with the null rows zeroed, in natural layout (no cross-only solve)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) Gs[gi * GS + gj + k] = (zrow[gi] || zrow[gj + k]) ? 0.0 : gv[k];
+                if (ilv)
+                    for (int e = tid; e < JP * VS; e += NT) Va[e] = ((e / VS) == (e % VS)) ? 1.0 : 0.0;
+                __syncthreads();
+                off = gram_offmax(Gs, red, tid);
+            }
+        } else {
         // ---- 3a. deflation
         if (tid == 0) flags[0] = 0;
         __syncthreads();
@@ -1267,7 +1347,7 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
             if (z) flags[0] = 1;
         }
         __syncthreads();
-        const bool any_null = flags[0] != 0;
+        any_null = flags[0] != 0;
         if (any_null) {
             for (int e = tid; e < JP * JP; e += NT) {
                 const int i = e / JP, j = e % JP;
@@ -1276,7 +1356,8 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
             __syncthreads();
         }
         // ---- 3b. convergence measure
-        const double off = gram_offmax(Gs, red, tid);
+        off = gram_offmax(Gs, red, tid);
+        }
         if (part == 0 && tid == 0) atomicMax(offmax_bits + (size_t)sw * sc.n_mats + mt.mat, (unsigned long long)__double_as_longlong(off));
         const bool skip = off <= mt.tol && !any_null; // pair already orthogonal: rows stay as they are
         if (!skip) {
@@ -1285,9 +1366,7 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
             double* Vc = Va;
             double* Vn = Vb;
             bool pos_is_interleaved = false; // cross-only solve: position 2k holds row k of block P, 2k + 1 row k of block Q
-            // (cross_every < 0: adaptive -- at least four full rounds per sweep of a matrix, whatever its block count)
-            const int cross_k = sc.cross_every > 0 ? sc.cross_every : max(4, (mt.nb + 2) / 4);
-            const bool cross = sc.cross_every != 0 && !any_null && mt.nb >= sc.cross_min_nb && (round % cross_k) != 0; // (the same in every part)
+            const bool cross = cross_terms && !any_null; // (the same in every part)
             if constexpr (CPLX) {
                 // ---- 3c'. rows are the interleaved embedding of complex rows: structure-preserving pivot solve by wave 0
                 //           (work arrays in G2, rotations in Vb, result M(Q_c) in Va, eigenvalues on the diagonal of Gs)
@@ -1295,8 +1374,10 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
                 __syncthreads();
             } else {
             // ---- 3c. eigensolve in position space (see the head of this section)
-            auto cpos = [](int i) { return i < JB ? 2 * i : 2 * (i - JB) + 1; };     // index -> interleaved position
             pos_is_interleaved = cross;
+            if constexpr (RP) {
+                // (the Gram lies in Gs in the layout of the solve and V holds its identity: the first step follows at once)
+            } else {
             if (cross) {
                 for (int e = tid; e < JP * JP; e += NT) {
                     const int i = e / JP, j = e % JP;
@@ -1309,6 +1390,7 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
             } else
                 for (int e = tid; e < JP * VS; e += NT) Va[e] = ((e / VS) == (e % VS)) ? 1.0 : 0.0;
             __syncthreads();
+            }
             {
                 const int pr = tid >> 4, pc = tid & 15;
                 const int r0 = 2 * pr, c0 = 2 * pc;
@@ -1363,13 +1445,43 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
                 }
             }
             } // (real pivot solve)
+            auto row_at = [&](int p) { return pos_is_interleaved ? cidx(p) : p; }; // the row of the pair that sits at position p
+            if constexpr (RP) {
+                // (both solves end behind a barrier of their own)
+                SWEEP_STAMP(4);
+                if (off > mt.tol) {
+                    // rank of every row by descending norm (padding rows last) on all four waves: wave w ranks the positions
+                    // 8 w .. 8 w + 7, eight lanes per position compare its key with four of the 32 keys each, the partial
+                    // ranks meet in the 8-lane group.  The lane that writes perm also forms zout.
+                    const int li = 8 * wave + (lane >> 3), ch = lane & 7;
+                    auto key = [&](int p) { return xrow(row_at(p), P, Q) < mt.nv ? Ga[p * GS + p] : -1.0e300; };
+                    const double g = key(li);
+                    int rk = 0;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int j = 4 * ch + k;
+                        const double gj = key(j);
+                        rk += (gj > g || (gj == g && j < li)) ? 1 : 0;
+                    }
+                    rk += __shfl_xor(rk, 1);
+                    rk += __shfl_xor(rk, 2);
+                    rk += __shfl_xor(rk, 4);
+                    if (ch == 0) {
+                        perm[rk] = li;
+                        zout[rk] = zrow[row_at(li)];
+                    }
+                } else if (tid < JP)
+                    zout[tid] = zrow[row_at(tid)]; // (perm is the identity of step 3a)
+                __syncthreads();
+                SWEEP_STAMP(5);
+            } else {
             __syncthreads();
             SWEEP_STAMP(4);
             if (off > mt.tol && tid < 64) {
                 // rank of every row by descending norm (padding rows last): lane i of wave 0 holds key i and takes the other
                 // keys from the lanes by v_readlane (a scalar broadcast) instead of 32 dependent LDS reads: 1.6 -> 0.4 us
                 const int li = lane & (JP - 1);
-                const int li_idx = pos_is_interleaved ? ((li & 1) ? JB + (li >> 1) : (li >> 1)) : li; // the row that sits at position li
+                const int li_idx = row_at(li);
                 const double g = xrow(li_idx, P, Q) < mt.nv ? Ga[li * GS + li] : -1.0e300;
                 const int glo = __double2loint(g), ghi = __double2hiint(g);
                 int rk = 0;
@@ -1386,12 +1498,10 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
                 const int k = e / JP, m = e % JP;
                 Qs[k * QS + m] = Vc[k * VS + perm[m]];
             }
-            if (tid < JP) { // (perm holds positions; zrow is per row of the pair)
-                const int pp = perm[tid];
-                zout[tid] = zrow[pos_is_interleaved ? ((pp & 1) ? JB + (pp >> 1) : (pp >> 1)) : pp];
-            }
+            if (tid < JP) zout[tid] = zrow[row_at(perm[tid])]; // (perm holds positions; zrow is per row of the pair)
             __syncthreads();
             SWEEP_STAMP(5);
+            }
             if (ct > nW) { // J is updated in this round: its rows must have been through every earlier round's update
                 if (tid == 0) {
                     flags[1] = spin_pair<RORD>(readyJ + (size_t)P * G + part, readyJ + (size_t)Q * G + part, (unsigned int)ground, sc.err) ? 1 : 0;
@@ -1407,13 +1517,17 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
                 }
             }
             if (ct > 0) {
-                const double* ap0 = Qs + (lane >> 4) * QS + (lane & 15);
-                const double* ap1 = ap0 + 16;
+                // ---- 4. X <- Qm^T X on the own chunks, stored write-through for the next owner.  Qm[k][m] = V[k][perm[m]]:
+                //         RP reads the MFMA operands from V through perm, the copy Qs is built only where a deferred J
+                //         update will read it, behind the update (below)
+                const double* ap0 = RP ? Vc + (lane >> 4) * VS + perm[lane & 15] : Qs + (lane >> 4) * QS + (lane & 15);
+                const double* ap1 = RP ? Vc + (lane >> 4) * VS + perm[16 + (lane & 15)] : ap0 + 16;
+                constexpr int AS = RP ? VS : QS;
                 double a0[JP / 4], a1[JP / 4];
 #pragma unroll
                 for (int kk = 0; kk < JP / 4; ++kk) {
-                    a0[kk] = ap0[kk * 4 * QS];
-                    a1[kk] = ap1[kk * 4 * QS];
+                    a0[kk] = ap0[kk * 4 * AS];
+                    a1[kk] = ap1[kk * 4 * AS];
                 }
                 int zr[2][4];
 #pragma unroll
@@ -1482,6 +1596,16 @@ jacobi_sweep_kernel(const RPair* __restrict__ pairs, int max_inner, unsigned lon
                         apply(c, xb);
 #pragma unroll
                         for (int kk = 0; kk < JP / 4; ++kk) xb[kk] = xn[kk];
+                    }
+                }
+            }
+            if constexpr (RP) {
+                // Qm for the deferred J update of the next round, off the chain: the W stores are on their way, the barrier
+                // of step 5 makes it visible (nobody else reads Qs: this round's J chunks took their operands above)
+                if (defer) {
+                    for (int e = tid; e < JP * JP; e += NT) {
+                        const int k = e / JP, m = e % JP;
+                        Qs[k * QS + m] = Vc[k * VS + perm[m]];
                     }
                 }
             }
@@ -1563,6 +1687,8 @@ struct JSwitches {       // CYB_JACOBI_* (DESIGN.md section 7), read once per pr
     bool gran_exchange;  // EXCHANGE=0: the partial Grams of the sweep kernel travel by stores, drain, ticket and poll (same sums
                          // in the same order: bit-identical results); default: as tagged granules
     bool round_order;    // ROUND_ORDER=0: the issue order a round had before (same arithmetic, same protocol: bit-identical results)
+    bool round_passes;   // ROUND_PASSES=0: the LDS passes and barriers around the pivot solve as they were before they were folded
+                         // (same arithmetic: bit-identical results); the folded form needs the default order and exchange
     bool no_defer_j;     // NODEFERJ: the sweep kernel updates J at once
     bool cross_small;    // CROSS_SMALL: cross-only pivot solves for lists of small matrices too
     int g;               // G: parts per pair (0: chosen by plan_parts / per split round)
@@ -1584,6 +1710,7 @@ const JSwitches& switches()
         w.no_predict = on("CYB_JACOBI_NOPREDICT");
         w.gran_exchange = num("CYB_JACOBI_EXCHANGE", 1) != 0;
         w.round_order = num("CYB_JACOBI_ROUND_ORDER", 1) != 0;
+        w.round_passes = num("CYB_JACOBI_ROUND_PASSES", 1) != 0 && w.round_order && w.gran_exchange;
         w.no_defer_j = on("CYB_JACOBI_NODEFERJ");
         w.cross_small = on("CYB_JACOBI_CROSS_SMALL");
         w.g = num("CYB_JACOBI_G", 0);
@@ -1725,14 +1852,15 @@ int descriptor_image(cyb_ctx_t ctx, ImageCache& cache, const std::vector<JMat>& 
 typedef void (*sweep_fn_t)(const RPair*, int, unsigned long long*, SScratch);
 int sweep_kernel_for(bool cplx, sweep_fn_t& fn)
 {
-    static const sweep_fn_t sweep_fns[2][2][2] = { // [CPLX][RORD][GRAN]
-        {{jacobi_sweep_kernel<false, false, false>, jacobi_sweep_kernel<false, false, true>},
-         {jacobi_sweep_kernel<false, true, false>, jacobi_sweep_kernel<false, true, true>}},
-        {{jacobi_sweep_kernel<true, false, false>, jacobi_sweep_kernel<true, false, true>},
-         {jacobi_sweep_kernel<true, true, false>, jacobi_sweep_kernel<true, true, true>}}};
+    static const sweep_fn_t sweep_fns[2][2][2] = { // [CPLX][RORD][GRAN], passes around the pivot solve as before
+        {{jacobi_sweep_kernel<false, false, false, false>, jacobi_sweep_kernel<false, false, true, false>},
+         {jacobi_sweep_kernel<false, true, false, false>, jacobi_sweep_kernel<false, true, true, false>}},
+        {{jacobi_sweep_kernel<true, false, false, false>, jacobi_sweep_kernel<true, false, true, false>},
+         {jacobi_sweep_kernel<true, true, false, false>, jacobi_sweep_kernel<true, true, true, false>}}};
+    static const sweep_fn_t sweep_fns_rp[2] = {jacobi_sweep_kernel<false, true, true, true>, jacobi_sweep_kernel<true, true, true, true>}; // [CPLX], folded
     const JSwitches& sw = switches();
-    static const sweep_fn_t sweep_fn[2] = {sweep_fns[0][sw.round_order ? 1 : 0][sw.gran_exchange ? 1 : 0],
-                                           sweep_fns[1][sw.round_order ? 1 : 0][sw.gran_exchange ? 1 : 0]};
+    static const sweep_fn_t sweep_fn[2] = {sw.round_passes ? sweep_fns_rp[0] : sweep_fns[0][sw.round_order ? 1 : 0][sw.gran_exchange ? 1 : 0],
+                                           sw.round_passes ? sweep_fns_rp[1] : sweep_fns[1][sw.round_order ? 1 : 0][sw.gran_exchange ? 1 : 0]};
     static bool attr_set = false;
     if (!attr_set) {
         for (int c = 0; c < 2; ++c)
