@@ -106,13 +106,14 @@ __device__ __forceinline__ double fast_rsqrt(double x)
 //   cos 2theta = |delta| / h,  c = sqrt((1 + cos 2theta) / 2),  s = sign(delta b) |b| / (h c).
 // Two v_rsq_f64 + a dozen FMAs instead of two IEEE divisions and two square roots: the inner
 // eigensolver runs one wave per SIMD, so every dependent long-latency op is exposed.
-__device__ __forceinline__ void jacobi_rot(double a, double d, double b, double& c, double& s)
+// thr2: relative threshold, as in jacobi_rot_bf below -- a coupling with b^2 <= thr2 a d is left alone.
+__device__ __forceinline__ void jacobi_rot(double a, double d, double b, double& c, double& s, double thr2 = 0.0)
 {
     const double delta = d - a;
     const double h2 = delta * delta + 4.0 * b * b;
     c = 1.0;
     s = 0.0;
-    if (fabs(b) > 1e-300 && h2 > 1e-300) {
+    if (fabs(b) > 1e-300 && h2 > 1e-300 && b * b > thr2 * a * d) {
         const double rh = fast_rsqrt(h2);            // 1 / h
         const double c2 = 0.5 + 0.5 * fabs(delta) * rh; // cos^2 theta in [1/2, 1]
         const double rc = fast_rsqrt(c2);            // 1 / c
@@ -351,7 +352,11 @@ jacobi_gram_kernel(const JMat* __restrict__ mats, const JWork* __restrict__ work
             const unsigned int sr = sched[r * NPAIR + pr], scl = sched[r * NPAIR + pc];
             const int i = sr & 255, j = sr >> 8, k = scl & 255, l = scl >> 8;
             double c2, s2;
-            jacobi_rot(Ga[k * GS + k], Ga[l * GS + l], Ga[k * GS + l], c2, s2);
+            // (tol / 2)^2: two rows of equal norm are not turned by 45 degrees on a coupling of rounding noise.  eigh iterates
+            // on A + shift, every row norm within a factor three of the next and the null space of A one exact cluster: without the
+            // threshold those turns went on sweep after sweep and left 1.4e-13 ... 2.2e-13 ||A||_F in the eigenvalues of a
+            // 128 / 256-row block with a null space of half its rows (tests/test_gpu_decomp_accuracy.py, variant per-round)
+            jacobi_rot(Ga[k * GS + k], Ga[l * GS + l], Ga[k * GS + l], c2, s2, 0.25 * mt.tol * mt.tol);
             const int srcl = (lane & 48) | pr;
             const double c1 = __shfl(c2, srcl), s1 = __shfl(s2, srcl);
             {   // G <- R^T G R on one 2x2 sub-block per thread: rows (i,j), cols (k,l)

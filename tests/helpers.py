@@ -24,3 +24,13 @@ def check_svd_invariants(a, U, S, Vh, tol=1e-10, sref=None):
     assert np.abs(Vh @ Vh.T - np.eye(k)).max() <= tol
     if sref is not None:
         assert np.abs(S - sref).max() <= tol * nrm
+
+
+def check_svd_accuracy(a, U, S, Vh, sref=None, cap=1e-13, name='block'):
+    """The strict sibling of `check_svd_invariants`: the same facts held to the rounding level.  S >= 0 and descending with no
+    slack, shapes and dtypes exactly; |U^H U - 1|, |Vh Vh^H - 1|, |U S Vh - A| / sigma_1 and -- with `sref`, reference values
+    whose own error is negligible (long double) -- |S - sref| / sigma_1, each formed in long double, each <= `cap`.
+    Returns the measures in units of 2^-52 (tests/decomp_accuracy_cases.py)."""
+    import decomp_accuracy_cases as dac
+    ref = None if sref is None else np.asarray(sref, dtype=np.longdouble)
+    return dac.check_svd(dac.Case(name, np.asarray(a), ref), U, S, Vh, cap_eps=cap / dac.EPS)
