@@ -13,6 +13,7 @@
 // ~ eps * |A|_F, the LAPACK dsyevd class of guarantee).
 #include "blocked_qr.h"
 #include "jacobi_engine.h"
+#include "svd_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -409,6 +410,49 @@ static inline int row_blocks(int nv, int nvp)
     return std::min(std::max(nb, 4), nvp / cyb::JB);
 }
 
+// nv vectors of length len in W (nvp x lenp), rotations accumulated in J (may be null); no deflation
+static inline JMat make_jmat(double* W, double* J, int nv, int len, int nvp, int lenp)
+{
+    JMat jm;
+    jm.W = W;
+    jm.J = J;
+    jm.nvp = nvp;
+    jm.lenp = lenp;
+    jm.nb = row_blocks(nv, nvp);
+    jm.nv = nv;
+    jm.len = len;
+    jm.rec_j = 0;
+    jm.tol = jacobi_tol(len);
+    jm.thr2 = 0.0;
+    return jm;
+}
+
+// the CYB_SVD_* switches (svd_plan.h), read from the environment once per process
+static const SvdSwitches& svd_switches()
+{
+    static const SvdSwitches sw = [] {
+        SvdSwitches s;
+        auto set = [](const char* name) { return getenv(name) != nullptr; };
+        auto count = [](const char* name, int dflt) { return getenv(name) ? atoi(getenv(name)) : dflt; };
+        auto ratio = [](const char* name, double dflt) { return getenv(name) ? atof(getenv(name)) : dflt; };
+        s.nolq = set("CYB_SVD_NOLQ");
+        s.lq_always = set("CYB_SVD_LQ_ALWAYS");
+        s.lq_skip_k = count("CYB_SVD_LQ_SKIP_K", s.lq_skip_k);
+        s.lq_skip_ratio = ratio("CYB_SVD_LQ_SKIP_RATIO", s.lq_skip_ratio);
+        s.nojrec = set("CYB_SVD_NOJREC");
+        s.jrec_ratio = ratio("CYB_SVD_JREC_RATIO", s.jrec_ratio);
+        s.jrec_min = count("CYB_SVD_JREC_MIN", s.jrec_min);
+        s.lq_force_redo = set("CYB_SVD_LQ_FORCE_REDO");
+        s.jrec_force_redo = set("CYB_SVD_JREC_FORCE_REDO");
+        s.trace_redo = set("CYB_SVD_TRACE_REDO");
+        s.noqr = set("CYB_SVD_NOQR");
+        s.nosmall = set("CYB_SVD_NOSMALL");
+        s.nomerge = set("CYB_SVD_NOMERGE");
+        return s;
+    }();
+    return sw;
+}
+
 // shared driver: mode 0 = SVD, 1 = eigh
 static int run_jacobi(cyb_ctx_t ctx, int mode, int64_t nmat, const cyb_svd_desc* sd, const cyb_eigh_desc* ed,
                       int32_t* info, bool cplx = false)
@@ -456,15 +500,7 @@ static int run_jacobi(cyb_ctx_t ctx, int mode, int64_t nmat, const cyb_svd_desc*
         o.shift = take(sizeof(double));
         o.scratch = take(sizeof(double) * (size_t)lenp * 2);
         o.nnull = take(sizeof(int32_t));
-        JMat& jm = mats[(size_t)b];
-        jm.nvp = nvp;
-        jm.lenp = lenp;
-        jm.nb = row_blocks(nv, nvp);
-        jm.nv = nv;
-        jm.len = len;
-        jm.rec_j = 0;
-        jm.tol = 2.220446049250313e-16 * std::max(16.0, 4.0 * std::sqrt((double)len));
-        jm.thr2 = 0.0;
+        mats[(size_t)b] = make_jmat(nullptr, nullptr, nv, len, nvp, lenp); // (W and J: once the workspace is there)
     }
     void* ws = nullptr;
     CYB_TRY(ctx->workspace(off, &ws));
@@ -712,11 +748,7 @@ struct LqDesc {
     double* sigo;        // kp: sigo[idx[i]] = sigma_i out for the rows that keep their left vector (PostDesc::sig_lq)
     const int32_t* idx;  // row of the full-size W that compact row i goes back to
 };
-// recovered rotations: max |J' J'^T - 1| above this sends the list to the plain iteration with accumulation.  The
-// recovered factor ends up, through orthogonal transformations only, in the U (or Vh) the caller checks to 1e-10; the
-// iteration adds its own drift of 2e-12, so 2e-11 leaves a factor 4 to the tolerance (tests/test_svd_jrecover_model.py
-// shows which blocks stay a further factor 10 inside it).
-constexpr double JREC_BOUND = 2e-11;
+// (JREC_BOUND, the largest max |J' J'^T - 1| of recovered rotations: svd_plan.h)
 constexpr int JREC_NB = 128; // rows per block row of the Gram check
 // Cq2[:, i] = [ J'[i, 0:r0] ; 0 ] (i < r0),  Cq2[:, t] = e_t (r0 <= t < k)
 __global__ void __launch_bounds__(256) lq_pack_kernel(const LqDesc* __restrict__ descs)
@@ -864,366 +896,315 @@ static int launch_row_moves(cyb_ctx_t ctx, const std::vector<RowMoveDesc>& v)
 
 } // namespace
 
-static int run_svd_qr(cyb_ctx_t ctx, int64_t nmat, const cyb_svd_desc* sd, int32_t* info, int flags, int32_t* rank_out)
-{
-    if (nmat == 0) return CYB_OK;
+namespace {
+
+// One call of the pipeline: the plan (svd_plan.h) decides, the methods below fill descriptors and launch, one per numbered
+// step of the header comment.  run_svd_qr calls them top to bottom.
+struct SvdPipeline {
+    struct Block {                  // what the host learns about a block before the sweeps
+        int r0 = 0;                 // rows surviving the up-front deflation
+        std::vector<int32_t> good0; // their indices
+        int n_fac = -1;             // panels the first QR factored before it stopped (-1: all), for the application of Q1
+        bool lq = false;            // chosen route: second (LQ) preconditioning step
+        bool jrec = false;          // ... without accumulation: J' is recovered from S Z^T and R2 after the sweeps
+    };
+    struct Route {
+        bool lq = false, jrec = false;
+    };
+    struct Comp {                   // a block with null rows to complete: its good / null rows in idx_all
+        int64_t b;
+        size_t good_off, null_off;
+        int r, q;
+    };
+
+    cyb_ctx_t ctx;
+    const int64_t nmat;
+    const cyb_svd_desc* sd;
+    const int flags;
     // CYB_SVD_EMBEDDED_COMPLEX: every block is the interleaved real embedding M(A) of a complex block (entry a + ib ->
     // [[a, -b], [b, a]]).  The QR steps preserve the structure by themselves (uniqueness); the iteration does through its
     // structure-preserving pivot solve (jacobi_engine.hip); here rows 2a, 2a + 1 are deflated, ranked and completed as pairs.
-    const bool cplx = (flags & CYB_SVD_EMBEDDED_COMPLEX) != 0;
-    hipStream_t st = ctx->stream;
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    struct Lay {
-        int m, n, k, L, kp;
-        bool tall;
-        size_t Ac, aux, W, J, sig, rank, inv, thr, nnull, Cq, Fc, aux2, Cn, idx, Wc, Jc;
-        size_t bad, Wq, aux3, Cq2, sig2; // second (LQ) preconditioning step
-        size_t stop;                     // early stop of the first QR: squared norms of the strips of one step
-        size_t ctl;                      // ... and its two control words, behind the flags: they ride in the same D2H copy as the row norms
-        int n_fac = -1;                  // panels the first QR factored before it stopped (-1: all), for the application of Q1
-        size_t sigo;                     // singular values of an LQ block by full-size row (PostDesc::sig_lq)
-        size_t dev;                      // max |J' J'^T - 1| of the recovered rotations (behind the flags: same D2H copy)
-        bool lq = false;
-        bool jrec = false;          // LQ branch without accumulation: J' is recovered from S Z^T and R2 after the sweeps
-        int r0 = 0;                 // rows surviving the up-front deflation
-        std::vector<int32_t> good0; // their indices
-    };
-    std::vector<Lay> lay((size_t)nmat);
-    size_t off = 0;
-    // all sig arrays first and contiguous: ONE device->host copy after the iteration
-    size_t sig_begin = off;
-    for (int64_t b = 0; b < nmat; ++b) {
-        Lay& l = lay[(size_t)b];
-        l.m = (int)sd[b].m;
-        l.n = (int)sd[b].n;
-        l.k = std::min(l.m, l.n);
-        l.L = std::max(l.m, l.n);
-        l.kp = round_up(l.k, 64);
-        l.tall = l.m >= l.n;
-        l.sig = off;
-        off += sizeof(double) * (size_t)l.kp;
-    }
-    for (int64_t b = 0; b < nmat; ++b) { // thresholds right behind the sig arrays: same D2H copy
-        lay[(size_t)b].thr = off;
-        off += sizeof(double);
-    }
-    for (int64_t b = 0; b < nmat; ++b) { // ... and the "no left vector" flags of the LQ step
-        lay[(size_t)b].bad = off;
-        off += sizeof(double);
-    }
-    for (int64_t b = 0; b < nmat; ++b) {
-        lay[(size_t)b].dev = off;
-        off += sizeof(double);
-    }
-    for (int64_t b = 0; b < nmat; ++b) {
-        lay[(size_t)b].ctl = off;
-        off += 2 * sizeof(double);
-    }
-    const size_t sig_bytes = off - sig_begin;
-    off = al(off);
-    for (int64_t b = 0; b < nmat; ++b) {
-        Lay& l = lay[(size_t)b];
-        auto take = [&](size_t bytes) {
-            const size_t o = off;
-            off += al(bytes);
-            return o;
-        };
-        l.Ac = take(sizeof(double) * (size_t)l.L * l.k);
-        l.aux = take(bqr_aux_bytes(l.L, l.k, l.L, l.k));
-        l.stop = take(sizeof(double) * (size_t)std::max(1, (l.k + cyb::NBK - 1) / cyb::NBK * cyb::bqr_strip_slots(l.L)));
-        l.W = take(sizeof(double) * (size_t)l.kp * l.kp);
-        l.J = take(sizeof(double) * (size_t)l.kp * l.kp);
-        l.rank = take(sizeof(int32_t) * (size_t)l.kp);
-        l.inv = take(sizeof(int32_t) * (size_t)l.kp);
-        l.nnull = take(sizeof(int32_t));
-        l.Cq = take(sizeof(double) * (size_t)l.L * l.k);
-        l.Fc = take(sizeof(double) * (size_t)l.k * l.k);
-        l.aux2 = take(bqr_aux_bytes(l.k, l.k, l.k, l.k));
-        l.Cn = take(sizeof(double) * (size_t)l.k * l.k);
-        l.Wc = take(sizeof(double) * (size_t)l.kp * l.kp);
-        l.Jc = take(sizeof(double) * (size_t)l.kp * l.kp);
-        l.Wq = take(sizeof(double) * (size_t)l.kp * l.kp);
-        l.aux3 = take(bqr_aux_bytes(l.k, l.k, l.kp, l.k));
-        l.Cq2 = take(sizeof(double) * (size_t)l.k * l.k);
-        l.sig2 = take(sizeof(double) * (size_t)l.kp);
-        l.sigo = take(sizeof(double) * (size_t)l.kp);
-    }
-    // the row-index lists (k entries per matrix) contiguous: ONE device copy fills all of them
-    const size_t idx_begin = off;
-    for (int64_t b = 0; b < nmat; ++b) {
-        lay[(size_t)b].idx = off;
-        off += sizeof(int32_t) * (size_t)lay[(size_t)b].k;
-    }
-    off = al(off);
-    void* ws = nullptr;
-    CYB_TRY(ctx->workspace(off, &ws, 0));
-    char* base = static_cast<char*>(ws);
-    CYB_HIP(hipMemsetAsync(ws, 0, off, st));
-    auto dp = [&](size_t o) { return reinterpret_cast<double*>(base + o); };
+    const bool cplx;
+    const SvdSwitches& sw;
+    hipStream_t st;
 
-    // ---- 1./2. A -> column-major working copy, blocked Householder QR
-    std::vector<BqrMat> qm((size_t)nmat);
-    std::vector<XposeDesc> x_in, x_r;
-    std::vector<EyeDesc> eyeJ;
-    std::vector<JMat> jm((size_t)nmat);
-    for (int64_t b = 0; b < nmat; ++b) {
-        const Lay& l = lay[(size_t)b];
-        BqrMat& q = qm[(size_t)b];
-        q.Ac = dp(l.Ac);
-        q.ld = l.L;
-        q.m = l.L;
-        q.n = l.k;
-        q.k = l.k;
-        bqr_carve(q, base + l.aux, l.k);
-        q.v_zeroed = 1; // (the workspace is memset below)
-        q.reflect_always = cplx ? 1 : 0;
-        // a rank-deficient block (every block of a two-site theta = A.B) stops factoring once the trailing block is at the
-        // level the up-front deflation below discards anyway: ||A[j:, j:]||_F <= L eps ||A||_F (numpy.linalg.matrix_rank's
-        // threshold; the reference norm the kernels use is a lower bound of ||A||_F, so they stop no earlier than this)
-        q.ctl = dp(l.ctl);
-        q.parts = dp(l.stop);
-        q.stop_rel2 = ((double)l.L * 2.220446049250313e-16) * ((double)l.L * 2.220446049250313e-16);
-        if (l.tall) // Ac (col-major m x n) <- A (row-major):  out(r = col, c = row) = A[c*lda + r]
-            x_in.push_back(XposeDesc{sd[b].A, q.Ac, sd[b].lda, l.L, l.n, l.m, 0, 0, 0, 0});
-        else        // Ac (col-major n x m) = A^T : column c of Ac is row c of A
-            x_in.push_back(XposeDesc{sd[b].A, q.Ac, sd[b].lda, l.L, l.m, l.n, 0, 0, 1, 0});
-        // W (kp x kp) <- R (k x k upper triangle): out(r, c) = Ac[c*L + r]
-        x_r.push_back(XposeDesc{q.Ac, dp(l.W), l.L, l.kp, l.k, l.k, 1, l.k, 0, 0});
-        eyeJ.push_back(EyeDesc{dp(l.J), l.kp, l.kp, l.kp, 0, 0});
-        JMat& j = jm[(size_t)b];
-        j.W = dp(l.W);
-        j.J = dp(l.J);
-        j.nvp = l.kp;
-        j.lenp = l.kp;
-        j.nb = row_blocks(l.k, l.kp);
-        j.nv = l.k;
-        j.len = l.k;
-        j.rec_j = 0;
-        j.tol = 2.220446049250313e-16 * std::max(16.0, 4.0 * std::sqrt((double)l.k));
-        j.thr2 = 0.0; // set after the row norms of R are known
-    }
-    CYB_TRY(xpose_batched(ctx, x_in));
-    CYB_TRY(bqr_factor(ctx, qm));
-    CYB_TRY(xpose_batched(ctx, x_r));
-    CYB_TRY(eye_cols_batched(ctx, eyeJ));
-    // descriptors of the read-off kernels (also used for the row norms of the up-front deflation)
-    std::vector<PostDesc> post((size_t)nmat);
-    for (int64_t b = 0; b < nmat; ++b) {
-        const Lay& l = lay[(size_t)b];
-        PostDesc& q = post[(size_t)b];
-        q.W = dp(l.W);
-        q.J = dp(l.J);
-        q.nvp = l.kp;
-        q.lenp = l.kp;
-        q.nv = l.k;
-        q.len = l.k;
-        q.transposed = l.tall ? 0 : 1; // wide: the W side (X) gives the COLUMNS of U
-        q.mode = 0;
-        q.sig = dp(l.sig);
-        q.rank = reinterpret_cast<int32_t*>(base + l.rank);
-        q.inv = reinterpret_cast<int32_t*>(base + l.inv);
-        q.S = sd[b].S;
-        q.U = l.tall ? nullptr : sd[b].U;
-        q.ldu = sd[b].ldu;
-        q.Vh = l.tall ? sd[b].Vh : nullptr;
-        q.ldvh = sd[b].ldvh;
-        q.shift = nullptr;
-        q.scratch = nullptr;
-        q.n_null = reinterpret_cast<int32_t*>(base + l.nnull);
-        q.null_scale = 1.0;
-        q.cplx = cplx ? 1 : 0;
-    }
-    void* d_post = nullptr;
-    const PostDesc* dpost = nullptr;
-    std::vector<double> h_sig(sig_bytes / sizeof(double));
-    auto sig_of = [&](const Lay& l) { return h_sig.data() + (l.sig - sig_begin) / sizeof(double); };
-    // ---- 2b. up-front deflation: rows of R below the numerical-rank threshold never enter the
-    //          iteration (for a rank-deficient block these are the trailing rows of R)
-    CYB_TRY(ctx->upload(post.data(), sizeof(PostDesc) * post.size(), &d_post));
-    dpost = static_cast<const PostDesc*>(d_post);
-    hipLaunchKernelGGL(row_norm_kernel, dim3(helper_grid_x((size_t)nmat), (unsigned)nmat), dim3(256), 0, st, dpost);
-    CYB_HIP(hipGetLastError());
-    CYB_TRY(ctx->d2h(h_sig.data(), base + sig_begin, sig_bytes));
+    SvdLayout lay;
+    char* base = nullptr;
+    std::vector<BqrMat> qm;        // the first factorisations
+    std::vector<JMat> jm0;         // the iteration on the rows of R (thr2 set by deflate_up_front)
+    std::vector<PostDesc> post;    // descriptors of the read-off kernels (also used for the row norms of the up-front deflation)
+    std::vector<double> head;      // host copy of the header (SvdLayout::head_begin)
+    std::vector<Block> blk;
+    std::vector<int32_t> pos_all;  // svd_append_positions
+    std::vector<int64_t> pos_off;
+    // ---- the iteration that ran last
+    std::vector<Route> route;      // blk's routes, LQ masked off in the plain iteration after a redo
+    std::vector<JMat> jm;
+    std::vector<BqrMat> qm3;       // the LQ factorisations (their Q2 also completes the deflated rows in step 5)
+    std::vector<LqDesc> lqd;
+    std::vector<int> jrec_blocks;  // rotation recovery: blocks that iterate without accumulation
+    // the two applications after the sweeps share one call: Q1 on the J side (targets 0 .. nmat - 1, matrices qm) and
+    // Q2 on [J'^T 0; 0 I] of the LQ blocks (matrices qm3, behind qm in the joint list)
+    std::vector<BqrTarget> tg1, tg3;
+    std::vector<JcqDesc> jc;
+    std::vector<int32_t> sweeps;
+    int jst = CYB_OK;
+    // ---- the read-off
+    std::vector<int32_t> idx_all;  // good rows, then null rows, of every block
+    std::vector<Comp> comps;
+
+    SvdPipeline(cyb_ctx_t c, int64_t n, const cyb_svd_desc* d, int f)
+        : ctx(c), nmat(n), sd(d), flags(f), cplx((f & CYB_SVD_EMBEDDED_COMPLEX) != 0), sw(svd_switches()), st(c->stream)
     {
-        std::vector<int32_t> idx_all;
-        std::vector<size_t> idx_off((size_t)nmat, 0);
+    }
+    double* dp(size_t o) const { return reinterpret_cast<double*>(base + o); }
+    int32_t* ip(size_t o) const { return reinterpret_cast<int32_t*>(base + o); }
+    const double* sig_of(size_t b) const { return head.data() + lay.head_index(lay.blk[b].sig); }
+    static int rp_of(int r0) { return std::max(round_up(r0, 64), 64); }
+
+    int carve()
+    {
+        std::vector<int> m, n;
+        std::vector<SvdAux> aux;
         for (int64_t b = 0; b < nmat; ++b) {
-            Lay& l = lay[(size_t)b];
-            const double* sg = sig_of(l);
-            // (the factorisation is over: ctl[0] is 1 + the first panel step it skipped, or 0)
-            const double stopped = h_sig[(l.ctl - sig_begin) / sizeof(double)];
-            l.n_fac = stopped != 0.0 ? (int)stopped - 1 : -1;
-            // numerical-rank threshold (numpy.linalg.matrix_rank's): ||A||_F * max(m,n) * eps, squared;
-            // ||A||_F = ||R||_F comes from the row norms just read
-            double fro2 = 0.0;
-            for (int j = 0; j < l.k; ++j) fro2 += sg[j] * sg[j];
-            const double sc = (double)l.L * 2.220446049250313e-16;
-            const double thr2 = fro2 * sc * sc;
-            jm[(size_t)b].thr2 = thr2;
-            std::vector<int32_t> nul;
-            for (int j = 0; j < l.k; ++j) {
-                const double v = cplx ? std::max(sg[j & ~1], sg[std::min(j | 1, l.k - 1)]) : sg[j];
-                (v * v > thr2 ? l.good0 : nul).push_back(j);
-            }
-            l.r0 = (int)l.good0.size();
-            idx_off[(size_t)b] = idx_all.size();
-            idx_all.insert(idx_all.end(), l.good0.begin(), l.good0.end());
-            idx_all.insert(idx_all.end(), nul.begin(), nul.end());
+            m.push_back((int)sd[b].m);
+            n.push_back((int)sd[b].n);
+            const int64_t k = std::min(m.back(), n.back()), L = std::max(m.back(), n.back());
+            aux.push_back(SvdAux{bqr_aux_bytes(L, k, L, k), bqr_aux_bytes(k, k, k, k), bqr_aux_bytes(k, k, svd_kp((int)k), k),
+                                 (size_t)((k + cyb::NBK - 1) / cyb::NBK * cyb::bqr_strip_slots(L))});
         }
-        // ---- 2c. second preconditioning step (LQ): the surviving rows R_g (r0 x k) are factored once more,
-        //          R_g^T = Q2 R2, and the iteration runs on the rows of the r0 x r0 triangle R2 instead of the rows
-        //          of R_g.  R2 R2^T is much closer to diagonal than R_g R_g^T (Drmac & Veselic, SIAM J. Matrix Anal.
-        //          Appl. 29 (2008), sec. 3: the second QR is what makes one-sided Jacobi converge in a few sweeps):
-        //          a theta of a DMRG bond (graded spectrum over 14 decades) needs 8 sweeps instead of 15, and the rows
-        //          the rounds stream are r0 long instead of k.  With R2 = J'^T S Z^T (iteration: W' = S Z^T, rotations J')
-        //              R_g = Z S (Q2 [J'^T; 0])^T,
-        //          so the pair the read-off expects is  W_equiv = S (Q2 [J'^T; 0])^T  and  J_equiv = Z^T, and the
-        //          trailing k - r0 columns of Q2 are an orthonormal basis of the complement of R_g's row space: the
-        //          completion of the up-front deflated rows needs no QR of its own any more.
-        //          ROUND 3: not for every block.  A FULL-RANK, well-conditioned large block (row norms of R within 1e4 of each
-        //          other, k >= 128) converges in the same number of sweeps on R itself -- 9-11 against 9-10 -- so the second
-        //          factorisation (k / 32 panel steps of ~170 us) is never repaid now that a sweep is cheap: Gaussian 1024^2 26.6 ->
-        //          22.9 ms, four 512^2 11.3 -> 9.9 ms (scripts/lq_choice_probe.py).  Rank-deficient blocks keep it (the iteration
-        //          shrinks to r0 x r0 and the completion falls out of Q2), graded ones too (fewer sweeps and the better
-        //          accuracy of the small values), small ones too (a sweep costs a launch there).  CYB_SVD_LQ_ALWAYS=1: every block.
-        static const bool no_lq = getenv("CYB_SVD_NOLQ") != nullptr;
-        static const bool lq_always = getenv("CYB_SVD_LQ_ALWAYS") != nullptr;
-        static const int lq_skip_k = getenv("CYB_SVD_LQ_SKIP_K") ? atoi(getenv("CYB_SVD_LQ_SKIP_K")) : 128;
-        static const double lq_skip_ratio = getenv("CYB_SVD_LQ_SKIP_RATIO") ? atof(getenv("CYB_SVD_LQ_SKIP_RATIO")) : 1e4;
+        lay = svd_layout(m, n, aux);
+        void* ws = nullptr;
+        CYB_TRY(ctx->workspace(lay.total, &ws, 0));
+        base = static_cast<char*>(ws);
+        CYB_HIP(hipMemsetAsync(ws, 0, lay.total, st));
+        head.assign(lay.head_bytes / sizeof(double), 0.0);
+        blk.assign((size_t)nmat, Block{});
+        return CYB_OK;
+    }
+
+    // ---- 1./2. A -> column-major working copy, blocked Householder QR, R -> W, J = 1
+    int factor_r()
+    {
+        std::vector<XposeDesc> x_in, x_r;
+        std::vector<EyeDesc> eyeJ;
+        qm.resize((size_t)nmat);
         for (int64_t b = 0; b < nmat; ++b) {
-            Lay& l = lay[(size_t)b];
-            bool skip = false;
-            if (!lq_always && l.r0 == l.k && l.k >= lq_skip_k) {
-                const double* sg = sig_of(l);
-                double lo = 1e300, hi = 0.0;
-                for (int j = 0; j < l.k; ++j) {
-                    lo = std::min(lo, sg[j]);
-                    hi = std::max(hi, sg[j]);
-                }
-                skip = hi <= lq_skip_ratio * lo;
-            }
-            l.lq = !no_lq && l.r0 >= 2 && !skip;
+            const SvdBlockLay& l = lay.blk[(size_t)b];
+            BqrMat& q = qm[(size_t)b];
+            q.Ac = dp(l.Ac);
+            q.ld = l.L;
+            q.m = l.L;
+            q.n = l.k;
+            q.k = l.k;
+            bqr_carve(q, base + l.aux, l.k);
+            q.v_zeroed = 1; // (the workspace is memset in carve())
+            q.reflect_always = cplx ? 1 : 0;
+            // a rank-deficient block (every block of a two-site theta = A.B) stops factoring once the trailing block is at the
+            // level the up-front deflation below discards anyway: ||A[j:, j:]||_F <= L eps ||A||_F (numpy.linalg.matrix_rank's
+            // threshold; the reference norm the kernels use is a lower bound of ||A||_F, so they stop no earlier than this)
+            q.ctl = dp(l.ctl);
+            q.parts = dp(l.stop);
+            q.stop_rel2 = ((double)l.L * kEps) * ((double)l.L * kEps);
+            if (l.tall) // Ac (col-major m x n) <- A (row-major):  out(r = col, c = row) = A[c*lda + r]
+                x_in.push_back(XposeDesc{sd[b].A, q.Ac, sd[b].lda, l.L, l.n, l.m, 0, 0, 0, 0});
+            else        // Ac (col-major n x m) = A^T : column c of Ac is row c of A
+                x_in.push_back(XposeDesc{sd[b].A, q.Ac, sd[b].lda, l.L, l.m, l.n, 0, 0, 1, 0});
+            // W (kp x kp) <- R (k x k upper triangle): out(r, c) = Ac[c*L + r]
+            x_r.push_back(XposeDesc{q.Ac, dp(l.W), l.L, l.kp, l.k, l.k, 1, l.k, 0, 0});
+            eyeJ.push_back(EyeDesc{dp(l.J), l.kp, l.kp, l.kp, 0, 0});
+            jm0.push_back(make_jmat(dp(l.W), dp(l.J), l.k, l.k, l.kp, l.kp)); // (thr2: once the row norms of R are known)
         }
-        // ---- rotation recovery: which LQ blocks iterate WITHOUT accumulating J' (it is rebuilt from S Z^T and R2 after the
-        //      sweeps, see iterate()).  The rebuilt factor carries the relative error the iteration leaves in a row of S Z^T
-        //      (eps sqrt(32 rounds sweeps), 3e-14 at r0 = 1024) times up to the condition of R2, which the spread of the
-        //      surviving row norms of R -- already on the host -- follows within a factor 10.  tests/test_svd_jrecover_model.py:
-        //      the default ratio is the largest power of ten that keeps every admitted family 10x inside JREC_BOUND and
-        //      refuses the others with that factor 10 to spare; it admits the blocks of a theta = A.B (condition ~10) and
-        //      refuses a full-rank Gaussian block (4e3) and every graded spectrum.
-        //      Below CYB_SVD_JREC_MIN rows the accumulation costs nothing and the recovery three launches (chi = 1024 step, blocks of
-        //      r0 = 180 .. 212: 4.85 ms without, 5.0 - 5.5 with; neutral from 256).  Embedded complex
-        //      blocks are excluded: the recovery product does not keep the pair structure bit for bit.
-        static const bool no_jrec = getenv("CYB_SVD_NOJREC") != nullptr;
-        static const double jrec_ratio = getenv("CYB_SVD_JREC_RATIO") ? atof(getenv("CYB_SVD_JREC_RATIO")) : 1e1;
-        static const int jrec_min = getenv("CYB_SVD_JREC_MIN") ? atoi(getenv("CYB_SVD_JREC_MIN")) : 256;
+        CYB_TRY(xpose_batched(ctx, x_in));
+        CYB_TRY(bqr_factor(ctx, qm));
+        CYB_TRY(xpose_batched(ctx, x_r));
+        CYB_TRY(eye_cols_batched(ctx, eyeJ));
+        return CYB_OK;
+    }
+
+    void fill_post()
+    {
+        post.resize((size_t)nmat);
         for (int64_t b = 0; b < nmat; ++b) {
-            Lay& l = lay[(size_t)b];
-            if (!l.lq || no_jrec || cplx || l.r0 < jrec_min) continue;
-            const double* sg = sig_of(l);
-            double lo = 1e300, hi = 0.0;
-            for (int32_t j : l.good0) {
-                lo = std::min(lo, sg[j]);
-                hi = std::max(hi, sg[j]);
-            }
-            l.jrec = hi <= jrec_ratio * lo;
+            const SvdBlockLay& l = lay.blk[(size_t)b];
+            PostDesc& q = post[(size_t)b];
+            q.W = dp(l.W);
+            q.J = dp(l.J);
+            q.nvp = l.kp;
+            q.lenp = l.kp;
+            q.nv = l.k;
+            q.len = l.k;
+            q.transposed = l.tall ? 0 : 1; // wide: the W side (X) gives the COLUMNS of U
+            q.mode = 0;
+            q.sig = dp(l.sig);
+            q.rank = ip(l.rank);
+            q.inv = ip(l.inv);
+            q.S = sd[b].S;
+            q.U = l.tall ? nullptr : sd[b].U;
+            q.ldu = sd[b].ldu;
+            q.Vh = l.tall ? sd[b].Vh : nullptr;
+            q.ldvh = sd[b].ldvh;
+            q.shift = nullptr;
+            q.scratch = nullptr;
+            q.n_null = ip(l.nnull);
+            q.null_scale = 1.0;
+            q.cplx = cplx ? 1 : 0;
         }
+    }
+    // row norms of W -> sig -> the host copy of the header.  (The descriptors are uploaded by every caller: the slot of
+    // an earlier upload may have been recycled.)
+    int upload_post(const PostDesc*& dpost)
+    {
+        void* d_post = nullptr;
+        CYB_TRY(ctx->upload(post.data(), sizeof(PostDesc) * post.size(), &d_post));
+        dpost = static_cast<const PostDesc*>(d_post);
+        return CYB_OK;
+    }
+    int read_row_norms()
+    {
+        const PostDesc* dpost = nullptr;
+        CYB_TRY(upload_post(dpost));
+        hipLaunchKernelGGL(row_norm_kernel, dim3(helper_grid_x((size_t)nmat), (unsigned)nmat), dim3(256), 0, st, dpost);
+        CYB_HIP(hipGetLastError());
+        return ctx->d2h(head.data(), base + lay.head_begin, lay.head_bytes);
+    }
+    // the index lists of every block (k entries each, in block order) -> the workspace.  They must outlive many later
+    // uploads: staged through the ring, kept in the workspace
+    int write_index_lists()
+    {
         void* d_idx_v = nullptr;
         CYB_TRY(ctx->upload(idx_all.data(), sizeof(int32_t) * idx_all.size(), &d_idx_v));
-        // (k entries per matrix, in the order of the lists in the workspace)
-        CYB_HIP(hipMemcpyAsync(base + idx_begin, d_idx_v, sizeof(int32_t) * idx_all.size(), hipMemcpyDeviceToDevice, st));
+        CYB_HIP(hipMemcpyAsync(base + lay.idx_begin, d_idx_v, sizeof(int32_t) * idx_all.size(), hipMemcpyDeviceToDevice, st));
+        return CYB_OK;
     }
-    // compact row of every full-size row (-1: deflated up front), k entries per matrix: the J side is read off the compact
-    // rotations without a scatter into the full-size J (j_to_cq_kernel)
-    std::vector<int32_t> pos_all;
-    std::vector<int64_t> pos_off((size_t)nmat, 0);
-    for (int64_t b = 0; b < nmat; ++b) {
-        const Lay& l = lay[(size_t)b];
-        pos_off[(size_t)b] = (int64_t)pos_all.size();
-        pos_all.resize(pos_all.size() + (size_t)l.k, -1);
-        for (size_t g = 0; g < l.good0.size(); ++g) pos_all[(size_t)pos_off[(size_t)b] + (size_t)l.good0[g]] = (int32_t)g;
+
+    // ---- 2b. up-front deflation: rows of R below the numerical-rank threshold never enter the
+    //          iteration (for a rank-deficient block these are the trailing rows of R)
+    int deflate_up_front()
+    {
+        fill_post();
+        CYB_TRY(read_row_norms());
+        idx_all.clear();
+        for (int64_t b = 0; b < nmat; ++b) {
+            const SvdBlockLay& l = lay.blk[(size_t)b];
+            Block& bk = blk[(size_t)b];
+            // (the factorisation is over: ctl[0] is 1 + the first panel step it skipped, or 0)
+            const double stopped = head[lay.head_index(l.ctl)];
+            bk.n_fac = stopped != 0.0 ? (int)stopped - 1 : -1;
+            const double thr2 = svd_rank_thr2(sig_of((size_t)b), l.k, l.L);
+            jm0[(size_t)b].thr2 = thr2;
+            SvdSplit s = svd_split_rows(sig_of((size_t)b), l.k, thr2, cplx);
+            idx_all.insert(idx_all.end(), s.good.begin(), s.good.end());
+            idx_all.insert(idx_all.end(), s.nul.begin(), s.nul.end());
+            bk.good0 = std::move(s.good);
+            bk.r0 = (int)bk.good0.size();
+            pos_off.push_back(svd_append_positions(pos_all, l.k, bk.good0));
+        }
+        return CYB_OK;
     }
-    const std::vector<JMat> jm0 = jm;
-    std::vector<BqrMat> qm3; // the LQ factorisations (their Q2 also completes the deflated rows in step 5)
-    std::vector<int> qm3_of((size_t)nmat, -1);
-    std::vector<int32_t> sweeps;
-    auto iterate = [&](bool allow_lq, int& jst) -> int {
-        jm = jm0;
-        qm3.clear();
-        std::fill(qm3_of.begin(), qm3_of.end(), -1);
+
+    // ---- 2c. which blocks take the second preconditioning step (LQ), and which of those recover their rotations: the
+    //          rules and their reasons are wants_lq and wants_jrec (svd_plan.h)
+    int choose_routes()
+    {
+        for (int64_t b = 0; b < nmat; ++b) {
+            const SvdBlockLay& l = lay.blk[(size_t)b];
+            Block& bk = blk[(size_t)b];
+            const double* sg = sig_of((size_t)b);
+            SvdSpread all, kept;
+            for (int j = 0; j < l.k; ++j) all.add(sg[j]);
+            for (int32_t j : bk.good0) kept.add(sg[j]);
+            bk.lq = wants_lq(bk.r0, l.k, all.lo, all.hi, sw);
+            bk.jrec = wants_jrec(bk.lq, bk.r0, kept.lo, kept.hi, cplx, sw);
+        }
+        return write_index_lists();
+    }
+
+    // ---- descriptors of one iteration, and what runs before the sweeps: the surviving rows W -> Wc, the deflated rows of W
+    //      zeroed, Jc = 1, the LQ factorisation, R2 -> Wq
+    struct Staged {
         std::vector<RowMoveDesc> gat, zer;
         std::vector<EyeDesc> eyeJc;
         std::vector<XposeDesc> x_r2;
-        std::vector<LqDesc> lqd;
-        std::vector<int> jrec_blocks; // rotation recovery: blocks that iterate without accumulation
-        // the two applications after the sweeps share one call: Q1 on the J side (targets 0 .. nmat - 1, matrices qm) and
-        // Q2 on [J'^T 0; 0 I] of the LQ blocks (matrices qm3, behind qm in the joint list)
-        std::vector<BqrTarget> tg1, tg3;
-        std::vector<JcqDesc> jc;
+    };
+    // an LQ block: factor R_g^T = Q2 R2 in place, iterate on R2
+    void stage_lq(int64_t b, Staged& s)
+    {
+        const SvdBlockLay& l = lay.blk[(size_t)b];
+        const int r0 = blk[(size_t)b].r0, rp = rp_of(r0);
+        const bool jrec = route[(size_t)b].jrec;
+        JMat& j = jm[(size_t)b];
+        // Wc (r0 x kp row-major) read column-major with ld = kp IS R_g^T (k x r0): factored in place
+        BqrMat q;
+        q.Ac = dp(l.Wc);
+        q.ld = l.kp;
+        q.m = l.k;
+        q.n = r0;
+        q.k = r0;
+        bqr_carve(q, base + l.aux3, l.k);
+        q.v_zeroed = 1; // (first use of aux3 after the memset of the workspace: the iteration after a redo has no LQ block)
+        q.reflect_always = cplx ? 1 : 0;
+        // Wq (rp x rp row-major) <- R2 (upper triangle of the factored Wc)
+        s.x_r2.push_back(XposeDesc{dp(l.Wc), dp(l.Wq), l.kp, rp, r0, r0, 1, r0, 0, 0});
+        j.W = dp(l.Wq);
+        j.lenp = rp;
+        j.len = r0;
+        const double thr2 = j.thr2;
+        j.thr2 = 0.0; // no deflation inside the iteration: every row of S Z^T must keep its left vector
+        lqd.push_back(LqDesc{dp(l.Wq), dp(l.Jc), dp(l.Wc), dp(l.Cq2), dp(l.sig2), dp(l.bad), thr2, rp, l.kp, l.k, r0, cplx ? 1 : 0,
+                             jrec ? 1 : 0, dp(l.Fc), dp(l.Fc), dp(l.dev), dp(l.sigo), ip(l.idx)});
+        if (jrec) {
+            // no accumulation.  The sweeps turn R2 into S Z^T = J' R2, so afterwards (row-major, C = Cq2 read with ld k)
+            //     C[0:r0, 0:r0] = J' = (S^-2 S Z^T) R2^T :  C[i, c] = sum_{t >= c} Ws[i, t] R2[c, t],
+            // one product per block column with the k range cut at the diagonal (R2 is upper triangular).  The
+            // sweeps overwrite Wq and the application of Q2 overwrites Wc, so a copy of R2 goes to Cn and Ws to Fc
+            // (the completion scratch an LQ block never uses); the Gram matrix of the check then reuses Fc.
+            j.J = nullptr;
+            j.rec_j = 1;
+            s.x_r2.push_back(XposeDesc{dp(l.Wc), dp(l.Cn), l.kp, r0, r0, r0, 1, r0, 0, 0});
+            jrec_blocks.push_back((int)b);
+        }
+        tg3.push_back(BqrTarget{(int)(nmat + (int64_t)qm3.size()), dp(l.Cq2), l.k, l.k});
+        qm3.push_back(q);
+    }
+    int stage_iteration()
+    {
+        jm = jm0;
+        qm3.clear();
+        lqd.clear();
+        jrec_blocks.clear();
+        tg1.clear();
+        tg3.clear();
+        jc.clear();
+        Staged s;
         for (int64_t b = 0; b < nmat; ++b) {
-            Lay& l = lay[(size_t)b];
-            l.lq = l.lq && allow_lq;
-            tg1.push_back(BqrTarget{(int)b, dp(l.Cq), l.L, l.k, l.n_fac >= 0 ? l.n_fac : (l.k + cyb::NBK - 1) / cyb::NBK});
-            if (l.r0 == l.k && !l.lq) {
-                jc.push_back(JcqDesc{dp(l.J), nullptr, dp(l.Cq), l.L, l.kp, 0, l.k, l.r0});
+            const SvdBlockLay& l = lay.blk[(size_t)b];
+            const Block& bk = blk[(size_t)b];
+            const Route& r = route[(size_t)b];
+            tg1.push_back(BqrTarget{(int)b, dp(l.Cq), l.L, l.k, bk.n_fac >= 0 ? bk.n_fac : (l.k + cyb::NBK - 1) / cyb::NBK});
+            if (bk.r0 == l.k && !r.lq) { // the iteration on the full R
+                jc.push_back(JcqDesc{dp(l.J), nullptr, dp(l.Cq), l.L, l.kp, 0, l.k, bk.r0});
                 continue;
             }
-            jc.push_back(JcqDesc{dp(l.Jc), reinterpret_cast<const int32_t*>(base + l.idx), dp(l.Cq), l.L, std::max(round_up(l.r0, 64), 64),
-                                 pos_off[(size_t)b], l.k, l.r0});
-            const int32_t* didx = reinterpret_cast<const int32_t*>(base + l.idx);
-            const int rp = std::max(round_up(l.r0, 64), 64);
-            gat.push_back(RowMoveDesc{dp(l.W), dp(l.Wc), didx, l.kp, l.kp, l.r0, l.kp, 0, 0});
-            if (l.r0 < l.k) zer.push_back(RowMoveDesc{nullptr, dp(l.W), didx + l.r0, 0, l.kp, l.k - l.r0, l.kp, 2, 0});
-            const bool jrec = l.lq && l.jrec && allow_lq;
-            if (!jrec) eyeJc.push_back(EyeDesc{dp(l.Jc), rp, rp, rp, 0, 0});
+            const int rp = rp_of(bk.r0);
+            jc.push_back(JcqDesc{dp(l.Jc), ip(l.idx), dp(l.Cq), l.L, rp, pos_off[(size_t)b], l.k, bk.r0});
+            s.gat.push_back(RowMoveDesc{dp(l.W), dp(l.Wc), ip(l.idx), l.kp, l.kp, bk.r0, l.kp, 0, 0});
+            if (bk.r0 < l.k) s.zer.push_back(RowMoveDesc{nullptr, dp(l.W), ip(l.idx) + bk.r0, 0, l.kp, l.k - bk.r0, l.kp, 2, 0});
+            if (!r.jrec) s.eyeJc.push_back(EyeDesc{dp(l.Jc), rp, rp, rp, 0, 0});
             JMat& j = jm[(size_t)b];
             j.W = dp(l.Wc);
             j.J = dp(l.Jc);
             j.nvp = rp;
-            j.nb = row_blocks(l.r0, rp);
-            j.nv = l.r0;
-            if (l.lq) {
-                // Wc (r0 x kp row-major) read column-major with ld = kp IS R_g^T (k x r0): factored in place
-                BqrMat q;
-                q.Ac = dp(l.Wc);
-                q.ld = l.kp;
-                q.m = l.k;
-                q.n = l.r0;
-                q.k = l.r0;
-                bqr_carve(q, base + l.aux3, l.k);
-                q.v_zeroed = allow_lq ? 1 : 0; // (first use of aux3 after the memset of the workspace)
-                q.reflect_always = cplx ? 1 : 0;
-                // Wq (rp x rp row-major) <- R2 (upper triangle of the factored Wc)
-                x_r2.push_back(XposeDesc{dp(l.Wc), dp(l.Wq), l.kp, rp, l.r0, l.r0, 1, l.r0, 0, 0});
-                j.W = dp(l.Wq);
-                j.lenp = rp;
-                j.len = l.r0;
-                const double thr2 = j.thr2;
-                j.thr2 = 0.0; // no deflation inside the iteration: every row of S Z^T must keep its left vector
-                lqd.push_back(LqDesc{dp(l.Wq), dp(l.Jc), dp(l.Wc), dp(l.Cq2), dp(l.sig2), dp(l.bad), thr2, rp, l.kp, l.k, l.r0, cplx ? 1 : 0,
-                                     jrec ? 1 : 0, dp(l.Fc), dp(l.Fc), dp(l.dev), dp(l.sigo), didx});
-                if (jrec) {
-                    // no accumulation.  The sweeps turn R2 into S Z^T = J' R2, so afterwards (row-major, C = Cq2 read with ld k)
-                    //     C[0:r0, 0:r0] = J' = (S^-2 S Z^T) R2^T :  C[i, c] = sum_{t >= c} Ws[i, t] R2[c, t],
-                    // one product per block column with the k range cut at the diagonal (R2 is upper triangular).  The
-                    // sweeps overwrite Wq and the application of Q2 overwrites Wc, so a copy of R2 goes to Cn and Ws to Fc
-                    // (the completion scratch an LQ block never uses); the Gram matrix of the check then reuses Fc.
-                    j.J = nullptr;
-                    j.rec_j = 1;
-                    x_r2.push_back(XposeDesc{dp(l.Wc), dp(l.Cn), l.kp, l.r0, l.r0, l.r0, 1, l.r0, 0, 0});
-                    jrec_blocks.push_back((int)b);
-                }
-                tg3.push_back(BqrTarget{(int)(nmat + (int64_t)qm3.size()), dp(l.Cq2), l.k, l.k});
-                qm3_of[(size_t)b] = (int)qm3.size();
-                qm3.push_back(q);
-            }
+            j.nb = row_blocks(bk.r0, rp);
+            j.nv = bk.r0;
+            if (r.lq) stage_lq(b, s);
         }
-        CYB_TRY(launch_row_moves(ctx, gat));
-        CYB_TRY(launch_row_moves(ctx, zer));
-        CYB_TRY(eye_cols_batched(ctx, eyeJc));
+        CYB_TRY(launch_row_moves(ctx, s.gat));
+        CYB_TRY(launch_row_moves(ctx, s.zer));
+        CYB_TRY(eye_cols_batched(ctx, s.eyeJc));
         if (!qm3.empty()) {
             CYB_TRY(bqr_factor(ctx, qm3));
-            CYB_TRY(xpose_batched(ctx, x_r2));
+            CYB_TRY(xpose_batched(ctx, s.x_r2));
         }
         if (cplx) {
             std::vector<PairDesc> prs;
@@ -1236,235 +1217,262 @@ static int run_svd_qr(cyb_ctx_t ctx, int64_t nmat, const cyb_svd_desc* sd, int32
                 CYB_HIP(hipGetLastError());
             }
         }
-        // ---- 3. block Jacobi (plain mode: threshold deflation stays on for rows that fall below it later)
+        return CYB_OK;
+    }
+
+    // the recovery product J' = (S^-2 S Z^T) R2^T into Cq2 and the upper block triangle of its Gram matrix into Fc
+    int recover_rotations()
+    {
+        // block columns of 128, or of 64 when the 128-wide tiles of the list would leave compute units idle
+        int64_t tiles = 0;
+        for (int b : jrec_blocks) tiles += (int64_t)((blk[(size_t)b].r0 + 127) / 128) * ((blk[(size_t)b].r0 + 127) / 128);
+        const int nbc = tiles >= 2 * (int64_t)ctx->n_cu ? 128 : 64;
+        GemmBatch g_rec, g_chk;
+        for (int b : jrec_blocks) {
+            const SvdBlockLay& l = lay.blk[(size_t)b];
+            const int64_t r0 = blk[(size_t)b].r0, k = l.k;
+            for (int64_t c0 = 0; c0 < r0; c0 += nbc)
+                g_rec.add(dp(l.Cq2) + c0, r0, std::min<int64_t>(nbc, r0 - c0), k, dp(l.Fc) + c0, r0, 1, dp(l.Cn) + c0 * r0 + c0, 1, r0,
+                          r0 - c0, 1.0, 0.0);
+            for (int64_t i0 = 0; i0 < r0; i0 += JREC_NB)
+                g_chk.add(dp(l.Fc) + i0 * r0 + i0, std::min<int64_t>(JREC_NB, r0 - i0), r0 - i0, r0, dp(l.Cq2) + i0 * k, k, 1,
+                          dp(l.Cq2) + i0 * k, 1, k, r0, 1.0, 0.0);
+        }
+        CYB_TRY(g_rec.launch(ctx));
+        return g_chk.launch(ctx);
+    }
+    // after the sweeps of the LQ blocks: Cq2 = [J'^T 0; 0 I], the row norms of S Z^T and Z^T, the recovered rotations and
+    // their Gram check, the flag check of the rows at rounding level
+    int finish_lq()
+    {
+        if (qm3.empty()) return CYB_OK;
+        void* d = nullptr;
+        CYB_TRY(ctx->upload(lqd.data(), sizeof(LqDesc) * lqd.size(), &d));
+        const LqDesc* dl = static_cast<const LqDesc*>(d);
+        hipLaunchKernelGGL(lq_pack_kernel, dim3(64, (unsigned)lqd.size()), dim3(256), 0, st, dl);
+        hipLaunchKernelGGL(lq_rows_kernel, dim3(64, (unsigned)lqd.size()), dim3(256), 0, st, dl);
+        if (!jrec_blocks.empty()) {
+            CYB_TRY(recover_rotations());
+            CYB_TRY(ctx->upload(lqd.data(), sizeof(LqDesc) * lqd.size(), &d)); // (slot may have been recycled)
+            dl = static_cast<const LqDesc*>(d);
+            hipLaunchKernelGGL(jrec_check_kernel, dim3(16, (unsigned)lqd.size()), dim3(256), 0, st, dl);
+        }
+        // (its waves share the Gram rows of the flagged directions: a large graded block has hundreds -- 0.94 ms on 64 workgroups)
+        hipLaunchKernelGGL(lq_check_kernel, dim3(helper_grid_x(lqd.size()), (unsigned)lqd.size()), dim3(256), 0, st, dl);
+        CYB_HIP(hipGetLastError());
+        return CYB_OK;
+    }
+    // the J side, unsorted: column j of Cq is row j of J (Z^T of an LQ block, the accumulated rotations otherwise)
+    int j_side()
+    {
+        void *d = nullptr, *dpos = nullptr;
+        CYB_TRY(upload_packed(ctx, {{jc.data(), sizeof(JcqDesc) * jc.size(), &d}, {pos_all.data(), sizeof(int32_t) * pos_all.size(), &dpos}}));
+        hipLaunchKernelGGL(j_to_cq_kernel, dim3(helper_grid_x((size_t)nmat), (unsigned)nmat), dim3(256), 0, st, static_cast<const JcqDesc*>(d),
+                           static_cast<const int32_t*>(dpos));
+        CYB_HIP(hipGetLastError());
+        return CYB_OK;
+    }
+    // Q2's targets are ordered behind Q1's; every target takes the route a call of its own application would give it
+    int apply_q_pair()
+    {
+        std::vector<BqrMat> qall(qm);
+        qall.insert(qall.end(), qm3.begin(), qm3.end());
+        std::vector<BqrTarget> tg(tg1);
+        tg.insert(tg.end(), tg3.begin(), tg3.end());
+        return bqr_apply_q_pair(ctx, qall, tg, (size_t)nmat);
+    }
+    int lq_unpack()
+    {
+        if (qm3.empty()) return CYB_OK;
+        void* d = nullptr;
+        CYB_TRY(ctx->upload(lqd.data(), sizeof(LqDesc) * lqd.size(), &d));
+        hipLaunchKernelGGL(lq_unpack_kernel, dim3(64, (unsigned)lqd.size()), dim3(256), 0, st, static_cast<const LqDesc*>(d));
+        CYB_HIP(hipGetLastError());
+        return CYB_OK;
+    }
+    // ---- 3. one iteration on the chosen routes, or (allow_lq false) on a copy of them with the LQ step masked off
+    int iterate(bool allow_lq)
+    {
+        route.clear();
+        for (const Block& bk : blk) route.push_back(Route{bk.lq && allow_lq, bk.lq && bk.jrec && allow_lq});
+        CYB_TRY(stage_iteration());
+        // block Jacobi (plain mode: threshold deflation stays on for rows that fall below it later)
         jst = jacobi_orthogonalise(ctx, jm, 40, sweeps, cplx);
         if (jst != CYB_OK && jst != CYB_ERR_NOCONV) return jst;
-        if (!qm3.empty()) {
-            void* d = nullptr;
-            CYB_TRY(ctx->upload(lqd.data(), sizeof(LqDesc) * lqd.size(), &d));
-            const LqDesc* dl = static_cast<const LqDesc*>(d);
-            hipLaunchKernelGGL(lq_pack_kernel, dim3(64, (unsigned)lqd.size()), dim3(256), 0, st, dl);
-            hipLaunchKernelGGL(lq_rows_kernel, dim3(64, (unsigned)lqd.size()), dim3(256), 0, st, dl);
-            if (!jrec_blocks.empty()) {
-                // block columns of 128, or of 64 when the 128-wide tiles of the list would leave compute units idle
-                int64_t tiles = 0;
-                for (int b : jrec_blocks) tiles += (int64_t)((lay[(size_t)b].r0 + 127) / 128) * ((lay[(size_t)b].r0 + 127) / 128);
-                const int nbc = tiles >= 2 * (int64_t)ctx->n_cu ? 128 : 64;
-                GemmBatch g_rec, g_chk;
-                for (int b : jrec_blocks) {
-                    const Lay& l = lay[(size_t)b];
-                    const int64_t r0 = l.r0, k = l.k;
-                    for (int64_t c0 = 0; c0 < r0; c0 += nbc)
-                        g_rec.add(dp(l.Cq2) + c0, r0, std::min<int64_t>(nbc, r0 - c0), k, dp(l.Fc) + c0, r0, 1, dp(l.Cn) + c0 * r0 + c0, 1, r0,
-                                  r0 - c0, 1.0, 0.0);
-                    for (int64_t i0 = 0; i0 < r0; i0 += JREC_NB)
-                        g_chk.add(dp(l.Fc) + i0 * r0 + i0, std::min<int64_t>(JREC_NB, r0 - i0), r0 - i0, r0, dp(l.Cq2) + i0 * k, k, 1,
-                                  dp(l.Cq2) + i0 * k, 1, k, r0, 1.0, 0.0);
-                }
-                CYB_TRY(g_rec.launch(ctx));
-                CYB_TRY(g_chk.launch(ctx));
-                CYB_TRY(ctx->upload(lqd.data(), sizeof(LqDesc) * lqd.size(), &d)); // (slot may have been recycled)
-                dl = static_cast<const LqDesc*>(d);
-                hipLaunchKernelGGL(jrec_check_kernel, dim3(16, (unsigned)lqd.size()), dim3(256), 0, st, dl);
-            }
-            // (its waves share the Gram rows of the flagged directions: a large graded block has hundreds -- 0.94 ms on 64 workgroups)
-            hipLaunchKernelGGL(lq_check_kernel, dim3(helper_grid_x(lqd.size()), (unsigned)lqd.size()), dim3(256), 0, st, dl);
-            CYB_HIP(hipGetLastError());
-        }
-        {   // the J side, unsorted: column j of Cq is row j of J (Z^T of an LQ block, the accumulated rotations otherwise)
-            void *d = nullptr, *dpos = nullptr;
-            CYB_TRY(upload_packed(ctx, {{jc.data(), sizeof(JcqDesc) * jc.size(), &d}, {pos_all.data(), sizeof(int32_t) * pos_all.size(), &dpos}}));
-            hipLaunchKernelGGL(j_to_cq_kernel, dim3(helper_grid_x((size_t)nmat), (unsigned)nmat), dim3(256), 0, st, static_cast<const JcqDesc*>(d),
-                               static_cast<const int32_t*>(dpos));
-            CYB_HIP(hipGetLastError());
-        }
-        {
-            // Q2's targets are ordered behind Q1's; every target takes the route a call of its own application would give it
-            std::vector<BqrMat> qall(qm);
-            qall.insert(qall.end(), qm3.begin(), qm3.end());
-            tg1.insert(tg1.end(), tg3.begin(), tg3.end());
-            CYB_TRY(bqr_apply_q_pair(ctx, qall, tg1, (size_t)nmat));
-        }
-        if (!qm3.empty()) {
-            void* d = nullptr;
-            CYB_TRY(ctx->upload(lqd.data(), sizeof(LqDesc) * lqd.size(), &d));
-            hipLaunchKernelGGL(lq_unpack_kernel, dim3(64, (unsigned)lqd.size()), dim3(256), 0, st, static_cast<const LqDesc*>(d));
-            CYB_HIP(hipGetLastError());
-        }
-        return CYB_OK;
-    };
-    int jst = CYB_OK;
-    CYB_TRY(iterate(true, jst));
-    if (!qm3.empty()) {
-        // a row of S Z^T that is exactly zero has no left vector to read off, and rows of pure rounding noise can
-        // keep the iteration from settling: both are cases for the plain iteration (deflation on), from the rows of
-        // R that W still holds
-        std::vector<double> bad((size_t)nmat * 2, 0.0); // flags, then the deviations of the recovered rotations
-        CYB_TRY(ctx->d2h(bad.data(), base + lay[0].bad, sizeof(double) * (size_t)nmat * 2));
-        const std::vector<double> jdev(bad.begin() + nmat, bad.end());
-        bad.resize((size_t)nmat);
-        static const bool force_redo = getenv("CYB_SVD_LQ_FORCE_REDO") != nullptr; // (test hook: exercise the fallback)
-        static const bool force_jredo = getenv("CYB_SVD_JREC_FORCE_REDO") != nullptr; // (same, only where rotations were recovered)
-        bool redo = jst == CYB_ERR_NOCONV || force_redo;
-        for (double v : bad) redo = redo || v != 0.0;
-        for (const Lay& l : lay) redo = redo || (force_jredo && l.lq && l.jrec);
-        static const bool trace_redo = getenv("CYB_SVD_TRACE_REDO") != nullptr;
-        if (trace_redo)
-            for (int64_t b = 0; b < nmat; ++b) {
-                const Lay& l = lay[(size_t)b];
-                const char* route = !l.lq ? "no LQ step" : !l.jrec ? "excluded" : redo ? "recovered then redone" : "recovered";
-                fprintf(stderr, "[cyb] svd jrec: block %lld (%d x %d, r0 %d): %s (deviation %.2e, flagged %d)\n", (long long)b, l.m, l.n, l.r0,
-                        route, jdev[(size_t)b], (int)(bad[(size_t)b] != 0.0));
-            }
-        if (redo && trace_redo) {
-            int nb = 0;
-            for (double v : bad) nb += v != 0.0;
-            fprintf(stderr, "[cyb] svd: plain iteration after the LQ one (%d of %lld blocks flagged, noconv %d)\n", nb, (long long)nmat,
-                    (int)(jst == CYB_ERR_NOCONV));
-        }
-        if (redo) CYB_TRY(iterate(false, jst));
-    } else if (getenv("CYB_SVD_TRACE_REDO") != nullptr) {
-        for (int64_t b = 0; b < nmat; ++b)
-            fprintf(stderr, "[cyb] svd jrec: block %lld (%d x %d, r0 %d): no LQ step (deviation %.2e, flagged 0)\n", (long long)b,
-                    lay[(size_t)b].m, lay[(size_t)b].n, lay[(size_t)b].r0, 0.0);
+        CYB_TRY(finish_lq());
+        CYB_TRY(j_side());
+        CYB_TRY(apply_q_pair());
+        return lq_unpack();
     }
-    if (info)
-        for (int64_t b = 0; b < nmat; ++b) info[b] = sweeps[(size_t)b];
-    if (jst != CYB_OK && jst != CYB_ERR_NOCONV) return jst;
-    {   // compact results back into the full-size W (the J side went from the compact rotations into Cq, see iterate())
-        std::vector<RowMoveDesc> sw;
-        for (int64_t b = 0; b < nmat; ++b) {
-            const Lay& l = lay[(size_t)b];
-            if ((l.r0 == l.k && !l.lq) || l.r0 == 0) continue;
-            const int32_t* didx = reinterpret_cast<const int32_t*>(base + l.idx);
-            sw.push_back(RowMoveDesc{dp(l.Wc), dp(l.W), didx, l.kp, l.kp, l.r0, l.kp, 1, 0});
-        }
-        CYB_TRY(launch_row_moves(ctx, sw));
-    }
-    // ---- 4. singular values (row norms) -> host, to find the deflated rows
-    for (int64_t b = 0; b < nmat; ++b) post[(size_t)b].sig_lq = lay[(size_t)b].lq ? dp(lay[(size_t)b].sigo) : nullptr;
-    CYB_TRY(ctx->upload(post.data(), sizeof(PostDesc) * post.size(), &d_post));
-    dpost = static_cast<const PostDesc*>(d_post);
-    hipLaunchKernelGGL(row_norm_kernel, dim3(helper_grid_x((size_t)nmat), (unsigned)nmat), dim3(256), 0, st, dpost);
-    CYB_HIP(hipGetLastError());
-    CYB_TRY(ctx->d2h(h_sig.data(), base + sig_begin, sig_bytes));
-    // ---- 5. orthonormal completion of the deflated rows from a full Householder Q
+
+    // CYB_SVD_TRACE_REDO: one line per block with the route it took
+    void trace_routes(const double* bad, const double* jdev, bool redo) const
     {
-        std::vector<int32_t> idx_all;
-        struct Comp {
-            int64_t b;
-            size_t good_off, null_off;
-            int r, q;
-        };
-        std::vector<Comp> comps;
         for (int64_t b = 0; b < nmat; ++b) {
-            const Lay& l = lay[(size_t)b];
-            const double* sg = sig_of(l);
-            std::vector<int32_t> good, nul;
-            for (int j = 0; j < l.k; ++j) {
-                const double v = cplx ? std::max(sg[j & ~1], sg[std::min(j | 1, l.k - 1)]) : sg[j];
-                (v > 0.0 ? good : nul).push_back(j);
-            }
-            if (rank_out) rank_out[b] = (int32_t)good.size();
-            Comp c{b, idx_all.size(), 0, (int)good.size(), (int)nul.size()};
-            idx_all.insert(idx_all.end(), good.begin(), good.end()); // (every matrix: the lists are rewritten in one copy)
+            const SvdBlockLay& l = lay.blk[(size_t)b];
+            const Route& r = route[(size_t)b];
+            const char* name = !r.lq ? "no LQ step" : !r.jrec ? "excluded" : redo ? "recovered then redone" : "recovered";
+            fprintf(stderr, "[cyb] svd jrec: block %lld (%d x %d, r0 %d): %s (deviation %.2e, flagged %d)\n", (long long)b, l.m, l.n,
+                    blk[(size_t)b].r0, name, jdev[b], (int)(bad[b] != 0.0));
+        }
+        if (!redo) return;
+        int nb = 0;
+        for (int64_t b = 0; b < nmat; ++b) nb += bad[b] != 0.0;
+        fprintf(stderr, "[cyb] svd: plain iteration after the LQ one (%d of %lld blocks flagged, noconv %d)\n", nb, (long long)nmat,
+                (int)(jst == CYB_ERR_NOCONV));
+    }
+    // a row of S Z^T that is exactly zero has no left vector to read off, and rows of pure rounding noise can keep the
+    // iteration from settling: both are cases for the plain iteration (deflation on), from the rows of R that W still holds
+    int needs_redo(bool& redo)
+    {
+        std::vector<double> fl(2 * (size_t)nmat, 0.0); // flags, then the deviations of the recovered rotations
+        redo = false;
+        if (!qm3.empty()) {
+            CYB_TRY(ctx->d2h(fl.data(), base + lay.flags_begin(), lay.flags_bytes()));
+            redo = jst == CYB_ERR_NOCONV || sw.lq_force_redo;
+            for (int64_t b = 0; b < nmat; ++b) redo = redo || fl[(size_t)b] != 0.0 || (sw.jrec_force_redo && route[(size_t)b].jrec);
+        }
+        if (sw.trace_redo) trace_routes(fl.data(), fl.data() + nmat, redo);
+        return CYB_OK;
+    }
+
+    // compact results back into the full-size W (the J side went from the compact rotations into Cq, see j_side())
+    int restore_rows()
+    {
+        std::vector<RowMoveDesc> back;
+        for (int64_t b = 0; b < nmat; ++b) {
+            const SvdBlockLay& l = lay.blk[(size_t)b];
+            const int r0 = blk[(size_t)b].r0;
+            if ((r0 == l.k && !route[(size_t)b].lq) || r0 == 0) continue;
+            back.push_back(RowMoveDesc{dp(l.Wc), dp(l.W), ip(l.idx), l.kp, l.kp, r0, l.kp, 1, 0});
+        }
+        return launch_row_moves(ctx, back);
+    }
+
+    // ---- 4. singular values (row norms) -> host, to find the deflated rows
+    int read_values(int32_t* rank_out)
+    {
+        for (int64_t b = 0; b < nmat; ++b) post[(size_t)b].sig_lq = route[(size_t)b].lq ? dp(lay.blk[(size_t)b].sigo) : nullptr;
+        CYB_TRY(read_row_norms());
+        idx_all.clear();
+        comps.clear();
+        for (int64_t b = 0; b < nmat; ++b) {
+            const SvdSplit s = svd_split_rows(sig_of((size_t)b), lay.blk[(size_t)b].k, 0.0, cplx);
+            if (rank_out) rank_out[b] = (int32_t)s.good.size();
+            Comp c{b, idx_all.size(), 0, (int)s.good.size(), (int)s.nul.size()};
+            idx_all.insert(idx_all.end(), s.good.begin(), s.good.end()); // (every matrix: the lists are rewritten in one copy)
             c.null_off = idx_all.size();
-            idx_all.insert(idx_all.end(), nul.begin(), nul.end());
+            idx_all.insert(idx_all.end(), s.nul.begin(), s.nul.end());
             // CYB_SVD_SKIP_NULL_VECTORS: the caller will discard the singular vectors of the deflated (numerically zero)
             // singular values -- a truncated SVD keeps the chi_max largest -- so their orthonormal completion is not
             // computed; those rows of the W-side factor stay zero
-            if (nul.empty() || (flags & CYB_SVD_SKIP_NULL_VECTORS)) continue;
+            if (s.nul.empty() || (flags & CYB_SVD_SKIP_NULL_VECTORS)) continue;
             comps.push_back(c);
         }
-        if (!comps.empty()) {
-            // the index lists must outlive many later uploads: stage through the ring, keep in the workspace
-            void* d_idx_v = nullptr;
-            CYB_TRY(ctx->upload(idx_all.data(), sizeof(int32_t) * idx_all.size(), &d_idx_v));
-            CYB_HIP(hipMemcpyAsync(base + idx_begin, d_idx_v, sizeof(int32_t) * idx_all.size(), hipMemcpyDeviceToDevice, st));
-            std::vector<RowsDesc> gath, scat;
-            std::vector<int32_t> cols_all;                    // LQ mode: column of Cq2 for every null row ...
-            std::vector<std::pair<size_t, size_t>> lq_scat;   // ... (index into scat, offset into cols_all)
-            std::vector<BqrMat> qm2;
-            std::vector<BqrTarget> tg2;
-            std::vector<EyeDesc> eyes;
-            for (const Comp& c : comps) {
-                const Lay& l = lay[(size_t)c.b];
-                if (l.lq) {
-                    // every null row has its unit vector in Cq2 = Q2 [J'^T 0; 0 I] already (step 2c): a row deflated up
-                    // front takes one of the trailing columns (the complement of R_g's row space), a row the read-off
-                    // of the LQ iteration found numerically null (sigma_i^2 <= thr2) its own column i -- no QR
-                    const size_t c0 = cols_all.size();
-                    int t = 0;
-                    size_t g = 0;
-                    const int32_t* nulp = idx_all.data() + c.null_off;
-                    for (int qn = 0; qn < c.q; ++qn) {
-                        const int32_t j = nulp[qn];
-                        while (g < l.good0.size() && l.good0[g] < j) ++g;
-                        if (g < l.good0.size() && l.good0[g] == j) cols_all.push_back((int32_t)g);
-                        else cols_all.push_back((int32_t)(l.r0 + t++));
-                    }
-                    lq_scat.push_back({scat.size(), c0});
-                    scat.push_back(RowsDesc{dp(l.W), dp(l.sig), reinterpret_cast<const int32_t*>(base + l.idx) + c.r, dp(l.Cq2), l.kp,
-                                            l.k, c.q, 0, nullptr});
-                    continue;
-                }
-                if (c.r > 0) {
-                    gath.push_back(RowsDesc{dp(l.W), dp(l.sig), reinterpret_cast<const int32_t*>(base + l.idx), dp(l.Fc), l.kp, l.k, c.r, 0, nullptr});
-                    BqrMat q;
-                    q.Ac = dp(l.Fc);
-                    q.ld = l.k;
-                    q.m = l.k;
-                    q.n = c.r;
-                    q.k = std::min(l.k, c.r);
-                    bqr_carve(q, base + l.aux2, c.q);
-                    tg2.push_back(BqrTarget{(int)qm2.size(), dp(l.Cn), l.k, c.q});
-                    qm2.push_back(q);
-                }
-                // Cn (k x q) = columns r .. r+q-1 of the identity (r = 0: the completion is the identity itself)
-                eyes.push_back(EyeDesc{dp(l.Cn), l.k, l.k, c.q, c.r, 0});
-                scat.push_back(RowsDesc{dp(l.W), dp(l.sig), reinterpret_cast<const int32_t*>(base + l.idx) + c.r, dp(l.Cn), l.kp, l.k, c.q, 0, nullptr});
+        return CYB_OK;
+    }
+
+    // ---- 5. orthonormal completion of the deflated rows: from Q2 for an LQ block (svd_null_columns), from a full
+    //         Householder Q of the good rows otherwise
+    int complete_null()
+    {
+        if (comps.empty()) return CYB_OK;
+        CYB_TRY(write_index_lists());
+        std::vector<RowsDesc> gath, scat;
+        std::vector<int32_t> cols_all;                    // LQ blocks: column of Cq2 for every null row ...
+        std::vector<std::pair<size_t, size_t>> lq_scat;   // ... (index into scat, offset into cols_all)
+        std::vector<BqrMat> qm2;
+        std::vector<BqrTarget> tg2;
+        std::vector<EyeDesc> eyes;
+        for (const Comp& c : comps) {
+            const SvdBlockLay& l = lay.blk[(size_t)c.b];
+            if (route[(size_t)c.b].lq) { // no QR
+                const std::vector<int32_t> cols = svd_null_columns(blk[(size_t)c.b].good0, idx_all.data() + c.null_off, c.q);
+                lq_scat.push_back({scat.size(), cols_all.size()});
+                cols_all.insert(cols_all.end(), cols.begin(), cols.end());
+                scat.push_back(RowsDesc{dp(l.W), dp(l.sig), ip(l.idx) + c.r, dp(l.Cq2), l.kp, l.k, c.q, 0, nullptr});
+                continue;
             }
-            if (!gath.empty()) {
-                void* d = nullptr;
-                CYB_TRY(ctx->upload(gath.data(), sizeof(RowsDesc) * gath.size(), &d));
-                hipLaunchKernelGGL(gather_rows_kernel, dim3(64, (unsigned)gath.size()), dim3(256), 0, st,
-                                   static_cast<const RowsDesc*>(d));
-                CYB_HIP(hipGetLastError());
-                CYB_TRY(bqr_factor(ctx, qm2));
+            if (c.r > 0) {
+                gath.push_back(RowsDesc{dp(l.W), dp(l.sig), ip(l.idx), dp(l.Fc), l.kp, l.k, c.r, 0, nullptr});
+                BqrMat q;
+                q.Ac = dp(l.Fc);
+                q.ld = l.k;
+                q.m = l.k;
+                q.n = c.r;
+                q.k = std::min(l.k, c.r);
+                bqr_carve(q, base + l.aux2, c.q);
+                tg2.push_back(BqrTarget{(int)qm2.size(), dp(l.Cn), l.k, c.q});
+                qm2.push_back(q);
             }
-            CYB_TRY(eye_cols_batched(ctx, eyes));
-            if (!tg2.empty()) CYB_TRY(bqr_apply_q(ctx, qm2, tg2));
-            void* d = nullptr;
-            if (!cols_all.empty()) {
-                void* d_cols = nullptr;
-                CYB_TRY(ctx->upload(cols_all.data(), sizeof(int32_t) * cols_all.size(), &d_cols));
-                for (const auto& pr : lq_scat) scat[pr.first].col = static_cast<const int32_t*>(d_cols) + pr.second;
-            }
-            CYB_TRY(ctx->upload(scat.data(), sizeof(RowsDesc) * scat.size(), &d));
-            hipLaunchKernelGGL(scatter_rows_kernel, dim3(64, (unsigned)scat.size()), dim3(256), 0, st,
-                               static_cast<const RowsDesc*>(d));
-            CYB_HIP(hipGetLastError());
+            // Cn (k x q) = columns r .. r+q-1 of the identity (r = 0: the completion is the identity itself)
+            eyes.push_back(EyeDesc{dp(l.Cn), l.k, l.k, c.q, c.r, 0});
+            scat.push_back(RowsDesc{dp(l.W), dp(l.sig), ip(l.idx) + c.r, dp(l.Cn), l.kp, l.k, c.q, 0, nullptr});
         }
+        if (!gath.empty()) {
+            void* d = nullptr;
+            CYB_TRY(ctx->upload(gath.data(), sizeof(RowsDesc) * gath.size(), &d));
+            hipLaunchKernelGGL(gather_rows_kernel, dim3(64, (unsigned)gath.size()), dim3(256), 0, st, static_cast<const RowsDesc*>(d));
+            CYB_HIP(hipGetLastError());
+            CYB_TRY(bqr_factor(ctx, qm2));
+        }
+        CYB_TRY(eye_cols_batched(ctx, eyes));
+        if (!tg2.empty()) CYB_TRY(bqr_apply_q(ctx, qm2, tg2));
+        void* d = nullptr;
+        if (!cols_all.empty()) {
+            void* d_cols = nullptr;
+            CYB_TRY(ctx->upload(cols_all.data(), sizeof(int32_t) * cols_all.size(), &d_cols));
+            for (const auto& pr : lq_scat) scat[pr.first].col = static_cast<const int32_t*>(d_cols) + pr.second;
+        }
+        CYB_TRY(ctx->upload(scat.data(), sizeof(RowsDesc) * scat.size(), &d));
+        hipLaunchKernelGGL(scatter_rows_kernel, dim3(64, (unsigned)scat.size()), dim3(256), 0, st, static_cast<const RowsDesc*>(d));
+        CYB_HIP(hipGetLastError());
+        return CYB_OK;
     }
-    // ---- 6. sort, write the W side directly; the J side (Q1 applied in iterate(), columns in the order of the rows of J)
-    //         takes the descending order where it is written out: output column c is column inv[c] of Cq
-    CYB_TRY(ctx->upload(post.data(), sizeof(PostDesc) * post.size(), &d_post)); // (slot may have been recycled)
-    dpost = static_cast<const PostDesc*>(d_post);
-    hipLaunchKernelGGL(rank_kernel, dim3(8, (unsigned)nmat), dim3(256), 0, st, dpost);
-    hipLaunchKernelGGL(write_factors_kernel, dim3(helper_grid_x((size_t)nmat), (unsigned)nmat), dim3(256), 0, st, dpost);
-    CYB_HIP(hipGetLastError());
-    std::vector<XposeDesc> x_out;
-    for (int64_t b = 0; b < nmat; ++b) {
-        const Lay& l = lay[(size_t)b];
-        const int32_t* inv = reinterpret_cast<const int32_t*>(base + l.inv);
-        if (l.tall) // U (row-major m x k): out(r, c) = Cq[inv[c]*L + r]
-            x_out.push_back(XposeDesc{dp(l.Cq), sd[b].U, l.L, sd[b].ldu, l.m, l.k, 0, 0, 0, 0, inv});
-        else        // Vh (row-major k x n): row r = column inv[r] of Cq
-            x_out.push_back(XposeDesc{dp(l.Cq), sd[b].Vh, l.L, sd[b].ldvh, l.k, l.n, 0, 0, 1, 0, inv});
+
+    // ---- 6. sort, write the W side directly; the J side (Q1 applied in apply_q_pair(), columns in the order of the rows of
+    //         J) takes the descending order where it is written out: output column c is column inv[c] of Cq
+    int write_out()
+    {
+        const PostDesc* dpost = nullptr;
+        CYB_TRY(upload_post(dpost));
+        hipLaunchKernelGGL(rank_kernel, dim3(8, (unsigned)nmat), dim3(256), 0, st, dpost);
+        hipLaunchKernelGGL(write_factors_kernel, dim3(helper_grid_x((size_t)nmat), (unsigned)nmat), dim3(256), 0, st, dpost);
+        CYB_HIP(hipGetLastError());
+        std::vector<XposeDesc> x_out;
+        for (int64_t b = 0; b < nmat; ++b) {
+            const SvdBlockLay& l = lay.blk[(size_t)b];
+            if (l.tall) // U (row-major m x k): out(r, c) = Cq[inv[c]*L + r]
+                x_out.push_back(XposeDesc{dp(l.Cq), sd[b].U, l.L, sd[b].ldu, l.m, l.k, 0, 0, 0, 0, ip(l.inv)});
+            else        // Vh (row-major k x n): row r = column inv[r] of Cq
+                x_out.push_back(XposeDesc{dp(l.Cq), sd[b].Vh, l.L, sd[b].ldvh, l.k, l.n, 0, 0, 1, 0, ip(l.inv)});
+        }
+        return xpose_batched(ctx, x_out);
     }
-    CYB_TRY(xpose_batched(ctx, x_out));
-    if (info) CYB_HIP(hipStreamSynchronize(st));
-    return jst;
+};
+
+} // namespace
+
+static int run_svd_qr(cyb_ctx_t ctx, int64_t nmat, const cyb_svd_desc* sd, int32_t* info, int flags, int32_t* rank_out)
+{
+    if (nmat == 0) return CYB_OK;
+    SvdPipeline p(ctx, nmat, sd, flags);
+    CYB_TRY(p.carve());
+    CYB_TRY(p.factor_r());
+    CYB_TRY(p.deflate_up_front());
+    CYB_TRY(p.choose_routes());
+    CYB_TRY(p.iterate(true));
+    bool redo = false;
+    CYB_TRY(p.needs_redo(redo));
+    if (redo) CYB_TRY(p.iterate(false));
+    if (info)
+        for (int64_t b = 0; b < nmat; ++b) info[b] = p.sweeps[(size_t)b];
+    CYB_TRY(p.restore_rows());
+    CYB_TRY(p.read_values(rank_out));
+    CYB_TRY(p.complete_null());
+    CYB_TRY(p.write_out());
+    if (info) CYB_HIP(hipStreamSynchronize(ctx->stream));
+    return p.jst;
 }
 
 } // namespace cyb
@@ -1494,37 +1502,19 @@ static int svd_batched_impl(cyb_ctx_t ctx, const cyb_svd_desc* descs, int64_t n,
             idx.push_back(b);
         }
     }
-    // small blocks: direct Jacobi; larger ones: QR-preconditioned pipeline
-    static const bool no_qr = getenv("CYB_SVD_NOQR") != nullptr;
-    // tiny blocks (min <= 64, max <= 128): the whole iteration in LDS, one workgroup per block (svd_small.hip)
-    static const bool no_small = getenv("CYB_SVD_NOSMALL") != nullptr;
-    // ... when they are the whole list or many: a few tiny sectors next to large ones (the two or three smallest blocks
-    // of a chi=4096 theta) ride along in the rounds of the large blocks for free, whereas the fused kernel would sit in
-    // front of the pipeline on the same stream (0.66 ms of a 53 ms call)
-    size_t n_fit = 0;
-    for (const auto& d : nz) n_fit += cyb::svd_small_fits(d.m, d.n) ? 1 : 0;
-    const bool embedded = (flags & CYB_SVD_EMBEDDED_COMPLEX) != 0; // (complex blocks as real embeddings: one pipeline for every size)
-    const bool use_small = !embedded && !no_small && (n_fit == nz.size() || n_fit >= 16);
+    // tiny blocks: the in-LDS kernel; small ones: direct Jacobi; the others: QR-preconditioned pipeline (svd_split_list)
+    std::vector<cyb::SvdShape> shapes;
+    for (const auto& d : nz) shapes.push_back(cyb::SvdShape{d.m, d.n, cyb::svd_small_fits(d.m, d.n)});
+    const std::vector<cyb::SvdRoute> route =
+        cyb::svd_split_list(shapes, (flags & CYB_SVD_EMBEDDED_COMPLEX) != 0, cyb::svd_switches());
     std::vector<cyb_svd_desc> tiny, small, large;
     std::vector<int64_t> idx_t, idx_s, idx_l;
-    // blocks with min(m, n) >= 48 go through the QR-preconditioned pipeline; once there is one, the smaller blocks of the
-    // list join it (their panels and sweeps ride along in the same launches) instead of forming a second, serial
-    // iteration behind it -- a DMRG bond at chi = 256 has sectors from 4 x 4 to 140 x 140 in one call
-    static const bool no_merge = getenv("CYB_SVD_NOMERGE") != nullptr;
-    bool any_large = false;
-    for (const auto& d : nz) any_large = any_large || (!no_qr && std::min(d.m, d.n) >= 48 && !(use_small && cyb::svd_small_fits(d.m, d.n)));
-    // A block that does not fit the in-LDS kernel goes through the pipeline as well, whatever its size: the direct iteration
-    // (run_jacobi on the rows of A) has no deflation of numerically zero rows, and a rank-deficient 38 x 135 block with 105
-    // zero columns kept rotating rounding noise for 40 sweeps (scripts/tensor_fuzz.py, seed 11; the up-front deflation of
-    // the pipeline takes those rows out before the first sweep).  CYB_SVD_NOMERGE keeps the old split for the tests.
-    (void)any_large;
-    const int64_t large_min = embedded ? 1 : no_merge ? 48 : 2;
     for (size_t k = 0; k < nz.size(); ++k) {
-        if (use_small && cyb::svd_small_fits(nz[k].m, nz[k].n)) {
+        if (route[k] == cyb::SvdRoute::tiny) {
             CYB_REQUIRE(nz[k].S, "svd block %lld: S is NULL", (long long)idx[k]);
             tiny.push_back(nz[k]);
             idx_t.push_back(idx[k]);
-        } else if (!no_qr && std::min(nz[k].m, nz[k].n) >= large_min) {
+        } else if (route[k] == cyb::SvdRoute::pipeline) {
             large.push_back(nz[k]);
             idx_l.push_back(idx[k]);
         } else {
@@ -1567,9 +1557,8 @@ static int eigh_batched_impl(cyb_ctx_t ctx, const cyb_eigh_desc* descs, int64_t 
     }
     std::vector<int32_t> inf(nz.size());
     // lists made of small blocks only (n <= 64): the fused in-LDS kernel of svd_small.hip
-    static const bool no_small = getenv("CYB_SVD_NOSMALL") != nullptr;
     const bool embedded = (flags & CYB_EIGH_EMBEDDED_COMPLEX) != 0;
-    bool all_small = !no_small && !nz.empty() && !embedded;
+    bool all_small = !cyb::svd_switches().nosmall && !nz.empty() && !embedded;
     for (const auto& d : nz) all_small = all_small && d.n <= 64;
     const int st = all_small ? cyb::eigh_small_batched(ctx, nz.data(), (int64_t)nz.size(), inf.data())
                              : cyb::run_jacobi(ctx, 1, (int64_t)nz.size(), nullptr, nz.data(), info ? inf.data() : nullptr, embedded);
@@ -1578,15 +1567,43 @@ static int eigh_batched_impl(cyb_ctx_t ctx, const cyb_eigh_desc* descs, int64_t 
     return st;
 }
 
+} // extern "C"
+
 // ---- range-safe entry points (scaling.hip): blocks whose entries sit outside [1e-90, 1e90] are decomposed as
-//      s*A (s a power of two) and the scale is taken out of the singular values / eigenvalues afterwards
-static int svd_batched_ranged(cyb_ctx_t ctx, const cyb_svd_desc* descs, int64_t n, int32_t* info, int flags, int32_t* rank)
+//      s*A (s a power of two) and the scale is taken out of the singular values / eigenvalues afterwards.  One wrapper
+//      for both decompositions; what differs is in the traits
+struct SvdRanged {
+    typedef cyb_svd_desc Desc;
+    static const char* name() { return "svd"; }
+    static int64_t rows(const Desc& d) { return d.m; }
+    static int64_t cols(const Desc& d) { return d.n; }
+    static double* values(const Desc& d) { return d.S; } // what the scale is taken out of: min(m, n) singular values
+    static int run(cyb_ctx_t ctx, const Desc* descs, int64_t n, int32_t* info, int flags, int32_t* rank)
+    {
+        return svd_batched_impl(ctx, descs, n, info, flags, rank);
+    }
+};
+struct EighRanged {
+    typedef cyb_eigh_desc Desc;
+    static const char* name() { return "eigh"; }
+    static int64_t rows(const Desc& d) { return d.n; }
+    static int64_t cols(const Desc& d) { return d.n; }
+    static double* values(const Desc& d) { return d.W; } // n eigenvalues
+    static int run(cyb_ctx_t ctx, const Desc* descs, int64_t n, int32_t* info, int flags, int32_t*)
+    {
+        return eigh_batched_impl(ctx, descs, n, info, flags);
+    }
+};
+// rank: SVD only (null for eigh)
+template <class T>
+static int batched_ranged(cyb_ctx_t ctx, const typename T::Desc* descs, int64_t n, int32_t* info, int flags, int32_t* rank)
 {
+    typedef typename T::Desc Desc;
     std::vector<cyb::MatRef> refs;
     std::vector<int64_t> which;
     for (int64_t b = 0; b < n; ++b)
-        if (descs[b].m > 0 && descs[b].n > 0 && descs[b].A) {
-            refs.push_back(cyb::MatRef{descs[b].A, descs[b].lda, descs[b].m, descs[b].n});
+        if (T::rows(descs[b]) > 0 && T::cols(descs[b]) > 0 && descs[b].A) {
+            refs.push_back(cyb::MatRef{descs[b].A, descs[b].lda, T::rows(descs[b]), T::cols(descs[b])});
             which.push_back(b);
         }
     std::vector<double> amax;
@@ -1599,7 +1616,7 @@ static int svd_batched_ranged(cyb_ctx_t ctx, const cyb_svd_desc* descs, int64_t 
     for (size_t k = 0; k < refs.size(); ++k)
         if (amax[k] != amax[k]) bad.push_back(which[k]);
     if (!bad.empty()) {
-        std::vector<cyb_svd_desc> good;
+        std::vector<Desc> good;
         std::vector<int64_t> good_idx;
         for (int64_t b = 0, nb = 0; b < n; ++b) {
             if (nb < (int64_t)bad.size() && bad[(size_t)nb] == b) {
@@ -1610,8 +1627,8 @@ static int svd_batched_ranged(cyb_ctx_t ctx, const cyb_svd_desc* descs, int64_t 
             good_idx.push_back(b);
         }
         std::vector<int32_t> ginfo(good.size() + 1, 0), grank(good.size() + 1, 0);
-        const int st = good.empty() ? CYB_OK : svd_batched_ranged(ctx, good.data(), (int64_t)good.size(), info ? ginfo.data() : nullptr, flags,
-                                                                  rank ? grank.data() : nullptr);
+        const int st = good.empty() ? CYB_OK : batched_ranged<T>(ctx, good.data(), (int64_t)good.size(), info ? ginfo.data() : nullptr, flags,
+                                                                 rank ? grank.data() : nullptr);
         if (st != CYB_OK && st != CYB_ERR_NOCONV) return st;
         if (rank) CYB_HIP(hipStreamSynchronize(ctx->stream));
         for (size_t g = 0; g < good.size(); ++g) {
@@ -1622,28 +1639,29 @@ static int svd_batched_ranged(cyb_ctx_t ctx, const cyb_svd_desc* descs, int64_t 
             if (info) info[b] = -1;
             if (rank) rank[b] = 0;
         }
-        cyb::set_error("svd: %zu block(s) hold NaN or Inf entries (first: block %lld)", bad.size(), (long long)bad[0]);
+        cyb::set_error("%s: %zu block(s) hold NaN or Inf entries (first: block %lld)", T::name(), bad.size(), (long long)bad[0]);
         return CYB_ERR_NOCONV;
     }
-    std::vector<cyb_svd_desc> mod;
+    std::vector<Desc> mod;
     std::vector<void*> temps;
     std::vector<cyb::ScaleJob> pre, post;
     for (size_t k = 0; k < refs.size(); ++k) {
         const double sc = cyb::range_scale(amax[k]);
         if (sc == 1.0) continue;
         if (mod.empty()) mod.assign(descs, descs + n);
-        cyb_svd_desc& d = mod[(size_t)which[k]];
+        Desc& d = mod[(size_t)which[k]];
+        const int64_t rows = T::rows(d), cols = T::cols(d);
         void* t = nullptr;
-        CYB_HIP(hipMalloc(&t, sizeof(double) * (size_t)d.m * (size_t)d.n));
+        CYB_HIP(hipMalloc(&t, sizeof(double) * (size_t)rows * (size_t)cols));
         temps.push_back(t);
-        pre.push_back(cyb::ScaleJob{d.A, d.lda, static_cast<double*>(t), d.n, d.m, d.n, sc});
+        pre.push_back(cyb::ScaleJob{d.A, d.lda, static_cast<double*>(t), cols, rows, cols, sc});
         d.A = static_cast<const double*>(t);
-        d.lda = d.n;
-        post.push_back(cyb::ScaleJob{d.S, 1, d.S, 1, std::min(d.m, d.n), 1, 1.0 / sc});
+        d.lda = cols;
+        post.push_back(cyb::ScaleJob{T::values(d), 1, T::values(d), 1, std::min(rows, cols), 1, 1.0 / sc});
     }
-    if (mod.empty()) return svd_batched_impl(ctx, descs, n, info, flags, rank);
+    if (mod.empty()) return T::run(ctx, descs, n, info, flags, rank);
     int st = cyb::scale_copy_batched(ctx, pre);
-    if (st == CYB_OK) st = svd_batched_impl(ctx, mod.data(), n, info, flags, rank);
+    if (st == CYB_OK) st = T::run(ctx, mod.data(), n, info, flags, rank);
     if (st == CYB_OK || st == CYB_ERR_NOCONV) {
         const int st2 = cyb::scale_copy_batched(ctx, post);
         if (st2 != CYB_OK) st = st2;
@@ -1652,6 +1670,16 @@ static int svd_batched_ranged(cyb_ctx_t ctx, const cyb_svd_desc* descs, int64_t 
     for (void* t : temps) (void)hipFree(t);
     return st;
 }
+static int svd_batched_ranged(cyb_ctx_t ctx, const cyb_svd_desc* descs, int64_t n, int32_t* info, int flags, int32_t* rank)
+{
+    return batched_ranged<SvdRanged>(ctx, descs, n, info, flags, rank);
+}
+static int eigh_batched_ranged(cyb_ctx_t ctx, const cyb_eigh_desc* descs, int64_t n, int32_t* info, int flags)
+{
+    return batched_ranged<EighRanged>(ctx, descs, n, info, flags, nullptr);
+}
+
+extern "C" {
 
 int cyb_svd_batched_f64(cyb_ctx_t ctx, const cyb_svd_desc* descs, int64_t n, int32_t* info)
 {
@@ -1672,70 +1700,6 @@ int cyb_svd_batched_ex_f64(cyb_ctx_t ctx, const cyb_svd_desc* descs, int64_t n, 
     //  of two, the rank threshold is relative)
     const int st = svd_batched_ranged(ctx, descs, n, info, flags, rank);
     if (rank && !info) CYB_HIP(hipStreamSynchronize(ctx->stream)); // (the ranks are host data read during the call)
-    return st;
-}
-
-static int eigh_batched_ranged(cyb_ctx_t ctx, const cyb_eigh_desc* descs, int64_t n, int32_t* info, int flags)
-{
-    std::vector<cyb::MatRef> refs;
-    std::vector<int64_t> which;
-    for (int64_t b = 0; b < n; ++b)
-        if (descs[b].n > 0 && descs[b].A) {
-            refs.push_back(cyb::MatRef{descs[b].A, descs[b].lda, descs[b].n, descs[b].n});
-            which.push_back(b);
-        }
-    std::vector<double> amax;
-    CYB_TRY(cyb::matrix_amax(ctx, refs, amax));
-    // (blocks with NaN or Inf entries: as in svd_batched_ranged)
-    std::vector<int64_t> bad;
-    for (size_t k = 0; k < refs.size(); ++k)
-        if (amax[k] != amax[k]) bad.push_back(which[k]);
-    if (!bad.empty()) {
-        std::vector<cyb_eigh_desc> good;
-        std::vector<int64_t> good_idx;
-        for (int64_t b = 0, nb = 0; b < n; ++b) {
-            if (nb < (int64_t)bad.size() && bad[(size_t)nb] == b) {
-                ++nb;
-                continue;
-            }
-            good.push_back(descs[b]);
-            good_idx.push_back(b);
-        }
-        std::vector<int32_t> ginfo(good.size() + 1, 0);
-        const int st = good.empty() ? CYB_OK : eigh_batched_ranged(ctx, good.data(), (int64_t)good.size(), info ? ginfo.data() : nullptr, flags);
-        if (st != CYB_OK && st != CYB_ERR_NOCONV) return st;
-        for (size_t g = 0; g < good.size(); ++g)
-            if (info) info[good_idx[g]] = ginfo[g];
-        for (int64_t b : bad)
-            if (info) info[b] = -1;
-        cyb::set_error("eigh: %zu block(s) hold NaN or Inf entries (first: block %lld)", bad.size(), (long long)bad[0]);
-        return CYB_ERR_NOCONV;
-    }
-    std::vector<cyb_eigh_desc> mod;
-    std::vector<void*> temps;
-    std::vector<cyb::ScaleJob> pre, post;
-    for (size_t k = 0; k < refs.size(); ++k) {
-        const double sc = cyb::range_scale(amax[k]);
-        if (sc == 1.0) continue;
-        if (mod.empty()) mod.assign(descs, descs + n);
-        cyb_eigh_desc& d = mod[(size_t)which[k]];
-        void* t = nullptr;
-        CYB_HIP(hipMalloc(&t, sizeof(double) * (size_t)d.n * (size_t)d.n));
-        temps.push_back(t);
-        pre.push_back(cyb::ScaleJob{d.A, d.lda, static_cast<double*>(t), d.n, d.n, d.n, sc});
-        d.A = static_cast<const double*>(t);
-        d.lda = d.n;
-        post.push_back(cyb::ScaleJob{d.W, 1, d.W, 1, d.n, 1, 1.0 / sc});
-    }
-    if (mod.empty()) return eigh_batched_impl(ctx, descs, n, info, flags);
-    int st = cyb::scale_copy_batched(ctx, pre);
-    if (st == CYB_OK) st = eigh_batched_impl(ctx, mod.data(), n, info, flags);
-    if (st == CYB_OK || st == CYB_ERR_NOCONV) {
-        const int st2 = cyb::scale_copy_batched(ctx, post);
-        if (st2 != CYB_OK) st = st2;
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    for (void* t : temps) (void)hipFree(t);
     return st;
 }
 

@@ -6,7 +6,7 @@ accumulated, the sweeps leave ``W_f = J' R2 = S Z^T`` and the factor the read-of
     J' = S^-2 W_f R2^T        (= (R2 Z S^-1)^T : one triangular x dense product and a row scaling).
 
 This file restates that in numpy, together with the rule that decides BEFORE the sweeps which blocks take the route
-(``jrec_admits``: the constants of ``svd_jacobi.hip``), and pins where the default of ``CYB_SVD_JREC_RATIO`` comes
+(``jrec_admits``: ``wants_jrec`` and the constants of ``svd_plan.h``), and pins where the default of ``CYB_SVD_JREC_RATIO`` comes
 from: the largest power of ten for which every block the rule admits is recovered at least 10x inside the bound the
 device checks (``JREC_BOUND``), and for which the 12- and 14-decade blocks are refused.
 
@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 
 EPS = 2.220446049250313e-16
-# ---- the constants of svd_jacobi.hip (kept in step by test_constants_match_the_source)
+# ---- the constants of svd_plan.h (kept in step by test_constants_match_the_source)
 JREC_BOUND = 2e-11   # device: max |J' J'^T - 1| above this -> the list is redone with accumulation
 JREC_RATIO = 1e1     # CYB_SVD_JREC_RATIO default
 JREC_MIN = 256       # CYB_SVD_JREC_MIN default
@@ -165,7 +165,8 @@ def test_default_ratio_is_the_largest_power_of_ten_that_holds(table):
 def test_constants_match_the_source():
     import os
     import re
-    src = open(os.path.join(os.path.dirname(__file__), '..', 'cyten_amd', 'csrc', 'svd_jacobi.hip')).read()
+    # (the bound and the defaults of SvdSwitches: the member initialisers)
+    src = open(os.path.join(os.path.dirname(__file__), '..', 'cyten_amd', 'csrc', 'svd_plan.h')).read()
     assert float(re.search(r'JREC_BOUND\s*=\s*([0-9.e+-]+)', src).group(1)) == JREC_BOUND
-    assert float(re.search(r'"CYB_SVD_JREC_RATIO"\)\)\s*:\s*([0-9.e+-]+)', src).group(1)) == JREC_RATIO
-    assert int(re.search(r'"CYB_SVD_JREC_MIN"\)\)\s*:\s*([0-9]+)', src).group(1)) == JREC_MIN
+    assert float(re.search(r'double\s+jrec_ratio\s*=\s*([0-9.e+-]+)', src).group(1)) == JREC_RATIO
+    assert int(re.search(r'int\s+jrec_min\s*=\s*([0-9]+)', src).group(1)) == JREC_MIN
