@@ -353,6 +353,10 @@ PROTOTYPES = {
     'cyb_multi_dot_weighted_c128': [_ctx, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp],
     'cyb_gram_schmidt_weighted_f64': [_ctx, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, _vp, _vp],
     'cyb_gram_schmidt_weighted_c128': [_ctx, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, _vp, _vp],
+    'cyb_orthonormalize_f64': [_ctx, _vp, C.c_int64, C.c_int64, C.c_double, _vp],
+    'cyb_orthonormalize_c128': [_ctx, _vp, C.c_int64, C.c_int64, C.c_double, _vp],
+    'cyb_orthonormalize_weighted_f64': [_ctx, _vp, C.c_int64, C.c_int64, C.c_double, _vp, _vp],
+    'cyb_orthonormalize_weighted_c128': [_ctx, _vp, C.c_int64, C.c_int64, C.c_double, _vp, _vp],
     'cyb_fill_f64': [_ctx, _vp, C.c_int64, C.c_double],
     'cyb_eye_f64': [_ctx, _vp, C.c_int64],
     'cyb_random_normal_f64': [_ctx, _vp, C.c_int64, C.c_uint64, C.c_double],

@@ -464,9 +464,101 @@ static int multi_axpy(const char* fn, cyb_ctx_t ctx, const double* const* basis,
     return CYB_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Orthonormalising a LIST of vectors (gram_schmidt(vecs, rcond), sparse.cpp:420-436) without a host wait between its steps:
+// step k is the CGS2 sequence above of vecs[k] against vecs[0..k-1], then the kernel below, which reads the norm that
+// sequence left on the device and either scales the vector by 1 / norm or WRITES zeros over it.  A dropped vector is then
+// all +0.0 bytes whatever it held (NaN, Inf): as a basis vector of the later steps its coefficient is a sum of zeros and its
+// share of every update is a zero, so the list runs on without the host knowing which vectors were dropped.
+//
+// The vector is a range of `words` doubles (a complex vector: 2n of them, both parts take the same factor), cut into items by
+// the cutter of flat_items.h; one pass, 2 words moved per element.  An item starts at an even word (chunks are multiples of
+// 1024), so after at most one leading word -- an f64 vector that is only 8-byte aligned -- every access is 16 bytes wide.
+__global__ void __launch_bounds__(NT) normalize_or_zero_kernel(const Item* __restrict__ items, double* __restrict__ x_,
+                                                                const double* __restrict__ norm_dev, double rcond,
+                                                                double* __restrict__ norm_out, double* __restrict__ flag_out)
+{
+    const Item it = items[blockIdx.x];
+    const double norm = norm_dev[0];
+    const bool keep = norm > rcond; // false for a NaN norm
+    const double f = 1.0 / norm;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        norm_out[0] = norm;
+        flag_out[0] = keep ? 1.0 : 0.0;
+    }
+    gp x = (gp)x_ + it.start;
+    const int64_t head = min(it.count, (int64_t)(((uintptr_t)x >> 3) & 1));
+    const int64_t nv = (it.count - head) / 2;
+    if (threadIdx.x == 0 && head) x[0] = keep ? x[0] * f : 0.0;
+    GLOBAL_AS d2* xv = (GLOBAL_AS d2*)(x + head);
+    if (keep) {
+        for (int64_t i = threadIdx.x; i < nv; i += NT) {
+            const d2 a = xv[i];
+            xv[i] = d2{a.x * f, a.y * f};
+        }
+    } else {
+        for (int64_t i = threadIdx.x; i < nv; i += NT) xv[i] = d2{0.0, 0.0};
+    }
+    const int64_t tail = head + 2 * nv;
+    if (threadIdx.x == 0 && tail < it.count) x[tail] = keep ? x[tail] * f : 0.0;
+}
+
+template <bool CPLX>
+static int orthonormalize(const char* fn, cyb_ctx_t ctx, double* const* vecs, int64_t m, int64_t n, double rcond, double* out_dev,
+                          bool weighted = false, const double* wt = nullptr)
+{
+    CYB_REQUIRE(ctx, "%s: NULL argument", fn);
+    BasisPtrs P;
+    CYB_TRY(gs_args(fn, vecs, m, (m > 0 && vecs) ? vecs[0] : nullptr, m > 0 ? n : 0, CPLX, &P));
+    CYB_TRY(gs_weights(fn, weighted, wt, n));
+    if (m == 0 || n == 0) return CYB_OK;
+    CYB_REQUIRE(out_dev && (uintptr_t)out_dev % 8 == 0, "%s: NULL or misaligned out_dev", fn);
+    // Workspace slot 0 for the longest step at once (a slot that grows waits for the stream): the steps then find it large
+    // enough.  Behind the part gram_schmidt uses, the coefficients and the norm of the current step.
+    const GsGrid g = gs_grid(n, CPLX);
+    const size_t np_max = (size_t)g.groups * (size_t)m * 2, gs_doubles = np_max + 4 * GS_MAX_M;
+    void* ws = nullptr;
+    CYB_TRY(ctx->workspace(sizeof(double) * (gs_doubles + 2 * GS_MAX_M + 1), &ws));
+    double* step_out = static_cast<double*>(ws) + gs_doubles;
+    const int64_t words = (CPLX ? 2 : 1) * n;
+    std::vector<Item> items;
+    CYB_CUT(fn, items, std::vector<int64_t>{words}, chunk_real(words));
+    // ONE upload of the items for the whole list: every step cuts its vector the same way
+    return with_arrays(ctx, fn, items.size(), arrays(items), [&](dim3 grid, const Item* d_items) -> int {
+        for (int64_t k = 0; k < m; ++k) {
+            CYB_TRY(gram_schmidt<CPLX>(fn, ctx, vecs, k, vecs[k], n, 2, step_out, weighted, wt));
+            hipLaunchKernelGGL(normalize_or_zero_kernel, grid, dim3(NT), 0, ctx->stream, d_items, vecs[k],
+                               step_out + (CPLX ? 2 : 1) * k, rcond, out_dev + k, out_dev + m + k);
+        }
+        return CYB_OK;
+    });
+}
+
 } // namespace
 
 extern "C" {
+
+int cyb_orthonormalize_f64(cyb_ctx_t ctx, double* const* vecs, int64_t m, int64_t n, double rcond, double* out_dev)
+{
+    return orthonormalize<false>("cyb_orthonormalize_f64", ctx, vecs, m, n, rcond, out_dev);
+}
+
+int cyb_orthonormalize_c128(cyb_ctx_t ctx, double* const* vecs, int64_t m, int64_t n, double rcond, double* out_dev)
+{
+    return orthonormalize<true>("cyb_orthonormalize_c128", ctx, vecs, m, n, rcond, out_dev);
+}
+
+int cyb_orthonormalize_weighted_f64(cyb_ctx_t ctx, double* const* vecs, int64_t m, int64_t n, double rcond, const double* weights_dev,
+                                    double* out_dev)
+{
+    return orthonormalize<false>("cyb_orthonormalize_weighted_f64", ctx, vecs, m, n, rcond, out_dev, true, weights_dev);
+}
+
+int cyb_orthonormalize_weighted_c128(cyb_ctx_t ctx, double* const* vecs, int64_t m, int64_t n, double rcond, const double* weights_dev,
+                                     double* out_dev)
+{
+    return orthonormalize<true>("cyb_orthonormalize_weighted_c128", ctx, vecs, m, n, rcond, out_dev, true, weights_dev);
+}
 
 int cyb_gram_schmidt_f64(cyb_ctx_t ctx, const double* const* basis, int64_t m, double* w, int64_t n, int32_t passes, double* out_dev)
 {

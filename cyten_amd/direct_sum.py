@@ -1,0 +1,148 @@
+"""Direct sums of tensors as ONE Krylov vector (include/cyten/tensors/direct_sum.h, src/tensors/direct_sum.cpp): the second
+``VectorLike`` of the reference beside ``Tensor``.
+
+:class:`DirectSum` is a plain container of tensors on unrelated legs -- abelian tensors and fusion-tree tensors, mixed freely.
+The module functions are what ``vector_norm`` / ``vector_inner`` / ``scaled`` / ``axpy`` / ``compatible_with`` are in the
+reference (direct_sum.cpp:113-174): componentwise calls of :mod:`cyten_amd.abelian` and :mod:`cyten_amd.fusion_tree`, so they
+need nothing of the backend beyond what those call and run on a numpy stand-in.  Only the conjugating inner product exists.
+The pool form of a direct sum, on which the solvers run on the device, is ``krylov._FlatDirectSumOps``.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import abelian as ab
+from . import fusion_tree as ft
+
+
+class DirectSum:
+    """``DirectSum(components)``: a non-empty sequence of ``AbelianTensor`` / ``TreeTensor`` (direct_sum.cpp:29-54: no None,
+    no nested direct sum)."""
+
+    def __init__(self, components):
+        comps = tuple(components)
+        if not comps:
+            raise ValueError('DirectSum: needs at least one component')
+        for i, c in enumerate(comps):
+            if c is None:
+                raise ValueError(f'DirectSum: component {i} is None')
+            if isinstance(c, DirectSum):
+                raise ValueError(f'DirectSum: component {i} is a DirectSum (nested direct sums are not supported)')
+            if not isinstance(c, (ab.AbelianTensor, ft.TreeTensor)):
+                raise ValueError(f'DirectSum: component {i} is a {type(c).__name__}, not a tensor')
+        self.components = comps
+
+    def __len__(self) -> int:
+        return len(self.components)
+
+    def __getitem__(self, i):
+        n = len(self.components)
+        if not isinstance(i, (int, np.integer)) or not -n <= i < n:
+            raise IndexError(f'DirectSum index {i} out of range for {n} components')
+        return self.components[int(i)]
+
+    def __iter__(self):
+        return iter(self.components)
+
+    @property
+    def blocks(self) -> list:
+        """the blocks of all components in order (what the solvers look at to choose the dtype of a run)"""
+        return [b for c in self.components for b in c.blocks]
+
+    def is_complex(self) -> bool:
+        return any(_is_complex_block(b) for b in self.blocks)
+
+
+def _is_complex_block(b) -> bool:
+    return np.iscomplexobj(b) if isinstance(b, np.ndarray) else bool(b.is_complex)
+
+
+def _is_tree(t) -> bool:
+    return isinstance(t, ft.TreeTensor)
+
+
+# -- one component ----------------------------------------------------------------------------------------------------------
+
+def _same_legs(a, b) -> bool:
+    return len(a.legs) == len(b.legs) and all(
+        x.sign == y.sign and np.array_equal(x.sectors, y.sectors) and np.array_equal(x.mults, y.mults)
+        for x, y in zip(a.legs, b.legs))
+
+
+def _compatible1(a, b) -> bool:
+    if _is_tree(a) or _is_tree(b):
+        return _is_tree(a) and _is_tree(b) and ft.same_space(a.codomain, b.codomain) and ft.same_space(a.domain, b.domain)
+    return isinstance(a, ab.AbelianTensor) and isinstance(b, ab.AbelianTensor) and _same_legs(a, b)
+
+
+def _norm1(bb, t):
+    return ft.norm(bb, t.data, t.codomain) if _is_tree(t) else ab.norm(bb, t)
+
+
+def _inner1(bb, a, b):
+    return ft.inner(bb, a.data, b.data, a.codomain, do_dagger=True) if _is_tree(a) else ab.inner(bb, a, b)
+
+
+def _scale1(bb, a, t):
+    return t.like(ft.mul(bb, a, t.data)) if _is_tree(t) else ab.scale(bb, a, t)
+
+
+def _lincomb1(bb, a, x, b, y):
+    return x.like(ft.linear_combination(bb, a, x.data, b, y.data)) if _is_tree(x) else ab.linear_combination(bb, a, x, b, y)
+
+
+def _almost_equal1(bb, x, y, rtol, atol) -> bool:
+    if _is_tree(x):
+        return ft.almost_equal(bb, x.data, y.data, rtol, atol)
+    # abelian tensors have no blockwise comparison in this code base: the same criterion on the norms
+    return _norm1(bb, _lincomb1(bb, 1.0, x, -1.0, y)) <= atol + rtol * _norm1(bb, y)
+
+
+# -- the vector algebra -------------------------------------------------------------------------------------------------------
+
+def _pair(op, x, y):
+    """both operands as direct sums of one length (as_direct_sum, direct_sum.cpp:97-111)"""
+    for v in (x, y):
+        if not isinstance(v, DirectSum):
+            raise ValueError(f'DirectSum.{op}: expected a DirectSum, got {type(v).__name__}')
+    if len(x) != len(y):
+        raise ValueError(f'DirectSum.{op}: size mismatch ({len(x)} and {len(y)} components)')
+    return zip(x.components, y.components)
+
+
+def compatible(x, y) -> bool:
+    """same length and componentwise compatible; False between a tensor and a direct sum, whichever comes first"""
+    if not isinstance(x, DirectSum) or not isinstance(y, DirectSum):
+        return False
+    return len(x) == len(y) and all(_compatible1(a, b) for a, b in zip(x.components, y.components))
+
+
+def norm(bb, x: DirectSum) -> float:
+    """sqrt(sum_i |x_i|^2)"""
+    return float(np.sqrt(sum(float(_norm1(bb, c)) ** 2 for c in x.components)))
+
+
+def inner(bb, x: DirectSum, y: DirectSum):
+    """sum_i <x_i, y_i>, conjugating x; tree components carry their quantum dimensions"""
+    s = 0.0
+    for a, b in _pair('inner', x, y):
+        s = s + _inner1(bb, a, b)
+    return s
+
+
+def scale(bb, a, x: DirectSum) -> DirectSum:
+    return DirectSum([_scale1(bb, a, c) for c in x.components])
+
+
+def linear_combination(bb, a, x: DirectSum, b, y: DirectSum) -> DirectSum:
+    """a x + b y"""
+    return DirectSum([_lincomb1(bb, a, u, b, v) for u, v in _pair('linear_combination', x, y)])
+
+
+def axpy(bb, a, x: DirectSum, y: DirectSum) -> DirectSum:
+    """a x + y"""
+    return DirectSum([_lincomb1(bb, a, u, 1.0, v) for u, v in _pair('axpy', x, y)])
+
+
+def almost_equal(bb, x: DirectSum, y: DirectSum, rtol: float = 1e-5, atol: float = 1e-8) -> bool:
+    return all(_almost_equal1(bb, u, v, rtol, atol) for u, v in _pair('almost_equal', x, y))

@@ -17,6 +17,8 @@
 * Every solver takes fusion-tree vectors (:class:`cyten_amd.fusion_tree.TreeTensor`) as well: the recurrences are the same
   code, the vector operations are :class:`_TreeTensorOps` (tensors) or :class:`_FlatTreeOps` (pools whose reductions carry the
   quantum dimension of the coupled sector); :class:`TreeChainOperator` is an operator to apply to them.
+* ... and direct sums of both (:class:`cyten_amd.direct_sum.DirectSum`): :class:`_DirectSumOps` on tensors,
+  :class:`_FlatDirectSumOps` on pools that hold the components' pools one after the other.
 
 Leg orders used here (signs: + ket-like, - dual):
     theta [vL, p0, p1, vR]
@@ -29,6 +31,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import abelian as ab
+from . import direct_sum as ds
 from . import fusion_tree as ft
 
 
@@ -495,6 +498,32 @@ class _FlatOps:
             self._lib.check(bb.lib.cyb_multi_axpy_f64(bb.ctx.handle, self._ptrs(basis), len(basis), hp, float(np.real(alpha)),
                                                       C.c_void_p(w.data_ptr()), self.total))
 
+    def orthonormalize(self, pools, rcond):
+        """The list `pools` (at most MAX_BASIS, of the dtype of this run) orthonormalised in place by ONE library call
+        (krylov_vec.hip: cyb_orthonormalize_*): CGS2 of each against the earlier ones, then scaled by 1 / norm if the norm is
+        > rcond, else overwritten with zeros -- no host wait between the steps.  ONE download at the end: (norms, kept)."""
+        bb, C, m = self.bb, self._C, len(pools)
+        if any(p.is_complex() != self.cplx for p in pools):
+            raise _NeedComplex()
+        if m == 0 or self.total == 0:
+            return np.zeros(0), np.zeros(0, dtype=bool)
+        out = bb.ctx.empty(2 * m)
+        bb.ctx.sync_stream()
+        sfx = 'c128' if self.cplx else 'f64'
+        if self._weights_ptr() is None:
+            rc = getattr(bb.lib, 'cyb_orthonormalize_' + sfx)(bb.ctx.handle, self._ptrs(pools), m, self.total, float(rcond),
+                                                              C.c_void_p(out.data_ptr()))
+        else:
+            rc = getattr(bb.lib, 'cyb_orthonormalize_weighted_' + sfx)(bb.ctx.handle, self._ptrs(pools), m, self.total, float(rcond),
+                                                                       self._weights_ptr(), C.c_void_p(out.data_ptr()))
+        self._lib.check(rc)
+        r = bb.ctx.d2h(out, 2 * m, np.float64)
+        return r[:m].copy(), r[m:] != 0.0
+
+    def _weights_ptr(self):
+        """the granule table of the weighted entries (None: the unweighted entries run)"""
+        return None
+
     def project_out(self, basis, w, passes=2):
         """(w - V h, h, |w - V h|) with h = V^H w: ONE fused classical Gram-Schmidt call (passes=2: CGS2, h summed over the
         passes) that updates w in place, and ONE device-to-host copy of the m coefficients and the norm.  A basis of mixed
@@ -643,6 +672,9 @@ class _FlatTreeOps(_FlatOps):
     def _wptr(self):
         return self._C.c_void_p(self._wdev.data_ptr())
 
+    def _weights_ptr(self):
+        return self._wptr()
+
     def _gs(self, basis, w, passes, out, off=0):
         bb = self.bb
         fn = bb.lib.cyb_gram_schmidt_weighted_c128 if w.is_complex() else bb.lib.cyb_gram_schmidt_weighted_f64
@@ -675,13 +707,146 @@ class _FlatTreeOps(_FlatOps):
         return float(np.sqrt(max(np.real(self.inner(w, w)), 0.0)))
 
 
+class _DirectSumOps(_TensorOps):
+    """:class:`_TensorOps` on direct sums (:class:`direct_sum.DirectSum`): every operation is the componentwise one of
+    :mod:`cyten_amd.direct_sum` -- per-component launches; runs on a numpy stand-in."""
+
+    def norm(self, w):
+        return ds.norm(self.bb, w)
+
+    def inner(self, v, w):
+        return ds.inner(self.bb, v, w)
+
+    def scale(self, a, w):
+        return ds.scale(self.bb, a, w)
+
+    def lincomb(self, a, w, b, v):
+        return ds.linear_combination(self.bb, a, w, b, v)
+
+
+class _PoolPart:
+    """the blocks of one component of a direct-sum pool: positions first .. first + n - 1 of the pool's block list"""
+
+    def __init__(self, first, block_inds):
+        self.first, self.block_inds, self.n = first, block_inds, len(block_inds)
+        self.key = block_inds.tobytes()
+        self.index = None
+
+    def positions(self, block_inds):
+        """pool positions of the blocks of a tensor of this component (_NotFlat: a block the pool does not have)"""
+        if block_inds.tobytes() == self.key:
+            return list(range(self.first, self.first + self.n))
+        if self.index is None:
+            self.index = {tuple(r): self.first + i for i, r in enumerate(self.block_inds.tolist())}
+        try:
+            return [self.index[tuple(r)] for r in block_inds.tolist()]
+        except KeyError:
+            raise _NotFlat()
+
+
+class _FlatDirectSumOps(_FlatTreeOps):
+    """The pool of a direct sum: the pools of its components -- each with the layout it has alone, abelian
+    segments over every charge-allowed block at multiples of 32 elements, tree segments as :func:`tree_pool_layout` -- one
+    after the other in ONE allocation, so that every recurrence, the fused CGS2 step and the projected matvec are the single
+    launches they are for one tensor.  Without a tree component the unweighted entries run over the whole range; with one,
+    every segment starts at a multiple of 256 elements and the weighted entries run with weight 1.0 on the granules of the
+    abelian segments.  Gaps are zero.  With ONE component the pool is byte for byte that of :class:`_FlatOps` /
+    :class:`_FlatTreeOps`.  ``enter`` is one memset and ONE batched copy over the blocks of all components, ``leave`` a
+    direct sum of views; the support is tracked per block, hence per component."""
+
+    def __init__(self, bb, H, template, cplx=False):
+        from .block_backend import _c_strides
+        self._bind(bb, H, template, cplx)
+        self.weighted = any(_is_tree(c) for c in template.components)
+        align = self.GRANULE if self.weighted else 32
+        self.parts, self.shapes, self.offs, weights, tot = [], [], [], [], 0
+        for c in template.components:
+            if _is_tree(c):
+                inds, shapes, offs, n, w = tree_pool_layout(c.codomain, c.domain, self.GRANULE)
+            else:
+                inds = ab.AbelianTensor.allowed_block_inds(c.symmetry, c.legs)
+                shapes = [c.block_shape(r) for r in inds]
+                offs, n = [], 0
+                for sh in shapes:
+                    k = 1
+                    for x in sh:
+                        k *= x
+                    offs.append(n)
+                    n += (k + 31) // 32 * 32
+                n = (n + align - 1) // align * align
+                w = [1.0] * (n // self.GRANULE) if self.weighted else []
+            self.parts.append(_PoolPart(len(self.offs), inds))
+            self.offs += [tot + o for o in offs]
+            self.shapes += list(shapes)
+            weights += list(w)
+            tot += n
+        self.total = tot
+        self.strides = [_c_strides(sh) for sh in self.shapes]
+        self.support = set()
+        self.weights = np.array(weights, dtype=np.float64)
+        if self.weighted:
+            self._wdev = bb.ctx.empty(max(len(self.weights), 1))
+            if len(self.weights):
+                bb.ctx.h2d(self._wdev, self.weights)
+
+    @staticmethod
+    def usable(bb, t) -> bool:
+        return _FlatOps.usable(bb, t)
+
+    def enter(self, x):
+        """direct sum -> pool: one memset + ONE batched copy over the blocks of all components"""
+        if not isinstance(x, ds.DirectSum) or len(x) != len(self.parts):
+            raise _NotFlat()
+        blocks = x.blocks
+        if not self.cplx and any(b.is_complex for b in blocks):
+            raise _NeedComplex()
+        buf = self._alloc(True)
+        pos = [p for part, c in zip(self.parts, x.components) for p in part.positions(c.block_inds)]
+        views = self._views(buf, pos)
+        if any(v.shape != tuple(b.shape) for v, b in zip(views, blocks)):
+            raise _NotFlat()
+        self.support.update(pos)
+        if views:
+            self.bb.copy_many([(v if b.is_complex or not self.cplx else self.bb._plane(v, 0), b) for v, b in zip(views, blocks)])
+        return buf
+
+    def leave(self, buf):
+        comps = []
+        for part, t in zip(self.parts, self.t.components):
+            idx = [p for p in range(part.first, part.first + part.n) if p in self.support]
+            rows = part.block_inds[[p - part.first for p in idx]]
+            views = self._views(buf, idx)
+            if _is_tree(t):
+                comps.append(t.like(ft.FusionTreeData(rows.copy(), views)))
+            else:
+                comps.append(ab.AbelianTensor(t.symmetry, t.legs, views, rows, t.num_codomain, t.labels))
+        return ds.DirectSum(comps)
+
+    def _weights_ptr(self):
+        return self._wptr() if self.weighted else None
+
+    def _gs(self, basis, w, passes, out, off=0):
+        return (_FlatTreeOps if self.weighted else _FlatOps)._gs(self, basis, w, passes, out, off)
+
+    def _multi(self, kind, basis, w, h, off=0, alpha=1.0):
+        return (_FlatTreeOps if self.weighted else _FlatOps)._multi(self, kind, basis, w, h, off, alpha)
+
+    def inner(self, v, w):
+        return (_FlatTreeOps if self.weighted else _FlatOps).inner(self, v, w)
+
+    def norm(self, w):
+        return (_FlatTreeOps if self.weighted else _FlatOps).norm(self, w)
+
+
 def _is_tree(t) -> bool:
     return isinstance(t, ft.TreeTensor)
 
 
 def _vector_ops(bb, H, template, mode):
     """The vector operations of a run on vectors like `template`: pools (`mode` False / True: float64 / complex128) or
-    tensors (`mode` None), abelian or fusion-tree by the type of the template."""
+    tensors (`mode` None); abelian, fusion-tree or direct-sum by the type of the template."""
+    if isinstance(template, ds.DirectSum):
+        return _FlatDirectSumOps(bb, H, template, mode) if mode is not None else _DirectSumOps(bb, H)
     if _is_tree(template):
         return _FlatTreeOps(bb, H, template, mode) if mode is not None else _TreeTensorOps(bb, H)
     if mode is None:
@@ -691,6 +856,8 @@ def _vector_ops(bb, H, template, mode):
 
 
 def _flat_usable(bb, t) -> bool:
+    if isinstance(t, ds.DirectSum):
+        return _FlatDirectSumOps.usable(bb, t)
     return _FlatTreeOps.usable(bb, t) if _is_tree(t) else _FlatOps.usable(bb, t)
 
 
@@ -1076,7 +1243,7 @@ class ArnoldiEvolution(Arnoldi):
         self._result_norm = 1.0
         self.delta = None
         # (Arnoldi._build_krylov does not record it)
-        self._psi0_norm = ft.norm(bb, psi0.data, psi0.codomain) if _is_tree(psi0) else ab.norm(bb, psi0)
+        self._psi0_norm = _vector_ops(bb, H, psi0, None).norm(psi0)
 
     def run(self, delta, normalize=None):
         if self.N_cache < self.N_max:
@@ -1120,6 +1287,14 @@ class ArnoldiEvolution(Arnoldi):
         return V.scale(1.0 / V.norm(psif), psif)
 
 
+def compatible(a, b) -> bool:
+    """two vectors a solver can combine: direct sums of one length with compatible components, fusion-tree tensors on the
+    same spaces, abelian tensors on the same legs -- never a tensor and a direct sum"""
+    if isinstance(a, ds.DirectSum) or isinstance(b, ds.DirectSum):
+        return ds.compatible(a, b)
+    return _same_legs(a, b)
+
+
 def _same_legs(a, b) -> bool:
     if _is_tree(a) or _is_tree(b):
         return (_is_tree(a) and _is_tree(b) and ft.same_space(a.codomain, b.codomain) and ft.same_space(a.domain, b.domain))
@@ -1153,7 +1328,7 @@ class GMRES:
             raise ValueError('A must not be null')
         if x is None or b is None:
             raise ValueError('x and b must not be null')
-        if not _same_legs(x, b):
+        if not compatible(x, b):
             raise ValueError('x and b must have the same legs')
         self.bb, self.A, self.x_in, self.b_in = bb, A, x, b
         self.options = o

@@ -8,8 +8,12 @@
   is removed from the current vector in turn.  For orthonormal ortho vectors that is the projector above; for others it is
   what the reference computes (its docstring, py_sparse.cpp:322-324, promises a Gram-Schmidt the code does not do).
 
+* :class:`TensorLinearOperator` -- a two-leg abelian tensor acting on one-leg tensors (sparse.cpp:68-140).
+* :class:`DirectSumLinearOperator` -- the block-diagonal operator on a ``direct_sum.DirectSum`` (sparse.cpp:346-418).
+* :func:`gram_schmidt` -- a list of vectors orthonormalised, the dependent ones dropped (sparse.cpp:420-436).
+
 Every wrapper acts on block-sparse tensors -- abelian ones or fusion-tree ones (``fusion_tree.TreeTensor``, whose inner product
-carries the quantum dimensions) -- through ``.matvec(tensor)`` with the block backend of the wrapped operator (or the
+carries the quantum dimensions) -- and on direct sums of them (``direct_sum.DirectSum``) through ``.matvec(tensor)`` with the block backend of the wrapped operator (or the
 ``bb`` given), exposes ``is_complex`` as the solvers expect and has ``adjoint()`` where the wrapped operators have one.  On
 flat Krylov pools the solvers do not call these ``matvec``s: ``krylov._FlatOps`` recognises the wrappers and does their
 vector work on the pools.
@@ -19,6 +23,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import abelian as ab
+from . import direct_sum as ds
 from . import fusion_tree as ft
 
 
@@ -32,19 +37,25 @@ def _is_complex_tensor(t) -> bool:
 
 def _inner(bb, a, b):
     """<a|b> of two vectors of the kind the solvers take: abelian tensors, or fusion-tree tensors (weighted by the quantum
-    dimensions of the codomain)"""
+    dimensions of the codomain), or direct sums of them"""
+    if isinstance(a, ds.DirectSum) or isinstance(b, ds.DirectSum):
+        return ds.inner(bb, a, b)
     if isinstance(a, ft.TreeTensor):
         return ft.inner(bb, a.data, b.data, a.codomain, do_dagger=True)
     return ab.inner(bb, a, b)
 
 
 def _lincomb(bb, a, v, b, w):
+    if isinstance(v, ds.DirectSum) or isinstance(w, ds.DirectSum):
+        return ds.linear_combination(bb, a, v, b, w)
     if isinstance(v, ft.TreeTensor):
         return v.like(ft.linear_combination(bb, a, v.data, b, w.data))
     return ab.linear_combination(bb, a, v, b, w)
 
 
 def _compatible(a, b) -> bool:
+    if isinstance(a, ds.DirectSum) or isinstance(b, ds.DirectSum):
+        return ds.compatible(a, b)
     if isinstance(a, ft.TreeTensor) or isinstance(b, ft.TreeTensor):
         return (isinstance(a, ft.TreeTensor) and isinstance(b, ft.TreeTensor) and ft.same_space(a.codomain, b.codomain)
                 and ft.same_space(a.domain, b.domain))
@@ -170,3 +181,122 @@ class ProjectedLinearOperator(LinearOperatorWrapper):
     def adjoint(self):
         p = None if self.penalty is None else self.penalty.conjugate()
         return ProjectedLinearOperator(self.original_operator.adjoint(), self.ortho_vecs, self.project_operator, p, self.bb)
+
+
+class TensorLinearOperator:
+    """A two-leg abelian tensor as an operator on one-leg tensors (sparse.cpp:68-140): ``matvec(v)`` contracts leg
+    `which_leg` of the tensor with the leg of `v`.  The fusion-tree counterpart is a one-step ``krylov.TreeChainOperator``."""
+
+    def __init__(self, bb, tensor, which_leg: int = -1):
+        if tensor is None:
+            raise ValueError('tensor must not be null')
+        if tensor.nlegs != 2:
+            raise ValueError('Expected a two-leg tensor')
+        if not isinstance(which_leg, (int, np.integer)) or not -2 <= which_leg < 2:
+            raise ValueError('which_leg must refer to a single leg')
+        self.bb, self.tensor = bb, tensor
+        self.which_leg = int(which_leg) % 2
+        self.other_leg = 1 - self.which_leg
+        if not tensor.legs[self.which_leg].can_contract_with(tensor.legs[self.other_leg]):
+            raise ValueError('Expected contractible legs')
+        self.vector_legs = [tensor.legs[self.other_leg]]
+
+    @property
+    def is_complex(self) -> bool:
+        return _is_complex_tensor(self.tensor)
+
+    def matvec(self, vec):
+        if not isinstance(vec, ab.AbelianTensor):
+            raise ValueError('TensorLinearOperator.matvec expects a Tensor input')
+        if vec.nlegs != 1:
+            raise ValueError('TensorLinearOperator.matvec expects a single-leg tensor')
+        res = ab.tdot(self.bb, self.tensor, vec, [self.which_leg], [0])
+        res.num_codomain = vec.num_codomain
+        return res
+
+    def to_tensor(self):
+        if self.which_leg == 1:
+            return self.tensor
+        return ab.permute_legs(self.bb, self.tensor, [self.other_leg, self.which_leg])
+
+    def adjoint(self):
+        return TensorLinearOperator(self.bb, ab.dagger(self.bb, self.tensor), self.which_leg)
+
+
+class DirectSumLinearOperator:
+    """The block-diagonal operator on a :class:`direct_sum.DirectSum` (sparse.cpp:346-418): component i of the vector goes
+    through ``operators[i]``.  On flat pools (``krylov._FlatDirectSumOps``) wrappers around it work on the whole pool; the
+    operators inside it, their own wrappers included, see the tensors of their component."""
+
+    def __init__(self, operators, bb=None):
+        self.operators = list(operators)
+        if not self.operators:
+            raise ValueError('DirectSumLinearOperator needs at least one operator')
+        for op in self.operators:
+            if op is None or not hasattr(op, 'matvec'):
+                raise ValueError('DirectSumLinearOperator operators must be objects with a matvec')
+        self.bb = bb if bb is not None else next((op.bb for op in self.operators if getattr(op, 'bb', None) is not None), None)
+
+    @property
+    def is_complex(self) -> bool:
+        return any(_is_complex_op(op) for op in self.operators)
+
+    def matvec(self, vec):
+        if not isinstance(vec, ds.DirectSum):
+            raise ValueError('DirectSumLinearOperator.matvec expects a DirectSum input')
+        if len(vec) != len(self.operators):
+            raise ValueError('DirectSumLinearOperator.matvec expects matching component count')
+        return ds.DirectSum([op.matvec(c) for op, c in zip(self.operators, vec.components)])
+
+    def to_tensor(self):
+        raise NotImplementedError('DirectSumLinearOperator has no single-tensor representation')
+
+    def adjoint(self):
+        return DirectSumLinearOperator([op.adjoint() for op in self.operators], self.bb)
+
+
+def _norm(bb, v):
+    if isinstance(v, ds.DirectSum):
+        return ds.norm(bb, v)
+    if isinstance(v, ft.TreeTensor):
+        return ft.norm(bb, v.data, v.codomain)
+    return ab.norm(bb, v)
+
+
+def gram_schmidt(bb, vecs, rcond: float = 1e-14):
+    """The orthonormal vectors of sparse.cpp:420-436 from a list of pairwise compatible vectors (tensors, tree tensors or
+    direct sums): a vector is kept iff the norm of what the earlier kept ones leave of it is ``> rcond`` -- strict and absolute,
+    a NaN norm drops it.  How the ortho_vecs of a :class:`ProjectedLinearOperator` are prepared.
+
+    On ``HipBlockBackend`` the list runs on pools in ONE library call (``cyb_orthonormalize_*``): CGS2 per
+    vector, dropped vectors zeroed on the device, and one download of the norms and flags at the end; elsewhere it is the
+    reference's loop on tensors."""
+    vecs = list(vecs)
+    for v in vecs[1:]:
+        if not _compatible(v, vecs[0]):
+            raise ValueError('gram_schmidt: all vectors must be mutually compatible')
+    from . import krylov
+    if vecs and len(vecs) <= krylov._FlatOps.MAX_BASIS and krylov._flat_usable(bb, vecs[0]):
+        try:
+            V = krylov._vector_ops(bb, None, vecs[0], any(_is_complex_tensor(v) for v in vecs))
+            pools = [V.enter(v) for v in vecs]
+            _, kept = V.orthonormalize(pools, rcond)
+            return [V.leave(p) for p, k in zip(pools, kept) if k]
+        except krylov._NotFlat:
+            pass
+    res = []
+    for v in vecs:
+        for o in res:
+            v = _lincomb(bb, _plain(-complex(_inner(bb, o, v))), o, 1.0, v)
+        n = _norm(bb, v)
+        if n > rcond:
+            res.append(_scaled(bb, 1.0 / n, v))
+    return res
+
+
+def _scaled(bb, a, v):
+    if isinstance(v, ds.DirectSum):
+        return ds.scale(bb, a, v)
+    if isinstance(v, ft.TreeTensor):
+        return v.like(ft.mul(bb, a, v.data))
+    return ab.scale(bb, a, v)

@@ -411,6 +411,20 @@ int cyb_gram_schmidt_weighted_f64(cyb_ctx_t ctx, const double* const* basis, int
                                   const double* weights_dev, double* out_dev);
 int cyb_gram_schmidt_weighted_c128(cyb_ctx_t ctx, const double* const* basis, int64_t m, double* w, int64_t n, int32_t passes,
                                    const double* weights_dev, double* out_dev);
+/* Orthonormalises a LIST in place (gram_schmidt(vecs, rcond), sparse.cpp:420-436) with no host wait between its steps.
+ * vecs: a HOST array of m <= 64 device pointers to contiguous vectors of n elements, alignment and n as above.  For
+ * k = 0 .. m-1: the CGS2 step above (passes = 2) of vecs[k] against vecs[0..k-1], then one streaming pass that reads the
+ * norm the step left on the device: norm > rcond (false for NaN) multiplies every element by the double 1.0 / norm (both
+ * parts of a complex one), anything else WRITES +0.0 over the vector, so that a dropped vector -- whatever it held --
+ * contributes exactly nothing to the later steps.  out_dev: 2m device doubles, out[k] the norm, out[m + k] 1.0 (kept) or
+ * 0.0 (dropped).  The weighted forms take the norms and coefficients with the granule table of the weighted entries.
+ * m == 0 or n == 0: nothing is launched, out_dev is not written; m > 64: CYB_ERR_UNSUPPORTED. */
+int cyb_orthonormalize_f64(cyb_ctx_t ctx, double* const* vecs, int64_t m, int64_t n, double rcond, double* out_dev);
+int cyb_orthonormalize_c128(cyb_ctx_t ctx, double* const* vecs, int64_t m, int64_t n, double rcond, double* out_dev);
+int cyb_orthonormalize_weighted_f64(cyb_ctx_t ctx, double* const* vecs, int64_t m, int64_t n, double rcond, const double* weights_dev,
+                                    double* out_dev);
+int cyb_orthonormalize_weighted_c128(cyb_ctx_t ctx, double* const* vecs, int64_t m, int64_t n, double rcond, const double* weights_dev,
+                                     double* out_dev);
 
 /* ---- host-side sector matching of a contraction (no device work) ------------------------------------------------
  * The int64 bookkeeping of abelian_compose_worker (src/backends/abelian.cpp:1239-1469) in C++, as in the reference:
