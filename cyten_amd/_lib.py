@@ -357,6 +357,7 @@ PROTOTYPES = {
     'cyb_orthonormalize_c128': [_ctx, _vp, C.c_int64, C.c_int64, C.c_double, _vp],
     'cyb_orthonormalize_weighted_f64': [_ctx, _vp, C.c_int64, C.c_int64, C.c_double, _vp, _vp],
     'cyb_orthonormalize_weighted_c128': [_ctx, _vp, C.c_int64, C.c_int64, C.c_double, _vp, _vp],
+    'cyb_basis_rotate_f64': [_ctx, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64],
     'cyb_fill_f64': [_ctx, _vp, C.c_int64, C.c_double],
     'cyb_eye_f64': [_ctx, _vp, C.c_int64],
     'cyb_random_normal_f64': [_ctx, _vp, C.c_int64, C.c_uint64, C.c_double],

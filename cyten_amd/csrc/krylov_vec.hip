@@ -534,9 +534,156 @@ static int orthonormalize(const char* fn, cyb_ctx_t ctx, double* const* vecs, in
     });
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Basis rotation Y = V S of a thick restart (Wu & Simon): dst[i][p] = sum_{j < m} q[j][i] src[j][p], i < k.  One pass that
+// reads the m basis vectors once and writes the k results once: (m + k) n words, against k (m + 1) n for k linear
+// combinations.
+//
+// One thread per position (two adjacent ones, 16 bytes, when every pointer is 16-byte aligned; a pointer that is only 8-byte
+// aligned sends the whole call to the 8-byte instantiation -- the same chain per position, hence the same bits).  A thread
+// keeps KC accumulators per position (KC = k rounded up to 4 / 8 / 16 / 32, the columns i >= k of the uploaded matrix are
+// zero and are not stored) and adds the terms with j ASCENDING, one fma each: no atomics, no reduction across threads,
+// bit-identical from run to run.
+//
+// ALIASING: a dst[i] may be any src[j].  Every accumulator depends on all m loads of the thread's positions, so every one of
+// its k stores comes after all of them (a data dependence; the pointers carry no __restrict__), and a thread reads and writes
+// its own positions only: whatever a store overwrites has been read by the only thread that needs it.  Keep both properties --
+// all loads of a position before its first store, no position shared between threads -- when changing this kernel.  Ranges
+// that overlap only partly would break the second one; the host refuses them.
+//
+// The coefficients are wave-uniform: the matrix (m x KC doubles in a ring slot) is read through the constant address space,
+// i.e. by scalar loads through the scalar cache into SGPRs, and enters the fma as its scalar operand.  No VGPRs, no LDS
+// traffic and no barrier; LDS would cost KC / 2 ds_read_b128 per j next to KC (or 2 KC) fma.
+constexpr int ROT_MAX_K = 32;
+
+struct RotDst {
+    double* v[ROT_MAX_K];
+};
+
+typedef const __attribute__((address_space(4))) double* rot_cq;
+
+template <class T> struct RotFma;
+template <> struct RotFma<double> {
+    static __device__ __forceinline__ double zero() { return 0.0; }
+    static __device__ __forceinline__ double fma(double c, double x, double a) { return __builtin_fma(c, x, a); }
+};
+template <> struct RotFma<d2> {
+    static __device__ __forceinline__ d2 zero() { return d2{0.0, 0.0}; }
+    static __device__ __forceinline__ d2 fma(double c, d2 x, d2 a) { return d2{__builtin_fma(c, x.x, a.x), __builtin_fma(c, x.y, a.y)}; }
+};
+
+// the positions [off, off + sizeof(T) / 8) of every vector
+template <int KC, class T>
+__device__ __forceinline__ void rotate_at(const BasisPtrs& S, int m, const RotDst& D, int k, rot_cq q, int64_t off)
+{
+    T acc[KC];
+#pragma unroll
+    for (int i = 0; i < KC; ++i) acc[i] = RotFma<T>::zero();
+#pragma unroll 4
+    for (int j = 0; j < m; ++j) {
+        const T x = *reinterpret_cast<const GLOBAL_AS T*>((gcp)S.v[j] + off);
+#pragma unroll
+        for (int i = 0; i < KC; ++i) acc[i] = RotFma<T>::fma(q[j * KC + i], x, acc[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < KC; ++i)
+        if (i < k) *reinterpret_cast<GLOBAL_AS T*>((gp)D.v[i] + off) = acc[i];
+}
+
+// workgroup g owns the tiles [g * tpg, (g + 1) * tpg) of NT * W positions, W = 2 (VEC) or 1
+template <int KC, bool VEC>
+__global__ void __launch_bounds__(NT) basis_rotate_kernel(BasisPtrs S, int m, RotDst D, int k, const double* q_, int64_t n, int64_t tpg)
+{
+    constexpr int W = VEC ? 2 : 1;
+    constexpr int64_t TS = (int64_t)NT * W;
+    const rot_cq q = (rot_cq)q_;
+    const int64_t t_end = min(((int64_t)blockIdx.x + 1) * tpg, (n + TS - 1) / TS);
+    for (int64_t t = (int64_t)blockIdx.x * tpg; t < t_end; ++t) {
+        const int64_t off = t * TS + (int64_t)threadIdx.x * W;
+        if (VEC && off + 1 < n)
+            rotate_at<KC, d2>(S, m, D, k, q, off);
+        else if (off < n) // (VEC: the last position of an odd n)
+            rotate_at<KC, double>(S, m, D, k, q, off);
+    }
+}
+
+template <bool VEC>
+static void rot_launch(int KC, dim3 grid, hipStream_t s, const BasisPtrs& S, int m, const RotDst& D, int k, const double* q, int64_t n,
+                       int64_t tpg)
+{
+#define ROT_CASE(KK)                                                                                                   \
+    case KK: hipLaunchKernelGGL((basis_rotate_kernel<KK, VEC>), grid, dim3(NT), 0, s, S, m, D, k, q, n, tpg); break;
+    switch (KC) {
+        ROT_CASE(4)
+        ROT_CASE(8)
+        ROT_CASE(16)
+        default: ROT_CASE(32)
+    }
+#undef ROT_CASE
+}
+
+static int basis_rotate(const char* fn, cyb_ctx_t ctx, const double* const* src, int64_t m, double* const* dst, int64_t k,
+                        const double* q_host, int64_t n)
+{
+    CYB_REQUIRE(ctx, "%s: ctx is NULL", fn);
+    CYB_REQUIRE(m >= 0 && k >= 0 && n >= 0, "%s: negative size", fn);
+    CYB_REQUIRE(m <= GS_MAX_M, "%s: %lld basis vectors, at most %d are supported", fn, (long long)m, GS_MAX_M);
+    CYB_REQUIRE(k <= ROT_MAX_K, "%s: %lld columns, at most %d are supported (split the columns)", fn, (long long)k, ROT_MAX_K);
+    if (m == 0 || k == 0 || n == 0) return CYB_OK;
+    CYB_REQUIRE(src && dst && q_host, "%s: NULL table", fn);
+    CYB_REQUIRE(n <= (INT64_MAX >> 4), "%s: vector too long", fn);
+    BasisPtrs S;
+    RotDst D;
+    uintptr_t bits = 0;
+    for (int64_t j = 0; j < GS_MAX_M; ++j) {
+        S.v[j] = j < m ? src[j] : nullptr;
+        CYB_REQUIRE(j >= m || (src[j] && (uintptr_t)src[j] % 8 == 0), "%s: src %lld NULL or misaligned", fn, (long long)j);
+        bits |= (uintptr_t)S.v[j];
+    }
+    for (int64_t i = 0; i < ROT_MAX_K; ++i) {
+        D.v[i] = i < k ? dst[i] : nullptr;
+        CYB_REQUIRE(i >= k || (dst[i] && (uintptr_t)dst[i] % 8 == 0), "%s: dst %lld NULL or misaligned", fn, (long long)i);
+        bits |= (uintptr_t)D.v[i];
+    }
+    // a dst range is disjoint from every other dst range, and from every src range unless it IS that range
+    const uintptr_t len = (uintptr_t)n * sizeof(double);
+    const auto overlap = [len](const void* a, const void* b) {
+        const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+        return x < y + len && y < x + len;
+    };
+    for (int64_t i = 0; i < k; ++i) {
+        for (int64_t i2 = 0; i2 < i; ++i2)
+            CYB_REQUIRE(!overlap(dst[i], dst[i2]), "%s: dst %lld and dst %lld are equal or overlap", fn, (long long)i2, (long long)i);
+        for (int64_t j = 0; j < m; ++j)
+            CYB_REQUIRE(dst[i] == src[j] || !overlap(dst[i], src[j]), "%s: dst %lld overlaps src %lld partly", fn, (long long)i,
+                        (long long)j);
+    }
+    int KC = 4;
+    while (KC < k) KC *= 2;
+    std::vector<double> qp((size_t)m * KC, 0.0); // columns k .. KC - 1 are zero
+    for (int64_t j = 0; j < m; ++j) std::copy(q_host + j * k, q_host + (j + 1) * k, qp.begin() + j * KC);
+    void* q_dev = nullptr;
+    CYB_TRY(cyb::upload_packed(ctx, {{qp.data(), sizeof(double) * qp.size(), &q_dev}}));
+    const bool vec = bits % 16 == 0;
+    const int64_t tiles = cdiv64(n, (int64_t)NT * (vec ? 2 : 1));
+    const int64_t tpg = std::max<int64_t>(1, cdiv64(tiles, GS_MAX_GRID));
+    const dim3 grid((unsigned)cdiv64(tiles, tpg));
+    if (vec)
+        rot_launch<true>(KC, grid, ctx->stream, S, (int)m, D, (int)k, static_cast<const double*>(q_dev), n, tpg);
+    else
+        rot_launch<false>(KC, grid, ctx->stream, S, (int)m, D, (int)k, static_cast<const double*>(q_dev), n, tpg);
+    CYB_HIP(hipGetLastError());
+    return CYB_OK;
+}
+
 } // namespace
 
 extern "C" {
+
+int cyb_basis_rotate_f64(cyb_ctx_t ctx, const double* const* src, int64_t m, double* const* dst, int64_t k, const double* q_host, int64_t n)
+{
+    return basis_rotate("cyb_basis_rotate_f64", ctx, src, m, dst, k, q_host, n);
+}
 
 int cyb_orthonormalize_f64(cyb_ctx_t ctx, double* const* vecs, int64_t m, int64_t n, double rcond, double* out_dev)
 {

@@ -14,6 +14,9 @@
 * :class:`LanczosEvolution`, :class:`Arnoldi`, :class:`ArnoldiEvolution` -- exp(delta H) psi (the TDVP step) and the
   non-Hermitian eigensolver of the reference (krylov_based.cpp:532-800, 948-1019), on the same flat pools: float64 while the
   operator and the start vector are real, complex128 otherwise.
+* :class:`LanczosEigenpairs` / :func:`eigenvectors` -- several eigenpairs of a Hermitian operator by thick-restart Lanczos on one
+  bounded basis (the reference: ARPACK through a host array per matvec, sparse.py:410-504): full reorthogonalisation by the fused
+  CGS2 call, the restart ONE in-place basis rotation on the pools (krylov_vec.hip: cyb_basis_rotate_f64).
 * Every solver takes fusion-tree vectors (:class:`cyten_amd.fusion_tree.TreeTensor`) as well: the recurrences are the same
   code, the vector operations are :class:`_TreeTensorOps` (tensors) or :class:`_FlatTreeOps` (pools whose reductions carry the
   quantum dimension of the coupled sector); :class:`TreeChainOperator` is an operator to apply to them.
@@ -280,6 +283,11 @@ class _TensorOps:
         each coefficient taken against the vector the earlier ones left (`passes` concerns the fused step of the pools)."""
         return _mgs(self, basis, w)
 
+    def rotate(self, basis, Q):
+        """[sum_j Q[j, i] basis_j for every column i of the real m x k matrix `Q`]: k ``combine``, new vectors."""
+        Q = np.asarray(Q, dtype=np.float64)
+        return [self.combine([float(c) for c in Q[:, i]], basis) for i in range(Q.shape[1])]
+
 
 class _TreeTensorOps(_TensorOps):
     """:class:`_TensorOps` on fusion-tree vectors (:class:`fusion_tree.TreeTensor`): the inner product and the norm carry the
@@ -538,6 +546,41 @@ class _FlatOps:
         r = self.bb.ctx.d2h(out, k * m + 1, np.float64)
         h = (r[0:2 * m:2] + 1j * r[1:2 * m:2]) if cplx else r[:m].copy()
         return w, h, float(r[k * m])
+
+    MAX_ROTATE = 32    # columns of one cyb_basis_rotate_f64 call
+
+    def rotate(self, basis, Q):
+        """The pools sum_j Q[j, i] basis_j for every column i of the real m x k matrix `Q` (the restart of
+        :class:`LanczosEigenpairs`) by ONE cyb_basis_rotate_f64 call IN PLACE: the results replace basis[0 .. k-1] (which are
+        returned), basis[k:] is untouched; nothing is downloaded.  The matrix is real, so a complex pool is rotated as its
+        2 * total doubles.  More than MAX_ROTATE columns (or more columns than pools): chunks of MAX_ROTATE columns, each one
+        call of the same entry that writes to fresh pools.  A basis longer than the kernel takes runs k ``combine``."""
+        Q = np.ascontiguousarray(Q, dtype=np.float64)
+        m, k = Q.shape
+        if m != len(basis):
+            raise ValueError(f'rotate: {len(basis)} vectors, a matrix of {m} rows')
+        if k == 0:
+            return []
+        cplx = basis[0].is_complex()
+        if any(v.is_complex() != cplx for v in basis):
+            raise _NeedComplex()
+        if m > self.MAX_BASIS:
+            return _TensorOps.rotate(self, basis, Q)
+        words = (2 if cplx else 1) * self.total
+        in_place = k <= min(self.MAX_ROTATE, m)
+        out = []
+        for c0 in range(0, k, self.MAX_ROTATE):
+            Qc = Q if in_place else np.ascontiguousarray(Q[:, c0:c0 + self.MAX_ROTATE])
+            dst = list(basis[:k]) if in_place else [self._alloc(False, cplx) for _ in range(Qc.shape[1])]
+            self._rotate_call(basis, dst, Qc, words)
+            out += dst
+        return out
+
+    def _rotate_call(self, src, dst, Q, words):
+        bb, C = self.bb, self._C
+        bb.ctx.sync_stream()
+        self._lib.check(bb.lib.cyb_basis_rotate_f64(bb.ctx.handle, self._ptrs(src), len(src), self._ptrs(dst), len(dst),
+                                                    Q.ctypes.data_as(C.c_void_p), words))
 
     # -- BLAS-1 over the flat range
     def _desc(self, x, y, out, n=None):
@@ -1285,6 +1328,134 @@ class ArnoldiEvolution(Arnoldi):
             raise RuntimeError('ArnoldiEvolution: Krylov basis shorter than N')
         psif = V.combine(list(self._result_krylov[:N]), self._cache[:N])
         return V.scale(1.0 / V.norm(psif), psif)
+
+
+_WHICH_NAMES = ('LM', 'm>', 'SM', 'm<', 'LR', '>', 'LA', 'SR', '<', 'SA', 'LI', 'SI')
+
+
+class LanczosEigenpairs(LanczosGroundState):
+    """Several eigenpairs of a Hermitian ``H`` by thick-restart Lanczos (Wu & Simon, SIAM J. Matrix Anal. Appl. 22 (2000)) --
+    what the reference offers as ``HermitianNumpyArrayLinearOperator.eigenvectors`` / ``lanczos_arpack`` through a flat host
+    array per matvec (sparse.py:410-504), here on the vectors of the other solvers: pools where the backend allows it.
+
+    One bounded basis of `N_max` = m vectors.  A step is ``w = H v_j``, the fused CGS2 call against ALL of v_0 .. v_j (full
+    reorthogonalisation: one library call and one download per step) and ``v_{j+1} = w / beta``; the projection T of H is real
+    symmetric: tridiagonal, after a restart an arrow (diagonal + one row) followed by a tridiagonal.  Only T[j, j] = Re h_j and
+    the new beta are taken from the step; the other coefficients are rounding (below the arrow) or repeat the couplings the
+    restart predicted (on its row): ``coupling_error`` keeps the largest difference seen.  With j == m the basis is rotated onto
+    the `keep` = l Ritz vectors first in `which` order (``V.rotate``: on pools ONE in-place kernel call), v_m becomes v_l
+    and the couplings are beta S[m-1, i].  Ritz pair i has the residual estimate |beta S[j-1, i]|; the run ends when the first
+    `num_ev` are <= tol max(|theta_i|, tiny), or when beta < cutoff max|T|: the basis then spans an invariant subspace, its
+    min(num_ev, j) pairs are exact and are returned -- FEWER than num_ev pairs is a documented outcome of a start vector that
+    lives in a small invariant subspace, not an error.
+
+    As with ARPACK, one start vector finds ONE copy of a degenerate eigenvalue: the Krylov space of a single vector holds one
+    vector of every eigenspace.  (Rounding eventually brings further copies in, late and unreliably; a block method is the
+    tool for degenerate levels.)
+
+    Options: num_ev=1, which='SA' (any name of :func:`argsort_which`), N_max=max(2 num_ev + 1, 20) (> num_ev),
+    keep=num_ev + (N_max - num_ev) // 2 clipped to [num_ev, N_max - 1], tol=1e-10 (0.0: machine eps), max_restarts=100
+    (RuntimeError with the residual estimates when exceeded), cutoff=100 eps, flat=True (N_max <= 64, else tensors), E_shift
+    as in :class:`LanczosGroundState`.  After ``run``: ``restarts``, ``matvecs``, ``residuals``, ``coupling_error``, ``T``."""
+
+    def __init__(self, bb, H, psi0, options=None):
+        o = dict(options or {})
+        self.num_ev = int(o.get('num_ev', 1))
+        self.which = o.get('which', 'SA')
+        if self.num_ev < 1:
+            raise ValueError('num_ev must be at least 1')
+        if self.which not in _WHICH_NAMES:
+            raise ValueError(f'unknown which: {self.which!r}')
+        m = int(o.get('N_max', max(2 * self.num_ev + 1, 20)))
+        if not self.num_ev < m:
+            raise ValueError(f'num_ev = {self.num_ev} pairs need a basis of N_max > num_ev vectors, got {m}')
+        default_keep = min(max(self.num_ev + (m - self.num_ev) // 2, self.num_ev), m - 1)
+        self.keep = int(o.get('keep', default_keep))
+        if not self.num_ev <= self.keep <= m - 1:
+            raise ValueError(f'keep = {self.keep} outside [num_ev, N_max - 1] = [{self.num_ev}, {m - 1}]')
+        tol = float(o.get('tol', 1e-10))
+        self.tol = tol if tol > 0.0 else float(np.finfo(np.float64).eps)
+        self.max_restarts = int(o.get('max_restarts', 100))
+        base = {k: o[k] for k in ('cutoff', 'flat', 'E_shift') if k in o}
+        super().__init__(bb, H, psi0, dict(base, N_max=m))
+        if m > _FlatOps.MAX_BASIS:      # (the fused step and the rotation take at most that many vectors)
+            self.flat = False
+        self.restarts = self.matvecs = 0
+        self.residuals = np.zeros(0)
+        self.coupling_error = 0.0
+        self.T = np.zeros((m + 1, m + 1))
+
+    def _orthogonalize(self, basis, w):
+        V = self.V
+        w, h, beta = V.project_out(basis, w, passes=2)
+        if not isinstance(V, _FlatOps):
+            # the tensor operations run ONE pass of modified Gram-Schmidt: a second one, as the fused CGS2 step has
+            w, h2, beta = V.project_out(basis, w, passes=2)
+            h = np.asarray(h) + np.asarray(h2)
+        return w, np.asarray(h), float(beta)
+
+    def run(self):
+        """(Es, vectors, N): the Ritz values in `which` order (an ndarray of min(num_ev, dimension of the Krylov space)
+        floats), their orthonormal Ritz vectors and the number of matvecs."""
+        return self._solve(self._run)
+
+    def _run(self):
+        V, m, nev, l = self.V, self.N_max, self.num_ev, self.keep
+        tiny = float(np.finfo(np.float64).tiny)
+        beta = V.norm(self.psi0)
+        if beta < self.cutoff:
+            raise ValueError(f'Norm of self.psi0 too small: {beta}')
+        basis = [V.scale(1.0 / beta, self.psi0)]
+        T = self.T = np.zeros((m + 1, m + 1))
+        self.restarts = self.matvecs = 0
+        self.coupling_error = 0.0
+        j = 0
+        while True:
+            self._cache = [basis[j]]          # (_matvec adds E_shift times the vector it finds there)
+            w = self._matvec(basis[j])
+            self.matvecs += 1
+            w, h, beta = self._orthogonalize(basis[:j + 1], w)
+            T[j, j] = float(np.real(h[j]))
+            if j > 0:
+                self.coupling_error = max(self.coupling_error, float(np.abs(h[:j] - T[:j, j]).max()))
+            T[j + 1, j] = T[j, j + 1] = beta
+            j += 1
+            broke = beta == 0.0 or beta < self.cutoff * float(np.abs(T[:j + 1, :j + 1]).max())
+            if not broke and j < nev:
+                basis.append(V.scale(1.0 / beta, w))
+                continue
+            theta, S = np.linalg.eigh(T[:j, :j])
+            order = argsort_which(theta, self.which)
+            theta, S = theta[order], S[:, order]
+            n_out = min(nev, j)
+            self.residuals = np.abs(beta * S[j - 1, :n_out])
+            if broke or bool(np.all(self.residuals <= self.tol * np.maximum(np.abs(theta[:n_out]), tiny))):
+                break
+            basis.append(V.scale(1.0 / beta, w))
+            if j == m:
+                if self.restarts >= self.max_restarts:
+                    raise RuntimeError(f'LanczosEigenpairs: not converged after {self.restarts} restarts and {self.matvecs} '
+                                       f'matvecs; residual estimates {self.residuals.tolist()}')
+                basis = list(V.rotate(basis[:m], S[:, :l])) + [basis[m]]
+                T[:] = 0.0
+                T[np.arange(l), np.arange(l)] = theta[:l]
+                T[l, :l] = T[:l, l] = beta * S[m - 1, :l]
+                j = l
+                self.restarts += 1
+        vecs = V.rotate(basis[:j], S[:, :n_out])
+        self._cache = []
+        Es = theta[:n_out].copy()
+        if self.E_shift is not None:
+            Es -= float(self.E_shift)
+        return Es, [V.leave(y) for y in vecs], self.matvecs
+
+
+def eigenvectors(bb, H, psi0, num_ev=1, which='SA', **options):
+    """(eta, vectors) -- the return of the reference's ``HermitianNumpyArrayLinearOperator.eigenvectors`` (sparse.py:502-504):
+    `num_ev` eigenvalues of the Hermitian ``H`` in `which` order as an ndarray and the list of their eigenvectors, found from
+    the start vector `psi0` by :class:`LanczosEigenpairs` (whose options are the keywords)."""
+    Es, vecs, _ = LanczosEigenpairs(bb, H, psi0, dict(options, num_ev=num_ev, which=which)).run()
+    return Es, vecs
 
 
 def compatible(a, b) -> bool:

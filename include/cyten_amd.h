@@ -425,6 +425,20 @@ int cyb_orthonormalize_weighted_f64(cyb_ctx_t ctx, double* const* vecs, int64_t 
                                     double* out_dev);
 int cyb_orthonormalize_weighted_c128(cyb_ctx_t ctx, double* const* vecs, int64_t m, int64_t n, double rcond, const double* weights_dev,
                                      double* out_dev);
+/* Basis rotation of thick-restart Lanczos, Y = V S in ONE streaming pass: dst[i][p] = sum_{j<m} q[j * k + i] * src[j][p] for
+ * i < k, p < n.  src / dst: HOST arrays of m <= 64 / k <= 32 device pointers to contiguous vectors of n doubles (8-byte
+ * aligned; 16-byte accesses when every pointer is 16-byte aligned).  q_host: m x k row-major doubles in HOST memory, uploaded
+ * through the context's ring (no allocation, no host wait).  One thread per position, j ascending, no atomics: bit-identical
+ * from run to run and whatever the alignment.  A dst[i] may BE any src[j] (in place, dst[i] = src[i], or any other
+ * assignment): a thread loads all m values of its positions before it stores any of its k results and touches no other
+ * position.  Two equal dst entries, or a dst range that overlaps another dst or a src range only partly: CYB_ERR_INVALID,
+ * as are m > 64, k > 32, a NULL table or entry and a pointer that is not 8-byte aligned; nothing is launched then.
+ * m == 0, k == 0 or n == 0: success, nothing is launched.  V (m n words) is read once and Y (k n words) written once.
+ * complex128 pools need no second entry: the small matrix is real (the Ritz vectors of a real symmetric tridiagonal or arrow
+ * matrix), so a pool of n complex numbers is rotated as 2n doubles.  There is no weighted form: the rotation is linear, and
+ * the zero gaps of a pool stay zero. */
+int cyb_basis_rotate_f64(cyb_ctx_t ctx, const double* const* src, int64_t m, double* const* dst, int64_t k, const double* q_host,
+                         int64_t n);
 
 /* ---- host-side sector matching of a contraction (no device work) ------------------------------------------------
  * The int64 bookkeeping of abelian_compose_worker (src/backends/abelian.cpp:1239-1469) in C++, as in the reference:
