@@ -5,6 +5,8 @@
 The module functions are what ``vector_norm`` / ``vector_inner`` / ``scaled`` / ``axpy`` / ``compatible_with`` are in the
 reference (direct_sum.cpp:113-174): componentwise calls of :mod:`cyten_amd.abelian` and :mod:`cyten_amd.fusion_tree`, so they
 need nothing of the backend beyond what those call and run on a numpy stand-in.  Only the conjugating inner product exists.
+The ``vector_*`` functions at the end take any vector of the solvers, a tensor or a direct sum: the one statement of the
+dispatch on the kind of a vector that :mod:`cyten_amd.sparse` and :mod:`cyten_amd.krylov` go through.
 The pool form of a direct sum, on which the solvers run on the device, is ``krylov._FlatDirectSumOps``.
 """
 from __future__ import annotations
@@ -146,3 +148,34 @@ def axpy(bb, a, x: DirectSum, y: DirectSum) -> DirectSum:
 
 def almost_equal(bb, x: DirectSum, y: DirectSum, rtol: float = 1e-5, atol: float = 1e-8) -> bool:
     return all(_almost_equal1(bb, u, v, rtol, atol) for u, v in _pair('almost_equal', x, y))
+
+
+# -- any vector of the solvers: a tensor or a direct sum -----------------------------------------------------------------------
+# (with a direct sum on either side the functions above run, and raise for a tensor on the other side)
+
+def _any_sum(*vs) -> bool:
+    return any(isinstance(v, DirectSum) for v in vs)
+
+
+def vectors_compatible(a, b) -> bool:
+    """two vectors a solver can combine: direct sums of one length with compatible components, fusion-tree tensors on the
+    same spaces, abelian tensors on the same legs -- never a tensor and a direct sum"""
+    return compatible(a, b) if _any_sum(a, b) else _compatible1(a, b)
+
+
+def vector_norm(bb, x):
+    return norm(bb, x) if _any_sum(x) else _norm1(bb, x)
+
+
+def vector_inner(bb, a, b):
+    """<a|b>, conjugating a; fusion-tree tensors carry the quantum dimensions of the codomain"""
+    return inner(bb, a, b) if _any_sum(a, b) else _inner1(bb, a, b)
+
+
+def vector_scale(bb, a, x):
+    return scale(bb, a, x) if _any_sum(x) else _scale1(bb, a, x)
+
+
+def vector_lincomb(bb, a, x, b, y):
+    """a x + b y"""
+    return linear_combination(bb, a, x, b, y) if _any_sum(x, y) else _lincomb1(bb, a, x, b, y)

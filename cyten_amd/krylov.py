@@ -17,11 +17,11 @@
 * :class:`LanczosEigenpairs` / :func:`eigenvectors` -- several eigenpairs of a Hermitian operator by thick-restart Lanczos on one
   bounded basis (the reference: ARPACK through a host array per matvec, sparse.py:410-504): full reorthogonalisation by the fused
   CGS2 call, the restart ONE in-place basis rotation on the pools (krylov_vec.hip: cyb_basis_rotate_f64).
-* Every solver takes fusion-tree vectors (:class:`cyten_amd.fusion_tree.TreeTensor`) as well: the recurrences are the same
-  code, the vector operations are :class:`_TreeTensorOps` (tensors) or :class:`_FlatTreeOps` (pools whose reductions carry the
-  quantum dimension of the coupled sector); :class:`TreeChainOperator` is an operator to apply to them.
-* ... and direct sums of both (:class:`cyten_amd.direct_sum.DirectSum`): :class:`_DirectSumOps` on tensors,
-  :class:`_FlatDirectSumOps` on pools that hold the components' pools one after the other.
+* Every solver takes fusion-tree vectors (:class:`cyten_amd.fusion_tree.TreeTensor`) as well, and direct sums of both kinds
+  (:class:`cyten_amd.direct_sum.DirectSum`): the recurrences are the same code, the vector operations come from
+  :mod:`cyten_amd.krylov_vectors` -- on tensors, or on pools whose layout holds the components one after the other and whose
+  reductions carry the quantum dimension of the coupled sector where there is a tree (DESIGN.md 4.14, 4.23);
+  :class:`TreeChainOperator` is an operator to apply to fusion-tree vectors.
 
 Leg orders used here (signs: + ket-like, - dual):
     theta [vL, p0, p1, vR]
@@ -36,6 +36,10 @@ import numpy as np
 from . import abelian as ab
 from . import direct_sum as ds
 from . import fusion_tree as ft
+# the vectors of the solvers live in krylov_vectors; the names below are reached through this module as well (the solvers look
+# `_vector_ops` and `_flat_usable` up HERE, so that replacing them on this module redirects a run)
+from .krylov_vectors import (PoolLayout, _DirectSumOps, _FlatDirectSumOps, _FlatOps, _FlatTreeOps, _NeedComplex,  # noqa: F401
+                             _NotFlat, _TensorOps, _TreeTensorOps, _flat_usable, _vector_ops, tree_pool_layout)
 
 
 def _is_complex_block(b) -> bool:
@@ -232,685 +236,27 @@ class TreeChainOperator:
         return ft.TreeTensor(data, cod, dom)
 
 
-class _NotFlat(Exception):
-    """The vector left the block structure the flat representation was built for (caught by the solvers' run)."""
+class _Fallback:
+    """The representations of the Krylov vectors a run tries, in order: flat pools where the backend allows it
+    (:class:`_FlatOps`) -- float64 pools while the vectors and the operator are real (`cplx` False), then complex128 pools --
+    and tensors last.  ``run(attempt)`` calls ``attempt(mode)`` (`mode` as :func:`_vector_ops` takes it) until one returns: a
+    complex vector out of the operator (_NeedComplex) moves on to the next representation, a vector that leaves the block
+    structure of the template (_NotFlat: an operator that creates blocks the pool does not have) to tensors.  The position is
+    kept, so an object that is kept goes on where it stands."""
 
+    def __init__(self, bb, flat, template, cplx):
+        flat = bool(flat) and _flat_usable(bb, template)
+        self.modes = (([cplx] if cplx else [False, True]) if flat else []) + [None]
+        self.i = 0
 
-class _NeedComplex(_NotFlat):
-    """A complex vector met a float64 pool (the operator is complex): the run restarts on complex128 pools."""
-
-
-def _is_real_scalar(c) -> bool:
-    return not isinstance(c, (complex, np.complexfloating)) or complex(c).imag == 0.0
-
-
-class _TensorOps:
-    """Vector operations of the recurrences on block-sparse tensors (one launch per block LIST, per-block host work)."""
-
-    def __init__(self, bb, H):
-        self.bb, self.H = bb, H
-
-    def enter(self, t):
-        return t
-
-    def leave(self, w):
-        return w
-
-    def matvec(self, w):
-        return self.H.matvec(w)
-
-    def norm(self, w):
-        return ab.norm(self.bb, w)
-
-    def inner(self, v, w):
-        return ab.inner(self.bb, v, w)
-
-    def scale(self, a, w):
-        return ab.scale(self.bb, a, w)
-
-    def lincomb(self, a, w, b, v):
-        return ab.linear_combination(self.bb, a, w, b, v)
-
-    def combine(self, coeffs, vecs, acc=None):
-        """acc + sum_k coeffs[k] vecs[k] (acc None: 0)."""
-        out = acc
-        for c, v in zip(coeffs, vecs):
-            out = self.scale(c, v) if out is None else self.lincomb(1.0, out, c, v)
-        return out
-
-    def project_out(self, basis, w, passes=2):
-        """(w - sum_j h_j basis_j, h, |w|) by the reference's modified Gram-Schmidt loop (krylov_based.cpp:458-465): one pass,
-        each coefficient taken against the vector the earlier ones left (`passes` concerns the fused step of the pools)."""
-        return _mgs(self, basis, w)
-
-    def rotate(self, basis, Q):
-        """[sum_j Q[j, i] basis_j for every column i of the real m x k matrix `Q`]: k ``combine``, new vectors."""
-        Q = np.asarray(Q, dtype=np.float64)
-        return [self.combine([float(c) for c in Q[:, i]], basis) for i in range(Q.shape[1])]
-
-
-class _TreeTensorOps(_TensorOps):
-    """:class:`_TensorOps` on fusion-tree vectors (:class:`fusion_tree.TreeTensor`): the inner product and the norm carry the
-    quantum dimension of the coupled sector (``FusionTreeBackend::inner`` / ``::norm``); needs nothing of the backend beyond
-    what :mod:`cyten_amd.fusion_tree` calls, so it runs on a numpy stand-in."""
-
-    def norm(self, w):
-        return ft.norm(self.bb, w.data, w.codomain)
-
-    def inner(self, v, w):
-        return ft.inner(self.bb, v.data, w.data, v.codomain, do_dagger=True)
-
-    def scale(self, a, w):
-        return w.like(ft.mul(self.bb, a, w.data))
-
-    def lincomb(self, a, w, b, v):
-        return w.like(ft.linear_combination(self.bb, a, w.data, b, v.data))
-
-
-def tree_pool_layout(codomain, domain, granule=256):
-    """The pool of a fusion-tree vector on (codomain, domain): one block per pair of ``ft.common_sectors`` -- every block an
-    operator can create -- of shape ``(codomain.block_size(i), domain.block_size(j))``, each starting at a multiple of
-    `granule` elements.  Returns (block_inds, shapes, offsets, total, weights): `total` is a multiple of `granule` and
-    ``weights[g]`` = ``codomain.qdims[i]`` for every granule g of block (i, j) -- the table the weighted pool reductions read
-    (one entry per granule, so a tile of the kernel never sees two weights)."""
-    pairs = ft.common_sectors(codomain, domain)
-    shapes = [(int(codomain.block_size(i)), int(domain.block_size(j))) for i, j in pairs]
-    offs, weights, tot = [], [], 0
-    for (i, _), (r, c) in zip(pairs, shapes):
-        g = (r * c + granule - 1) // granule
-        offs.append(tot)
-        tot += g * granule
-        weights += [float(codomain.qdims[i])] * g
-    return (np.array(pairs, dtype=np.int64).reshape(len(pairs), 2), shapes, offs, tot, np.array(weights, dtype=np.float64))
-
-
-class _FlatOps:
-    """The same operations on Krylov vectors kept as ONE contiguous pool each: the block offsets of
-    the structure are computed once, every ``scale / axpy / inner / norm`` of the recurrences is a single-descriptor
-    launch over the whole pool -- no per-block host work, one descriptor copy.  The pools are zero between blocks
-    (32-element alignment gaps), so reductions over the flat range are exact.  Only the operator application sees
-    tensors: its input is a list of views into the pool, its output is copied back in one batched launch.
-
-    Pools are float64 while the start vector and the operator are real -- the Lanczos / Arnoldi bases of a real operator
-    are real whatever the evolution step delta; only the result assembly ``sum_k c_k v_k`` then has complex coefficients,
-    ONE launch of the complex linear combination with real sources.  A complex start vector or operator uses complex128
-    pools (interleaved, the same offsets).  Every operation dispatches on the dtype of its pools.  HIP backend only;
-    anything else uses :class:`_TensorOps`."""
-
-    def __init__(self, bb, H, template, block_inds=None, cplx=False):
-        """`template`: a tensor on the legs of the vectors; `block_inds` (default: the template's): the block table of the
-        pool -- a superset of the template's when the operator creates blocks the start vector does not have.
-        `cplx`: the Krylov vectors are complex128 pools."""
-        from .block_backend import _c_strides
-        self._bind(bb, H, template, cplx)
-        self.block_inds = template.block_inds if block_inds is None else block_inds
-        self.shapes = [template.block_shape(r) for r in self.block_inds]
-        self.strides = [_c_strides(sh) for sh in self.shapes]
-        offs, tot = [], 0
-        for sh in self.shapes:
-            n = 1
-            for x in sh:
-                n *= x
-            offs.append(tot)
-            tot += (n + 31) // 32 * 32
-        self.offs, self.total = offs, tot
-        self.key = self.block_inds.tobytes()
-        self.index = None     # block row -> position, built only if a tensor has fewer blocks than the pool
-        # positions of the pool's blocks that any vector so far holds (the start vector's, plus what the operator produced):
-        # the pool is laid out over every charge-allowed block, but the operator only ever sees -- and the result only carries --
-        # this support, as the reference's tensors do (krylov_based.cpp works on tensors whose block tables grow the same way)
-        self.support = set()
-
-    def _bind(self, bb, H, template, cplx):
-        from .block_backend import HipBlock
-        from . import _lib
-        import ctypes
-        self.bb, self.H, self.t, self.cplx = bb, H, template, bool(cplx)
-        self._HipBlock, self._lib, self._C = HipBlock, _lib, ctypes
-
-    @staticmethod
-    def usable(bb, t) -> bool:
-        return (hasattr(bb, 'ctx') and len(t.blocks) > 0 and not any(b.is_bool for b in t.blocks)
-                and type(bb).__name__ != 'DeferredBlockBackend')
-
-    # -- pools
-    def _alloc(self, zero, cplx=None):
-        bb = self.bb
-        cplx = self.cplx if cplx is None else cplx
-        buf = bb.ctx.empty(self.total, 'complex128' if cplx else 'float64')
-        if zero:
-            bb.ctx.sync_stream()
-            self._lib.check(bb.lib.cyb_memset(bb.ctx.handle, self._C.c_void_p(buf.data_ptr()), 0, buf.element_size() * self.total))
-        return buf
-
-    def _views(self, buf, which=None):
-        bb, mk = self.bb, self._HipBlock._trusted
-        idx = range(len(self.offs)) if which is None else which
-        return [mk(bb, buf, self.offs[i], self.shapes[i], self.strides[i], True) for i in idx]
-
-    def enter(self, t):
-        """tensor -> pool (one memset + one batched copy); a real tensor enters a complex pool as its real plane."""
-        if not self.cplx and any(b.is_complex for b in t.blocks):
-            raise _NeedComplex()
-        buf = self._alloc(True)
-        if t.block_inds.tobytes() == self.key:
-            which = None
-        else:   # fewer blocks than the template (missing blocks are zero); a block outside the template ends flat mode
-            if self.index is None:
-                self.index = {tuple(r): i for i, r in enumerate(self.block_inds.tolist())}
+    def run(self, attempt):
+        while True:
             try:
-                which = [self.index[tuple(r)] for r in t.block_inds.tolist()]
-            except KeyError:
-                raise _NotFlat()
-        views = self._views(buf, which)
-        if any(v.shape != tuple(b.shape) for v, b in zip(views, t.blocks)):
-            raise _NotFlat()
-        self.support.update(range(len(self.offs)) if which is None else which)
-        self.bb.copy_many([(v if b.is_complex or not self.cplx else self.bb._plane(v, 0), b) for v, b in zip(views, t.blocks)])
-        return buf
-
-    def leave(self, buf):
-        t = self.t
-        if len(self.support) == len(self.offs):
-            return ab.AbelianTensor(t.symmetry, t.legs, self._views(buf), self.block_inds, t.num_codomain, t.labels)
-        idx = sorted(self.support)     # (positions ascend with the lexsorted block table)
-        return ab.AbelianTensor(t.symmetry, t.legs, self._views(buf, idx), self.block_inds[idx], t.num_codomain, t.labels)
-
-    def matvec(self, buf):
-        return self._apply(self.H, buf)
-
-    def _apply(self, op, buf):
-        """op(buf) on the pools.  The wrappers of cyten_amd.sparse do their vector work here: a shift is one axpby, a sum
-        one combine, a projection runs on the device with its coefficients kept there (no host synchronisation); anything
-        else sees tensors."""
-        from . import sparse
-        if isinstance(op, sparse.ShiftedLinearOperator):
-            return self.lincomb(1.0, self._apply(op.original_operator, buf), sparse._plain(op.shift), buf)
-        if isinstance(op, sparse.SumLinearOperator):
-            terms = [self._apply(o, buf) for o in [op.original_operator] + op.more_operators]
-            return self.combine([1.0] * len(terms), terms)
-        if isinstance(op, sparse.ProjectedLinearOperator):
-            return self._projected(op, buf)
-        if type(op) is sparse.LinearOperatorWrapper:
-            return self._apply(op.original_operator, buf)
-        return self.enter(op.matvec(self.leave(buf)))
-
-    def _ortho_pools(self, op):
-        """The ortho vectors of a projected operator as pools of this run (entered once)."""
-        if not hasattr(self, '_ortho'):
-            self._ortho = {}
-        got = self._ortho.get(id(op))
-        if got is None or got[0] is not op:
-            got = (op, [self.enter(o) for o in op.ortho_vecs])
-            self._ortho[id(op)] = got
-        return got[1]
-
-    def _projected(self, op, buf):
-        """The sequential projection of sparse.cpp:294-327 on the pools: every coefficient stays in device memory, each
-        projection is one m = 1 Gram-Schmidt launch sequence in the reference's order, the penalty one multi-axpy per vector
-        (m = 1: the reference's order) or, for project_operator=False, one multi-dot and one multi-axpy over all of them."""
-        O = self._ortho_pools(op)
-        cplx = self.cplx
-        if any(o.is_complex() != cplx for o in O) or buf.is_complex() != cplx:
-            raise _NeedComplex()
-        m, stride = len(O), (3 if cplx else 2)
-        coef = self.bb.ctx.empty(max(m, 1) * stride)
-        res = self.scale(1.0, buf)
-        if op.project_operator:
-            for j, o in enumerate(O):
-                self._gs([o], res, 1, coef, j * stride)
-        elif op.penalty is not None and m:
-            self._multi('dot', O, res, coef)
-        res = self._apply(op.original_operator, res)
-        if res.is_complex() != cplx:
-            raise _NeedComplex()
-        if op.project_operator:
-            scratch = self.bb.ctx.empty(stride)
-            for o in O:
-                self._gs([o], res, 1, scratch, 0)
-        if op.penalty is not None and m:
-            p = op.penalty if cplx else op.penalty.real
-            if op.project_operator:
-                for j, o in enumerate(O):
-                    self._multi('axpy', [o], res, coef, j * stride, p)
-            else:
-                self._multi('axpy', O, res, coef, 0, p)
-        return res
-
-    # -- projections against a basis (krylov_vec.hip: cyb_gram_schmidt / cyb_multi_dot / cyb_multi_axpy)
-    MAX_BASIS = 64
-
-    def _ptrs(self, basis):
-        return (self._C.c_void_p * max(len(basis), 1))(*[v.data_ptr() for v in basis])
-
-    def _gs(self, basis, w, passes, out, off=0):
-        bb = self.bb
-        fn = bb.lib.cyb_gram_schmidt_c128 if w.is_complex() else bb.lib.cyb_gram_schmidt_f64
-        bb.ctx.sync_stream()
-        self._lib.check(fn(bb.ctx.handle, self._ptrs(basis), len(basis), self._C.c_void_p(w.data_ptr()), self.total, int(passes),
-                           self._C.c_void_p(out.data_ptr() + 8 * off)))
-
-    def _multi(self, kind, basis, w, h, off=0, alpha=1.0):
-        bb, C = self.bb, self._C
-        cp = w.is_complex()
-        bb.ctx.sync_stream()
-        hp = C.c_void_p(h.data_ptr() + 8 * off)
-        if kind == 'dot':
-            fn = bb.lib.cyb_multi_dot_c128 if cp else bb.lib.cyb_multi_dot_f64
-            self._lib.check(fn(bb.ctx.handle, self._ptrs(basis), len(basis), C.c_void_p(w.data_ptr()), self.total, hp))
-        elif cp:
-            a = complex(alpha)
-            self._lib.check(bb.lib.cyb_multi_axpy_c128(bb.ctx.handle, self._ptrs(basis), len(basis), hp, a.real, a.imag,
-                                                       C.c_void_p(w.data_ptr()), self.total))
-        else:
-            self._lib.check(bb.lib.cyb_multi_axpy_f64(bb.ctx.handle, self._ptrs(basis), len(basis), hp, float(np.real(alpha)),
-                                                      C.c_void_p(w.data_ptr()), self.total))
-
-    def orthonormalize(self, pools, rcond):
-        """The list `pools` (at most MAX_BASIS, of the dtype of this run) orthonormalised in place by ONE library call
-        (krylov_vec.hip: cyb_orthonormalize_*): CGS2 of each against the earlier ones, then scaled by 1 / norm if the norm is
-        > rcond, else overwritten with zeros -- no host wait between the steps.  ONE download at the end: (norms, kept)."""
-        bb, C, m = self.bb, self._C, len(pools)
-        if any(p.is_complex() != self.cplx for p in pools):
-            raise _NeedComplex()
-        if m == 0 or self.total == 0:
-            return np.zeros(0), np.zeros(0, dtype=bool)
-        out = bb.ctx.empty(2 * m)
-        bb.ctx.sync_stream()
-        sfx = 'c128' if self.cplx else 'f64'
-        if self._weights_ptr() is None:
-            rc = getattr(bb.lib, 'cyb_orthonormalize_' + sfx)(bb.ctx.handle, self._ptrs(pools), m, self.total, float(rcond),
-                                                              C.c_void_p(out.data_ptr()))
-        else:
-            rc = getattr(bb.lib, 'cyb_orthonormalize_weighted_' + sfx)(bb.ctx.handle, self._ptrs(pools), m, self.total, float(rcond),
-                                                                       self._weights_ptr(), C.c_void_p(out.data_ptr()))
-        self._lib.check(rc)
-        r = bb.ctx.d2h(out, 2 * m, np.float64)
-        return r[:m].copy(), r[m:] != 0.0
-
-    def _weights_ptr(self):
-        """the granule table of the weighted entries (None: the unweighted entries run)"""
-        return None
-
-    def project_out(self, basis, w, passes=2):
-        """(w - V h, h, |w - V h|) with h = V^H w: ONE fused classical Gram-Schmidt call (passes=2: CGS2, h summed over the
-        passes) that updates w in place, and ONE device-to-host copy of the m coefficients and the norm.  A basis of mixed
-        dtypes or longer than the kernel takes runs the modified Gram-Schmidt loop of _TensorOps."""
-        m = len(basis)
-        cplx = w.is_complex()
-        if m > self.MAX_BASIS or any(v.is_complex() != cplx for v in basis):
-            return _mgs(self, basis, w)
-        k = 2 if cplx else 1
-        out = self.bb.ctx.empty(k * m + 1)
-        self._gs(basis, w, passes, out)
-        r = self.bb.ctx.d2h(out, k * m + 1, np.float64)
-        h = (r[0:2 * m:2] + 1j * r[1:2 * m:2]) if cplx else r[:m].copy()
-        return w, h, float(r[k * m])
-
-    MAX_ROTATE = 32    # columns of one cyb_basis_rotate_f64 call
-
-    def rotate(self, basis, Q):
-        """The pools sum_j Q[j, i] basis_j for every column i of the real m x k matrix `Q` (the restart of
-        :class:`LanczosEigenpairs`) by ONE cyb_basis_rotate_f64 call IN PLACE: the results replace basis[0 .. k-1] (which are
-        returned), basis[k:] is untouched; nothing is downloaded.  The matrix is real, so a complex pool is rotated as its
-        2 * total doubles.  More than MAX_ROTATE columns (or more columns than pools): chunks of MAX_ROTATE columns, each one
-        call of the same entry that writes to fresh pools.  A basis longer than the kernel takes runs k ``combine``."""
-        Q = np.ascontiguousarray(Q, dtype=np.float64)
-        m, k = Q.shape
-        if m != len(basis):
-            raise ValueError(f'rotate: {len(basis)} vectors, a matrix of {m} rows')
-        if k == 0:
-            return []
-        cplx = basis[0].is_complex()
-        if any(v.is_complex() != cplx for v in basis):
-            raise _NeedComplex()
-        if m > self.MAX_BASIS:
-            return _TensorOps.rotate(self, basis, Q)
-        words = (2 if cplx else 1) * self.total
-        in_place = k <= min(self.MAX_ROTATE, m)
-        out = []
-        for c0 in range(0, k, self.MAX_ROTATE):
-            Qc = Q if in_place else np.ascontiguousarray(Q[:, c0:c0 + self.MAX_ROTATE])
-            dst = list(basis[:k]) if in_place else [self._alloc(False, cplx) for _ in range(Qc.shape[1])]
-            self._rotate_call(basis, dst, Qc, words)
-            out += dst
-        return out
-
-    def _rotate_call(self, src, dst, Q, words):
-        bb, C = self.bb, self._C
-        bb.ctx.sync_stream()
-        self._lib.check(bb.lib.cyb_basis_rotate_f64(bb.ctx.handle, self._ptrs(src), len(src), self._ptrs(dst), len(dst),
-                                                    Q.ctypes.data_as(C.c_void_p), words))
-
-    # -- BLAS-1 over the flat range
-    def _desc(self, x, y, out, n=None):
-        arr = np.zeros(1, dtype=self._lib.VEC_DTYPE)
-        arr['x'][0] = x.data_ptr()
-        arr['y'][0] = y.data_ptr() if y is not None else 0
-        arr['out'][0] = out.data_ptr() if out is not None else 0
-        arr['n'][0] = self.total if n is None else n
-        return arr
-
-    def _call(self, name, arr, *args):
-        bb = self.bb
-        bb.ctx.sync_stream()
-        self._lib.check(getattr(bb.lib, name)(bb.ctx.handle, arr.ctypes.data_as(self._C.POINTER(self._lib.VecDesc)), 1, *args))
-
-    def combine(self, coeffs, vecs, acc=None):
-        """acc + sum_k coeffs[k] vecs[k] in ONE launch over the flat range (the result assembly of the solvers).  Complex
-        coefficients or pools: the complex linear combination, float64 pools read as real sources (`src_real`), the
-        result a complex pool; `acc` (a complex pool) is updated in place.  Real throughout: the float64 form."""
-        bb, L = self.bb, self._lib
-        cplx = (any(v.is_complex() for v in vecs) or not all(_is_real_scalar(c) for c in coeffs)
-                or (acc is not None and acc.is_complex()))
-        if acc is not None and acc.is_complex() != cplx:
-            acc = self._promote(acc)
-        out = acc if acc is not None else self._alloc(False, cplx)
-        desc = np.zeros(1, dtype=L.LINCOMB_DTYPE)
-        desc['dst'][0] = out.data_ptr()
-        desc['ndim'][0] = 1
-        desc['accumulate'][0] = 1 if acc is not None else 0
-        desc['term_begin'][0], desc['term_end'][0] = 0, len(vecs)
-        desc['shape'][0, 0] = self.total
-        desc['dst_strides'][0, 0] = 1
-        terms = np.zeros(len(vecs), dtype=L.LINTERM_C128_DTYPE if cplx else L.LINTERM_DTYPE)
-        terms['src'] = [v.data_ptr() for v in vecs]
-        terms['src_strides'][:, 0] = 1
-        if cplx:
-            cs = [complex(c) for c in coeffs]
-            terms['coeff_re'] = [c.real for c in cs]
-            terms['coeff_im'] = [c.imag for c in cs]
-            terms['src_real'] = [0 if v.is_complex() else 1 for v in vecs]
-        else:
-            terms['coeff'] = [float(np.real(c)) for c in coeffs]
-        bb.ctx.sync_stream()
-        fn = bb.lib.cyb_lincomb_strided_batched_c128 if cplx else bb.lib.cyb_lincomb_strided_batched_f64
-        T = L.LincombTermC128 if cplx else L.LincombTerm
-        self._lib.check(fn(bb.ctx.handle, desc.ctypes.data_as(self._C.POINTER(L.LincombDesc)), 1,
-                           terms.ctypes.data_as(self._C.POINTER(T)), len(vecs)))
-        return out
-
-    def _promote(self, w):
-        """complex128 copy of a float64 pool."""
-        return self.combine([1.0 + 0.0j], [w])
-
-    def lincomb(self, a, w, b, v):
-        if w.is_complex() != v.is_complex() or (not w.is_complex() and not (_is_real_scalar(a) and _is_real_scalar(b))):
-            return self.combine([a, b], [w, v])
-        out = self._alloc(False, w.is_complex())
-        if w.is_complex():
-            a, b = complex(a), complex(b)
-            self._call('cyb_axpby_batched_c128', self._desc(w, v, out), a.real, a.imag, b.real, b.imag)
-        else:
-            self._call('cyb_axpby_batched_f64', self._desc(w, v, out), float(np.real(a)), float(np.real(b)))
-        return out
-
-    def scale(self, a, w):
-        if not w.is_complex() and not _is_real_scalar(a):
-            return self.combine([a], [w])
-        out = self._alloc(False, w.is_complex())
-        if w.is_complex():
-            a = complex(a)
-            self._call('cyb_axpby_batched_c128', self._desc(w, None, out), a.real, a.imag, 0.0, 0.0)
-        else:
-            self._call('cyb_axpby_batched_f64', self._desc(w, None, out), float(np.real(a)), 0.0)
-        return out
-
-    def inner(self, v, w):
-        """<v, w> = sum conj(v) w: a float on float64 pools, a complex number otherwise (cyb_dot_batched_c128)."""
-        bb = self.bb
-        if not v.is_complex() and not w.is_complex():
-            res = bb.ctx.empty(1)
-            self._call('cyb_dot_batched_f64', self._desc(v, w, None), self._C.c_void_p(res.data_ptr()))
-            return float(bb.ctx.d2h(res, 1, np.float64)[0])
-        v = v if v.is_complex() else self._promote(v)
-        w = w if w.is_complex() else self._promote(w)
-        res = bb.ctx.empty(2)
-        self._call('cyb_dot_batched_c128', self._desc(v, w, None), self._C.c_void_p(res.data_ptr()))
-        re, im = bb.ctx.d2h(res, 2, np.float64)
-        return complex(float(re), float(im))
-
-    def norm(self, w):
-        if not w.is_complex():
-            return float(np.sqrt(self.inner(w, w)))
-        # the float64 reduction over the interleaved storage: sum re^2 + im^2
-        bb = self.bb
-        res = bb.ctx.empty(1)
-        self._call('cyb_dot_batched_f64', self._desc(w, w, None, 2 * self.total), self._C.c_void_p(res.data_ptr()))
-        return float(np.sqrt(bb.ctx.d2h(res, 1, np.float64)[0]))
-
-
-class _FlatTreeOps(_FlatOps):
-    """:class:`_FlatOps` for fusion-tree vectors.  The pool holds the blocks themselves -- ``leave`` stays a list of views and
-    the operator reads and writes plain blocks -- so the inner product sum_c d_c <X_c, Y_c> is not the plain one over the flat
-    range: the reductions (``inner``, ``norm``, the fused Gram-Schmidt step, the multi-dot) are the weighted entries of
-    krylov_vec.hip, which read the quantum dimension of a granule of 256 elements from a table built ONCE per structure and
-    kept on the device (:func:`tree_pool_layout`).  Everything linear (``scale``, ``lincomb``, ``combine``, the multi-axpy) is
-    inherited: it does not see the weights."""
-
-    GRANULE = 256
-
-    def __init__(self, bb, H, template, cplx=False):
-        from .block_backend import _c_strides
-        self._bind(bb, H, template, cplx)
-        self.block_inds, self.shapes, self.offs, self.total, self.weights = tree_pool_layout(template.codomain, template.domain,
-                                                                                             self.GRANULE)
-        self.strides = [_c_strides(sh) for sh in self.shapes]
-        self.key = self.block_inds.tobytes()
-        self.index = None
-        self.support = set()
-        self._wdev = bb.ctx.empty(max(len(self.weights), 1))
-        if len(self.weights):
-            bb.ctx.h2d(self._wdev, self.weights)
-
-    @staticmethod
-    def usable(bb, t) -> bool:
-        return _FlatOps.usable(bb, t) and tree_pool_layout(t.codomain, t.domain)[3] > 0
-
-    def leave(self, buf):
-        idx = None if len(self.support) == len(self.offs) else sorted(self.support)
-        rows = self.block_inds if idx is None else self.block_inds[idx]
-        return self.t.like(ft.FusionTreeData(rows.copy(), self._views(buf, idx)))
-
-    def _wptr(self):
-        return self._C.c_void_p(self._wdev.data_ptr())
-
-    def _weights_ptr(self):
-        return self._wptr()
-
-    def _gs(self, basis, w, passes, out, off=0):
-        bb = self.bb
-        fn = bb.lib.cyb_gram_schmidt_weighted_c128 if w.is_complex() else bb.lib.cyb_gram_schmidt_weighted_f64
-        bb.ctx.sync_stream()
-        self._lib.check(fn(bb.ctx.handle, self._ptrs(basis), len(basis), self._C.c_void_p(w.data_ptr()), self.total, int(passes),
-                           self._wptr(), self._C.c_void_p(out.data_ptr() + 8 * off)))
-
-    def _multi(self, kind, basis, w, h, off=0, alpha=1.0):
-        if kind != 'dot':
-            return super()._multi(kind, basis, w, h, off, alpha)
-        bb, C = self.bb, self._C
-        fn = bb.lib.cyb_multi_dot_weighted_c128 if w.is_complex() else bb.lib.cyb_multi_dot_weighted_f64
-        bb.ctx.sync_stream()
-        self._lib.check(fn(bb.ctx.handle, self._ptrs(basis), len(basis), C.c_void_p(w.data_ptr()), self.total, self._wptr(),
-                           C.c_void_p(h.data_ptr() + 8 * off)))
-
-    def inner(self, v, w):
-        """<v, w> = sum_c d_c sum conj(v_c) w_c: the weighted multi-dot with the basis [v]"""
-        cplx = v.is_complex() or w.is_complex()
-        if cplx:
-            v = v if v.is_complex() else self._promote(v)
-            w = w if w.is_complex() else self._promote(w)
-        k = 2 if cplx else 1
-        res = self.bb.ctx.empty(k)
-        self._multi('dot', [v], w, res)
-        r = self.bb.ctx.d2h(res, k, np.float64)
-        return complex(float(r[0]), float(r[1])) if cplx else float(r[0])
-
-    def norm(self, w):
-        return float(np.sqrt(max(np.real(self.inner(w, w)), 0.0)))
-
-
-class _DirectSumOps(_TensorOps):
-    """:class:`_TensorOps` on direct sums (:class:`direct_sum.DirectSum`): every operation is the componentwise one of
-    :mod:`cyten_amd.direct_sum` -- per-component launches; runs on a numpy stand-in."""
-
-    def norm(self, w):
-        return ds.norm(self.bb, w)
-
-    def inner(self, v, w):
-        return ds.inner(self.bb, v, w)
-
-    def scale(self, a, w):
-        return ds.scale(self.bb, a, w)
-
-    def lincomb(self, a, w, b, v):
-        return ds.linear_combination(self.bb, a, w, b, v)
-
-
-class _PoolPart:
-    """the blocks of one component of a direct-sum pool: positions first .. first + n - 1 of the pool's block list"""
-
-    def __init__(self, first, block_inds):
-        self.first, self.block_inds, self.n = first, block_inds, len(block_inds)
-        self.key = block_inds.tobytes()
-        self.index = None
-
-    def positions(self, block_inds):
-        """pool positions of the blocks of a tensor of this component (_NotFlat: a block the pool does not have)"""
-        if block_inds.tobytes() == self.key:
-            return list(range(self.first, self.first + self.n))
-        if self.index is None:
-            self.index = {tuple(r): self.first + i for i, r in enumerate(self.block_inds.tolist())}
-        try:
-            return [self.index[tuple(r)] for r in block_inds.tolist()]
-        except KeyError:
-            raise _NotFlat()
-
-
-class _FlatDirectSumOps(_FlatTreeOps):
-    """The pool of a direct sum: the pools of its components -- each with the layout it has alone, abelian
-    segments over every charge-allowed block at multiples of 32 elements, tree segments as :func:`tree_pool_layout` -- one
-    after the other in ONE allocation, so that every recurrence, the fused CGS2 step and the projected matvec are the single
-    launches they are for one tensor.  Without a tree component the unweighted entries run over the whole range; with one,
-    every segment starts at a multiple of 256 elements and the weighted entries run with weight 1.0 on the granules of the
-    abelian segments.  Gaps are zero.  With ONE component the pool is byte for byte that of :class:`_FlatOps` /
-    :class:`_FlatTreeOps`.  ``enter`` is one memset and ONE batched copy over the blocks of all components, ``leave`` a
-    direct sum of views; the support is tracked per block, hence per component."""
-
-    def __init__(self, bb, H, template, cplx=False):
-        from .block_backend import _c_strides
-        self._bind(bb, H, template, cplx)
-        self.weighted = any(_is_tree(c) for c in template.components)
-        align = self.GRANULE if self.weighted else 32
-        self.parts, self.shapes, self.offs, weights, tot = [], [], [], [], 0
-        for c in template.components:
-            if _is_tree(c):
-                inds, shapes, offs, n, w = tree_pool_layout(c.codomain, c.domain, self.GRANULE)
-            else:
-                inds = ab.AbelianTensor.allowed_block_inds(c.symmetry, c.legs)
-                shapes = [c.block_shape(r) for r in inds]
-                offs, n = [], 0
-                for sh in shapes:
-                    k = 1
-                    for x in sh:
-                        k *= x
-                    offs.append(n)
-                    n += (k + 31) // 32 * 32
-                n = (n + align - 1) // align * align
-                w = [1.0] * (n // self.GRANULE) if self.weighted else []
-            self.parts.append(_PoolPart(len(self.offs), inds))
-            self.offs += [tot + o for o in offs]
-            self.shapes += list(shapes)
-            weights += list(w)
-            tot += n
-        self.total = tot
-        self.strides = [_c_strides(sh) for sh in self.shapes]
-        self.support = set()
-        self.weights = np.array(weights, dtype=np.float64)
-        if self.weighted:
-            self._wdev = bb.ctx.empty(max(len(self.weights), 1))
-            if len(self.weights):
-                bb.ctx.h2d(self._wdev, self.weights)
-
-    @staticmethod
-    def usable(bb, t) -> bool:
-        return _FlatOps.usable(bb, t)
-
-    def enter(self, x):
-        """direct sum -> pool: one memset + ONE batched copy over the blocks of all components"""
-        if not isinstance(x, ds.DirectSum) or len(x) != len(self.parts):
-            raise _NotFlat()
-        blocks = x.blocks
-        if not self.cplx and any(b.is_complex for b in blocks):
-            raise _NeedComplex()
-        buf = self._alloc(True)
-        pos = [p for part, c in zip(self.parts, x.components) for p in part.positions(c.block_inds)]
-        views = self._views(buf, pos)
-        if any(v.shape != tuple(b.shape) for v, b in zip(views, blocks)):
-            raise _NotFlat()
-        self.support.update(pos)
-        if views:
-            self.bb.copy_many([(v if b.is_complex or not self.cplx else self.bb._plane(v, 0), b) for v, b in zip(views, blocks)])
-        return buf
-
-    def leave(self, buf):
-        comps = []
-        for part, t in zip(self.parts, self.t.components):
-            idx = [p for p in range(part.first, part.first + part.n) if p in self.support]
-            rows = part.block_inds[[p - part.first for p in idx]]
-            views = self._views(buf, idx)
-            if _is_tree(t):
-                comps.append(t.like(ft.FusionTreeData(rows.copy(), views)))
-            else:
-                comps.append(ab.AbelianTensor(t.symmetry, t.legs, views, rows, t.num_codomain, t.labels))
-        return ds.DirectSum(comps)
-
-    def _weights_ptr(self):
-        return self._wptr() if self.weighted else None
-
-    def _gs(self, basis, w, passes, out, off=0):
-        return (_FlatTreeOps if self.weighted else _FlatOps)._gs(self, basis, w, passes, out, off)
-
-    def _multi(self, kind, basis, w, h, off=0, alpha=1.0):
-        return (_FlatTreeOps if self.weighted else _FlatOps)._multi(self, kind, basis, w, h, off, alpha)
-
-    def inner(self, v, w):
-        return (_FlatTreeOps if self.weighted else _FlatOps).inner(self, v, w)
-
-    def norm(self, w):
-        return (_FlatTreeOps if self.weighted else _FlatOps).norm(self, w)
-
-
-def _is_tree(t) -> bool:
-    return isinstance(t, ft.TreeTensor)
-
-
-def _vector_ops(bb, H, template, mode):
-    """The vector operations of a run on vectors like `template`: pools (`mode` False / True: float64 / complex128) or
-    tensors (`mode` None); abelian, fusion-tree or direct-sum by the type of the template."""
-    if isinstance(template, ds.DirectSum):
-        return _FlatDirectSumOps(bb, H, template, mode) if mode is not None else _DirectSumOps(bb, H)
-    if _is_tree(template):
-        return _FlatTreeOps(bb, H, template, mode) if mode is not None else _TreeTensorOps(bb, H)
-    if mode is None:
-        return _TensorOps(bb, H)
-    # pool structure: every block the charge rule allows on these legs (what an operator can create at most)
-    return _FlatOps(bb, H, template, ab.AbelianTensor.allowed_block_inds(template.symmetry, template.legs), mode)
-
-
-def _flat_usable(bb, t) -> bool:
-    if isinstance(t, ds.DirectSum):
-        return _FlatDirectSumOps.usable(bb, t)
-    return _FlatTreeOps.usable(bb, t) if _is_tree(t) else _FlatOps.usable(bb, t)
-
-
-def _mgs(V, basis, w):
-    h = []
-    for v in basis:
-        c = V.inner(v, w)
-        h.append(c)
-        w = V.lincomb(1.0, w, -c, v)
-    return w, np.array(h), V.norm(w)
+                return attempt(self.modes[self.i])
+            except _NeedComplex:
+                self.i += 1
+            except _NotFlat:
+                self.i = len(self.modes) - 1
 
 
 class LanczosGroundState:
@@ -967,29 +313,20 @@ class LanczosGroundState:
         return out
 
     def _solve(self, body):
-        """``body()`` with the recurrences on flat pools where the backend allows it (:class:`_FlatOps`): float64 pools
-        while the start vector and the operator are real, complex128 pools otherwise (a complex vector out of the operator
-        restarts the run on them); a vector that leaves the block structure of psi0 (an operator that creates blocks psi0
-        does not have) restarts it on tensors."""
+        """``body()`` in the first representation of the vectors that holds (:class:`_Fallback`), every ``run`` from the first
+        one again."""
         psi_in = self.psi0
-        flat = bool(self.flat) and _flat_usable(self.bb, psi_in)
         cplx = any(_is_complex_block(b) for b in psi_in.blocks) or bool(getattr(self.H, 'is_complex', False))
-        modes = ([cplx] if cplx else [False, True]) if flat else []
-        modes.append(None)   # tensors
-        i = 0
-        while True:
-            mode = modes[i]
+
+        def attempt(mode):
             self.V = _vector_ops(self.bb, self.H, psi_in, mode)
             self._reset_krylov_state()
             try:
                 self.psi0 = self.V.enter(psi_in)
                 return body()
-            except _NeedComplex:
-                i += 1
-            except _NotFlat:
-                i = len(modes) - 1
             finally:
                 self.psi0 = psi_in     # (the working copy is a pool buffer: a second run() starts from the caller's tensor again)
+        return _Fallback(self.bb, self.flat, psi_in, cplx).run(attempt)
 
     def run(self):
         def body():
@@ -1013,25 +350,33 @@ class LanczosGroundState:
             self._psi0_norm = beta
         performed = 0
         for k in range(self.N_max):
-            w = V.scale(1.0 / beta, w)
-            self._to_cache(w)
-            w = self._matvec(w)
-            alpha = float(np.real(V.inner(w, self._cache[-1])))   # krylov_based.cpp:861: inner(...).real()
+            w, alpha = self._lanczos_step(k, V.scale(1.0 / beta, w), beta)
             self._h[k, k] = alpha
             self._calc_result_krylov(k)
-            w = V.lincomb(1.0, w, -alpha, self._cache[-1])
-            if self.reortho:
-                for v in self._cache[:-1]:
-                    ov = V.inner(v, w)
-                    w = V.lincomb(1.0, w, -ov, v)
-            elif k > 0:
-                w = V.lincomb(1.0, w, -beta, self._cache[-2])
             beta = V.norm(w)
             self._h[k, k + 1] = self._h[k + 1, k] = beta
             performed = k + 1
             if abs(beta) < self.cutoff or (k + 1 >= self.N_min and self._converged(k)):
                 break
         return performed
+
+    def _lanczos_step(self, k, v, beta, alpha=None):
+        """Step k of the three-term recurrence on the normalised v = v_k, which goes to the cache: (H v_k - alpha v_k - beta
+        v_{k-1}, alpha), with full reorthogonalisation against the cache in place of the beta term if `reortho`.  `alpha`
+        None: taken as Re <H v_k, v_k>; given (the rebuild of vectors that fell out of the cache): the recorded one."""
+        V = self.V
+        self._to_cache(v)
+        w = self._matvec(v)
+        if alpha is None:
+            alpha = float(np.real(V.inner(w, self._cache[-1])))   # krylov_based.cpp:861: inner(...).real()
+        w = V.lincomb(1.0, w, -alpha, self._cache[-1])
+        if self.reortho:
+            for u in self._cache[:-1]:
+                ov = V.inner(u, w)
+                w = V.lincomb(1.0, w, -ov, u)
+        elif k > 0:
+            w = V.lincomb(1.0, w, -beta, self._cache[-2])
+        return w, alpha
 
     def _converged(self, k):
         v0k = self._result_krylov[k]
@@ -1072,16 +417,7 @@ class LanczosGroundState:
         w = self.psi0
         beta = 0.0
         for k in range(max(n_rebuild, 0)):
-            self._to_cache(w)
-            w = self._matvec(w)
-            alpha = self._h[k, k]
-            w = V.lincomb(1.0, w, -alpha, self._cache[-1])
-            if self.reortho:
-                for v in self._cache[:-1]:
-                    ov = V.inner(v, w)
-                    w = V.lincomb(1.0, w, -ov, v)
-            elif k > 0:
-                w = V.lincomb(1.0, w, -beta, self._cache[-2])
+            w, _ = self._lanczos_step(k, w, beta, self._h[k, k])
             beta = self._h[k, k + 1]
             w = V.scale(1.0 / beta, w)
             psif = self._add_to_result(psif, vf[k + 1], w)
@@ -1096,52 +432,67 @@ def lanczos(bb, H, psi, options=None):
     return LanczosGroundState(bb, H, psi, options).run()
 
 
-class LanczosEvolution(LanczosGroundState):
-    """exp(delta H) psi0 for a Hermitian ``H`` by Lanczos (krylov_based.cpp:948-1019): the Krylov recurrences of
-    :class:`LanczosGroundState` (real tridiagonal matrix), the small problem solved as exp(delta E) in the eigenbasis of
-    that matrix, converged when the last Krylov coefficient is below P_tol.  With a real ``H`` and a real psi0 the Krylov
-    vectors stay float64 whatever delta; the complex coefficients only enter the result assembly."""
+class _Evolution:
+    """What the two evolution solvers share, mixed in before the eigensolver whose ``_build_krylov`` they run: ``run``, the
+    coefficients of exp(delta H) psi0 in the Krylov basis from the small matrix, normalised, and the convergence test on the
+    last of them.  A solver says how exp(delta h) e_0 is taken (``_small_exp``), how the result is assembled (``_evolved``) and
+    what `normalize` defaults to (``_normalize_default``)."""
 
     def __init__(self, bb, H, psi0, options=None):
         super().__init__(bb, H, psi0, options)
         self._result_norm = 1.0
         self.delta = None
 
+    def _check_run(self):
+        pass
+
     def run(self, delta, normalize=None):
-        """(psi, N).  `normalize` (default: delta.real == 0): return the normalised state, else the state scaled by
+        """(psi, N).  `normalize` None: the solver's default; True: return the normalised state, else the state scaled by
         |psi0| times the norm of the Krylov result, i.e. exp(delta H) psi0 itself."""
+        self._check_run()
         self.delta = delta
-        do_normalize = (complex(delta).real == 0.0) if normalize is None else bool(normalize)
+        do_normalize = self._normalize_default(delta) if normalize is None else bool(normalize)
 
         def body():
             V = self.V
             N = self._build_krylov()
-            if N == 1:
-                res = V.scale(self._result_krylov[0], self.psi0)    # (a phase)
-            else:
-                res = self._calc_result_full(N)
+            res = V.scale(self._result_krylov[0], self.psi0) if N == 1 else self._evolved(N)    # (N == 1: a phase)
             if not do_normalize:
-                res = V.scale((1.0 if self._psi0_norm is None else self._psi0_norm) * self._result_norm, res)
+                res = V.scale(self._psi0_norm * self._result_norm, res)
             return V.leave(res), N
         return self._solve(body)
 
     def _calc_result_krylov(self, k):
-        d = self.delta
         if k == 0:
-            e = np.exp(d * self._h[0, 0])
+            e = np.exp(self.delta * self._h[0, 0])
             self._result_norm = float(abs(e))
             self._result_krylov = np.array([e / self._result_norm])
             return
-        n = k + 1
-        E_kr, v_kr = np.linalg.eigh(self._h[:n, :n])
-        r = v_kr @ (np.exp(E_kr * d) * np.conj(v_kr[0]))
+        r = self._small_exp(self._h[:k + 1, :k + 1], self.delta)
         self._result_norm = float(np.linalg.norm(r))
         self._result_krylov = r / self._result_norm
 
     def _converged(self, k):
         return abs(self._result_krylov[k]) < self.P_tol
 
-    def _calc_result_full(self, N):
+
+class LanczosEvolution(_Evolution, LanczosGroundState):
+    """exp(delta H) psi0 for a Hermitian ``H`` by Lanczos (krylov_based.cpp:948-1019): the Krylov recurrences of
+    :class:`LanczosGroundState` (real tridiagonal matrix), the small problem solved as exp(delta E) in the eigenbasis of
+    that matrix, converged when the last Krylov coefficient is below P_tol.  With a real ``H`` and a real psi0 the Krylov
+    vectors stay float64 whatever delta; the complex coefficients only enter the result assembly.  `normalize` defaults to
+    delta.real == 0."""
+
+    @staticmethod
+    def _normalize_default(delta):
+        return complex(delta).real == 0.0
+
+    @staticmethod
+    def _small_exp(h, d):
+        E_kr, v_kr = np.linalg.eigh(h)
+        return v_kr @ (np.exp(E_kr * d) * np.conj(v_kr[0]))
+
+    def _evolved(self, N):
         """sum_k c_k v_k as ONE combination of psi0 and the cached vectors (krylov_based.cpp:310-341), the vectors that
         fell out of the cache regenerated and added one at a time."""
         V = self.V
@@ -1276,53 +627,31 @@ class Arnoldi(LanczosGroundState):
         return psis
 
 
-class ArnoldiEvolution(Arnoldi):
+class ArnoldiEvolution(_Evolution, Arnoldi):
     """exp(delta H) psi0 for a general ``H`` by Arnoldi (krylov_based.cpp:697-800): the small problem solved through
     numpy.linalg.eig and a linear solve for the start vector's coefficients; converged when the last Krylov coefficient is
     below P_tol.  `normalize` defaults to False."""
 
     def __init__(self, bb, H, psi0, options=None):
         super().__init__(bb, H, psi0, options)
-        self._result_norm = 1.0
-        self.delta = None
-        # (Arnoldi._build_krylov does not record it)
-        self._psi0_norm = _vector_ops(bb, H, psi0, None).norm(psi0)
+        self._psi0_norm = ds.vector_norm(bb, psi0)      # (Arnoldi._build_krylov does not record it)
 
-    def run(self, delta, normalize=None):
+    def _check_run(self):
         if self.N_cache < self.N_max:
             raise ValueError('ArnoldiEvolution requires N_cache >= N_max')
-        self.delta = delta
-        do_normalize = False if normalize is None else bool(normalize)
 
-        def body():
-            V = self.V
-            N = self._build_krylov()
-            res = V.scale(self._result_krylov[0], self.psi0) if N == 1 else self._calc_result_full_evolution(N)
-            if not do_normalize:
-                res = V.scale(self._psi0_norm * self._result_norm, res)
-            return V.leave(res), N
-        return self._solve(body)
+    @staticmethod
+    def _normalize_default(delta):
+        return False
 
-    def _calc_result_krylov(self, k):
-        d = self.delta
-        if k == 0:
-            e = np.exp(d * self._h[0, 0])
-            self._result_norm = float(abs(e))
-            self._result_krylov = np.array([e / self._result_norm])
-            return
-        n = k + 1
-        E_kr, v_kr = np.linalg.eig(self._h[:n, :n])
-        e0 = np.zeros(n, dtype=np.complex128)
+    @staticmethod
+    def _small_exp(h, d):
+        E_kr, v_kr = np.linalg.eig(h)
+        e0 = np.zeros(len(h), dtype=np.complex128)
         e0[0] = 1.0
-        coeff = np.linalg.solve(v_kr, e0)
-        r = v_kr @ (np.exp(E_kr * d) * coeff)
-        self._result_norm = float(np.linalg.norm(r))
-        self._result_krylov = r / self._result_norm
+        return v_kr @ (np.exp(E_kr * d) * np.linalg.solve(v_kr, e0))
 
-    def _converged(self, k):
-        return abs(self._result_krylov[k]) < self.P_tol
-
-    def _calc_result_full_evolution(self, N):
+    def _evolved(self, N):
         V = self.V
         if len(self._cache) < N:
             raise RuntimeError('ArnoldiEvolution: Krylov basis shorter than N')
@@ -1388,7 +717,7 @@ class LanczosEigenpairs(LanczosGroundState):
     def _orthogonalize(self, basis, w):
         V = self.V
         w, h, beta = V.project_out(basis, w, passes=2)
-        if not isinstance(V, _FlatOps):
+        if not V.fused_cgs2:
             # the tensor operations run ONE pass of modified Gram-Schmidt: a second one, as the fused CGS2 step has
             w, h2, beta = V.project_out(basis, w, passes=2)
             h = np.asarray(h) + np.asarray(h2)
@@ -1458,20 +787,7 @@ def eigenvectors(bb, H, psi0, num_ev=1, which='SA', **options):
     return Es, vecs
 
 
-def compatible(a, b) -> bool:
-    """two vectors a solver can combine: direct sums of one length with compatible components, fusion-tree tensors on the
-    same spaces, abelian tensors on the same legs -- never a tensor and a direct sum"""
-    if isinstance(a, ds.DirectSum) or isinstance(b, ds.DirectSum):
-        return ds.compatible(a, b)
-    return _same_legs(a, b)
-
-
-def _same_legs(a, b) -> bool:
-    if _is_tree(a) or _is_tree(b):
-        return (_is_tree(a) and _is_tree(b) and ft.same_space(a.codomain, b.codomain) and ft.same_space(a.domain, b.domain))
-    return len(a.legs) == len(b.legs) and all(
-        x.sign == y.sign and np.array_equal(x.sectors, y.sectors) and np.array_equal(x.mults, y.mults)
-        for x, y in zip(a.legs, b.legs))
+compatible = ds.vectors_compatible     # (GMRES compares x and b with it)
 
 
 class GMRES:
@@ -1508,27 +824,16 @@ class GMRES:
         self.restart = int(o.get('restart', 10))
         self.res = float(o.get('res', 1e-8))
         self.flat = o.get('flat', True)
-        flat = bool(self.flat) and _flat_usable(bb, b)
         cplx = (any(_is_complex_block(t) for v in (x, b) for t in v.blocks) or bool(getattr(A, 'is_complex', False)))
-        self._modes = ([cplx] if cplx else [False, True]) if flat else []
-        self._modes.append(None)   # tensors
-        self._mode_i = 0
-        self._start_any()
+        # kept across run() calls: a second run goes on in the representation the first one ended in
+        self._fallback = _Fallback(bb, self.flat, b, cplx)
+        self._fallback.run(self._start)
 
     # -- state -------------------------------------------------------------------------------------
-    def _start_any(self):
-        """The constructor's work (:375-386) in the first vector representation that holds: pools, else tensors."""
-        while True:
-            try:
-                self._start(self._modes[self._mode_i])
-                return
-            except _NeedComplex:
-                self._mode_i += 1
-            except _NotFlat:
-                self._mode_i = len(self._modes) - 1
-
     def _start(self, mode):
+        """The constructor's work (:375-386) with the vectors in the representation `mode`."""
         bb = self.bb
+        self._mode = mode
         self.V = _vector_ops(bb, self.A, self.b_in, mode)
         V = self.V
         self.x = V.enter(self.x_in)
@@ -1562,14 +867,11 @@ class GMRES:
     def run(self):
         """(x, rel_residual, total_error, total_iters): total_error holds one list per cycle (the residual after the restart,
         then one entry per step), total_iters the steps of each cycle, rel_residual = |A x - b| / |b| recomputed at the end."""
-        while True:
-            try:
-                return self._run()
-            except _NeedComplex:
-                self._mode_i += 1
-            except _NotFlat:
-                self._mode_i = len(self._modes) - 1
-            self._start_any()
+        def attempt(mode):
+            if mode is not self._mode:      # (the representation the state is in did not hold: start again in the next one)
+                self._start(mode)
+            return self._run()
+        return self._fallback.run(attempt)
 
     def _run(self):
         V = self.V

@@ -24,7 +24,7 @@ import numpy as np
 
 from . import abelian as ab
 from . import direct_sum as ds
-from . import fusion_tree as ft
+from .direct_sum import vectors_compatible as _compatible
 
 
 def _is_complex_op(op) -> bool:
@@ -33,35 +33,6 @@ def _is_complex_op(op) -> bool:
 
 def _is_complex_tensor(t) -> bool:
     return any(np.iscomplexobj(b) if isinstance(b, np.ndarray) else bool(b.is_complex) for b in t.blocks)
-
-
-def _inner(bb, a, b):
-    """<a|b> of two vectors of the kind the solvers take: abelian tensors, or fusion-tree tensors (weighted by the quantum
-    dimensions of the codomain), or direct sums of them"""
-    if isinstance(a, ds.DirectSum) or isinstance(b, ds.DirectSum):
-        return ds.inner(bb, a, b)
-    if isinstance(a, ft.TreeTensor):
-        return ft.inner(bb, a.data, b.data, a.codomain, do_dagger=True)
-    return ab.inner(bb, a, b)
-
-
-def _lincomb(bb, a, v, b, w):
-    if isinstance(v, ds.DirectSum) or isinstance(w, ds.DirectSum):
-        return ds.linear_combination(bb, a, v, b, w)
-    if isinstance(v, ft.TreeTensor):
-        return v.like(ft.linear_combination(bb, a, v.data, b, w.data))
-    return ab.linear_combination(bb, a, v, b, w)
-
-
-def _compatible(a, b) -> bool:
-    if isinstance(a, ds.DirectSum) or isinstance(b, ds.DirectSum):
-        return ds.compatible(a, b)
-    if isinstance(a, ft.TreeTensor) or isinstance(b, ft.TreeTensor):
-        return (isinstance(a, ft.TreeTensor) and isinstance(b, ft.TreeTensor) and ft.same_space(a.codomain, b.codomain)
-                and ft.same_space(a.domain, b.domain))
-    return len(a.legs) == len(b.legs) and all(
-        x.sign == y.sign and np.array_equal(x.sectors, y.sectors) and np.array_equal(x.mults, y.mults)
-        for x, y in zip(a.legs, b.legs))
 
 
 def _plain(c):
@@ -108,7 +79,7 @@ class SumLinearOperator(LinearOperatorWrapper):
     def matvec(self, vec):
         res = self.original_operator.matvec(vec)
         for op in self.more_operators:
-            res = _lincomb(self.bb, 1.0, op.matvec(vec), 1.0, res)
+            res = ds.vector_lincomb(self.bb, 1.0, op.matvec(vec), 1.0, res)
         return res
 
     def adjoint(self):
@@ -128,7 +99,7 @@ class ShiftedLinearOperator(LinearOperatorWrapper):
 
     def matvec(self, vec):
         res = self.original_operator.matvec(vec)
-        return _lincomb(self.bb, _plain(self.shift), vec, 1.0, res)
+        return ds.vector_lincomb(self.bb, _plain(self.shift), vec, 1.0, res)
 
     def adjoint(self):
         return ShiftedLinearOperator(self.original_operator.adjoint(), self.shift.conjugate(), self.bb)
@@ -163,19 +134,19 @@ class ProjectedLinearOperator(LinearOperatorWrapper):
         coeffs = []
         if self.project_operator:
             for o in self.ortho_vecs:
-                c = _inner(bb, o, res)
+                c = ds.vector_inner(bb, o, res)
                 coeffs.append(c)
-                res = _lincomb(bb, 1.0, res, _plain(-c), o)
+                res = ds.vector_lincomb(bb, 1.0, res, _plain(-c), o)
         else:
-            coeffs = [_inner(bb, o, res) for o in self.ortho_vecs]
+            coeffs = [ds.vector_inner(bb, o, res) for o in self.ortho_vecs]
         res = self.original_operator.matvec(res)
         if self.project_operator:
             for o in self.ortho_vecs:
-                c = _inner(bb, o, res)
-                res = _lincomb(bb, 1.0, res, _plain(-c), o)
+                c = ds.vector_inner(bb, o, res)
+                res = ds.vector_lincomb(bb, 1.0, res, _plain(-c), o)
         if self.penalty is not None:
             for o, c in zip(self.ortho_vecs, coeffs):
-                res = _lincomb(bb, 1.0, res, _plain(self.penalty * c), o)
+                res = ds.vector_lincomb(bb, 1.0, res, _plain(self.penalty * c), o)
         return res
 
     def adjoint(self):
@@ -255,14 +226,6 @@ class DirectSumLinearOperator:
         return DirectSumLinearOperator([op.adjoint() for op in self.operators], self.bb)
 
 
-def _norm(bb, v):
-    if isinstance(v, ds.DirectSum):
-        return ds.norm(bb, v)
-    if isinstance(v, ft.TreeTensor):
-        return ft.norm(bb, v.data, v.codomain)
-    return ab.norm(bb, v)
-
-
 def gram_schmidt(bb, vecs, rcond: float = 1e-14):
     """The orthonormal vectors of sparse.cpp:420-436 from a list of pairwise compatible vectors (tensors, tree tensors or
     direct sums): a vector is kept iff the norm of what the earlier kept ones leave of it is ``> rcond`` -- strict and absolute,
@@ -287,16 +250,9 @@ def gram_schmidt(bb, vecs, rcond: float = 1e-14):
     res = []
     for v in vecs:
         for o in res:
-            v = _lincomb(bb, _plain(-complex(_inner(bb, o, v))), o, 1.0, v)
-        n = _norm(bb, v)
+            v = ds.vector_lincomb(bb, _plain(-complex(ds.vector_inner(bb, o, v))), o, 1.0, v)
+        n = ds.vector_norm(bb, v)
         if n > rcond:
-            res.append(_scaled(bb, 1.0 / n, v))
+            res.append(ds.vector_scale(bb, 1.0 / n, v))
     return res
 
-
-def _scaled(bb, a, v):
-    if isinstance(v, ds.DirectSum):
-        return ds.scale(bb, a, v)
-    if isinstance(v, ft.TreeTensor):
-        return v.like(ft.mul(bb, a, v.data))
-    return ab.scale(bb, a, v)
