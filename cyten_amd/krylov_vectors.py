@@ -32,6 +32,11 @@ def _is_real_scalar(c) -> bool:
     return not isinstance(c, (complex, np.complexfloating)) or complex(c).imag == 0.0
 
 
+def _negative(c) -> bool:
+    """the real part of the scalar has its sign bit set"""
+    return bool(np.signbit(complex(c).real))
+
+
 def _is_tree(t) -> bool:
     return isinstance(t, ft.TreeTensor)
 
@@ -384,6 +389,8 @@ class _FlatOps:
             for o in O:
                 self._gs([o], res, 1, scratch, 0)
         if op.penalty is not None and m:
+            if not cplx and op.penalty.imag != 0.0:
+                raise _NeedComplex()
             p = op.penalty if cplx else op.penalty.real
             if op.project_operator:
                 for j, o in enumerate(O):
@@ -509,13 +516,15 @@ class _FlatOps:
         bb.ctx.sync_stream()
         self._lib.check(getattr(bb.lib, name)(bb.ctx.handle, arr.ctypes.data_as(self._C.POINTER(self._lib.VecDesc)), 1, *args))
 
-    def combine(self, coeffs, vecs, acc=None):
+    def combine(self, coeffs, vecs, acc=None, cplx=None):
         """acc + sum_k coeffs[k] vecs[k] in ONE launch over the flat range (the result assembly of the solvers).  Complex
         coefficients or pools: the complex linear combination, float64 pools read as real sources (`src_real`), the
-        result a complex pool; `acc` (a complex pool) is updated in place.  Real throughout: the float64 form."""
+        result a complex pool; `acc` of the result's dtype is updated in place, a float64 `acc` under a complex result is
+        left alone (the sum goes to its complex copy).  Real throughout: the float64 form.  `cplx` True: the complex form
+        whatever the coefficients and pools are."""
         bb, L = self.bb, self._lib
-        cplx = (any(v.is_complex() for v in vecs) or not all(_is_real_scalar(c) for c in coeffs)
-                or (acc is not None and acc.is_complex()))
+        cplx = bool(cplx or any(v.is_complex() for v in vecs) or not all(_is_real_scalar(c) for c in coeffs)
+                    or (acc is not None and acc.is_complex()))
         if acc is not None and acc.is_complex() != cplx:
             acc = self._promote(acc)
         out = acc if acc is not None else self._alloc(False, cplx)
@@ -544,11 +553,16 @@ class _FlatOps:
         return out
 
     def _promote(self, w):
-        """complex128 copy of a float64 pool."""
-        return self.combine([1.0 + 0.0j], [w])
+        """complex128 copy of a float64 pool (a complex pool: itself): ONE launch of the complex linear combination with a
+        real source, (1 + 0i) * (x + 0i) added to +0.0 -- the real parts are those of `w`, the imaginary parts +0.0.  The
+        complex form is asked for by name: the coefficient 1 alone is a real scalar and would give a float64 pool."""
+        return w if w.is_complex() else self.combine([1.0], [w], cplx=True)
 
     def lincomb(self, a, w, b, v):
-        if w.is_complex() != v.is_complex() or (not w.is_complex() and not (_is_real_scalar(a) and _is_real_scalar(b))):
+        # (two coefficients with negative real parts: a * 0 + b * 0 is -0.0 in the axpby kernels, and the gaps of a pool stay
+        # +0.0; the linear combination adds its terms to +0.0)
+        if (w.is_complex() != v.is_complex() or (not w.is_complex() and not (_is_real_scalar(a) and _is_real_scalar(b)))
+                or (_negative(a) and _negative(b))):
             return self.combine([a, b], [w, v])
         out = self._alloc(False, w.is_complex())
         if w.is_complex():
@@ -562,11 +576,13 @@ class _FlatOps:
         if not w.is_complex() and not _is_real_scalar(a):
             return self.combine([a], [w])
         out = self._alloc(False, w.is_complex())
+        # a negative real part: a * 0 is -0.0, so the kernel adds 0 * w -- the same values, and the gaps stay +0.0
+        y = w if _negative(a) else None
         if w.is_complex():
             a = complex(a)
-            self._call('cyb_axpby_batched_c128', self._desc(w, None, out), a.real, a.imag, 0.0, 0.0)
+            self._call('cyb_axpby_batched_c128', self._desc(w, y, out), a.real, a.imag, 0.0, 0.0)
         else:
-            self._call('cyb_axpby_batched_f64', self._desc(w, None, out), float(np.real(a)), 0.0)
+            self._call('cyb_axpby_batched_f64', self._desc(w, y, out), float(np.real(a)), 0.0)
         return out
 
     def inner(self, v, w):
