@@ -1241,6 +1241,9 @@ int cyb_complex_expand_batched_f64(cyb_ctx_t ctx, const cyb_cexpand_desc* descs,
         CYB_REQUIRE(d.K >= 0 && d.N >= 0, "complex expand desc %lld: negative extent", (long long)i);
         totals[(size_t)i] = d.K * d.N;
         CYB_REQUIRE(totals[(size_t)i] == 0 || (d.src && d.dst), "complex expand desc %lld: NULL pointer", (long long)i);
+        // the kernel loads and stores whole (re, im) pairs as 16-byte accesses
+        CYB_REQUIRE(totals[(size_t)i] == 0 || ((((uintptr_t)d.src) | ((uintptr_t)d.dst)) & 15) == 0,
+                    "complex expand desc %lld: src and dst must be 16-byte aligned", (long long)i);
         hd[(size_t)i] = CExpandDev{d.src, d.rs, d.cs, d.K, d.N, d.dst};
     }
     std::vector<Item> items;

@@ -18,7 +18,7 @@
  *  - All work is enqueued on the context's HIP stream and is asynchronous with
  *    respect to the host unless stated otherwise.
  *  - fp64 is the arithmetic type of the hot path (BASELINE.json).  Data
- *    movement entry points are byte-size generic (elem_size 1..16).
+ *    movement entry points are byte-size generic (elem_size 1, 4, 8, 16).
  *  - DTYPE RESTRICTION (deliberate).  The reference's Dtype set is bool, int64,
  *    float32, complex64, float64, complex128 (include/cyten/block_backend/
  *    dtypes.h:12-21).  Arithmetic entry points exist for float64 (`_f64`) and
@@ -234,7 +234,10 @@ int cyb_eigh_batched_ex_f64(cyb_ctx_t ctx, const cyb_eigh_desc* descs, int64_t n
 /* ---- data movement: strided N-d copies (permute_axes / reshape-copy / get_item / set_item,
  *      combine_legs / split_legs sub-block scatter/gather) ------------------------------------
  * dst[sum_d i_d*dst_strides[d]] = src[sum_d i_d*src_strides[d]]  for i_d in [0, shape[d]).
- * Strides in elements of elem_size bytes (1,2,4,8,16). ndim <= CYB_MAX_NDIM. Replaces the numpy
+ * Strides in elements of elem_size bytes (1, 4, 8 or 16; any other size is CYB_ERR_INVALID); dst and src are
+ * aligned to elem_size.  A stride may be 0 (a broadcast read on the source side) or negative; a destination
+ * whose strides make two index tuples meet at one address is the caller's error and is not checked.
+ * ndim <= CYB_MAX_NDIM. Replaces the numpy
  * views of numpy.cpp:924-931 (permute_axes), :1057-1064 (reshape) once a contiguous result is
  * needed, and the `new_block[slices] = combined` scatter of abelian.cpp:1212-1214 /
  * `old_block[slices]` gather of abelian.cpp:3414-3427.  The whole list is one launch. */
@@ -326,7 +329,8 @@ int cyb_allclose_count(cyb_ctx_t ctx, const double* x, const double* y, int64_t 
                        uint64_t* result_dev);
 
 /* out[i, j, k] = x[i, j, k] * f[j]  for a block viewed as (outer, axis, inner), contiguous.
- * Replaces scale_axis (numpy.cpp:1373-1385). */
+ * Replaces scale_axis (numpy.cpp:1373-1385).  In place (out == x) is supported: every element is read and
+ * written by the same thread.  Any other overlap of out with x or f is the caller's error. */
 typedef struct {
     const double* x;
     const double* f;
@@ -355,10 +359,11 @@ int cyb_mask_scatter_batched_f64(cyb_ctx_t ctx, const cyb_mask_desc* descs, int6
  * as a real M x 2N matrix, and B is expanded once into the real 2K x 2N matrix [[br, bi], [-bi, br]] per element
  * (cyb_complex_expand_batched_f64).  Decompositions of complex blocks: the *_c128 entries further down. */
 typedef struct cyb_cexpand_desc {
-    const double* src; /* complex K x N view, element (k, n) at src + 2*(k*rs + n*cs) */
+    const double* src; /* complex K x N view, element (k, n) at src + 2*(k*rs + n*cs); 16-byte aligned */
     int64_t rs, cs;    /* strides in complex elements */
     int64_t K, N;
-    double* dst;       /* 2K x 2N doubles, row-major, contiguous */
+    double* dst;       /* 2K x 2N doubles, row-major, contiguous; 16-byte aligned.  A src or dst that is not
+                          16-byte aligned is refused with CYB_ERR_INVALID (unless K * N == 0) */
 } cyb_cexpand_desc;
 int cyb_complex_expand_batched_f64(cyb_ctx_t ctx, const cyb_cexpand_desc* descs, int64_t n);
 /* out = a*x + b*y on complex vectors of desc.n complex elements (y may be NULL): Block::operator+ / mul /
