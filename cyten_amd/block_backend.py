@@ -26,7 +26,9 @@ import numpy as np
 
 from . import _lib
 from . import decomp as _decomp
+from . import tree_records as _rec
 from .runtime import Context, get_context
+from .tree_records import DeviceIndex, c_strides as _c_strides
 
 __all__ = ['HipBlock', 'Scalar', 'HipBlockBackend', 'GemmPlan', 'DeviceIndex']
 
@@ -51,20 +53,6 @@ def _norm_dtype(dtype) -> np.dtype:
 
 
 _ZERO_PAD = [(0,) * (_lib.CYB_MAX_NDIM - k) for k in range(_lib.CYB_MAX_NDIM + 1)]
-
-
-@functools.lru_cache(maxsize=16384)
-def _c_strides_cached(shape):
-    st, acc = [], 1
-    for s in reversed(shape):
-        st.append(acc)
-        acc *= max(int(s), 1)
-    return tuple(reversed(st))
-
-
-def _c_strides(shape):
-    """C-order element strides of `shape` (block shapes repeat: memoised)."""
-    return _c_strides_cached(shape if type(shape) is tuple else tuple(int(x) for x in shape))
 
 
 def _nocopy_reshape_strides(shape, strides, new_shape):
@@ -426,16 +414,6 @@ class Scalar:
         return Scalar(self._blk.backend._pow(self._blk, e))
 
     __pow__ = pow
-
-
-class DeviceIndex:
-    """`n` ascending int64 positions in device memory at `ptr` (one sector's kept singular values as written by
-    ``truncate_select``); accepted by ``mask_gather_many`` in place of a host mask.  `owner` keeps the table alive."""
-
-    __slots__ = ('ptr', 'n', 'owner')
-
-    def __init__(self, ptr, n, owner):
-        self.ptr, self.n, self.owner = int(ptr), int(n), owner
 
 
 class GemmPlan:
@@ -1218,13 +1196,7 @@ class HipBlockBackend:
         return self.enlarge_leg_many([(block, mask, axis)])[0]
 
     # ------------------------------------------------------------------ BLAS-1 class ops
-    @staticmethod
-    def _numeric_only(blocks, what):
-        """The float64 / complex128 kernels address 8-byte words: a boolean block (1-byte storage) must be converted with
-        ``to_dtype`` first -- fail loudly instead of reading past its buffer."""
-        for b in blocks:
-            if b is not None and b.is_bool:
-                raise TypeError(f'{what}: boolean block where a float64 / complex128 block is required (use to_dtype)')
+    _numeric_only = staticmethod(_rec.numeric_only)
 
     def _vec_descs(self, xs, ys=None, outs=None):
         self._numeric_only(xs, 'elementwise / reduction kernel')
@@ -1492,17 +1464,29 @@ class HipBlockBackend:
         return self.scale_axis_many([(block, factors, axis)])[0]
 
     # ------------------------------------------------------------------ tree blocks of fusion-tree tensors
-    @staticmethod
-    def _tree_view(blk: HipBlock, side: int, what: str):
-        """(stride of the tree index, stride of the other index, extent of the other index) of a coupled block whose tree
-        blocks are row ranges (side 0, codomain) or column ranges (side 1, domain); a 1-D block is a one-column matrix"""
-        if blk.ndim == 1:
-            if side != 0:
-                raise ValueError(f'tree_axis_many: a 1-D {what} block has a codomain side only')
-            return blk.strides[0], 0, 1
-        if blk.ndim != 2:
-            raise ValueError(f'tree_axis_many: {what} blocks are coupled blocks (2-D) or diagonal blocks (1-D)')
-        return (blk.strides[0], blk.strides[1], blk.shape[1]) if side == 0 else (blk.strides[1], blk.strides[0], blk.shape[0])
+    # Every method below is the device-side preparation it needs, its packer in :mod:`cyten_amd.tree_records` (all checks and
+    # all stride arithmetic, host only) and one launch.
+    def _upload(self, host):
+        """a contiguous host array as a device buffer of its dtype: (its address, the buffer, which keeps it alive)"""
+        buf = self.ctx.empty(host.size, host.dtype.name)
+        self.ctx.h2d(buf, host)
+        return buf.data_ptr(), buf
+
+    def _launch_records(self, launch):
+        """the one launch of a :class:`tree_records.Launch` (``None``: nothing to do)"""
+        if launch is None:
+            return
+        fn = getattr(self.lib, f'{launch.stem}_{"c128" if launch.cplx else "f64"}')
+        self.ctx.sync_stream()
+        args = [x for arr, struct, n in launch.arrays for x in (arr.ctypes.data_as(C.POINTER(struct)), n)]
+        _lib.check(fn(self.ctx.handle, *args, *launch.tail))
+
+    def _widen_mixed(self, *lists):
+        """the block lists of a reduction, their float64 blocks widened where a block of the call is complex (a boolean
+        block is left as it is, for the packer to refuse)"""
+        if not any(x.is_complex for blocks in lists if blocks is not None for x in blocks):
+            return lists
+        return tuple(blocks and [x if x.is_bool else self.as_complex(x) for x in blocks] for blocks in lists)
 
     def tree_axis_many(self, records, mode, fill=()):
         """scale / gather / scatter along one leg of tree blocks, ONE launch for all `records` of a tensor operation
@@ -1514,77 +1498,13 @@ class HipBlockBackend:
         ('gather' / 'scatter') as a host int64 array or a :class:`DeviceIndex`.  Host tables are uploaded once,
         concatenated.  `fill`: blocks (contiguous) the launch sets to zero first.  The destinations decide the entry:
         all float64, or all complex128 (a float64 source is then widened in the kernel)."""
-        if mode not in _lib.TREE_AXIS_MODES:
-            raise ValueError(f'tree_axis_many: unknown mode {mode!r}')
-        records, fill = list(records), list(fill)
-        self._numeric_only([r.src for r in records] + [r.dst for r in records] + fill, 'tree_axis_many')
-        kinds = {r.dst.is_complex for r in records} | {b.is_complex for b in fill}
-        if len(kinds) > 1:
-            raise ValueError('tree_axis_many: the destination blocks of one call share one dtype')
-        cplx = bool(kinds and kinds.pop())
-        n = len(records)
-        arr = np.zeros(max(n, 1), dtype=_lib.TREE_AXIS_DTYPE)
-        keep = []
-        if mode == 'scale':
-            tables = [None] * n
+        records = list(records)
+        if mode == 'scale':      # the kernel reads the factors with the stride 1: a strided vector is copied first
             for i, r in enumerate(records):
                 f = r.table
-                if f.is_bool or f.ndim != 1 or f.shape[0] != r.A:
-                    raise ValueError('tree_axis_many: the factors of a record are a 1-D numeric block of A entries')
-                if f.is_complex and not cplx:
-                    raise ValueError('tree_axis_many: complex factors need complex destination blocks')
-                if f.strides[0] != 1 and f.shape[0] > 1:
-                    f = self.contiguous(f)
-                    keep.append(f)
-                tables[i] = (f.ptr, 1 if f.is_complex else 0)
-        else:
-            host = [np.ascontiguousarray(r.table, dtype=np.int64) for r in records if not isinstance(r.table, DeviceIndex)]
-            offs = np.concatenate([[0], np.cumsum([len(x) for x in host])]).astype(np.int64)
-            didx = None
-            if offs[-1]:     # (nothing is allocated or uploaded when every table already is on the device)
-                didx = self.ctx.empty(int(offs[-1]), 'int64')
-                self.ctx.h2d(didx, np.concatenate(host))
-                keep.append(didx)
-            base = didx.data_ptr() if didx is not None else 0
-            tables, h = [None] * n, 0
-            for i, r in enumerate(records):
-                if isinstance(r.table, DeviceIndex):
-                    ptr, cnt = r.table.ptr, r.table.n
-                else:
-                    ptr, cnt = (base + 8 * int(offs[h]) if len(host[h]) else 0), len(host[h])
-                    large = r.A if mode == 'gather' else r.A_dst
-                    if len(host[h]) and not (0 <= host[h].min() and host[h].max() < large):
-                        raise ValueError('tree_axis_many: a kept position lies outside the large leg')
-                    h += 1
-                if cnt != (r.A_dst if mode == 'gather' else r.A):
-                    raise ValueError('tree_axis_many: the table of a record does not match its small extent')
-                tables[i] = (ptr, 0)
-        for i, r in enumerate(records):
-            s_ts, s_xs, X = self._tree_view(r.src, r.side, 'source')
-            d_ts, d_xs, Xd = self._tree_view(r.dst, r.side, 'destination')
-            if X != Xd:
-                raise ValueError('tree_axis_many: source and destination differ in the extent of the other index')
-            if r.src.is_complex and not cplx:
-                raise ValueError('tree_axis_many: a complex source needs complex destination blocks')
-            ext_s, ext_d = r.outer * r.A * r.inner, r.outer * r.A_dst * r.inner
-            if min(r.src_start, r.dst_start, r.outer, r.A, r.A_dst, r.inner) >= 0 and (
-                    r.src_start + ext_s > r.src.shape[r.side if r.src.ndim == 2 else 0]
-                    or r.dst_start + ext_d > r.dst.shape[r.side if r.dst.ndim == 2 else 0]):
-                raise ValueError('tree_axis_many: a tree block reaches beyond its coupled block')
-            arr[i] = (r.src.ptr, r.dst.ptr, tables[i][0], s_ts, s_xs, d_ts, d_xs, r.src_start, r.dst_start, X, r.outer, r.A, r.A_dst,
-                      r.inner, _lib.TREE_AXIS_MODES[mode], 0 if r.src.is_complex else 1, tables[i][1], 0)
-        fills = np.zeros(max(len(fill), 1), dtype=_lib.TREE_FILL_DTYPE)
-        for i, b in enumerate(fill):
-            if not b.is_contiguous():
-                raise ValueError('tree_axis_many: only contiguous blocks can be zero-filled')
-            fills[i] = (b.ptr, b.size * (16 if b.is_complex else 8))
-        if not n and not fill:
-            return
-        fn = self.lib.cyb_tree_axis_c128 if cplx else self.lib.cyb_tree_axis_f64
-        self.ctx.sync_stream()
-        _lib.check(fn(self.ctx.handle, arr.ctypes.data_as(C.POINTER(_lib.TreeAxisRec)), n,
-                      fills.ctypes.data_as(C.POINTER(_lib.TreeFill)), len(fill)))
-        del keep
+                if len(f.strides) == 1 and f.strides[0] != 1 and f.shape[0] > 1 and not f.is_bool:
+                    records[i] = r._replace(table=self.contiguous(f))
+        self._launch_records(_rec.pack_axis(records, mode, fill, upload=self._upload))
 
     def tree_trace_many(self, outputs):
         """Weighted partial traces into strided tiles, ONE descriptor upload and ONE launch for all result blocks of a
@@ -1597,73 +1517,7 @@ class HipBlockBackend:
         source is then read as it stands, no promotion pass).  More than ``CYB_MAX_NDIM`` source axes or more than
         ``CYB_TRACE_MAX_PAIRS`` pairs: ValueError.  Fixed summation order, bit-identical from run to run
         (csrc/tree_trace.hip)."""
-        outputs = [(dst, list(terms)) for dst, terms in outputs]
-        if not outputs:
-            return
-        dsts = [dst for dst, _ in outputs]
-        srcs = [tm[0] for _, terms in outputs for tm in terms]
-        cplx = self._tree_entry('tree_trace_many', dsts, srcs)
-        nd_max, np_max = _lib.CYB_MAX_NDIM, _lib.CYB_TRACE_MAX_PAIRS
-        zeros_nd, zeros_np = (0,) * nd_max, (0,) * np_max
-        o_first, o_n, o_shape, o_str = [], [], [], []
-        t_re, t_im, t_real, t_pairs, t_rem, t_ext, t_str = [], [], [], [], [], [], []
-        for dst, terms in outputs:
-            shape = dst.shape
-            if len(shape) > nd_max:
-                raise ValueError(f'tree_trace_many: a destination view with more than {nd_max} axes')
-            o_first.append(len(t_pairs))
-            o_n.append(len(terms))
-            o_shape.append((shape + zeros_nd)[:nd_max])
-            o_str.append((dst.strides + zeros_nd)[:nd_max])
-            for a, idcs1, idcs2, remaining, coeff in terms:
-                nd = a.ndim
-                if len(idcs1) > np_max:
-                    raise ValueError(f'tree_trace_many: more than {np_max} traced pairs')
-                if nd > nd_max:
-                    raise ValueError(f'tree_trace_many: a source view with more than {nd_max} axes')
-                idcs1, idcs2, remaining = [i % nd for i in idcs1], [i % nd for i in idcs2], [i % nd for i in remaining]
-                if len(idcs1) != len(idcs2) or sorted(idcs1 + idcs2 + remaining) != list(range(nd)):
-                    raise ValueError('tree_trace_many: idcs1, idcs2 and remaining_idcs must list every axis once, in pairs')
-                sh, st = a.shape, a.strides
-                if any(sh[p] != sh[q] for p, q in zip(idcs1, idcs2)):
-                    raise ValueError('tree_trace_many: traced legs do not match')
-                if tuple(sh[k] for k in remaining) != shape:
-                    raise ValueError(f'tree_trace_many: remaining axes {tuple(sh[k] for k in remaining)} of a term do not have the '
-                                     f'shape {shape} of its destination view')
-                coeff = complex(coeff)
-                if not cplx and (a.is_complex or coeff.imag != 0):
-                    raise ValueError('tree_trace_many: a complex source or coefficient needs complex destination views')
-                t_re.append(coeff.real)
-                t_im.append(coeff.imag)
-                t_real.append(0 if a.is_complex or not cplx else 1)
-                t_pairs.append(len(idcs1))
-                t_rem.append((tuple(st[k] for k in remaining) + zeros_nd)[:nd_max])
-                t_ext.append((tuple(sh[p] for p in idcs1) + zeros_np)[:np_max])
-                t_str.append((tuple(st[p] + st[q] for p, q in zip(idcs1, idcs2)) + zeros_np)[:np_max])
-        oarr = np.zeros(len(outputs), dtype=_lib.TRACE_WEIGHTED_OUT_DTYPE)
-        oarr['dst'], oarr['ndim'] = [d.ptr for d in dsts], [d.ndim for d in dsts]
-        oarr['first_term'], oarr['n_terms'], oarr['shape'], oarr['dst_strides'] = o_first, o_n, o_shape, o_str
-        n_t = len(srcs)
-        tarr = np.zeros(max(n_t, 1), dtype=_lib.TRACE_WEIGHTED_TERM_DTYPE)
-        if n_t:
-            tarr['src'], tarr['coeff_re'], tarr['coeff_im'], tarr['src_real'] = [a.ptr for a in srcs], t_re, t_im, t_real
-            tarr['n_pairs'], tarr['rem_strides'], tarr['pair_extent'], tarr['pair_stride'] = t_pairs, t_rem, t_ext, t_str
-        fn = self.lib.cyb_trace_weighted_c128 if cplx else self.lib.cyb_trace_weighted_f64
-        self.ctx.sync_stream()
-        _lib.check(fn(self.ctx.handle, oarr.ctypes.data_as(C.POINTER(_lib.TraceWeightedOut)), len(outputs),
-                      tarr.ctypes.data_as(C.POINTER(_lib.TraceWeightedTerm)), n_t))
-
-    def _tree_entry(self, what, dsts, srcs, ndim_error=None):
-        """What the ``tree_*_many`` methods ask of their views before they look at one: no boolean view; `ndim_error`, the
-        complaint about views with the wrong number of axes where there are some; destination views of one dtype.  Returns
-        whether the call takes the complex128 entry."""
-        self._numeric_only(dsts + srcs, what)
-        if ndim_error:
-            raise ValueError(f'{what}: {ndim_error}')
-        kinds = {d.is_complex for d in dsts}
-        if len(kinds) > 1:
-            raise ValueError(f'{what}: the destination views of one call share one dtype')
-        return kinds.pop()
+        self._launch_records(_rec.pack_trace(outputs))
 
     def tree_outer_many(self, outputs):
         """Weighted Kronecker products into strided tiles, ONE descriptor upload and ONE launch for all result blocks of a
@@ -1675,53 +1529,7 @@ class HipBlockBackend:
         ``dst[ra * hb + rb, ca * wb + cb] = sum_terms coeff * a[ra, ca] * b[rb, cb]``, zeros without a term.  The destinations
         decide the entry: all float64 (real sources, real coefficients) or all complex128 (a float64 source is then read as
         it stands, no promotion pass).  Fixed summation order, bit-identical from run to run (csrc/tree_outer.hip)."""
-        outputs = [(dst, list(terms)) for dst, terms in outputs]
-        if not outputs:
-            return
-        dsts = [dst for dst, _ in outputs]
-        a_srcs = [tm[0] for _, terms in outputs for tm in terms]
-        b_srcs = [tm[1] for _, terms in outputs for tm in terms]
-        cplx = self._tree_entry('tree_outer_many', dsts, a_srcs + b_srcs,
-                                any(x.ndim != 2 for x in dsts + a_srcs + b_srcs) and 'destinations and sources are 2-D views')
-        o_ext, o_ldd, o_first, o_n, t_re, t_im = [], [], [], [], [], []
-        for dst, terms in outputs:
-            H, W = dst.shape
-            if dst.strides[1] != 1 and W > 1:
-                raise ValueError('tree_outer_many: a destination view needs the column stride 1')
-            ext = (H, 1, 1, W)          # (an output without terms: zeros, whatever the factorisation)
-            for k, (a, b, coeff) in enumerate(terms):
-                e = (a.shape[0], b.shape[0], a.shape[1], b.shape[1])
-                if k and e != ext:
-                    raise ValueError(f'tree_outer_many: the terms of one output differ in their extents, {ext} and {e}')
-                ext = e
-                if (e[0] * e[1], e[2] * e[3]) != (H, W):
-                    raise ValueError(f'tree_outer_many: a destination view of shape {(H, W)} for sources of the shapes '
-                                     f'{tuple(a.shape)} and {tuple(b.shape)}')
-                coeff = complex(coeff)
-                if not cplx and (a.is_complex or b.is_complex or coeff.imag != 0):
-                    raise ValueError('tree_outer_many: a complex source or coefficient needs complex destination views')
-                t_re.append(coeff.real)
-                t_im.append(coeff.imag)
-            o_first.append(len(t_re) - len(terms))
-            o_n.append(len(terms))
-            o_ext.append(ext)
-            o_ldd.append(dst.strides[0] if H > 1 else W)
-        oarr = np.zeros(len(outputs), dtype=_lib.OUTER_WEIGHTED_OUT_DTYPE)
-        ext = np.array(o_ext, dtype=np.int64).reshape(len(outputs), 4)
-        oarr['dst'], oarr['ha'], oarr['hb'], oarr['wa'], oarr['wb'] = [d.ptr for d in dsts], ext[:, 0], ext[:, 1], ext[:, 2], ext[:, 3]
-        oarr['ldd'], oarr['first_term'], oarr['n_terms'] = o_ldd, o_first, o_n
-        n_t = len(a_srcs)
-        tarr = np.zeros(max(n_t, 1), dtype=_lib.OUTER_WEIGHTED_TERM_DTYPE)
-        if n_t:
-            tarr['a'], tarr['b'], tarr['coeff_re'], tarr['coeff_im'] = [a.ptr for a in a_srcs], [b.ptr for b in b_srcs], t_re, t_im
-            tarr['a_real'] = [0 if a.is_complex or not cplx else 1 for a in a_srcs]
-            tarr['b_real'] = [0 if b.is_complex or not cplx else 1 for b in b_srcs]
-            tarr['a_rs'], tarr['a_cs'] = [a.strides[0] for a in a_srcs], [a.strides[1] for a in a_srcs]
-            tarr['b_rs'], tarr['b_cs'] = [b.strides[0] for b in b_srcs], [b.strides[1] for b in b_srcs]
-        fn = self.lib.cyb_outer_weighted_c128 if cplx else self.lib.cyb_outer_weighted_f64
-        self.ctx.sync_stream()
-        _lib.check(fn(self.ctx.handle, oarr.ctypes.data_as(C.POINTER(_lib.OuterWeightedOut)), len(outputs),
-                      tarr.ctypes.data_as(C.POINTER(_lib.OuterWeightedTerm)), n_t))
+        self._launch_records(_rec.pack_outer(outputs))
 
     def tree_compose_many(self, outputs):
         """Weighted short contractions into strided tiles, ONE descriptor upload and ONE launch for all result blocks of a
@@ -1735,65 +1543,7 @@ class HipBlockBackend:
         differ from term to term; an output without terms becomes zeros.  The destinations decide the entry: all float64 (real
         sources, real coefficients) or all complex128 (a float64 source is then read as it stands, no promotion pass).  Fixed
         summation order, bit-identical from run to run (csrc/tree_compose.hip)."""
-        outputs = [(dst, side, int(m0), int(m2), list(terms)) for dst, side, m0, m2, terms in outputs]
-        if not outputs:
-            return
-        dsts = [o[0] for o in outputs]
-        a_srcs = [tm[0] for o in outputs for tm in o[4]]
-        b_srcs = [tm[1] for o in outputs for tm in o[4]]
-        cplx = self._tree_entry('tree_compose_many', dsts, a_srcs + b_srcs,
-                                any(x.ndim != 2 for x in dsts + a_srcs + b_srcs) and 'destinations and sources are 2-D views')
-        o_ext, o_sd, o_axis, o_first, o_n = [], [], [], [], []
-        t_re, t_im, t_K, t_sa, t_bn, t_bk = [], [], [], [], [], []
-        for dst, side, m0, m2, terms in outputs:
-            if side not in ('domain', 'codomain'):
-                raise ValueError(f"tree_compose_many: side is 'domain' or 'codomain', not {side!r}")
-            dom = side == 'domain'
-            H, W = dst.shape
-            if dst.strides[1] != 1 and W > 1:
-                raise ValueError('tree_compose_many: a destination view needs the column stride 1')
-            other, mine = (H, W) if dom else (W, H)          # the untouched extent, the extent m0 * N * m2
-            N = mine // (m0 * m2) if m0 > 0 and m2 > 0 else 0
-            if m0 < 0 or m2 < 0 or m0 * N * m2 != mine:
-                raise ValueError(f'tree_compose_many: a destination view of shape {(H, W)} does not factor as m0 * N * m2 with '
-                                 f'm0 = {m0}, m2 = {m2} in the {side}')
-            ldd = dst.strides[0]
-            for a, b, coeff in terms:
-                K = b.shape[0] if dom else b.shape[1]
-                want_a = (other, m0 * K * m2) if dom else (m0 * K * m2, other)
-                want_b = (K, N) if dom else (N, K)
-                if tuple(a.shape) != want_a or tuple(b.shape) != want_b:
-                    raise ValueError(f'tree_compose_many: a destination view of shape {(H, W)} with m0 = {m0}, m2 = {m2} in the {side} '
-                                     f'for sources of the shapes {tuple(a.shape)} and {tuple(b.shape)}')
-                coeff = complex(coeff)
-                if not cplx and (a.is_complex or b.is_complex or coeff.imag != 0):
-                    raise ValueError('tree_compose_many: a complex source or coefficient needs complex destination views')
-                ars, acs = a.strides
-                t_re.append(coeff.real)
-                t_im.append(coeff.imag)
-                t_K.append(K)
-                t_sa.append((ars, K * m2 * acs, m2 * acs, acs) if dom else (K * m2 * ars, m2 * ars, ars, acs))
-                t_bn.append(b.strides[1] if dom else b.strides[0])
-                t_bk.append(b.strides[0] if dom else b.strides[1])
-            o_first.append(len(t_re) - len(terms))
-            o_n.append(len(terms))
-            o_ext.append((other, m0, N, m2) if dom else (m0, N, m2, other))
-            o_sd.append((ldd, N * m2, m2, 1) if dom else (N * m2 * ldd, m2 * ldd, ldd, 1))
-            o_axis.append(2 if dom else 1)
-        oarr = np.zeros(len(outputs), dtype=_lib.COMPOSE_WEIGHTED_OUT_DTYPE)
-        oarr['dst'], oarr['ext'], oarr['sd'], oarr['axis'] = [d.ptr for d in dsts], o_ext, o_sd, o_axis
-        oarr['first_term'], oarr['n_terms'] = o_first, o_n
-        n_t = len(a_srcs)
-        tarr = np.zeros(max(n_t, 1), dtype=_lib.COMPOSE_WEIGHTED_TERM_DTYPE)
-        if n_t:
-            tarr['a'], tarr['b'], tarr['coeff_re'], tarr['coeff_im'] = [a.ptr for a in a_srcs], [b.ptr for b in b_srcs], t_re, t_im
-            tarr['a_real'] = [0 if a.is_complex or not cplx else 1 for a in a_srcs]
-            tarr['b_real'] = [0 if b.is_complex or not cplx else 1 for b in b_srcs]
-            tarr['K'], tarr['sa'], tarr['b_ns'], tarr['b_ks'] = t_K, t_sa, t_bn, t_bk
-        fn = self.lib.cyb_compose_weighted_c128 if cplx else self.lib.cyb_compose_weighted_f64
-        self.ctx.sync_stream()
-        _lib.check(fn(self.ctx.handle, oarr.ctypes.data_as(C.POINTER(_lib.ComposeWeightedOut)), len(outputs),
-                      tarr.ctypes.data_as(C.POINTER(_lib.ComposeWeightedTerm)), n_t))
+        self._launch_records(_rec.pack_compose(outputs))
 
     def tree_place_many(self, records):
         """Weighted strided window copies, ONE descriptor upload and ONE launch for all result blocks of a fusion-tree
@@ -1807,37 +1557,7 @@ class HipBlockBackend:
         the window becomes zeros.  The destinations decide the entry: all float64 (real sources, real coefficients) or all
         complex128 (a float64 source is then read as it stands, no promotion pass).  ``coeff == 1`` copies bits; every element
         has one owner, bit-identical from run to run (csrc/tree_place.hip)."""
-        what = 'tree_place_many'
-        records = [(dst, src, int(n_row), complex(coeff)) for dst, src, n_row, coeff in records]
-        if not records:
-            return
-        dsts = [r[0] for r in records]
-        cplx = self._tree_entry(what, dsts, [r[1] for r in records if r[1] is not None],
-                                any(d.ndim != 3 for d in dsts) and 'destinations are 3-D views (rows, runs, columns of a run)')
-        nl = _lib.CYB_TREE_PLACE_MAX_LEVELS
-        pad = (0,) * nl
-        arr = np.zeros(len(records), dtype=_lib.TREE_PLACE_DTYPE)
-        for i, (dst, src, n_row, coeff) in enumerate(records):
-            h, nq, wn = dst.shape
-            if dst.strides[2] != 1 and wn > 1:
-                raise ValueError(f'{what}: a destination view needs the stride 1 on its last axis')
-            if src is None:
-                arr[i] = (dst.ptr, 0, h, nq, wn, dst.strides[1], dst.strides[0], 0, 0, pad, pad, pad, pad, 0.0, 0.0, 0, 0)
-                continue
-            n_col = src.ndim - n_row
-            if not (0 <= n_row <= nl and 0 <= n_col <= nl):
-                raise ValueError(f'{what}: a source view with {n_row} row axes and {n_col} column axes, at most {nl} each')
-            if (math.prod(src.shape[:n_row]), math.prod(src.shape[n_row:])) != (h, nq * wn):
-                raise ValueError(f'{what}: a source view of shape {tuple(src.shape)} with {n_row} row axes for a window of {h} rows and '
-                                 f'{nq} x {wn} columns')
-            if not cplx and (src.is_complex or coeff.imag != 0):
-                raise ValueError(f'{what}: a complex source or coefficient needs complex destination views')
-            arr[i] = (dst.ptr, src.ptr, h, nq, wn, dst.strides[1], dst.strides[0], n_row, n_col,
-                      (src.shape[:n_row] + pad)[:nl], (src.strides[:n_row] + pad)[:nl], (src.shape[n_row:] + pad)[:nl],
-                      (src.strides[n_row:] + pad)[:nl], coeff.real, coeff.imag, 0 if src.is_complex or not cplx else 1, 0)
-        fn = self.lib.cyb_tree_place_c128 if cplx else self.lib.cyb_tree_place_f64
-        self.ctx.sync_stream()
-        _lib.check(fn(self.ctx.handle, arr.ctypes.data_as(C.POINTER(_lib.TreePlaceRec)), len(records)))
+        self._launch_records(_rec.pack_place(records))
 
     def tree_strip_many(self, outs):
         """Weighted sums of permuted strips, ONE descriptor upload and ONE launch for all strips of one side of a factorized
@@ -1854,98 +1574,7 @@ class HipBlockBackend:
         decide the entry: all float64 (real sources, real coefficients) or all complex128 (a float64 source is then read as it
         stands, no promotion pass).  One term with ``coeff == 1`` copies bits; every element has one owner, bit-identical from
         run to run (csrc/tree_strip.hip)."""
-        what = 'tree_strip_many'
-        outs = [(dst, side, start, stop, tuple(dims), tuple(axes), list(terms)) for dst, side, start, stop, dims, axes, terms in outs]
-        if not outs:
-            return
-        dsts = [o[0] for o in outs]
-        srcs = [tm[0] for o in outs for tm in o[6]]
-        cplx = self._tree_entry(what, dsts, srcs, any(x.ndim != 2 for x in dsts + srcs) and 'destinations and sources are 2-D blocks')
-        nl = _lib.CYB_TREE_PLACE_MAX_LEVELS
-        pad = (0,) * nl
-        es = 16 if cplx else 8
-        rows, splits = [], {}         # one record per row, as the int64 words of cyb_tree_strip_out
-        t_re, t_im, t_base = [], [], []
-        for dst, side, start, stop, dims, axes, terms in outs:
-            if side not in (0, 1):
-                raise ValueError(f'{what}: side is 0 (rows) or 1 (columns), not {side}')
-            if dst.strides[1] != 1 and dst.shape[1] > 1:
-                raise ValueError(f'{what}: a destination block needs the column stride 1')
-            if not 0 <= start <= stop <= dst.shape[side]:
-                raise ValueError(f'{what}: the strip {start}:{stop} leaves axis {side} of its block of shape {tuple(dst.shape)}')
-            n, other = stop - start, dst.shape[1 - side]
-            split = splits.get((dims, axes))
-            if split is None:                # (the strips of one side share the permutation and, per class of trees, the dimensions)
-                if len(dims) > nl:
-                    raise ValueError(f'{what}: a strip of {len(dims)} levels, at most {nl}')
-                if sorted(axes) != list(range(len(dims))) or min(dims, default=1) < 0:
-                    raise ValueError(f'{what}: the dimensions {dims} under the axes {axes} for a strip of {n}')
-                old = _c_strides(dims)
-                split = splits[(dims, axes)] = (math.prod(dims), (tuple(dims[a] for a in axes) + pad)[:nl], tuple(old[a] for a in axes))
-            if split[0] != n:
-                raise ValueError(f'{what}: the dimensions {dims} under the axes {axes} for a strip of {n}')
-            ext, lev, strides = split[1], (), None
-            for src, src_start, coeff in terms:
-                coeff = complex(coeff)
-                if not cplx and (src.is_complex or coeff.imag != 0):
-                    raise ValueError(f'{what}: a complex source or coefficient needs complex destination blocks')
-                if src.shape[1 - side] != other or not 0 <= src_start <= src_start + n <= src.shape[side]:
-                    raise ValueError(f'{what}: the strip {src_start}:{src_start + n} of axis {side} of a source of shape {tuple(src.shape)} '
-                                     f'for a destination of shape {tuple(dst.shape)}')
-                if strides is None:
-                    strides = src.strides
-                    lev = tuple(u * strides[side] for u in split[2])
-                elif src.strides != strides:
-                    raise ValueError(f'{what}: the sources of one strip differ in their strides, {strides} and {src.strides}')
-                t_re.append(coeff.real)
-                t_im.append(coeff.imag)
-                t_base.append(src_start * strides[side])
-            across = strides[1 - side] if terms else 0
-            ldd = dst.strides[0]
-            one, step = (other,) + pad[1:], (across,) + pad[1:]
-            lev = (lev + pad)[:nl]
-            if side == 0:     # (the two int32 level counts share a word: rows low, columns high)
-                rows.append((dst.ptr + start * ldd * es, n, 1, other, other, ldd, len(dims) | 1 << 32) + ext + lev + one + step
-                            + (len(t_re) - len(terms), len(terms)))
-            else:
-                rows.append((dst.ptr + start * es, other, 1, n, n, ldd, 1 | len(dims) << 32) + one + step + ext + lev
-                            + (len(t_re) - len(terms), len(terms)))
-        oarr = np.array(rows, dtype=np.int64).view(_lib.TREE_STRIP_OUT_DTYPE).reshape(len(outs))
-        n_t = len(srcs)
-        tarr = np.zeros(max(n_t, 1), dtype=_lib.TREE_STRIP_TERM_DTYPE)
-        if n_t:
-            tarr['src'], tarr['coeff_re'], tarr['coeff_im'], tarr['base'] = [a.ptr for a in srcs], t_re, t_im, t_base
-            tarr['src_real'] = [0 if a.is_complex or not cplx else 1 for a in srcs]
-        fn = self.lib.cyb_tree_strip_c128 if cplx else self.lib.cyb_tree_strip_f64
-        self.ctx.sync_stream()
-        _lib.check(fn(self.ctx.handle, oarr.ctypes.data_as(C.POINTER(_lib.TreeStripOut)), len(outs),
-                      tarr.ctypes.data_as(C.POINTER(_lib.TreeStripTerm)), n_t))
-
-    def _tree_pair_table(self, tensors):
-        """the tree-pair tensors of one call (host arrays, each once) as ONE device table: (table block or None, offset of
-        every tensor by id, whether the table is complex)"""
-        uniq, offs, tot = [], {}, 0
-        for s in tensors:
-            if id(s) not in offs:
-                offs[id(s)] = tot
-                tot += s.size
-                uniq.append(s)
-        cplx = any(np.iscomplexobj(s) for s in uniq)
-        if not tot:
-            return None, offs, cplx
-        flat = np.concatenate([np.asarray(s, dtype=np.complex128 if cplx else np.float64).ravel() for s in uniq])
-        return self.block_from_numpy(flat), offs, cplx
-
-    @staticmethod
-    def _tree_dense_region(what, view, starts, dims, mults, J):
-        """checks one region of a dense view (axes in leg order) and returns its element offset inside the view"""
-        L = view.ndim
-        if not (len(starts) == len(dims) == len(mults) == L and 0 <= J <= L):
-            raise ValueError(f'{what}: a region names {len(starts)} starts, {len(dims)} dimensions and {len(mults)} multiplicities for a view of {L} axes')
-        if any(d < 1 or m < 0 or s < 0 or s + d * m > n for s, d, m, n in zip(starts, dims, mults, view.shape)):
-            raise ValueError(f'{what}: the region at {tuple(starts)} with the dimensions {tuple(dims)} and multiplicities {tuple(mults)} leaves the '
-                             f'view of shape {view.shape}')
-        return sum(s * st for s, st in zip(starts, view.strides))
+        self._launch_records(_rec.pack_strip(outs))
 
     def tree_to_dense_many(self, dst_view, regions):
         """Every region of a dense tensor from the coupled blocks of a fusion-tree tensor, ONE table upload, ONE descriptor
@@ -1961,51 +1590,7 @@ class HipBlockBackend:
         zeros without a term.  The regions of one call must not overlap; what no region covers stays as it is.  The destination
         decides the entry: float64 (real blocks, real S) or complex128 (a float64 block or a real table is then read as it
         stands, no promotion pass).  Fixed summation order, bit-identical from run to run (csrc/tree_dense.hip)."""
-        what = 'tree_to_dense_many'
-        regions = [(tuple(st), tuple(d), tuple(m), int(J), list(terms)) for st, d, m, J, terms in regions]
-        if not regions:
-            return
-        blocks = [tm[0] for r in regions for tm in r[4]]
-        L, cplx = dst_view.ndim, self._tree_entry(what, [dst_view], blocks)
-        if L > _lib.CYB_TREE_DENSE_MAX_LEGS:
-            raise ValueError(f'{what}: a destination view with more than {_lib.CYB_TREE_DENSE_MAX_LEGS} axes')
-        if any(b.ndim != 2 for b in blocks):
-            raise ValueError(f'{what}: blocks are 2-D views')
-        table, s_offs, s_cplx = self._tree_pair_table([tm[3] for r in regions for tm in r[4]])
-        if not cplx and (s_cplx or any(b.is_complex for b in blocks)):
-            raise ValueError(f'{what}: a complex block or tree tensor needs a complex destination view')
-        order = sorted(range(L), key=lambda l: -abs(dst_view.strides[l]))       # the last level: the contiguous run of the destination
-        nl = _lib.CYB_TREE_DENSE_MAX_LEVELS
-        oarr = np.zeros(len(regions), dtype=_lib.TREE_TO_DENSE_OUT_DTYPE)
-        tarr = np.zeros(max(len(blocks), 1), dtype=_lib.TREE_TO_DENSE_TERM_DTYPE)
-        es, t = (16 if cplx else 8), 0
-        for i, (starts, dims, mults, J, terms) in enumerate(regions):
-            off = self._tree_dense_region(what, dst_view, starts, dims, mults, J)
-            s_str = _c_strides(dims)
-            r_str, c_str = _c_strides(mults[:J]), _c_strides(mults[J:])
-            ext, sd, ss, sr, sc = [], [], [], [], []
-            for l in order:
-                ext += [dims[l], mults[l]]
-                sd += [mults[l] * dst_view.strides[l], dst_view.strides[l]]
-                ss += [s_str[l], 0]
-                sr += [0, r_str[l] if l < J else 0]
-                sc += [0, c_str[l - J] if l >= J else 0]
-            pad = (0,) * (nl - 2 * L)
-            H, W = math.prod(mults[:J]), math.prod(mults[J:])
-            for blk, r0, c0, S in terms:
-                if tuple(S.shape) != dims:
-                    raise ValueError(f'{what}: a tree tensor pair of shape {tuple(S.shape)} for the sector dimensions {dims}')
-                if r0 < 0 or c0 < 0 or r0 + H > blk.shape[0] or c0 + W > blk.shape[1]:
-                    raise ValueError(f'{what}: the tile at ({r0}, {c0}) of {H} x {W} elements leaves its block of shape {blk.shape}')
-                tarr[t] = (blk.ptr, r0, c0, blk.strides[0], blk.strides[1], s_offs[id(S)], 0 if blk.is_complex or not cplx else 1,
-                           0 if s_cplx or not cplx else 1)
-                t += 1
-            oarr[i] = (dst_view.ptr + es * off, 2 * L, 0, tuple(ext) + pad, tuple(sd) + pad, tuple(ss) + pad, tuple(sr) + pad, tuple(sc) + pad,
-                       t - len(terms), len(terms))
-        fn = self.lib.cyb_tree_to_dense_c128 if cplx else self.lib.cyb_tree_to_dense_f64
-        self.ctx.sync_stream()
-        _lib.check(fn(self.ctx.handle, oarr.ctypes.data_as(C.POINTER(_lib.TreeToDenseOut)), len(regions),
-                      tarr.ctypes.data_as(C.POINTER(_lib.TreeToDenseTerm)), t, C.c_void_p(table.ptr if table is not None else 0)))
+        self._launch_records(_rec.pack_to_dense(dst_view, regions, self._upload))
 
     def tree_from_dense_many(self, outputs):
         """Every tile of the coupled blocks of a fusion-tree tensor from a dense tensor, ONE table upload, ONE descriptor upload
@@ -2018,73 +1603,21 @@ class HipBlockBackend:
         ``dst[(m..), (n..)] = (sum_terms sum_k conj(S[k_1, ..]) * src[starts + (k_1 * m_1 + mu_1, ..)]) / divisor``, zeros without a term.
         The destinations decide the entry: all float64 (real source, real S) or all complex128 (a float64 source or a real table
         is then read as it stands).  Fixed summation order, bit-identical from run to run (csrc/tree_dense.hip)."""
-        what = 'tree_from_dense_many'
-        outputs = [(dst, float(div), tuple(d), tuple(m), int(J), list(terms)) for dst, div, d, m, J, terms in outputs]
-        if not outputs:
-            return
-        dsts = [o[0] for o in outputs]
-        srcs = [tm[0] for o in outputs for tm in o[5]]
-        cplx = self._tree_entry(what, dsts, srcs, any(d.ndim != 2 for d in dsts) and 'destinations are 2-D views')
-        table, s_offs, s_cplx = self._tree_pair_table([tm[2] for o in outputs for tm in o[5]])
-        if not cplx and (s_cplx or any(a.is_complex for a in srcs)):
-            raise ValueError(f'{what}: a complex source or tree tensor needs complex destination views')
-        nk = _lib.CYB_TREE_DENSE_MAX_LEGS
-        oarr = np.zeros(len(outputs), dtype=_lib.TREE_FROM_DENSE_OUT_DTYPE)
-        tarr = np.zeros(max(len(srcs), 1), dtype=_lib.TREE_FROM_DENSE_TERM_DTYPE)
-        t = 0
-        for i, (dst, div, dims, mults, J, terms) in enumerate(outputs):
-            L = len(dims)
-            if L > nk or len(mults) != L or not 0 <= J <= L:
-                raise ValueError(f'{what}: {len(dims)} dimensions and {len(mults)} multiplicities, at most {nk} legs')
-            if dst.shape != (math.prod(mults[:J]), math.prod(mults[J:])):
-                raise ValueError(f'{what}: a destination view of shape {dst.shape} for the multiplicities {mults[:J]} and {mults[J:]}')
-            if div == 0.0 or div != div:
-                raise ValueError(f'{what}: the divisor is zero or NaN')
-            a_str = terms[0][0].strides if terms else (0,) * L
-            for a, starts, S in terms:
-                off = self._tree_dense_region(what, a, starts, dims, mults, J)
-                if a.strides != a_str:
-                    raise ValueError(f'{what}: the source views of one output share their strides')
-                if tuple(S.shape) != dims:
-                    raise ValueError(f'{what}: a tree tensor pair of shape {tuple(S.shape)} for the sector dimensions {dims}')
-                tarr[t] = (a.ptr + (16 if a.is_complex else 8) * off, s_offs[id(S)], 0 if a.is_complex or not cplx else 1,
-                           0 if s_cplx or not cplx else 1)
-                t += 1
-            order = sorted(range(L), key=lambda l: -abs(a_str[l]))              # the last level: the contiguous run of the source
-            d_str = [x * dst.strides[0] for x in _c_strides(mults[:J])] + [x * dst.strides[1] for x in _c_strides(mults[J:])]
-            pad = (0,) * (nk - L)
-            oarr[i] = (dst.ptr, L, L, tuple(mults[l] for l in order) + pad, tuple(d_str[l] for l in order) + pad,
-                       tuple(a_str[l] for l in order) + pad, dims + pad, tuple(m * s for m, s in zip(mults, a_str)) + pad, div,
-                       t - len(terms), len(terms))
-        fn = self.lib.cyb_tree_from_dense_c128 if cplx else self.lib.cyb_tree_from_dense_f64
-        self.ctx.sync_stream()
-        _lib.check(fn(self.ctx.handle, oarr.ctypes.data_as(C.POINTER(_lib.TreeFromDenseOut)), len(outputs),
-                      tarr.ctypes.data_as(C.POINTER(_lib.TreeFromDenseTerm)), t, C.c_void_p(table.ptr if table is not None else 0)))
+        self._launch_records(_rec.pack_from_dense(outputs, self._upload))
 
-    def _wdot(self, descs, cplx, conj):
-        """launch chain of the weighted reduction + the one read of its result"""
-        n = len(descs)
-        arr = np.zeros(max(n, 1), dtype=_lib.WDOT_DTYPE)
-        for i, d in enumerate(descs):
-            arr[i] = d
+    def _wdot(self, launch):
+        """launch chain of the weighted reduction + the one read of its result (the float64 entry has no `conj` argument,
+        the tail of the launch)"""
+        (arr, struct, n), = launch.arrays
         res = self.ctx.empty(2)
-        p = arr.ctypes.data_as(C.POINTER(_lib.WDotDesc))
+        p = arr.ctypes.data_as(C.POINTER(struct))
         self.ctx.sync_stream()
-        if cplx:
-            _lib.check(self.lib.cyb_dot_weighted_c128(self.ctx.handle, p, n, 1 if conj else 0, C.c_void_p(res.data_ptr())))
+        if launch.cplx:
+            _lib.check(self.lib.cyb_dot_weighted_c128(self.ctx.handle, p, n, *launch.tail, C.c_void_p(res.data_ptr())))
             re, im = self.ctx.d2h(res, 2, np.float64)
             return complex(float(re), float(im))
         _lib.check(self.lib.cyb_dot_weighted_f64(self.ctx.handle, p, n, C.c_void_p(res.data_ptr())))
         return float(self.ctx.d2h(res, 1, np.float64)[0])
-
-    @staticmethod
-    def _as_matrix(b: HipBlock):
-        """(rows, cols, row stride, column stride) of a 1-D or 2-D block"""
-        if b.ndim == 1:
-            return b.shape[0], 1, b.strides[0], 0
-        if b.ndim != 2:
-            raise ValueError('inner_weighted_many: blocks are 1-D or 2-D')
-        return b.shape[0], b.shape[1], b.strides[0], b.strides[1]
 
     def inner_weighted_many(self, a_blocks, b_blocks, weights, do_dagger=False):
         """``sum_n weights[n] * inner(a_n, b_n, do_dagger)`` over lists of 1-D / 2-D blocks: ONE launch chain and one read of
@@ -2092,51 +1625,22 @@ class HipBlockBackend:
         reduction and a host wait per coupled sector).  ``do_dagger``: sum conj(a)[i, j] b[i, j]; else sum a[i, j] b[j, i] without
         conjugation (numpy.cpp:815-842).  ``b_blocks=None``: the weighted square norm sum_n w_n |a_n|^2 (real).  The blocks are
         read in place through their strides (transposed views included); a float64 block beside complex ones is promoted."""
-        a_blocks, weights = list(a_blocks), [float(w) for w in weights]
-        norm = b_blocks is None
-        b_blocks = a_blocks if norm else list(b_blocks)
-        if not (len(a_blocks) == len(b_blocks) == len(weights)):
-            raise ValueError('inner_weighted_many: one weight and one partner per block')
-        self._numeric_only(a_blocks + b_blocks, 'inner_weighted_many')
-        cplx = any(x.is_complex for x in a_blocks) or any(x.is_complex for x in b_blocks)
-        if cplx:
-            a_blocks = [self.as_complex(x) for x in a_blocks]
-            b_blocks = a_blocks if norm else [self.as_complex(x) for x in b_blocks]
-        descs = []
-        for x, y, w in zip(a_blocks, b_blocks, weights):
-            rows, cols, x_rs, x_cs = self._as_matrix(x)
-            yr, yc, y_rs, y_cs = self._as_matrix(y)
-            if not (do_dagger or norm):
-                if x.ndim != 2 or y.ndim != 2:
-                    raise ValueError('inner_weighted_many: do_dagger=False needs 2-D blocks')
-                yr, yc, y_rs, y_cs = yc, yr, y_cs, y_rs
-            if (rows, cols) != (yr, yc):
-                raise ValueError('inner: shape mismatch')
-            descs.append((x.ptr, 0 if norm else y.ptr, rows, cols, x_rs, x_cs, y_rs, y_cs, w))
-        res = self._wdot(descs, cplx, do_dagger or norm)
-        return res.real if norm and cplx else res
+        a_blocks, b_blocks = self._widen_mixed(list(a_blocks), None if b_blocks is None else list(b_blocks))
+        launch = _rec.pack_wdot_inner(a_blocks, b_blocks, weights, do_dagger)
+        res = self._wdot(launch)
+        return res.real if b_blocks is None and launch.cplx else res
 
     def trace_weighted_many(self, blocks, weights):
         """``sum_n weights[n] * trace(block_n)`` over square blocks (``FusionTreeBackend::trace_full``,
         fusion_tree_backend.cpp:1261-1278): the weighted reduction over the diagonals (element stride ld + 1) against a
         constant one -- the same launch chain as :meth:`inner_weighted_many`."""
-        blocks, weights = list(blocks), list(weights)
-        if len(blocks) != len(weights):
-            raise ValueError('trace_weighted_many: one weight per block')
-        self._numeric_only(blocks, 'trace_weighted_many')
+        blocks, = self._widen_mixed(list(blocks))
         cplx = any(b.is_complex for b in blocks)
-        if cplx:
-            blocks = [self.as_complex(b) for b in blocks]
         ones = self.__dict__.setdefault('_const_one', {})        # the constant one of either dtype, uploaded once
         one = ones.get(cplx)
         if one is None:
             one = ones[cplx] = self.as_block(np.ones(1, dtype=np.complex128 if cplx else np.float64))
-        descs = []
-        for b, w in zip(blocks, weights):
-            if b.ndim != 2 or b.shape[0] != b.shape[1]:
-                raise ValueError('trace_weighted_many: blocks must be square matrices')
-            descs.append((b.ptr, one.ptr, b.shape[0], 1, b.strides[0] + b.strides[1], 0, 0, 0, float(w)))
-        return self._wdot(descs, cplx, False)
+        return self._wdot(_rec.pack_wdot_trace(blocks, weights, one))
 
     def allclose(self, a, b, rtol=1e-5, atol=1e-8) -> bool:
         """``np.allclose(a, b, rtol, atol)`` (numpy.cpp:578-585): the ELEMENTWISE test ``|a - b| <= atol + rtol * |b|``,
