@@ -1578,6 +1578,14 @@ struct SvdRanged {
     static int64_t rows(const Desc& d) { return d.m; }
     static int64_t cols(const Desc& d) { return d.n; }
     static double* values(const Desc& d) { return d.S; } // what the scale is taken out of: min(m, n) singular values
+    static int check(const Desc& s, int64_t i)
+    {
+        if (s.m <= 0 || s.n <= 0) return CYB_OK;
+        CYB_REQUIRE(s.lda >= s.n && s.ldu >= std::min(s.m, s.n) && s.ldvh >= s.n,
+                    "svd block %lld: leading dimension too small (lda=%lld ldu=%lld ldvh=%lld for %lld x %lld)", (long long)i,
+                    (long long)s.lda, (long long)s.ldu, (long long)s.ldvh, (long long)s.m, (long long)s.n);
+        return CYB_OK;
+    }
     static int run(cyb_ctx_t ctx, const Desc* descs, int64_t n, int32_t* info, int flags, int32_t* rank)
     {
         return svd_batched_impl(ctx, descs, n, info, flags, rank);
@@ -1589,6 +1597,13 @@ struct EighRanged {
     static int64_t rows(const Desc& d) { return d.n; }
     static int64_t cols(const Desc& d) { return d.n; }
     static double* values(const Desc& d) { return d.W; } // n eigenvalues
+    static int check(const Desc& s, int64_t i)
+    {
+        if (s.n <= 0) return CYB_OK;
+        CYB_REQUIRE(s.lda >= s.n && (!s.V || s.ldv >= s.n), "eigh block %lld: leading dimension too small (lda=%lld ldv=%lld for n = %lld)",
+                    (long long)i, (long long)s.lda, (long long)s.ldv, (long long)s.n);
+        return CYB_OK;
+    }
     static int run(cyb_ctx_t ctx, const Desc* descs, int64_t n, int32_t* info, int flags, int32_t*)
     {
         return eigh_batched_impl(ctx, descs, n, info, flags);
@@ -1599,6 +1614,8 @@ template <class T>
 static int batched_ranged(cyb_ctx_t ctx, const typename T::Desc* descs, int64_t n, int32_t* info, int flags, int32_t* rank)
 {
     typedef typename T::Desc Desc;
+    // every route holds one rule for the leading dimensions, and a refused call has read, uploaded and launched nothing
+    for (int64_t b = 0; b < n; ++b) CYB_TRY(T::check(descs[b], b));
     std::vector<cyb::MatRef> refs;
     std::vector<int64_t> which;
     for (int64_t b = 0; b < n; ++b)

@@ -165,7 +165,10 @@ int cyb_mfma_f64_peak(cyb_ctx_t ctx, int iters, int waves_per_simd, double* tflo
  * Replaces NumpyBlockBackend::matrix_svd = scipy.linalg.svd(a, full_matrices=False)
  * (src/block_backend/numpy.cpp:1247-1297), called per block from AbelianBackend::svd
  * (src/backends/abelian.cpp:3517-3518) and FusionTreeBackend::svd (fusion_tree_backend.cpp:2211).
- * A is not modified. */
+ * A is not modified.
+ * Leading dimensions (every entry and every route): lda >= n, ldu >= k, ldvh >= n for a block with both extents positive,
+ * else the call is CYB_ERR_INVALID and nothing is read, uploaded or launched.  Nothing outside the addressed elements is
+ * written: the gaps of a strided U / Vh and everything around S stay as they were. */
 typedef struct {
     const double* A; int64_t lda;
     int64_t m, n;
@@ -203,7 +206,10 @@ int cyb_svd_batched_ex_f64(cyb_ctx_t ctx, const cyb_svd_desc* descs, int64_t n, 
 /* QR  A(m x n) = Q R.  economic: Q m x k, R k x n (k=min(m,n)); full: Q m x m, R m x n.
  * Replaces NumpyBlockBackend::matrix_qr = scipy.linalg.qr(a, mode=...) (numpy.cpp:1236-1245);
  * matrix_lq (block_backend.cpp:1033-1040) is built on it by the host.
- * Sign convention as LAPACK dgeqrf (R diagonal may be negative). */
+ * Sign convention as LAPACK dgeqrf (R diagonal may be negative).
+ * Leading dimensions: lda >= n, ldq >= k (full: m), ldr >= n for a block with both extents positive, else the call is
+ * CYB_ERR_INVALID and no output is written.  R is written whole (zeros below the diagonal and in rows k .. m-1 of a full
+ * R); the gaps of a strided Q / R stay as they were. */
 typedef struct {
     const double* A; int64_t lda;
     int64_t m, n;
@@ -216,7 +222,9 @@ int cyb_qr_batched_f64(cyb_ctx_t ctx, const cyb_qr_desc* descs, int64_t n);
 /* Hermitian (real symmetric) eigendecomposition  A(n x n) = V diag(W) V^T,  W ascending.
  * Replaces NumpyBlockBackend::eigh = np.linalg.eigh (numpy.cpp:658-680). Only the lower
  * triangle convention of LAPACK is not relied upon: A is assumed symmetric.
- * V may be NULL (eigvalsh, numpy.cpp:682-698). */
+ * V may be NULL (eigvalsh, numpy.cpp:682-698); ldv is not looked at then.
+ * Leading dimensions (every entry and every route): lda >= n, and ldv >= n where V != NULL, for a block with n > 0, else
+ * the call is CYB_ERR_INVALID and nothing is read, uploaded or launched.  The gaps of a strided V stay as they were. */
 typedef struct {
     const double* A; int64_t lda;
     int64_t n;
